@@ -17,9 +17,20 @@ products, fp32 accumulation = fp32-class), the policy whose a22 outputs stay wit
 shipped depths (`parity_err`, measured by this script on tests/golden/e2e_deep.npz and e2e_tiny.npz).  `fast_policy` is the
 out-of-tolerance fp16 throughput mode, timed beside it for reference only.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant hand-written kernel (gemm_kernel<320, split>: the four ViT
-linears, 128 launches per step), timed live with HIP events on the launch stream; `roofline_attention` the same for the global
-ViT attention kernel; `cpu_baseline` times the oracle (CPU restatement of the reference) on this host.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the headline (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step, and the workload description) -- nothing else.
+--full adds every other figure after the timed steps: `dp` (data-parallel evidence and start-up times), `roofline` for the dominant
+hand-written kernel (gemm_kernel<320, split>: the four ViT linears, 128 launches per step), timed live with HIP events on the launch
+stream, `roofline_attention` the same for the global ViT attention kernel, the PAD_MAX 4096 step, the full post-processing, the
+end-to-end and MaskCLIP legs, `parity_err`, the fast and mixed policies, the training step and `cpu_baseline` (the oracle, a CPU
+restatement of the reference, on this host); --no-cpu-baseline / --no-parity-leg / --no-train-leg drop legs of a --full run.
+
+--dump-outputs DIR writes what the LAST timed step computed, rank 0, as float32 .npy files (float64 for 64-bit inputs):
+`predictions.npy` = the gathered (global batch, 100, 7) block a step returns ([x0, y0, x1, y1, score, class, query index] per
+instance), and `a22.<key>.npy` = the a22 dictionary forward_raw handed over in that step.  Arrays of more than `cap` elements are
+replaced by a fixed sample: the flattened tensor at sorted indices drawn by torch.randint(0, numel, (cap,)) from
+torch.Generator().manual_seed(0), `cap` chosen so that everything stays under 64 MB.  The inputs and weights are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -224,6 +235,44 @@ def e2e_leg(model, batch, steps, dev):
             "results": sorted(res[0].keys()),
             "what": "model(batched_inputs): pinned uint8 host images -> double-buffered H2D on a copy stream -> forward -> HIPIE_IMG.inference "
                     "(instances + masks, sem_seg, panoptic_seg); the interval detectron2's evaluator times"}
+
+
+DUMP_BYTES = 60 << 20             # --dump-outputs stays under 64 MB
+
+
+def _tensors(prefix, v):
+    """(name, tensor) of every tensor inside nested dicts / lists / tuples; keys starting with "_" are internal state"""
+    if torch.is_tensor(v):
+        return [(prefix, v)]
+    out = []
+    if isinstance(v, dict):
+        for k, x in v.items():
+            if not str(k).startswith("_"):
+                out += _tensors("%s.%s" % (prefix, k), x)
+    elif isinstance(v, (list, tuple)):
+        for i, x in enumerate(v):
+            out += _tensors("%s.%d" % (prefix, i), x)
+    return out
+
+
+def dump_outputs(path, predictions, raw):
+    """--dump-outputs: the returned prediction block in full, every tensor of the a22 dictionary in full or as a fixed seeded
+    sample (module docstring); returns {name: stored shape} for the JSON line"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = [("predictions", predictions)] + _tensors("a22", raw or {})
+    fixed = sum(t.numel() for _, t in arrays[:1]) * 8
+    cap = max(4096, (DUMP_BYTES - fixed) // (8 * max(1, len(arrays) - 1)))      # elements per a22 array (8 bytes: float64 worst case)
+    stored = {}
+    for name, t in arrays:
+        t = t.detach()
+        if name != "predictions" and t.numel() > cap:
+            idx = torch.randint(0, t.numel(), (cap,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.flatten()[idx.to(t.device)]
+        a = (t.double() if t.dtype in (torch.float64, torch.int64, torch.int32) else t.float()).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        stored[name] = list(a.shape)
+    return stored
 
 
 def randomize_degenerate_inits(model):
@@ -435,9 +484,14 @@ def main():
     ap.add_argument("--precision", default="split", choices=["split", "fast", "parity", "bf16", "default"],
                     help="split (default, the timed policy): split-fp16 GEMMs and attention logits, within 1e-3 of the reference at the "
                          "shipped depths; fast: single-fp16 operands (out of tolerance); parity: fp32 library GEMMs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity-leg", action="store_true", help="skip parity_err and the fast-policy timing (rank 0, N = 1)")
-    ap.add_argument("--no-train-leg", action="store_true", help="skip the training-step figure (`train_step`: SURVEY f-4; rank 0, N = 1, ~25 s)")
+    ap.add_argument("--full", action="store_true", help="after the headline's timed steps, measure and check everything else: dp evidence, "
+                    "rooflines, PAD_MAX 4096, post-processing, end-to-end and MaskCLIP legs, parity_err, fast / mixed policies, training step, "
+                    "CPU baseline (off by default: a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy "
+                    "(the returned prediction block and the a22 dictionary; under 64 MB; module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-parity-leg", action="store_true", help="with --full: skip parity_err and the fast-policy timing (rank 0, N = 1)")
+    ap.add_argument("--no-train-leg", action="store_true", help="with --full: skip the training-step figure (`train_step`: SURVEY f-4; rank 0, N = 1, ~25 s)")
     ap.add_argument("--graph", action="store_true", help="capture the forward once into a hipGraph and replay it (same rate as "
                     "eager: the step is GPU-bound; the round-2 replay fault was torch.topk, replaced by hipie_topk -- DESIGN.md "
                     "section 9)")
@@ -454,6 +508,8 @@ def main():
     ap.add_argument("--breakdown", action="store_true", help="after the timed region, time every hand-written kernel class "
                     "and the main stages of one extra step (stderr)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config is not None:
         preset = {0: dict(model="r50", size=512, batch=1, classes=1, text_len=12, task="grounding"),
                   1: dict(model="r50", size=1024, batch=4, classes=80, text_len=194, task="detection"),
@@ -539,8 +595,12 @@ def main():
     batch = synth_batch(cfg, len(shard), args.size, n_classes, L, dev, seed=0, task=args.task, indices=shard,
                         ids_device=dev if args.graph else "cpu")
 
+    last = {"keep": False, "raw": None}                                     # --dump-outputs: the a22 dictionary of the last timed step
+
     def local_step():
         out = model.forward_raw(batch)
+        if last["keep"]:
+            last["raw"] = out
         # the step ends at the compact per-image predictions that the data-parallel all-gather carries: class
         # scores, NMS, top-100, box scaling -- built on the device without a host round trip (postprocess.inference_compact ==
         # compact_predictions(inference(...)), tests/test_gpu_post.py); instance masks and the semantic / panoptic maps of the
@@ -557,11 +617,13 @@ def main():
     t_first = time.perf_counter()
     for _ in range(max(args.warmup, 1) - 1):
         gathered = step()
-    dp = parallel.dp_evidence(gathered, args.batch, rank, world, dev)     # rccl_ranks (all-reduce of ones), shard, gathered shape
-    # per-rank start-up cost (it sits inside the driver's wall clock at --gpus N): process start -> model built and finalised -> first step done
-    dp["startup_s"] = {"build_max_over_ranks": round(parallel.max_over_ranks(t_built - t_start, dev), 2),
-                       "first_step_max_over_ranks": round(parallel.max_over_ranks(t_first - t_built, dev), 2),
-                       "host_cores_per_rank": host_cores, "torch_threads_per_rank": host_threads}
+    dp = None
+    if args.full:
+        dp = parallel.dp_evidence(gathered, args.batch, rank, world, dev)     # rccl_ranks (all-reduce of ones), shard, gathered shape
+        # per-rank start-up cost (it sits inside the driver's wall clock at --gpus N): process start -> model built and finalised -> first step done
+        dp["startup_s"] = {"build_max_over_ranks": round(parallel.max_over_ranks(t_built - t_start, dev), 2),
+                           "first_step_max_over_ranks": round(parallel.max_over_ranks(t_first - t_built, dev), 2),
+                           "host_cores_per_rank": host_cores, "torch_threads_per_rank": host_threads}
 
     # The forward has static shapes and no host<->device traffic, so it CAN be captured once into a hipGraph and replayed
     # (--graph).  Default is eager: with batched post-processing and the fused glue kernels the step is GPU-bound.
@@ -595,16 +657,58 @@ def main():
     parallel.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        last["keep"] = bool(args.dump_outputs) and i == args.steps - 1
+        result = step()
     torch.cuda.synchronize()
     parallel.barrier()
     dt = time.perf_counter() - t0
     dt = parallel.max_over_ranks(dt, dev)
+    last["keep"] = False
+
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, result, gout if graph is not None else last["raw"])
+    last["raw"] = None
 
     if args.timed_only:
         if rank == 0:
             emit_line({"ms_per_step": round(dt / args.steps * 1e3, 2), "images_per_sec": round(args.batch * world * args.steps / dt, 3)})
+        parallel.shutdown()
+        return
+
+    def headline():
+        return {
+            "metric": "images/sec @%dx%d %s bs=%d (single-image inference hot path: box, class and mask logits)"
+                      % (args.size, args.size, {"vit_huge": "ViT-H", "vit_large": "ViT-L", "vit_base": "ViT-B", "r50": "R50"}[args.model], args.batch),
+            "value": round(args.batch * world * args.steps / dt, 3), "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": {"split": "f16x3 (split-fp16 operands, fp32 accumulate: fp32-class)", "fast": "f16", "parity": "f32+f16attn", "bf16": "bf16",
+                      "default": "bf16+f32head"}[args.precision],
+            "data": "synthetic (uint8-valued random images resident in HBM BEFORE the timed region -- the 12.6 MB / image host-to-device copy that the "
+                    "reference's timer includes (detectron2/evaluation/evaluator.py:157-161) is outside the step; synthetic BERT token ids "
+                    + ("resident on the device (hipGraph capture)" if args.graph else "handed over as host tensors like a tokenizer's output")
+                    + "; random-init weights)",
+            "config": {"workload": "BASELINE.json configs[%s]: %s, %dx%d, batch %d per GPU, %d %s (L=%d), %s"
+                                   % (str(args.config) if args.config is not None else
+                                      {80: "1" if args.model == "r50" else ("2" if world == 1 else "2 per GPU (weak scaling of the metric's workload: "
+                                            "%d images, 80-class prompt; configs[3] literally = --config 3)" % (args.batch * world)), 150: "3",
+                                       1203: "4"}.get(n_classes, "-"),
+                                      args.model, args.size, args.size, args.batch, n_classes,
+                                      "text prompt" if args.task == "grounding" else "class prompts", L, args.task),
+                       "global_batch": args.batch * world, "parallelism": "dp%d" % world, "precision_policy": args.precision,
+                       "launch": "hipGraph replay" if graph is not None else "eager",
+                       "constants": "weight- and geometry-only tensors (rel-pos tables, position embeddings, valid ratios) are "
+                                    "built once; nothing that depends on image or text content is cached"},
+        }
+
+    if not args.full:
+        if rank == 0:
+            line = headline()
+            if dumped is not None:
+                line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+            emit_line(line)
+        parallel.barrier()
         parallel.shutdown()
         return
 
@@ -774,7 +878,6 @@ def main():
             pmc_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", pmc_file)
             if os.path.exists(pmc_path) and std:
                 pmc.update(json.load(open(pmc_path)))
-        images = args.batch * world * args.steps
         N = (args.size // 16) ** 2
         E = cfg.vit_embed_dim
         flops = 4.0 * N * N * E * args.batch          # QK^T + PV of one global block, all heads, this batch
@@ -812,28 +915,8 @@ def main():
                                     "WRITE_SIZE, separate passes: profiles/r06_pmc_kernels.json (the newest round present wins)"}
         else:
             roof = roof_attn
-        line = {
-            "metric": "images/sec @%dx%d %s bs=%d (single-image inference hot path: box, class and mask logits)"
-                      % (args.size, args.size, {"vit_huge": "ViT-H", "vit_large": "ViT-L", "vit_base": "ViT-B", "r50": "R50"}[args.model], args.batch),
-            "value": round(images / dt, 3), "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": {"split": "f16x3 (split-fp16 operands, fp32 accumulate: fp32-class)", "fast": "f16", "parity": "f32+f16attn", "bf16": "bf16",
-                      "default": "bf16+f32head"}[args.precision],
-            "data": "synthetic (uint8-valued random images resident in HBM BEFORE the timed region -- the 12.6 MB / image host-to-device copy that the "
-                    "reference's timer includes (detectron2/evaluation/evaluator.py:157-161) is outside the step; synthetic BERT token ids "
-                    + ("resident on the device (hipGraph capture)" if args.graph else "handed over as host tensors like a tokenizer's output")
-                    + "; random-init weights)",
-            "config": {"workload": "BASELINE.json configs[%s]: %s, %dx%d, batch %d per GPU, %d %s (L=%d), %s"
-                                   % (str(args.config) if args.config is not None else
-                                      {80: "1" if args.model == "r50" else ("2" if world == 1 else "2 per GPU (weak scaling of the metric's workload: "
-                                            "%d images, 80-class prompt; configs[3] literally = --config 3)" % (args.batch * world)), 150: "3",
-                                       1203: "4"}.get(n_classes, "-"),
-                                      args.model, args.size, args.size, args.batch, n_classes,
-                                      "text prompt" if args.task == "grounding" else "class prompts", L, args.task),
-                       "global_batch": args.batch * world, "parallelism": "dp%d" % world, "precision_policy": args.precision,
-                       "launch": "hipGraph replay" if graph is not None else "eager",
-                       "constants": "weight- and geometry-only tensors (rel-pos tables, position embeddings, valid ratios) are "
-                                    "built once; nothing that depends on image or text content is cached"},
+        line = headline()
+        line.update({
             "dp": dp,
             "roofline": roof,
             "roofline_attention": roof_attn,
@@ -846,7 +929,9 @@ def main():
             "pad_max_4096": pad_max,
             "fast_policy": other,
             "mixed_policy": mixed,
-        }
+        })
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         # SURVEY 8d names the measurement weights: default module init with the zero tensors redrawn = tests/golden/e2e_full_refinit.  `value`
         # stays the policy that ALSO passes the (much harder) default synthetic gate; value_8d says what the contract's own distribution allows:
         # the fastest policy measured here whose error on e2e_full_refinit is <= 5e-4, with its error on the gate fixture beside it

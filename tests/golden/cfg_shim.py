@@ -1,4 +1,4 @@
-"""The reference's REAL configuration surface without yacs / fvcore / detectron2 installed (build container only).
+"""The reference's REAL configuration surface without yacs / fvcore / detectron2 installed (`Recorded` needs only tests/golden).
 
 What runs here is the reference's own code, imported in place from /root/reference:
   detectron2/config/defaults.py                       (the detectron2 default tree `_C`)
@@ -7,12 +7,15 @@ What runs here is the reference's own code, imported in place from /root/referen
 over a small stand-in for `detectron2.config.CfgNode` with yacs' merge semantics (yacs/config.py: `_merge_a_into_b` -- a key that the
 defaults do not define is a KeyError "Non-existent config key", values are decoded with literal_eval, tuples / lists coerce into each
 other, other type changes raise) and fvcore's `_BASE_` inheritance (fvcore/common/config.py: load_yaml_with_base).  The yaml files are the
-reference's shipped ones, read where they lie.  Nothing of this travels to the GPU box: tests/golden/gen_cfg_golden.py writes the merged
-trees as flat key/value tables (tests/golden/eval_cfgs.json) and the GPU-side test rebuilds plain namespaces from them.
+reference's shipped ones, read where they lie.  None of the reference travels with the repository: tests/golden/gen_cfg_golden.py writes
+the merged trees as flat key/value tables (tests/golden/eval_cfgs.json), from which the tests rebuild plain namespaces, and the inputs of
+the merges (the defaults trees the reference's config code builds, the parsed yaml mappings: tests/golden/cfg_sources.json), over which
+`Recorded` repeats the merges with the stand-in wherever the tests run.
 """
 import ast
 import copy
 import importlib.util
+import json
 import os
 import sys
 import types
@@ -83,15 +86,16 @@ class CfgNode(dict):
                 self[k] = self._coerce(v, self[k], full)
 
     @staticmethod
-    def load_yaml_with_base(filename):
-        with open(filename) as f:
-            cfg = yaml.unsafe_load(f)           # detectron2's CfgNode loads unsafely by default (config.py:37-40); YAML 1.1: on / off are bools
+    def load_yaml_with_base(filename, read=None):
+        """`read(filename)` -> the parsed yaml mapping (default: the file on disk; Recorded passes its stored mappings)"""
+        read = read or _read_yaml
+        cfg = read(filename)
         base = cfg.pop("_BASE_", None)
         if base is None:
             return cfg
         if not os.path.isabs(base):
-            base = os.path.join(os.path.dirname(filename), base)
-        out = CfgNode.load_yaml_with_base(base)
+            base = os.path.normpath(os.path.join(os.path.dirname(filename), base))
+        out = CfgNode.load_yaml_with_base(base, read)
 
         def merge(a, b):
             for k, v in a.items():
@@ -102,8 +106,8 @@ class CfgNode(dict):
         merge(cfg, out)
         return out
 
-    def merge_from_file(self, filename, allow_unsafe=True):
-        self._merge(self.load_yaml_with_base(filename), [])
+    def merge_from_file(self, filename, allow_unsafe=True, read=None):
+        self._merge(self.load_yaml_with_base(filename, read), [])
 
     def merge_from_other_cfg(self, other):
         self._merge(other, [])
@@ -116,6 +120,11 @@ class CfgNode(dict):
             if parts[-1] not in node:
                 raise KeyError("Non-existent config key: %s" % k)
             node[parts[-1]] = self._coerce(self._decode(v), node[parts[-1]], k)
+
+
+def _read_yaml(filename):
+    with open(filename) as f:
+        return yaml.unsafe_load(f)              # detectron2's CfgNode loads unsafely by default (config.py:37-40); YAML 1.1: on / off are bools
 
 
 def _load(path, name, package=None):
@@ -194,3 +203,89 @@ def flatten(node, prefix=""):
 def eval_yamls():
     d = os.path.join(HIPIE, "configs", "eval")
     return sorted(os.path.join(d, f) for f in os.listdir(d) if f.endswith(".yaml"))
+
+
+# ---- the same inputs without the reference: tests/golden/cfg_sources.json -------------------------------------------------------------
+# gen_cfg_golden.py records what the reference's config code produces (the defaults tree after add_hipie_config; the one
+# build_maskdino starts from) and every yaml mapping the merges read (eval yamls, their _BASE_ chains, the MaskDINO yamls), keyed by
+# their path under the reference root.  Recorded replays the merges from those data alone, so the tests run wherever the repository is.
+SOURCES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cfg_sources.json")
+EVAL_DIR = "projects/HIPIE/configs/eval"
+
+
+def _encode(v):
+    if isinstance(v, dict):
+        return {k: _encode(x) for k, x in v.items()}
+    if isinstance(v, tuple):
+        return {"__tuple__": [_encode(x) for x in v]}         # yacs keeps tuples and lists apart (_coerce)
+    if isinstance(v, list):
+        return [_encode(x) for x in v]
+    return v
+
+
+def _decode_tree(v):
+    if isinstance(v, dict):
+        if set(v) == {"__tuple__"}:
+            return tuple(_decode_tree(x) for x in v["__tuple__"])
+        return {k: _decode_tree(x) for k, x in v.items()}
+    if isinstance(v, list):
+        return [_decode_tree(x) for x in v]
+    return v
+
+
+def _rel(path):
+    return os.path.relpath(path, REF) if os.path.isabs(path) else os.path.normpath(path)
+
+
+def record_sources():
+    """run the reference's config code once and return the tables Recorded needs (gen_cfg_golden.py writes them)"""
+    yamls = {}
+
+    def read(filename):
+        cfg = _read_yaml(filename)
+        yamls[_rel(filename)] = _encode(copy.deepcopy(cfg))
+        return cfg
+    with _Modules():
+        add = _load(os.path.join(HIPIE, "hipie", "config.py"), "_ref_hipie_config").add_hipie_config
+        hipie = d2_defaults()
+        add(hipie)
+        deeplab = _load(os.path.join(REF, "projects", "DeepLab", "deeplab", "config.py"), "_ref_deeplab_config").add_deeplab_config
+        md = _load(os.path.join(HIPIE, "hipie", "models", "maskdino", "config.py"), "_ref_maskdino_config").add_maskdino_config
+        mdc = d2_defaults()
+        deeplab(mdc)
+        md(mdc)
+    for y in eval_yamls():
+        cfg = hipie.clone()
+        cfg.merge_from_file(y, read=read)
+        mp = cfg.MODEL.MASKDINO.CONFIG_PATH
+        mdc.clone().merge_from_file(mp if os.path.isabs(mp) else os.path.join(REF, mp), read=read)
+    return {"hipie_defaults": _encode(hipie), "maskdino_defaults": _encode(mdc), "yamls": dict(sorted(yamls.items()))}
+
+
+class Recorded(object):
+    """eval_yamls / hipie_cfg / maskdino_cfg of this module over tests/golden/cfg_sources.json instead of the reference tree: the same
+    CfgNode merges (yacs semantics, _BASE_ inheritance) on the recorded defaults and yaml mappings; yaml paths are reference-relative"""
+
+    def __init__(self, path=SOURCES):
+        with open(path) as f:
+            src = json.load(f)
+        self.hipie = _decode_tree(src["hipie_defaults"])
+        self.maskdino = _decode_tree(src["maskdino_defaults"])
+        self.yamls = {k: _decode_tree(v) for k, v in src["yamls"].items()}
+
+    def _read(self, filename):
+        return copy.deepcopy(self.yamls[_rel(filename)])      # KeyError = a yaml the recording did not visit
+
+    def eval_yamls(self):
+        return sorted(k for k in self.yamls if os.path.dirname(k) == EVAL_DIR and k.endswith(".yaml"))
+
+    def hipie_cfg(self, yaml_path, opts=()):
+        cfg = CfgNode(copy.deepcopy(self.hipie))
+        cfg.merge_from_file(yaml_path, read=self._read)
+        cfg.merge_from_list(list(opts))
+        return cfg
+
+    def maskdino_cfg(self, config_path):
+        cfg = CfgNode(copy.deepcopy(self.maskdino))
+        cfg.merge_from_file(config_path, read=self._read)
+        return cfg

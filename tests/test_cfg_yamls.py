@@ -1,10 +1,11 @@
-"""SURVEY 8b1 on the REAL configuration surface: the 11 shipped eval yamls of the reference, merged by the reference's own config code.
+"""SURVEY 8b1 on the REAL configuration surface: the 11 shipped eval yamls of the reference, merged as the reference's own config code does.
 
-* build container (needs /root/reference; skipped elsewhere): `add_hipie_config` (projects/HIPIE/hipie/config.py:5-284) over detectron2's own
-  defaults.py, each configs/eval/*.yaml with its `_BASE_` inheritance, the MaskDINO yaml as hipie/models/maskdino/build.py:8-19 assembles
-  it -- through the CfgNode stand-in of tests/golden/cfg_shim.py (yacs / fvcore are not installed; PyYAML is) -- into
-  HipieConfig.from_yacs and a construction of HIPIE_IMG on the meta device; the flattened trees must equal tests/golden/eval_cfgs.json.
-* everywhere (the GPU box too): the same constructions from the committed tables alone.
+* the merges themselves: detectron2's defaults.py + `add_hipie_config` (projects/HIPIE/hipie/config.py:5-284), each configs/eval/*.yaml
+  with its `_BASE_` inheritance, the MaskDINO yaml as hipie/models/maskdino/build.py:8-19 assembles it -- through the CfgNode stand-in of
+  tests/golden/cfg_shim.py (yacs / fvcore are not installed; PyYAML is), over the defaults trees that the reference's config code builds
+  and the parsed yamls, recorded in tests/golden/cfg_sources.json by gen_cfg_golden.py -- into HipieConfig.from_yacs and a construction
+  of HIPIE_IMG on the meta device; the flattened trees must equal tests/golden/eval_cfgs.json.
+* the same constructions from the committed tables alone.
 """
 import json
 import os
@@ -15,7 +16,6 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 TABLES = os.path.join(HERE, "golden", "eval_cfgs.json")
-HAVE_REF = os.path.isdir("/root/reference/projects/HIPIE/configs/eval")
 
 # value -> yaml names (without the common prefix / suffix), read off the reference's yamls (configs/eval/*.yaml)
 MAX_QUERY_LEN = {"r50_pan_maskdino_ade_test": 8192, "vit_huge_32g_pan_maskdino_ade_test": 4096, "r50_pan_maskdino_pascal": 1536,
@@ -61,38 +61,38 @@ def _check_and_construct(name, cfg, md):
     return h
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="/root/reference is not present (GPU box): the committed tables are checked instead")
 def test_the_eleven_eval_yamls_through_the_references_own_config_code():
     import cfg_shim
-    yamls = cfg_shim.eval_yamls()
+    ref = cfg_shim.Recorded()
+    yamls = ref.eval_yamls()
     assert len(yamls) == 11
     committed = json.load(open(TABLES))
     keep = ("MODEL.", "TEST.", "INPUT.", "DATASETS.TEST", "VERSION")
     for y in yamls:
-        cfg = cfg_shim.hipie_cfg(y)                                   # KeyError here = a yaml key add_hipie_config does not define
-        md = cfg_shim.maskdino_cfg(cfg.MODEL.MASKDINO.CONFIG_PATH)
+        cfg = ref.hipie_cfg(y)                                        # KeyError here = a yaml key add_hipie_config does not define
+        md = ref.maskdino_cfg(cfg.MODEL.MASKDINO.CONFIG_PATH)
         name = os.path.basename(y)
         flat = {k: v for k, v in cfg_shim.flatten(cfg).items() if k.startswith(keep)}
         assert json.loads(json.dumps(flat)) == committed["eval"][name], name + ": tests/golden/eval_cfgs.json is stale (gen_cfg_golden.py)"
         _check_and_construct(name, cfg, md)
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="needs the reference's config code")
 def test_config_stand_in_has_yacs_semantics_and_unsupported_switches_raise():
     import cfg_shim
-    y = [p for p in cfg_shim.eval_yamls() if p.endswith("vit_huge_32g_pan_maskdino_ade_test.yaml")][0]
+    ref = cfg_shim.Recorded()
+    y = [p for p in ref.eval_yamls() if p.endswith("vit_huge_32g_pan_maskdino_ade_test.yaml")][0]
     with pytest.raises(KeyError, match="Non-existent config key"):
-        cfg_shim.hipie_cfg(y, opts=["MODEL.NO_SUCH_KEY", 1])
+        ref.hipie_cfg(y, opts=["MODEL.NO_SUCH_KEY", 1])
     with pytest.raises(ValueError, match="Type mismatch"):
-        cfg_shim.hipie_cfg(y, opts=["MODEL.DDETRS.HIDDEN_DIM", "wide"])
+        ref.hipie_cfg(y, opts=["MODEL.DDETRS.HIDDEN_DIM", "wide"])
     from hipie_amd.config import HipieConfig
     for key, val in (("MODEL.PARALLEL_DET", True), ("MODEL.DECOUPLE_TGT", False), ("MODEL.DDETRS.USE_DINO", False),
                      ("MODEL.MASKDINO.SHARE_CLS_HEAD", True), ("MODEL.MASKDINO.ENABLED", False)):
-        cfg = cfg_shim.hipie_cfg(y, opts=[key, val])
+        cfg = ref.hipie_cfg(y, opts=[key, val])
         with pytest.raises(NotImplementedError, match=key.replace(".", r"\.")):
-            HipieConfig.from_yacs(cfg, cfg_shim.maskdino_cfg(cfg.MODEL.MASKDINO.CONFIG_PATH))
-    cfg = cfg_shim.hipie_cfg(y, opts=["MODEL.LANGUAGE_BACKBONE.MAX_QUERY_LEN", 256, "MODEL.LANGUAGE_BACKBONE.PAD_MAX", False])
-    h = HipieConfig.from_yacs(cfg, cfg_shim.maskdino_cfg(cfg.MODEL.MASKDINO.CONFIG_PATH))
+            HipieConfig.from_yacs(cfg, ref.maskdino_cfg(cfg.MODEL.MASKDINO.CONFIG_PATH))
+    cfg = ref.hipie_cfg(y, opts=["MODEL.LANGUAGE_BACKBONE.MAX_QUERY_LEN", 256, "MODEL.LANGUAGE_BACKBONE.PAD_MAX", False])
+    h = HipieConfig.from_yacs(cfg, ref.maskdino_cfg(cfg.MODEL.MASKDINO.CONFIG_PATH))
     assert (h.max_query_len, h.pad_max) == (256, False)
 
 

@@ -4,18 +4,19 @@
 # whole -m gpu suite + smoke, the default bench line (all legs), the other BASELINE configs, the kernel-trace summary of the default bench
 # and of its timed steps, PMC passes of the two dominant kernels (separate --pmc passes, --kernel-trace only), stage times, the training step.
 R=${ROUND:-06}
+ROOT=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)     # the repository root
 cd "$GRAFT_REPO_ROOT"; O=$GRAFT_REPO_ROOT/gpurun_out/round_end; mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -x -q -rs 2>&1 | tail -8 > $O/r${R}_gpu_suite_tail.txt; cat $O/r${R}_gpu_suite_tail.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 > $O/r${R}_smoke.txt; cat $O/r${R}_smoke.txt
-timeout 1200 python bench.py > $O/r${R}_bench_line.json 2> $O/bench.err; echo "bench rc=$?"
-timeout 300 python bench.py --config 3 --steps 3 --warmup 2 --no-cpu-baseline --no-parity-leg > $O/r${R}_bench_config3_shard.json 2>/dev/null
-timeout 400 python bench.py --config 4 --steps 3 --warmup 2 --no-cpu-baseline --no-parity-leg > $O/r${R}_bench_config4.json 2>/dev/null
-timeout 200 python bench.py --config 1 --steps 5 --warmup 2 --no-cpu-baseline --no-parity-leg > $O/r${R}_bench_config1.json 2>/dev/null
-timeout 200 python bench.py --config 0 --steps 10 --warmup 3 --no-cpu-baseline --no-parity-leg > $O/r${R}_bench_config0.json 2>/dev/null
+timeout 1200 python bench.py --full > $O/r${R}_bench_line.json 2> $O/bench.err; echo "bench rc=$?"
+timeout 300 python bench.py --full --config 3 --steps 3 --warmup 2 --no-cpu-baseline --no-parity-leg > $O/r${R}_bench_config3_shard.json 2>/dev/null
+timeout 400 python bench.py --full --config 4 --steps 3 --warmup 2 --no-cpu-baseline --no-parity-leg > $O/r${R}_bench_config4.json 2>/dev/null
+timeout 200 python bench.py --full --config 1 --steps 5 --warmup 2 --no-cpu-baseline --no-parity-leg > $O/r${R}_bench_config1.json 2>/dev/null
+timeout 200 python bench.py --full --config 0 --steps 10 --warmup 3 --no-cpu-baseline --no-parity-leg > $O/r${R}_bench_config0.json 2>/dev/null
 timeout 600 python bench.py --graph --timed-only --steps 20 --warmup 3 2>/dev/null | tail -1 > $O/r${R}_bench_line_hipgraph.json
 for f in $O/r${R}_bench_config*.json; do tail -1 $f | cut -c1-200; done
 cd /tmp && export TMPDIR=/tmp
-(cd $GRAFT_REPO_ROOT && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -o b -- python bench.py --no-cpu-baseline --no-parity-leg --no-train-leg > $O/r${R}_bench_line_under_rocprof.json 2> $O/prof.err)
+(cd "$ROOT" && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -o b -- python bench.py --full --no-cpu-baseline --no-parity-leg --no-train-leg > $O/r${R}_bench_line_under_rocprof.json 2> $O/prof.err)
 cp $(find /tmp/kt -name "*kernel_stats.csv" | head -1) $O/r${R}_bench_vith_bs8_kernel_stats.csv
 (timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt2 -o b -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-parity-leg --timed-only > $O/prof_timed.json 2> $O/prof2.err)
 cd $GRAFT_REPO_ROOT
