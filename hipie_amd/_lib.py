@@ -52,6 +52,8 @@ SIGNATURES = {
     "hipie_add_cast": [c_p, c_p, c_p, c_l, c_i, c_p],
     "hipie_group_norm": [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_p],
     "hipie_gemm": [c_p, c_l, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_p] + [c_i] * 6 + [c_f, c_f, c_p],
+    "hipie_gemm_f8x": [c_p, c_l, c_p, c_l, c_p, c_p, c_p, c_l, c_p, c_l, c_p] + [c_i] * 6 + [c_f, c_f, c_p],
+    "hipie_to_f8x": [c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_p],
     "hipie_gemm_ln": [c_p, c_l, c_p, c_l, c_p, c_p, c_l, c_p, c_p, c_f, c_p, c_l, c_p, c_l, c_i, c_i, c_i, c_f, c_p],
     "hipie_gemm_gather": [c_p, c_l, c_l, c_p, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_p] + [c_i] * 6 + [c_f, c_f, c_p],
     "hipie_vit_attn_split": [c_p, c_p, c_p, c_p] + [c_i] * 5 + [c_p],

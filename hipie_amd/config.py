@@ -40,6 +40,8 @@ class Precision:
     split: bool = False                    # every linear as hipie_gemm on SPLIT fp16 operands (hi + lo, three MFMA products, fp32
                                            # accumulation = fp32-class results), ViT attention logits likewise (hipie_vit_attn_split)
     vit_attn16: bool = False               # with split: the ViT attention core on single fp16 operands (hipie_vit_attn_rel) -- `mixed`
+    fp8x_linears: tuple = ()               # with split: the ViT linear families ("qkv", "proj", "fc1", "fc2") whose product runs with its two
+                                           # cross terms on block-scaled e4m3 (hipie_gemm_f8x) -- `fp8x`; wired for "fc2" (Mlp.forward_split)
 
     @staticmethod
     def parity():
@@ -71,6 +73,20 @@ class Precision:
         (P as one fp16 alone costs 1e-3 there).  Reported by bench.py beside the headline as `mixed_policy`; NOT the timed policy."""
         p = Precision.split3()
         p.vit_attn16, p.name, p.attn_fast = True, "mixed", True
+        return p
+
+    @staticmethod
+    def fp8x():
+        """split3 with the ViT MLP output (fc2) on hipie_gemm_f8x: W_hi.X_hi on fp16 plus the two cross terms W_lo.X_hi and W_hi.X_lo on e4m3
+        operands with a power-of-two scale per 32 k-elements (v_mfma_scale_f32_32x32x64_f8f6f4, twice the fp16 rate): 2 + 2 fp16-equivalent
+        MFMA passes per 32 k instead of 6.  Where it stands: the product is 1.1e-5 from fp64 (three fp16 products: 6e-7; tools/fp8_cross_terms.py);
+        measured a22 errors (tools/bench_fp8x.py, profiles/fp8x_bench.json): e2e_tiny 5.1e-5, e2e_deep 1.6e-4, e2e_full 6.6e-4, e2e_full_refinit
+        2.5e-5, e2e_full_c80 6.5e-4 -- inside the 1e-3 tolerance.  The f8x kernel is not faster than the split one yet (docs/measurements.md).
+        Other families may be listed in `fp8x_linears` by a user, but the study (tools/fp8_e2e_study.py, profiles/r06_fp8_cross_terms_study.txt)
+        puts them at or over the gate (qkv alone 8.7e-4; proj and fc1 over it; every ViT linear 2.4e-3), and only fc2 is wired to the kernel.
+        NOT the timed policy."""
+        p = Precision.split3()
+        p.fp8x_linears, p.name = ("fc2",), "fp8x"
         return p
 
     @staticmethod

@@ -821,9 +821,9 @@ static int launch_gemm(GemmParams& p, hipStream_t st, int batches = 1) {
   return check_launch("gemm");
 }
 
-// gemm_ln.hip includes this file for the kernel template and its launcher only (its LayerNorm-epilogue instances are built without the
+// gemm_ln.hip and gemm_f8x.hip include this file for the kernel template, its epilogue and its launcher only (the LayerNorm-epilogue instances are built without the
 // SLP vectoriser, see the Makefile): everything below belongs to gemm.o alone.
-#ifndef HIPIE_GEMM_LN_TU
+#ifndef HIPIE_GEMM_INCLUDED_TU
 // fp32 / fp16 rows -> HL8 (optionally scaled): the generic producer of split operands (weights are split once on the host)
 template <typename T>
 __global__ __launch_bounds__(256) void to_hl8_kernel(const T* __restrict__ x, f16_t* __restrict__ out, long rows, int K, long ldx, long ldo,
@@ -1135,4 +1135,4 @@ extern "C" int hipie_to_hl8_t(const void* x, int64_t ldx, void* out, int64_t ldo
 }
 #else
 }  // namespace hipie (the part gemm_ln.hip uses ends inside it)
-#endif  // HIPIE_GEMM_LN_TU
+#endif  // HIPIE_GEMM_INCLUDED_TU

@@ -326,10 +326,13 @@ class Mlp(nn.Module):
     def forward(self, x):
         return self.fc2(self.act(self.fc1(x)))
 
-    def forward_split(self, h, resid):
+    def forward_split(self, h, resid, fp8x=()):
         """h (rows, 2C) HL8 -> resid + mlp(h), IN PLACE in the fp32 stream ``resid`` (rows, C): fc1 with the exact-erf GELU and the HL8
-        split in its epilogue, fc2 on that operand with the residual add in its epilogue."""
+        split in its epilogue, fc2 on that operand with the residual add in its epilogue.  ``fp8x``: the precision's f8x families -- with
+        "fc2" listed, fc2 runs on hipie_gemm_f8x (cross terms on block-scaled e4m3, Precision.fp8x)."""
         mid = ops.split_linear(h, self, "fc1", self.fc1.weight, self.fc1.bias, act=ops.ACT_GELU, out_fmt=ops.HL8, x_hl8=True, tag="gemm_fc1")
+        if "fc2" in fp8x:
+            return ops.f8x_linear(mid, self, "fc2", self.fc2.weight, self.fc2.bias, resid=resid, out=resid)
         return ops.split_linear(mid, self, "fc2", self.fc2.weight, self.fc2.bias, x_hl8=True, tag="gemm_fc2", resid=resid, out=resid)
 
 
@@ -391,7 +394,7 @@ def _block_forward_split(self, x, delta):
         trim = not getattr(self.attn.precision, "vit_attn16", False)
         self.attn.forward_split(y, nwin, ws, ws, xs, out_row=out_src, tok2win=delta_row if trim else None)
     h = ops.add_layernorm(x, None, n2.weight, n2.bias, n2.eps, "hl8")[1]
-    self.mlp.forward_split(h.view(B * H * W, 2 * C), xs)
+    self.mlp.forward_split(h.view(B * H * W, 2 * C), xs, self.precision.fp8x_linears)
     return x, None
 
 

@@ -1399,6 +1399,97 @@ def split_linear(x, owner, key, weight, bias=None, act=ACT_NONE, out_fmt=F32, re
     return out
 
 
+
+# ---------------------------------------------------------------------------------------------------------------------
+# hipie_gemm_f8x: the split product with its two cross terms on block-scaled e4m3 (the opt-in `fp8x` policy; hipie_amd/fp8x.py is the exact
+# host emulation).  Weights in the f8x format: (N, 4K) uint8 rows of 128-byte k slices [hi fp16 | q8(lo) | q8(hi)] + (N, K/32, 2) E8M0 scales.
+@_timed("to_f8x")
+def to_f8x(x_hl8):
+    """HL8 rows (rows, 2K) fp16 on the device -> (q (rows, 2K) uint8: per 32-element block [q8(hi) | q8(lo)] e4m3, scale (rows, K/32, 2) uint8
+    E8M0 [hi, lo]) with the quantiser hipie_gemm_f8x applies to its activations (hipie_to_f8x)."""
+    lib = _lib.load()
+    if x_hl8.dtype != torch.float16 or not x_hl8.is_cuda or x_hl8.shape[-1] % 64:
+        raise RuntimeError("to_f8x: HL8 rows (fp16, 2K columns with K a multiple of 32) on the device")
+    x2 = x_hl8.reshape(-1, x_hl8.shape[-1])
+    if x2.stride(-1) != 1:
+        x2 = x2.contiguous()
+    R, K = x2.shape[0], x2.shape[1] // 2
+    q = torch.empty(R, 2 * K, dtype=torch.uint8, device=x_hl8.device)
+    sc = torch.empty(R, K // 32, 2, dtype=torch.uint8, device=x_hl8.device)
+    rc = lib.hipie_to_f8x(x2.data_ptr(), x2.stride(0), q.data_ptr(), 2 * K, sc.data_ptr(), R, K, _stream())
+    _lib.check(rc, "hipie_to_f8x")
+    return q, sc
+
+
+def f8x_weight(owner, key, params, weight_fn, bias_fn=None):
+    """the f8x copy of a weight (N, K) -> ((Np, 4K) uint8, scales (Np, K/32, 2) uint8, bias (Np,) f32 | None, N): the HL8 split of split_weight,
+    quantised on the device by hipie_to_f8x and laid out as hipie_gemm_f8x reads it.  Cached on ``owner`` under ``key`` and invalidated by
+    (data_ptr, version) of ``params`` exactly as split_weight."""
+    from . import fp8x
+    ver = tuple((q.data_ptr(), q._version, str(q.device)) for q in params)
+    cache = owner.__dict__.setdefault("_f8x_cache", {})
+    e = cache.get(key)
+    if e is None or e[0] != ver:
+        w = weight_fn().detach().float()
+        b = None if bias_fn is None else bias_fn()
+        b = None if b is None else b.detach().float()
+        N = w.shape[0]
+        Np = (N + 7) // 8 * 8
+        if Np != N:
+            w = torch.nn.functional.pad(w, (0, 0, 0, Np - N))
+            b = None if b is None else torch.nn.functional.pad(b, (0, Np - N))
+        w_hl8 = hl8_pack(w)
+        q, sc = to_f8x(w_hl8) if w_hl8.is_cuda else (None, None)
+        w8, wsc = fp8x.pack_from_hl8(w_hl8, q, sc)
+        e = (ver, w8, wsc, None if b is None else b.contiguous(), N)
+        cache[key] = e
+    return e[1], e[2], e[3], e[4]
+
+
+@_timed("gemm_f8x")
+def gemm_f8x(a, w8, wsc, bias=None, resid=None, out_fmt=F32, act=ACT_NONE, alpha=1.0, oscale=1.0, out=None, out_row=None, out_rows=None):
+    """ops.gemm's split form with the cross terms on block-scaled e4m3 (hipie_gemm_f8x): a (..., 2K) HL8 rows against the f8x weight
+    (w8 (N, 4K) uint8, wsc (N, K/32, 2) uint8, from f8x_weight or fp8x.pack_weight); epilogue, output formats and row maps as ops.gemm."""
+    lib = _lib.load()
+    if a.dtype != torch.float16 or w8.dtype != torch.uint8 or wsc.dtype != torch.uint8 or not a.is_cuda:
+        raise RuntimeError("gemm_f8x: a HL8 (fp16) rows, w8 / wsc uint8, on the device")
+    N, K = w8.shape[0], w8.shape[1] // 4
+    a2 = a if a.dim() == 2 else a.reshape(-1, a.shape[-1])
+    if a2.stride(-1) != 1 or a2.shape[-1] != 2 * K or not w8.is_contiguous() or tuple(wsc.shape) != (N, K // 32, 2) or not wsc.is_contiguous():
+        raise RuntimeError("gemm_f8x: a rows %s against an f8x weight %s / scales %s" % (tuple(a.shape), tuple(w8.shape), tuple(wsc.shape)))
+    M = a2.shape[0]
+    lead = a.shape[:-1]
+    if out_row is not None:
+        if out is None:
+            lead = (int(out_rows),)
+        if out_row.dtype != torch.int32 or out_row.numel() != M or not out_row.is_contiguous():
+            raise RuntimeError("gemm_f8x: out_row must be a contiguous int32 vector with one entry per row of a")
+    if out is None:
+        dt, width = {F32: (torch.float32, N), F16: (torch.float16, N), HL8: (torch.float16, 2 * N)}[out_fmt]
+        out = torch.empty(*lead, width, dtype=dt, device=a.device)
+    o2 = out.reshape(-1, out.shape[-1])
+    r2 = None
+    if resid is not None:
+        r2 = resid.reshape(-1, N)
+        if r2.dtype != torch.float32 or r2.stride(-1) != 1:
+            raise RuntimeError("gemm_f8x: resid must be fp32 with contiguous rows")
+    if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous()):
+        raise RuntimeError("gemm_f8x: bias must be contiguous fp32")
+    rc = lib.hipie_gemm_f8x(a2.data_ptr(), a2.stride(0), _chk(w8, "w8"), 2 * K, _chk(wsc, "wsc"), None if bias is None else bias.data_ptr(),
+                            None if r2 is None else r2.data_ptr(), 0 if r2 is None else r2.stride(0), o2.data_ptr(), o2.stride(0),
+                            None if out_row is None else out_row.data_ptr(), M, N, K, HL8, int(out_fmt), int(act), float(alpha), float(oscale), _stream())
+    _lib.check(rc, "hipie_gemm_f8x")
+    return out
+
+
+def f8x_linear(x_hl8, owner, key, weight, bias=None, act=ACT_NONE, out_fmt=F32, resid=None, out=None):
+    """split_linear (HL8 input) on hipie_gemm_f8x: the weight's f8x copy is cached on ``owner`` under ``key``"""
+    params = [weight] + ([bias] if bias is not None else [])
+    w8, wsc, b, N = f8x_weight(owner, key, params, lambda: weight, (lambda: bias) if bias is not None else None)
+    if N != w8.shape[0]:
+        raise RuntimeError("f8x_linear: N %% 8 == 0 expected (got %d)" % N)
+    return gemm_f8x(x_hl8, w8, wsc, b, resid, out_fmt=out_fmt, act=act, out=out)
+
 def split_linear_ln_ok(x, weight, norm_weight):
     """the fused projection + residual LayerNorm (hipie_gemm_ln) applies: 256 output features = one column tile, split-able K."""
     return (x.is_cuda and weight.dtype == torch.float32 and weight.shape[0] == 256 and norm_weight.numel() == 256 and weight.shape[1] % 32 == 0

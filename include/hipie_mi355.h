@@ -447,6 +447,35 @@ int hipie_gemm(const void* A, int64_t lda, const void* W, int64_t ldw, const flo
                float oscale, void* stream);
 
 /*
+ * hipie_gemm (HIPIE_HL8 activations) with the two CROSS terms on block-scaled FP8 -- the opt-in `fp8x` precision policy:
+ *     acc = W_hi . A_hi  +  q8(W_lo) . q8(A_hi)  +  q8(W_hi) . q8(A_lo)          fp32 accumulation
+ * q8 = OCP e4m3 with one power-of-two (E8M0) scale per 32 k-elements: e = the largest integer with amax * 2^e <= 448 over the block (amax = 0:
+ * e = 0, clamped to [-127, 127]), code = RNE e4m3fn(v * 2^e), scale byte = 127 - e (hipie_amd/fp8x.py is the exact host emulation).  The
+ * cross terms run on v_mfma_scale_f32_32x32x64_f8f6f4 (e4m3 at twice the fp16 rate): 2 + 2 fp16-equivalent MFMA passes per 32 k instead of 6
+ * (the 256 x 256 tile of hipie_gemm's kernel: the 320-column one does not fit the register file with the e4m3 operands beside it).
+ * ~1e-5 relative against the exact product (three-product form: ~6e-7).  Replaces, under that policy, Mlp.fc2 of the ViT blocks
+ * (hipie/backbone/vit.py:193-197), which the reference runs in fp32.
+ *   A        HL8 rows as hipie_gemm's (in_fmt must be HIPIE_HL8); A's q8 is formed in the kernel, in registers
+ *   W        the f8x weight format, (N, 2K) in fp16 units: each 32-element k slice of a row is 128 bytes, hi fp16 [64 B] then the e4m3
+ *            codes [64 B] in the scaled MFMA's lane order, 8 bytes per (part, 8-group g):  lo g0, lo g2, hi g0, hi g2, lo g1, lo g3, hi g1, hi g3
+ *            (hi, lo = the HL8 split of the fp32 weight; lo / hi here = q8(W_lo) / q8(W_hi); hipie_amd/fp8x.py pack_from_hl8)
+ *   w_scale  (N, K/32, 2) uint8 E8M0 scales of the [lo, hi] e4m3 parts (contiguous)
+ *   the rest as hipie_gemm: ldw >= 2K fp16 elements, K a multiple of 32, N of 8; bias, resid, epilogue, out_fmt, out_row (resid may alias out).
+ * All pointers but w_scale 16-byte aligned.  Deterministic (fixed accumulation order).
+ */
+int hipie_gemm_f8x(const void* A, int64_t lda, const void* W, int64_t ldw, const void* w_scale, const float* bias, const float* resid,
+                   int64_t ldr, void* out, int64_t ldo, const int32_t* out_row, int M, int N, int K, int in_fmt, int out_fmt, int act,
+                   float alpha, float oscale, void* stream);
+
+/*
+ * HL8 rows -> q8 of their hi and lo parts with the device function hipie_gemm_f8x quantises its activations with (bit for bit the same codes):
+ * x (rows, 2K) fp16 HL8, row stride ldx fp16 elements;  out (rows, 2K) bytes, row stride ldo BYTES (multiple of 16): per 32-element k block
+ * [q8(hi) e4m3 32 B | q8(lo) e4m3 32 B];  scale (rows, K/32, 2) uint8 E8M0 [hi, lo], contiguous.  K a multiple of 32.  The weight packing of the
+ * `fp8x` policy runs on it (hipie_amd/ops.py f8x_weight).
+ */
+int hipie_to_f8x(const void* x, int64_t ldx, void* out, int64_t ldo, void* scale, int64_t rows, int K, void* stream);
+
+/*
  * hipie_gemm (split operands, N = 256) with the post-norm residual LayerNorm of the deformable encoder layer in its epilogue:
  *     y = LayerNorm_256( resid + alpha * A . W^T + bias ) * gamma + beta;   out = y as fp32 rows;  out_hl8 (or NULL) = y as HIPIE_HL8 rows
  * Replaces `src = norm1(src + dropout1(output_proj(msda)))` (models/deformable_detr/deformable_transformer_dino.py:387-389 with
