@@ -13,7 +13,7 @@ from collections import OrderedDict
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, derived
 from .config import HipieConfig, Precision
 from .modeling.ddetrs_dn import DDETRSegmUniDN
 from .modeling.text import BertEncoder
@@ -111,9 +111,7 @@ class HIPIE_IMG(nn.Module):
             # MIOpen "find": benchmark the applicable solvers once per convolution configuration instead of the
             # immediate-mode heuristic (the shapes are static over an evaluation run); -7 ms per bs-8 ViT-H step
             torch.backends.cudnn.benchmark = True
-        for m in self.modules():                       # per-geometry caches that fold (now final) parameters
-            if hasattr(m, "_own_cache"):
-                m._own_cache.clear()
+        derived.clear(self)                            # values folded from the (now final) parameters
         bb = self.detr.detr.backbone[0].backbone
         if hasattr(bb, "cast_weights"):
             bb.cast_weights()

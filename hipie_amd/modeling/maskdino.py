@@ -6,7 +6,6 @@ transformer_decoder/maskdino_decoder.py (MaskDINODecoder, eval path), transforme
 (TransformerDecoder) and meta_arch/maskdino_head.py (MaskDINOHead) with the reference's parameter names.
 The branch is called with mask=None (ddetrs_dn.py:885): all-False padding masks, valid_ratio 1.
 """
-import collections
 import os
 
 import torch
@@ -14,7 +13,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
-from .transformer import (MLP, _select_topk, DeformableTransformerDecoderLayer, DeformableTransformerEncoderLayer, FeatureResizer, geo_cached,
+from .transformer import (MLP, _select_topk, DeformableTransformerDecoderLayer, DeformableTransformerEncoderLayer, FeatureResizer, geo_cached, level_pos_flat,
                           PConv2d, PGroupNorm, PLayerNorm, PLinear, PositionEmbeddingSine, _get_clones, encoder_reference_points,
                           gen_encoder_output_proposals, level_tensors,
                           batched_decoder_values, decoder_box_refine, decoder_split_values, selected_proposal_boxes, decoder_fast_path, decoder_query_pos)
@@ -72,11 +71,7 @@ class MSDeformAttnTransformerEncoderOnly(nn.Module):
         B = src.shape[0]
         # all-valid masks: the geometry is (batch, level shapes) alone
         gk = ("md_enc", B, tuple(shapes_list), str(src.device), src.dtype)
-        if not hasattr(self, "_own_cache"):
-            self._own_cache = collections.OrderedDict()
-        pos = geo_cached(gk, "pos_flat", lambda: torch.cat(
-            [p.flatten(2).transpose(1, 2) + self.level_embed[i].view(1, 1, -1) for i, p in enumerate(pos_embeds)], 1).to(src.dtype),
-            store=self._own_cache)
+        pos = level_pos_flat(self, pos_embeds, src.dtype, gk)
         spatial_shapes, level_start_index = level_tensors(shapes_list, src.device)
         refs = geo_cached(gk, "enc_refs", lambda: encoder_reference_points(
             shapes_list, torch.ones(B, len(srcs), 2, device=src.device), src.device))

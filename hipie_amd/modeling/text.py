@@ -9,6 +9,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
+from ..derived import stamp
 
 
 class BertSelfAttention(nn.Module):
@@ -101,7 +102,7 @@ class BertModel(nn.Module):
         self.embeddings = BertEmbeddings(cfg.bert_vocab, cfg.bert_hidden, cfg.bert_max_pos)
         self.encoder = BertLayers(cfg)
         self.compute_dtype = torch.float32
-        self._fused = None
+        self._fused = self._fused_stamp = None
 
     def set_compute_dtype(self, dtype):
         """cast the GEMM weights (norms and embeddings stay fp32) and build the fused QKV weights; call after loading."""
@@ -118,18 +119,18 @@ class BertModel(nn.Module):
                 lin.weight.data = lin.weight.data.to(dtype)
                 lin.bias.data = lin.bias.data.to(dtype)
         self._fused = fused
-        self._fused_key = self._qkv_versions()
+        self._fused_stamp = self._qkv_stamp()
         return self
 
-    def _qkv_versions(self):
+    def _qkv_stamp(self):
         ps = []
         for layer in self.encoder.layer:
             at = layer.attention.self
             ps += [at.query.weight, at.key.weight, at.value.weight, at.query.bias, at.key.bias, at.value.bias]
-        return tuple((q.data_ptr(), q._version) for q in ps)
+        return stamp(ps)
 
     def _forward16(self, input_ids, attention_mask):
-        if self._fused is None or getattr(self, "_fused_key", None) != self._qkv_versions():
+        if self._fused is None or self._fused_stamp != self._qkv_stamp():
             # a sub-module load_state_dict / in-place update after finalize(): rebuild the fused 16-bit QKV weights (the other dense
             # layers are cast in place by set_compute_dtype, which a load into fp16 parameters preserves)
             self.set_compute_dtype(self.compute_dtype)

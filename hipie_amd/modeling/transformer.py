@@ -20,14 +20,19 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
+from ..derived import derived
 
 
 # --------------------------------------------------------------------------- policy-aware primitives
-def _lin(owner, key, x, w, b, act=ops.ACT_NONE, out_fmt=ops.F32, x_hl8=False):
+def _lin(owner, key, x, w, b, act=ops.ACT_NONE, out_fmt=ops.F32, x_hl8=False, rows=None):
     """F.linear(x, w, b) in the weight's dtype -- or, when ``owner.split`` is set (Precision.split3: set_split below), the same product
-    at fp32-class accuracy on hipie_gemm's split-fp16 operands (the HL8 copy of ``w`` is cached on ``owner`` under ``key``)."""
+    at fp32-class accuracy on hipie_gemm's split-fp16 operands (the HL8 copy of ``w`` is cached on ``owner`` under ``key``).
+    ``rows``: the slice of output features to compute; ``w`` / ``b`` stay the whole parameters, which is what the cache watches."""
     if getattr(owner, "split", False) and x.is_cuda and w.dtype == torch.float32 and ops.split_ok(w.shape[1] if not x_hl8 else w.shape[1]):
-        return ops.split_linear(x, owner, key, w, b, act=act, out_fmt=out_fmt, x_hl8=x_hl8)
+        fns = {} if rows is None else dict(weight_fn=lambda: w[rows], bias_fn=lambda: b[rows])
+        return ops.split_linear(x, owner, key, w, b, act=act, out_fmt=out_fmt, x_hl8=x_hl8, **fns)
+    if rows is not None:
+        w, b = w[rows], b[rows]
     y = F.linear(x.to(w.dtype), w, b)
     return F.relu(y) if act == ops.ACT_RELU else y
 
@@ -186,25 +191,33 @@ class FeatureResizer(nn.Module):
 _GEO_CACHE = collections.OrderedDict()
 
 
-def geo_cached(geo_key, what, build, store=None):
+def geo_cached(geo_key, what, build):
     """Everything that depends only on the padding masks -- level masks, sine position embeddings, valid ratios, encoder
     reference points, two-stage proposals -- is a function of the batch geometry (image sizes + padded canvas).  An
     evaluation run repeats a handful of geometries, so these are computed once per geometry and reused (read-only)
     instead of re-issuing a few hundred tiny cumsum / sin / cos / sum / cat kernels per forward.  geo_key None: no caching.
-    ``store``: a module-owned OrderedDict for values that also depend on that module's (frozen) parameters."""
+    Values that also depend on parameters go through ``derived`` (level_pos_flat)."""
     if geo_key is None:
         return build()
-    cache = _GEO_CACHE if store is None else store
+    cache = _GEO_CACHE
     key = (geo_key, what)
     v = cache.get(key)
     if v is None:
         v = build()
         cache[key] = v
-        if len(cache) > (512 if store is None else 32):
+        if len(cache) > 512:
             cache.popitem(last=False)
     else:
         cache.move_to_end(key)
     return v
+
+
+def level_pos_flat(enc, pos_embeds, dtype, geo_key):
+    """position + level embedding of all pyramid levels, flattened to (B, tokens, C) in ``dtype``: a function of the geometry AND of
+    enc.level_embed, so it is cached on ``enc`` per level_embed stamp with up to 32 geometries alive.  geo_key None: no caching."""
+    def build():
+        return torch.cat([p.flatten(2).transpose(1, 2) + enc.level_embed[i].view(1, 1, -1) for i, p in enumerate(pos_embeds)], 1).to(dtype)
+    return build() if geo_key is None else derived(enc, "pos_flat", [enc.level_embed], build, extra=geo_key, keep=32)
 
 
 class NestedTensor(object):
@@ -348,11 +361,8 @@ class MSDeformAttn(nn.Module):
 
     def _fused_proj(self):
         so, aw = self.sampling_offsets, self.attention_weights
-        key = tuple((p.data_ptr(), p._version, p.dtype) for p in (so.weight, aw.weight, so.bias, aw.bias))
-        if getattr(self, "_fp_key", None) != key:
-            self._fp = (torch.cat([so.weight, aw.weight], 0).contiguous(), torch.cat([so.bias, aw.bias], 0).contiguous())
-            self._fp_key = key
-        return self._fp
+        return derived(self, "fused_proj", (so.weight, aw.weight, so.bias, aw.bias), lambda: (
+            torch.cat([so.weight, aw.weight], 0).contiguous(), torch.cat([so.bias, aw.bias], 0).contiguous()))
 
 
 # --------------------------------------------------------------------------- VL fusion
@@ -467,20 +477,13 @@ class BiMultiHeadAttention(nn.Module):
 
     def _scaled_out(self, gamma):
         p = self.out_v_proj
-        key = tuple((t.data_ptr(), t._version, t.dtype) for t in (p.weight, p.bias, gamma))
-        if getattr(self, "_so_key", None) != key:
-            g = gamma.float()
-            self._so = ((p.weight.float() * g[:, None]).to(p.weight.dtype), (p.bias.float() * g).to(p.bias.dtype))
-            self._so_key = key
-        return self._so
+        return derived(self, "scaled_out", (p.weight, p.bias, gamma), lambda: (
+            (p.weight.float() * gamma.float()[:, None]).to(p.weight.dtype), (p.bias.float() * gamma.float()).to(p.bias.dtype)))
 
     def _scaled_q(self):
         p = self.v_proj
-        key = tuple((t.data_ptr(), t._version, t.dtype) for t in (p.weight, p.bias))
-        if getattr(self, "_sq_key", None) != key:
-            self._sq = ((p.weight.float() * self.scale).to(p.weight.dtype), (p.bias.float() * self.scale).to(p.bias.dtype))
-            self._sq_key = key
-        return self._sq
+        return derived(self, "scaled_q", (p.weight, p.bias), lambda: (
+            (p.weight.float() * self.scale).to(p.weight.dtype), (p.bias.float() * self.scale).to(p.bias.dtype)))
 
 
 class BiAttentionBlockForCheckpoint(nn.Module):
@@ -578,10 +581,7 @@ def _enc_layer_forward_split(self, src, pos, reference_points, spatial_shapes, l
 
 def _pos_hl8(layer, pos):
     """HL8 copy of the position embedding, cached on the layer: a per-geometry constant"""
-    key = (pos.data_ptr(), pos._version, tuple(pos.shape))
-    if getattr(layer, "_pos_h_key", None) != key:
-        layer._pos_h, layer._pos_h_key = ops.to_hl8(pos.contiguous()), key
-    return layer._pos_h
+    return derived(layer, "pos_hl8", [pos], lambda: ops.to_hl8(pos.contiguous()))
 
 
 DeformableTransformerEncoderLayer._forward_split = _enc_layer_forward_split
@@ -647,12 +647,12 @@ class MultiheadAttention(nn.Module):
         if split and x_qk.is_cuda and w.dtype == torch.float32 and ops.attn_f32_ok(hd):
             # split policy: fp32 projections (split GEMM) and the fp32-CLASS attention core (hipie_attn_split) -- the query self-attention is 0.1 % of the
             # step's flops, and fp16 q / k / v here cost 5e-4 .. 1e-3 on the decoder states at the headline configuration
-            qk = _lin(self, "in_qk", x_qk, w[:2 * C], b[:2 * C]).view(B, N, 2, self.n_heads, hd)
-            v = _lin(self, "in_v", x_v, w[2 * C:], b[2 * C:]).view(B, N, self.n_heads, hd)
+            qk = _lin(self, "in_qk", x_qk, w, b, rows=slice(0, 2 * C)).view(B, N, 2, self.n_heads, hd)
+            v = _lin(self, "in_v", x_v, w, b, rows=slice(2 * C, None)).view(B, N, self.n_heads, hd)
             return self.out_proj(ops.attn_split(qk[:, :, 0], qk[:, :, 1], v, hd ** -0.5))
         of = ops.F16 if (split and self.attn_dtype == torch.float16) else ops.F32
-        qk = _lin(self, "in_qk", x_qk, w[:2 * C], b[:2 * C], out_fmt=of).to(self.attn_dtype).view(B, N, 2, self.n_heads, hd)
-        v = _lin(self, "in_v", x_v, w[2 * C:], b[2 * C:], out_fmt=of).to(self.attn_dtype).view(B, N, self.n_heads, hd)
+        qk = _lin(self, "in_qk", x_qk, w, b, out_fmt=of, rows=slice(0, 2 * C)).to(self.attn_dtype).view(B, N, 2, self.n_heads, hd)
+        v = _lin(self, "in_v", x_v, w, b, out_fmt=of, rows=slice(2 * C, None)).to(self.attn_dtype).view(B, N, self.n_heads, hd)
         o = ops.flash_attn(qk[:, :, 0], qk[:, :, 1], v, hd ** -0.5, out_f32=split)   # strided q / k views of one GEMM output
         return self.out_proj(o)
 
@@ -719,11 +719,8 @@ def batched_decoder_values(owner, layers, src, padding_mask=None):
     """value projections of ALL decoder layers as one GEMM on the concatenated weights (they read the same memory); returns
     the per-layer (N, S, heads, hd) column blocks (views: hipie_msda samples them in place)."""
     ps = [l.cross_attn.value_proj for l in layers]
-    key = tuple((p.weight.data_ptr(), p.weight._version, p.weight.dtype) for p in ps)
-    if getattr(owner, "_bv_key", None) != key:
-        owner._bv = (torch.cat([p.weight for p in ps], 0).contiguous(), torch.cat([p.bias for p in ps], 0).contiguous())
-        owner._bv_key = key
-    w, b = owner._bv
+    w, b = derived(owner, "bv", [t for p in ps for t in (p.weight, p.bias)], lambda: (
+        torch.cat([p.weight for p in ps], 0).contiguous(), torch.cat([p.bias for p in ps], 0).contiguous()))
     v = _lin(owner, "bv", src, w, b)           # split policy: ONE thin-K split GEMM (N = layers x 256) instead of one 256-column GEMM per layer
     if padding_mask is not None:
         v.masked_fill_(padding_mask[..., None], 0.0)
@@ -904,11 +901,7 @@ class DeformableTransformerVLDINO(nn.Module):
         gk = None if geo_key is None else (geo_key, tuple(shapes_list), src.dtype)
         mask = geo_cached(gk, "mask_flat", lambda: torch.cat([m.flatten(1) for m in masks], 1))
         # position + level embedding, one cast (src + pos would promote per layer); constant per geometry at inference
-        if not hasattr(self, "_own_cache"):
-            self._own_cache = collections.OrderedDict()
-        pos = geo_cached(gk, "pos_flat", lambda: torch.cat(
-            [p.flatten(2).transpose(1, 2) + self.level_embed[i].view(1, 1, -1) for i, p in enumerate(pos_embeds)], 1).to(src.dtype),
-            store=self._own_cache)
+        pos = level_pos_flat(self, pos_embeds, src.dtype, gk)
         spatial_shapes, level_start_index = level_tensors(shapes_list, src.device)
         valid_ratios = geo_cached(gk, "valid_ratios", lambda: torch.stack([get_valid_ratio(m) for m in masks], 1))
 

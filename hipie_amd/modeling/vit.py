@@ -12,6 +12,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
+from ..derived import derived, stamp
 
 
 def get_rel_pos(q_size, k_size, rel_pos):
@@ -241,12 +242,10 @@ class Attention(nn.Module):
             # zero lo half for the projection GEMM)
             qkv16 = ops.split_linear(y, self, "qkv", self.qkv.weight, self.qkv.bias, out_fmt=ops.F16, x_hl8=True, weight_fn=wq, bias_fn=bq,
                                      tag="gemm_qkv")
-            key = (H, W, "f16", self._versions())
-            if getattr(self, "_tabs16_key", None) != key:
-                self._tabs16 = ((resize_rel_pos(H, self.rel_pos_h.detach().float()) / self.scale).half().contiguous(),
-                                (resize_rel_pos(W, self.rel_pos_w.detach().float()) / self.scale).half().contiguous())
-                self._tabs16_key = key
-            o16 = ops.vit_attn_rel(qkv16.view(B, H * W, 3 * C), self._tabs16[0], self._tabs16[1], (H, W), nh, fast=True)
+            th, tw = derived(self, "tabs16", self._params(), lambda: (
+                (resize_rel_pos(H, self.rel_pos_h.float()) / self.scale).half().contiguous(),
+                (resize_rel_pos(W, self.rel_pos_w.float()) / self.scale).half().contiguous()), extra=(H, W))
+            o16 = ops.vit_attn_rel(qkv16.view(B, H * W, 3 * C), th, tw, (H, W), nh, fast=True)
             o = ops.to_hl8(o16.view(B * H * W, C))
             return ops.split_linear(o, self, "proj", self.proj.weight, self.proj.bias, x_hl8=True, tag="gemm_proj",
                                     resid=resid, out=resid, out_row=out_row)
@@ -256,62 +255,52 @@ class Attention(nn.Module):
             # padding rows are filled with the HL8 bias row
             rows = y.shape[0]
             w_, b_, _ = ops.split_weight(self, "qkv", [self.qkv.weight, self.qkv.bias], wq, bq)
-            ver = self._versions()
-            if getattr(self, "_bias_hl8_key", None) != ver:
-                self._bias_hl8, self._bias_hl8_key = ops.to_hl8(b_.view(1, -1)).view(-1), ver
+            bias_hl8 = derived(self, "bias_hl8", self._params(), lambda: ops.to_hl8(b_.view(1, -1)).view(-1))
             # the window-layout qkv buffer with the bias in its padding rows: per block while the process-wide budget allows (padding
             # written once), else one shared scratch buffer refilled per block (QKV_BUFFERS)
-            qkv = QKV_BUFFERS.get(self, rows, 6 * C, y.device, window_pad_rows(out_row), self._bias_hl8, ver)
+            qkv = QKV_BUFFERS.get(self, rows, 6 * C, y.device, window_pad_rows(out_row), bias_hl8, stamp(self._params()))
             ops.split_linear(y, self, "qkv", self.qkv.weight, self.qkv.bias, out_fmt=ops.HL8, x_hl8=True, weight_fn=wq, bias_fn=bq,
                              tag="gemm_qkv", out=qkv, out_row=tok2win, a_row=tok2win)
         else:
             qkv = ops.split_linear(y, self, "qkv", self.qkv.weight, self.qkv.bias, out_fmt=ops.HL8, x_hl8=True, weight_fn=wq, bias_fn=bq,
                                    tag="gemm_qkv")
-        key = (H, W, self._versions())
-        if getattr(self, "_tabs_key", None) != key:
-            self._tabs = (ops.hl8_pack(resize_rel_pos(H, self.rel_pos_h.detach().float()) / self.scale),
-                          ops.hl8_pack(resize_rel_pos(W, self.rel_pos_w.detach().float()) / self.scale))
-            self._tabs_key = key
-        o = ops.vit_attn_split(qkv.view(B, H * W, 6 * C), self._tabs[0], self._tabs[1], (H, W), nh)
+        th, tw = derived(self, "tabs", self._params(), lambda: (
+            ops.hl8_pack(resize_rel_pos(H, self.rel_pos_h.float()) / self.scale),
+            ops.hl8_pack(resize_rel_pos(W, self.rel_pos_w.float()) / self.scale)), extra=(H, W))
+        o = ops.vit_attn_split(qkv.view(B, H * W, 6 * C), th, tw, (H, W), nh)
         if tok2win is not None:          # the projection reads the real tokens' rows out of the window layout and writes token order
             return ops.split_linear(o.view(B * H * W, 2 * C), self, "proj", self.proj.weight, self.proj.bias, x_hl8=True, tag="gemm_proj",
                                     resid=resid, out=resid, a_row=tok2win)
         return ops.split_linear(o.view(B * H * W, 2 * C), self, "proj", self.proj.weight, self.proj.bias, x_hl8=True, tag="gemm_proj",
                                 resid=resid, out=resid, out_row=out_row)
 
-    def _versions(self):
-        ps = (self.qkv.weight, self.qkv.bias, self.rel_pos_h, self.rel_pos_w)
-        return tuple((p.data_ptr(), p._version, p.dtype, str(p.device)) for p in ps)
+    def _params(self):
+        """what the folded qkv weights and the rel-pos tables are derived from"""
+        return (self.qkv.weight, self.qkv.bias, self.rel_pos_h, self.rel_pos_w)
 
     def _folded(self, H, W):
         """(qkv weight, bias) with the q rows multiplied by scale*log2(e) and the two rel-pos tables (re-interpolated to
         2*size-1 rows, get_rel_pos utils.py:63-86) divided by scale, rounded ONCE to the GEMM / attention dtypes.  Cached per
-        token grid; the key carries the parameters' version counters, so load_state_dict / .to() invalidate it."""
-        key = (H, W, self.precision.attn, self._versions())
-        if getattr(self, "_fold_key", None) != key:
+        token grid and parameter stamp (derived), so load_state_dict / .to() invalidate it."""
+        def build():
             C = self.qkv.weight.shape[1]
             c1 = self.scale * ops.LOG2E
-            w = self.qkv.weight.detach().float().clone()
-            b = self.qkv.bias.detach().float().clone()
+            w = self.qkv.weight.float().clone()
+            b = self.qkv.bias.float().clone()
             w[:C] *= c1
             b[:C] *= c1
             gd = self.qkv.weight.dtype
-            th = (resize_rel_pos(H, self.rel_pos_h.detach().float()) / self.scale).to(self.precision.attn).contiguous()
-            tw = (resize_rel_pos(W, self.rel_pos_w.detach().float()) / self.scale).to(self.precision.attn).contiguous()
-            self._fold = (w.to(gd).contiguous(), b.to(gd).contiguous(), th, tw)
-            self._fold_key = key
-        return self._fold
-
+            th = (resize_rel_pos(H, self.rel_pos_h.float()) / self.scale).to(self.precision.attn).contiguous()
+            tw = (resize_rel_pos(W, self.rel_pos_w.float()) / self.scale).to(self.precision.attn).contiguous()
+            return w.to(gd).contiguous(), b.to(gd).contiguous(), th, tw
+        return derived(self, "fold", self._params(), build, extra=(H, W, self.precision.attn))
 
     def _rel_tables(self, H, W):
         """rel_pos_h / rel_pos_w linearly re-interpolated to 2*size-1 rows when needed (get_rel_pos, utils.py:63-86), in the
         attention operand dtype, cached per token grid.  Entry [hq - hk + H - 1] is Rh[hq, hk] (:88-93)."""
-        key = (H, W, self.precision.attn, self._versions())
-        if getattr(self, "_rel_key", None) != key:
-            self._rel_cache = (resize_rel_pos(H, self.rel_pos_h.float()).to(self.precision.attn).contiguous(),
-                               resize_rel_pos(W, self.rel_pos_w.float()).to(self.precision.attn).contiguous())
-            self._rel_key = key
-        return self._rel_cache
+        return derived(self, "rel", self._params(), lambda: (
+            resize_rel_pos(H, self.rel_pos_h.float()).to(self.precision.attn).contiguous(),
+            resize_rel_pos(W, self.rel_pos_w.float()).to(self.precision.attn).contiguous()), extra=(H, W, self.precision.attn))
 
 
 class Mlp(nn.Module):
@@ -451,11 +440,7 @@ class ViT(nn.Module):
 
     def _abs_pos(self, hw):
         """bicubic-resized absolute position table, cached per token grid (weights are frozen at inference)."""
-        key = (hw, self.pos_embed.data_ptr(), self.pos_embed._version, str(self.pos_embed.device))
-        if getattr(self, "_abs_pos_key", None) != key:
-            self._abs_pos_cache = get_abs_pos(self.pos_embed.float(), True, hw)
-            self._abs_pos_key = key
-        return self._abs_pos_cache
+        return derived(self, "abs_pos", [self.pos_embed], lambda: get_abs_pos(self.pos_embed.float(), True, hw), extra=hw)
 
     def cast_weights(self):
         """put the GEMM/conv weights in the policy dtype (norms, pos tables stay fp32)."""

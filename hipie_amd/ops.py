@@ -7,6 +7,7 @@ tensors raise "Not implemented on the CPU", ops/src/ms_deform_attn.h:28-39).  Al
 import torch
 
 from . import _lib
+from .derived import derived
 
 _DT = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 F32, F16, BF16, HL8 = 0, 1, 2, 4          # include/hipie_mi355.h: HIPIE_F32 / F16 / BF16 / HL8
@@ -908,13 +909,9 @@ def sine_embed(ref, num_pos_feats=128, temperature=10000, out_dtype=torch.float3
 
 
 def _transposed(mod_layers, dtype=None):
-    """(in, out) copies of the Linear weights of a small MLP head + its biases, cached on the parameters' versions."""
-    owner = mod_layers[0]
-    key = tuple((l.weight.data_ptr(), l.weight._version, l.weight.dtype, l.bias._version) for l in mod_layers)
-    if getattr(owner, "_wt_key", None) != key:
-        owner._wt = [(l.weight.t().contiguous(), l.bias.contiguous()) for l in mod_layers]
-        owner._wt_key = key
-    return owner._wt
+    """(in, out) copies of the Linear weights of a small MLP head + its biases, cached on the first layer (derived)."""
+    return derived(mod_layers[0], "wt", [p for l in mod_layers for p in (l.weight, l.bias)],
+                   lambda: [(l.weight.t().contiguous(), l.bias.contiguous()) for l in mod_layers])
 
 
 def ref_point_mlp_ok(ref, head):
@@ -1276,25 +1273,27 @@ def vit_attn_split_ok(grid_hw, hd):
 
 
 # ---- split ("fp32-class") linears: cached HL8 copies of (derived) weights + the GEMM call ----------------------------------
+def _padded_f32(weight_fn, bias_fn):
+    """(weight (Np, K), bias (Np,) | None, N) in fp32 from weight_fn / bias_fn, N padded to a multiple of 8 with zero rows"""
+    w = weight_fn().detach().float()
+    b = None if bias_fn is None else bias_fn()
+    b = None if b is None else b.detach().float()
+    N = w.shape[0]
+    Np = (N + 7) // 8 * 8
+    if Np != N:
+        w = torch.nn.functional.pad(w, (0, 0, 0, Np - N))
+        b = None if b is None else torch.nn.functional.pad(b, (0, Np - N))
+    return w, None if b is None else b.contiguous(), N
+
+
 def split_weight(owner, key, params, weight_fn, bias_fn=None):
     """HL8 copy of a weight (N, K) -> ((Np, 2K) fp16, bias (Np,) f32 | None, N), N padded to a multiple of 8 with zero rows.
-    Cached on ``owner`` under ``key``; the cache entry carries (data_ptr, version) of ``params``, so load_state_dict / .to() /
-    in-place updates invalidate it.  weight_fn / bias_fn build the (possibly folded / concatenated) fp32 tensors."""
-    ver = tuple((q.data_ptr(), q._version, str(q.device)) for q in params)
-    cache = owner.__dict__.setdefault("_hl8_cache", {})
-    e = cache.get(key)
-    if e is None or e[0] != ver:
-        w = weight_fn().detach().float()
-        b = None if bias_fn is None else bias_fn()
-        b = None if b is None else b.detach().float()
-        N = w.shape[0]
-        Np = (N + 7) // 8 * 8
-        if Np != N:
-            w = torch.nn.functional.pad(w, (0, 0, 0, Np - N))
-            b = None if b is None else torch.nn.functional.pad(b, (0, Np - N))
-        e = (ver, hl8_pack(w), None if b is None else b.contiguous(), N)
-        cache[key] = e
-    return e[1], e[2], e[3]
+    Cached on ``owner`` under ``key`` and rebuilt when ``params`` change (derived): load_state_dict / .to() / in-place updates
+    invalidate it.  weight_fn / bias_fn build the (possibly folded / concatenated) fp32 tensors."""
+    def build():
+        w, b, N = _padded_f32(weight_fn, bias_fn)
+        return hl8_pack(w), b, N
+    return derived(owner, ("hl8", key), params, build)
 
 
 def conv3x3_split_ok(x, conv):
@@ -1423,27 +1422,15 @@ def to_f8x(x_hl8):
 
 def f8x_weight(owner, key, params, weight_fn, bias_fn=None):
     """the f8x copy of a weight (N, K) -> ((Np, 4K) uint8, scales (Np, K/32, 2) uint8, bias (Np,) f32 | None, N): the HL8 split of split_weight,
-    quantised on the device by hipie_to_f8x and laid out as hipie_gemm_f8x reads it.  Cached on ``owner`` under ``key`` and invalidated by
-    (data_ptr, version) of ``params`` exactly as split_weight."""
-    from . import fp8x
-    ver = tuple((q.data_ptr(), q._version, str(q.device)) for q in params)
-    cache = owner.__dict__.setdefault("_f8x_cache", {})
-    e = cache.get(key)
-    if e is None or e[0] != ver:
-        w = weight_fn().detach().float()
-        b = None if bias_fn is None else bias_fn()
-        b = None if b is None else b.detach().float()
-        N = w.shape[0]
-        Np = (N + 7) // 8 * 8
-        if Np != N:
-            w = torch.nn.functional.pad(w, (0, 0, 0, Np - N))
-            b = None if b is None else torch.nn.functional.pad(b, (0, Np - N))
+    quantised on the device by hipie_to_f8x and laid out as hipie_gemm_f8x reads it.  Cached on ``owner`` under ``key`` exactly as split_weight."""
+    def build():
+        from . import fp8x
+        w, b, N = _padded_f32(weight_fn, bias_fn)
         w_hl8 = hl8_pack(w)
         q, sc = to_f8x(w_hl8) if w_hl8.is_cuda else (None, None)
         w8, wsc = fp8x.pack_from_hl8(w_hl8, q, sc)
-        e = (ver, w8, wsc, None if b is None else b.contiguous(), N)
-        cache[key] = e
-    return e[1], e[2], e[3], e[4]
+        return w8, wsc, b, N
+    return derived(owner, ("f8x", key), params, build)
 
 
 @_timed("gemm_f8x")

@@ -78,7 +78,8 @@ class SplitLinearFunction(torch.autograd.Function):
         dW = dy^T . x               split operands dy^T and x^T, the contraction over the M rows (padded to 32) cut into chunks that run as
                                     one hipie_gemm_batched launch (_weight_grad)
         db = sum_m dy
-    The two transposed operands cost one pass each; the HL8 copies of W and W^T are cached per parameter version on `owner`."""
+    The two transposed operands cost one pass each; the HL8 copies of W and W^T are cached on `owner` (ops.split_weight; the training net
+    passes the weight tensor itself, so they die with it)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, owner, key):

@@ -37,15 +37,13 @@ def level_tensors(shapes, device, which="int"):
 class HipBackend:
     """the operator kernels with a hand-written backward (libhipie_mi355.so); no host path"""
 
-    _owners = {}
-
-    @classmethod
-    def linear(cls, x, sd, p):
+    @staticmethod
+    def linear(x, sd, p):
         """the big linears (ViT qkv / proj / mlp, encoder FFN) on the split-fp16 GEMM, forward and backward (functions.SplitLinearFunction);
-        the HL8 weight copies are cached on one small owner object per parameter name"""
+        the HL8 copies of W and W^T are cached on the weight tensor itself, so they die with it"""
         from .functions import split_linear
-        owner = cls._owners.setdefault(p, type("_W", (), {})())
-        return split_linear(x, sd[p + "weight"], sd.get(p + "bias"), owner, "w")
+        w = sd[p + "weight"]
+        return split_linear(x, w, sd.get(p + "bias"), w, "w")
 
     @staticmethod
     def msda(value, shapes, loc, aw):

@@ -228,10 +228,12 @@ def test_geometry_cache_keys_and_eviction():
     c = T.geo_cached(("k", 2), "x", lambda: build("c"))           # other geometry
     d = T.geo_cached(None, "x", lambda: build("d"))               # no key: never cached
     assert calls == ["a", "c", "d"] and a is b and c is not a and d is not a
-    own = T.collections.OrderedDict()
+    enc = torch.nn.Module()                # values that also depend on a module's parameters: derived(), 32 geometries alive per module
+    enc.level_embed = torch.nn.Parameter(torch.zeros(1, 4))
     for i in range(40):
-        T.geo_cached(("own", i), "y", lambda: build("o"), store=own)
-    assert len(own) <= 33 and ("own", 39) in [k[0] for k in own]
+        T.level_pos_flat(enc, [torch.zeros(1, 4, 2, 2)], torch.float32, ("own", i))
+    own = enc.__dict__["_derived"]["pos_flat"]
+    assert len(own) <= 33 and ("own", 39) in own
     imgs = [torch.zeros(3, 40, 50), torch.zeros(3, 33, 64)]
     nt1 = T.nested_tensor_from_images(imgs)
     nt2 = T.nested_tensor_from_images([torch.ones(3, 40, 50), torch.ones(3, 33, 64)])
