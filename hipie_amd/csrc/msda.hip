@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) void msda_d32_kernel(const T* __restrict__ val
   //          and a corner instruction of a coarse level touches 2-5 distinct lines instead of 8.
   //   map 2  (queries are the pyramid's own pixels, Lq == S, and every level is a multiple of 4 rows x 8 columns) a workgroup =
   //          an 8-wide x 4-high TILE of one level, wave w = row w of the tile: the y+1 corners of a wave are the y corners of
-  //          the next wave.  Falls back to map 1 when a level does not divide.
+  //          the next wave.  Falls back to map 1 when a level does not divide or level_start is not the dense packing of the levels.
   long g;
   bool live;
   if (map == 0) {
@@ -183,8 +183,15 @@ __global__ __launch_bounds__(256) void msda_d32_kernel(const T* __restrict__ val
     const int mh = (int)(blk - chunk * M);
     long bqn = chunk * 32 + (threadIdx.x >> 3);
     if (map == 2) {
+      // ... and the levels must tile [0, Lq) exactly: with gaps between the levels or rows behind the last one (a layout the
+      // backward supports too) the queries of the gap rows belong to no tile and the tile count of an image is not Lq / 32
       bool tiles = true;
-      for (int l = 0; l < L; ++l) tiles = tiles && (shapes[2 * l] % 4 == 0) && (shapes[2 * l + 1] % 8 == 0);
+      long dense = 0;
+      for (int l = 0; l < L; ++l) {
+        tiles = tiles && (shapes[2 * l] % 4 == 0) && (shapes[2 * l + 1] % 8 == 0) && (lstart[l] == dense);
+        dense += shapes[2 * l] * shapes[2 * l + 1];
+      }
+      tiles = tiles && dense == Lq;
       if (tiles) {
         const long cpi = Lq / 32;                        // tiles per image (every level divides, so does their sum)
         const long bi = chunk / cpi;

@@ -69,3 +69,31 @@ def test_new_entry_points_validate_on_the_host():
     # empty work is a no-op even with null data pointers
     assert lib.hipie_batched_nms(None, None, None, None, None, 0, 0, 0.7, 1, None) == 0
     assert lib.hipie_mask_finalize(None, 0, None, 0, 8, 8, 4, 32, 32, 32, 32, 0.5, None, None) == 0
+
+
+def test_msda_forward_refusals_without_a_launch():
+    """hipie_msda_fused_forward / _strided refuse on the host: an image whose value block does not fit the 32-bit sample offsets, a value
+    row stride that is not a multiple of 8 or below M*D, a reference-point width other than 2 or 4."""
+    lib = _lib.load()
+    p = ctypes.c_void_p(256)
+    M, D, L, P = 8, 32, 1, 1
+    shape = (M, D, L, 1, P)                                   # M, D, L, Lq, P
+    tail = (0, 0, M * L * P * 2, M * L * P, None)             # value dtype, aux dtype, offset / logit row strides, stream
+    fused = lambda S, ref_dim: lib.hipie_msda_fused_forward(p, p, p, p, p, p, p, 1, S, *shape, ref_dim, *tail)
+    strided = lambda row, S=64: lib.hipie_msda_fused_forward_strided(p, row, p, p, p, p, p, p, 1, S, *shape, 2, *tail)
+    # S * row >= 2^31: exactly at the limit is refused, one pixel below passes the check and trips the next one we provoke (ref_dim 3)
+    assert fused(2 ** 31 // (M * D), 2) == -22 and b"32-bit sample offsets" in lib.hipie_last_error()
+    assert fused(2 ** 31 // (M * D) - 1, 3) == -22 and b"ref_dim must be 2 or 4 (got 3)" in lib.hipie_last_error()
+    assert strided(3 * M * D, 2 ** 31 // (3 * M * D) + 1) == -22 and b"32-bit sample offsets" in lib.hipie_last_error()
+    assert lib.hipie_msda_forward(p, p, p, p, p, p, 1, 2 ** 31 // (M * D), M, D, L, 1, P, 0, None) == -22
+    assert b"32-bit sample offsets" in lib.hipie_last_error()
+    # value row stride
+    for row in (M * D + 4, M * D - 8, 8):
+        assert strided(row) == -22 and b"value row stride %d" % row in lib.hipie_last_error(), row
+    # ref_dim
+    for ref_dim in (3, 0, 1, 5):
+        assert fused(64, ref_dim) == -22 and b"ref_dim must be 2 or 4 (got %d)" % ref_dim in lib.hipie_last_error()
+    # a refused strided call leaves no row stride behind for the next dense call: this one passes every MSDA check up to L*P
+    assert strided(M * D + 4) == -22
+    assert lib.hipie_msda_fused_forward(p, p, p, p, p, p, p, 1, 64, M, D, 3, 1, 11, 2, 0, 0, M * 66, M * 33, None) == -22
+    assert b"L*P=33 > 32" in lib.hipie_last_error()
