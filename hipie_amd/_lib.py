@@ -39,6 +39,8 @@ SIGNATURES = {
     "hipie_dynamic_mask_backward": [c_p] * 7 + [c_i] * 6 + [c_p],
     "hipie_vit_relpos": [c_p, c_p, c_p, c_p, c_p] + [c_i] * 6 + [c_p],
     "hipie_add_layernorm": [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_f, c_i, c_i, c_i, c_p],
+    "hipie_layernorm_backward": [c_p] * 8 + [c_l, c_l, c_i, c_f, c_p],
+    "hipie_layernorm_backward_ws_bytes": [c_l, c_i],
     "hipie_add_layernorm_sum": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_f, c_i, c_i, c_i, c_p],
     "hipie_add_layernorm_rows": [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_f, c_i, c_i, c_i, c_p, c_p, c_p],
     "hipie_batched_nms": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_i, c_p],
@@ -111,7 +113,8 @@ def load():
             raise HipieLibraryError("%s does not export %s (stale build?)" % (LIB_PATH, name))
         fn.argtypes = argtypes
         fn.restype = (ctypes.c_char_p if name == "hipie_last_error" else
-                      ctypes.c_int64 if name in ("hipie_bi_xattn_workspace", "hipie_mask_einsum_workspace", "hipie_msda_backward_workspace") else ctypes.c_int)
+                      ctypes.c_int64 if name in ("hipie_bi_xattn_workspace", "hipie_mask_einsum_workspace", "hipie_msda_backward_workspace",
+                                                      "hipie_layernorm_backward_ws_bytes") else ctypes.c_int)
     _lib = lib
     return lib
 

@@ -699,6 +699,41 @@ def add_layernorm(x, delta, weight, bias, eps, norm_dtype, want_res=True, delta_
     return (x if delta is None else res), out
 
 
+@_timed("layernorm_bwd")
+def layernorm_backward(s, gy, weight, eps, gres=None, want_param_grads=True):
+    """backward of add_layernorm for the training step (hipie_layernorm_backward, fp32): s (..., C) = the tensor that was normalised,
+    gy = gradient of the LayerNorm output, gres = gradient arriving at s from the residual stream (or None) ->
+    (dx = LayerNorm input gradient + gres, dgamma, dbeta); the parameter sums are skipped (None, None) without want_param_grads.
+    mean / rstd are recomputed from s; dgamma / dbeta are summed in a fixed order (bit-reproducible)."""
+    for n, t in (("s", s), ("gy", gy), ("weight", weight), ("gres", gres)):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError("Not implemented on the CPU (%s must be a CUDA/HIP tensor)" % n)
+    lib = _lib.load()
+    C = s.shape[-1]
+    rows = s.numel() // C if C else 0
+    if gy.shape != s.shape or (gres is not None and gres.shape != s.shape) or weight.numel() != C:
+        raise RuntimeError("layernorm_backward: gy / gres must have the shape of s %s and weight its last dimension" % (tuple(s.shape),))
+
+    def rows16(t):                   # dense rows on a 16-byte boundary (a view at an odd storage offset is copied)
+        t = t.contiguous()
+        return t if t.data_ptr() % 16 == 0 else t.clone()
+    s, gy, weight = rows16(s), rows16(gy), rows16(weight)
+    gres = None if gres is None else rows16(gres)
+    dx = torch.empty_like(s)
+    dgamma = dbeta = ws = None
+    ws_bytes = 0
+    if want_param_grads:
+        dgamma, dbeta = torch.empty_like(weight), torch.empty_like(weight)
+        ws_bytes = int(lib.hipie_layernorm_backward_ws_bytes(rows, C))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=s.device)
+    rc = lib.hipie_layernorm_backward(_chk(s, "s", torch.float32), _chk(gy, "gy", torch.float32),
+                                      None if gres is None else _chk(gres, "gres", torch.float32), _chk(weight, "weight", torch.float32),
+                                      dx.data_ptr(), None if dgamma is None else dgamma.data_ptr(), None if dbeta is None else dbeta.data_ptr(),
+                                      None if ws is None else ws.data_ptr(), ws_bytes, rows, C, float(eps), _stream())
+    _lib.check(rc, "hipie_layernorm_backward")
+    return dx, dgamma, dbeta
+
+
 @_timed("add_layernorm")
 def add_layernorm_sum(x, delta, weight, bias, eps, addend):
     """n = LayerNorm(x + delta) and n + addend, both in x's dtype, one launch (the encoder's post-norm + next `src + pos`)."""

@@ -172,3 +172,38 @@ def fused_attention(qa, ka, v):
     qa_p = pad(torch.cat((qa, qa.new_ones(BH, N, 1)), -1), (0, 0, 0, Np - N))
     ka_p = torch.cat((pad(ka, (0, 0, 0, Np - N)), bias), -1)
     return FusedAttentionFunction.apply(qa_p, ka_p, pad(v, (0, 0, 0, Np - N)))[:, :N]
+
+
+class AddLayerNormFunction(torch.autograd.Function):
+    """s = x + delta;  y = LayerNorm(s) * weight + bias  -> (s, y): a residual add and the LayerNorm that follows it (Block.forward,
+    backbone/vit.py:212-230; the post-norms of DeformableTransformerEncoderLayer.forward, deformable_transformer_dino.py:384-394) as one
+    node of the graph.  forward = hipie_add_layernorm (the inference path's kernel, fp32 in and out), backward = ONE
+    hipie_layernorm_backward launch (+ its partial-row sum) that takes the gradient of y AND the gradient arriving at s from the residual
+    stream: d loss / d s, which is the gradient of x and of delta alike.  Saved: s and weight (the statistics are recomputed)."""
+
+    @staticmethod
+    def forward(ctx, x, delta, weight, bias, eps):
+        x = x.contiguous()
+        s, y = ops.add_layernorm(x, None if delta is None else delta.contiguous(), weight.detach(), bias.detach(), eps, torch.float32)
+        ctx.save_for_backward(s, weight)
+        ctx.eps, ctx.has_delta = float(eps), delta is not None
+        ctx.set_materialize_grads(False)          # an output nothing consumed arrives as None, not as a tensor of zeros to stream through
+        return s, y
+
+    @staticmethod
+    def backward(ctx, g_s, g_y):
+        s, weight = ctx.saved_tensors
+        want = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
+        if g_s is None and g_y is None:
+            return None, None, None, None, None
+        if g_y is None:                       # the normalised output went nowhere: s is a plain sum
+            dx, dg, db = g_s, (torch.zeros_like(weight) if want else None), (torch.zeros_like(weight) if want else None)
+        else:
+            dx, dg, db = ops.layernorm_backward(s, g_y, weight, ctx.eps, gres=g_s, want_param_grads=want)
+        return (dx if ctx.needs_input_grad[0] else None, dx if ctx.has_delta and ctx.needs_input_grad[1] else None,
+                dg if ctx.needs_input_grad[2] else None, db if ctx.needs_input_grad[3] else None, None)
+
+
+def add_layer_norm(x, delta, weight, bias, eps):
+    """(s, y) = (x + delta, LayerNorm(x + delta)) with a hand-written backward (AddLayerNormFunction); delta=None: s is x"""
+    return AddLayerNormFunction.apply(x, delta, weight, bias, eps)

@@ -3,7 +3,8 @@ state_dict layout as the reference, hipie_amd/hipie_img.py), written for autogra
 kernels have no backward.  What is hand-written HIP here is what has a backward kernel: multi-scale deformable attention
 (hipie_msda_forward / hipie_msda_backward), the mask contraction and the CondInst dynamic mask head (training/functions.py); the dense
 linears, LayerNorm / GroupNorm, the softmax attentions and the convolutions run on the library kernels PyTorch-ROCm dispatches to, with
-torch.autograd providing their backward.
+torch.autograd providing their backward (opt-in, HipBackendNorms: the LayerNorms of the ViT blocks and of the encoder layers on
+hipie_add_layernorm / hipie_layernorm_backward).
 
 Functional style over a dict ``sd`` of LIVE parameters (model.named_parameters() + buffers, reference key names), so gradients land in the
 model's own parameters.  Every function cites the reference code it follows.  Training-mode differences from the inference path:
@@ -77,6 +78,18 @@ class HipBackend:
         if not outs:
             return mask_feats.new_zeros(0, up * mask_feats.shape[2], up * mask_feats.shape[3])
         return torch.cat(outs, 0)
+
+
+class HipBackendNorms(HipBackend):
+    """HipBackend + the LayerNorms of the ViT blocks and of the deformable encoder layers on the hand-written pair hipie_add_layernorm /
+    hipie_layernorm_backward (opt-in: TrainStep's default stays HipBackend).  The decoder layers, the fusion block, BERT and the head
+    norms keep F.layer_norm: a few hundred rows each, launch-bound."""
+
+    @staticmethod
+    def add_layer_norm(x, delta, weight, bias, eps):
+        """(s, y) = (x + delta, LayerNorm(s) * weight + bias); delta None: s = x (functions.AddLayerNormFunction)"""
+        from .functions import add_layer_norm
+        return add_layer_norm(x, delta, weight, bias, eps)
 
 
 # ------------------------------------------------------------------------------------------------ small helpers
@@ -234,19 +247,30 @@ def vit_backbone(x, sd, p, cfg, be=None):
     """ViT.forward (vit.py:357-374) + the simple feature pyramid of D2ViT (fpn1 = ConvTranspose, identity, max pool)"""
     x = F.conv2d(x, sd[p + "patch_embed.proj.weight"], sd[p + "patch_embed.proj.bias"], stride=cfg["vit_patch"]).permute(0, 2, 3, 1)
     x = x + get_abs_pos(sd[p + "pos_embed"], (x.shape[1], x.shape[2]))
+    aln = getattr(be, "add_layer_norm", None)       # HipBackendNorms: every residual add is paired with the LayerNorm that follows it
+    pending = None                                  # the mlp branch of the previous block, not yet added to x
     for i in range(cfg["vit_depth"]):
         bp = "%sblocks.%d." % (p, i)
         win = cfg["vit_window"] if i in cfg["vit_window_blocks"] else 0
-        h = ln(x, sd, bp + "norm1.", 1e-6)
+        if aln is None:
+            h = ln(x, sd, bp + "norm1.", 1e-6)
+        else:                                     # x + (the previous block's mlp branch) and this norm1 as one node
+            x, h = aln(x, pending, sd[bp + "norm1.weight"], sd[bp + "norm1.bias"], 1e-6)
         if win > 0:
             H, W = h.shape[1], h.shape[2]
             h, pad_hw = window_partition(h, win)
         h = vit_attention(h, sd, bp + "attn.", cfg["vit_heads"], be)
         if win > 0:
             h = window_unpartition(h, win, pad_hw, (H, W))
-        x = x + h
-        h = ln(x, sd, bp + "norm2.", 1e-6)
-        x = x + _blin(F.gelu(_blin(h, sd, bp + "mlp.fc1.", be)), sd, bp + "mlp.fc2.", be)
+        if aln is None:
+            x = x + h
+            h = ln(x, sd, bp + "norm2.", 1e-6)
+            x = x + _blin(F.gelu(_blin(h, sd, bp + "mlp.fc1.", be)), sd, bp + "mlp.fc2.", be)
+        else:
+            x, h = aln(x, h, sd[bp + "norm2.weight"], sd[bp + "norm2.bias"], 1e-6)
+            pending = _blin(F.gelu(_blin(h, sd, bp + "mlp.fc1.", be)), sd, bp + "mlp.fc2.", be)
+            if i == cfg["vit_depth"] - 1:         # no norm follows the last block: a plain add
+                x = x + pending
     xp = x.permute(0, 3, 1, 2)
     return {"res3": F.conv_transpose2d(xp, sd[p + "fpn1.0.weight"], sd[p + "fpn1.0.bias"], stride=2), "res4": xp, "res5": F.max_pool2d(xp, 2, 2)}
 
@@ -337,6 +361,10 @@ def msda_module(query, ref_points, src, shapes, pad_mask, sd, p, be, heads=8, le
 
 def encoder_layer(src, pos, refs, shapes, pad_mask, sd, p, be):
     """DeformableTransformerEncoderLayer.forward (deformable_transformer_dino.py:384-394), dropout 0"""
+    aln = getattr(be, "add_layer_norm", None)
+    if aln is not None:                             # HipBackendNorms: both post-norms with their residual adds, one node each
+        _, src = aln(src, msda_module(src + pos, refs, src, shapes, pad_mask, sd, p + "self_attn.", be), sd[p + "norm1.weight"], sd[p + "norm1.bias"], 1e-5)
+        return aln(src, _blin(F.relu(_blin(src, sd, p + "linear1.", be)), sd, p + "linear2.", be), sd[p + "norm2.weight"], sd[p + "norm2.bias"], 1e-5)[1]
     src = ln(src + msda_module(src + pos, refs, src, shapes, pad_mask, sd, p + "self_attn.", be), sd, p + "norm1.")
     return ln(src + _blin(F.relu(_blin(src, sd, p + "linear1.", be)), sd, p + "linear2.", be), sd, p + "norm2.")
 

@@ -274,6 +274,25 @@ int hipie_add_layernorm(const void* x, const void* delta, const float* gamma, co
                         void* stream);
 
 /*
+ * Backward of hipie_add_layernorm for the training step (fp32): the input gradient with the residual stream's gradient added, and the
+ * parameter gradients, in one pass over the rows.
+ * Replaces: torch.autograd through torch.nn.LayerNorm as used by Block.forward (backbone/vit.py:212-230) and by the post-norm residuals
+ *           of DeformableTransformerEncoderLayer.forward (models/deformable_detr/deformable_transformer_dino.py:384-394), plus the
+ *           accumulation of the residual branch's gradient that autograd runs as a pass of its own.
+ *   s (rows, C): the tensor that was normalised (x + delta, the forward's res_out);  gy (rows, C): gradient of the LayerNorm output;
+ *   gres (rows, C) or NULL: gradient arriving at s from the residual stream;  gamma (C).
+ *   mean / rstd are recomputed from s with the forward's arithmetic;  xhat = (s - mean) * rstd,  g = gy * gamma:
+ *   dx (rows, C) = rstd * (g - mean_c(g) - xhat * mean_c(g * xhat)) + gres;  dx may alias gres (not s, not gy).
+ *   dgamma (C) = sum_rows gy * xhat,  dbeta (C) = sum_rows gy: overwritten; both NULL = input gradient only.  Summed without atomics in a
+ *   fixed order (one partial row per workgroup in `ws`, then a second kernel): bit-reproducible from call to call.
+ *   ws: at least hipie_layernorm_backward_ws_bytes(rows, C) bytes when dgamma is wanted = min(ceil(rows / 4), 1024) workgroups x 2 C floats.
+ *   C % 4 == 0, C <= 2048, 16-byte aligned buffers.  rows == 0: returns 0, zero-fills dgamma / dbeta when given.
+ */
+int hipie_layernorm_backward(const float* s, const float* gy, const float* gres, const float* gamma, float* dx, float* dgamma,
+                             float* dbeta, void* ws, int64_t ws_bytes, int64_t rows, int C, float eps, void* stream);
+int64_t hipie_layernorm_backward_ws_bytes(int64_t rows, int C);
+
+/*
  * hipie_vit_attn with the decomposed relative-position bias computed INSIDE the kernel from the (re-interpolated) tables
  * (get_rel_pos + add_decomposed_rel_pos, hipie/backbone/utils.py:63-125): bias_w[q, kx] = q . Rw[qx - kx + gw - 1] and
  * bias_h[q, ky] = q . Rh[qy - ky + gh - 1] are two MFMA products per wave in the prologue, so neither hipie_vit_relpos nor

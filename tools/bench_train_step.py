@@ -2,7 +2,8 @@
 """forward + backward time of ONE TRAINING STEP (hipie_amd/training/step.py) at the reference's training batch: ViT-H, 1024 x 1024, 2 images per
 GPU (configs/training/vit_huge_32g.yaml:1 -- 32 GPUs x 2), the 80-class caption, 8 synthetic targets per image (6 things, 2 stuff), DN_NUMBER 100,
 12544 mask points, random-init weights.  Prints ms for the forward (loss dictionary), the backward, and the peak memory.
-    python tools/bench_train_step.py [batch] [steps]
+    python tools/bench_train_step.py [batch] [steps] [--hand-norms]
+--hand-norms: net.HipBackendNorms (the ViT / encoder LayerNorms on hipie_add_layernorm / hipie_layernorm_backward) instead of HipBackend
 env: LIB_LINEAR=1 (library fp32 linears), PHASES=1 (synchronised forward phases), TORCH_PROF=1 (top kernels), HOSTPROF=1 (cProfile of a forward)"""
 import os
 import sys
@@ -40,8 +41,10 @@ def targets_for(batch, n_things, n_stuff, size, L, dev, seed=0):
 
 
 def main():
-    B = int(sys.argv[1]) if len(sys.argv) > 1 else 2
-    steps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+    argv = [a for a in sys.argv[1:] if a != "--hand-norms"]
+    hand_norms = "--hand-norms" in sys.argv[1:]
+    B = int(argv[0]) if len(argv) > 0 else 2
+    steps = int(argv[1]) if len(argv) > 1 else 3
     dev = torch.device("cuda", 0)
     cfg = HipieConfig.vit_huge()
     torch.manual_seed(0)
@@ -55,9 +58,11 @@ def main():
     targets = targets_for(B, 6, 2, size, L, dev)
     step = TrainStep(model)
     from hipie_amd.training import net
+    if hand_norms:
+        step.be = net.HipBackendNorms
     if os.environ.get("LIB_LINEAR") == "1":                  # A/B: the big linears on the library instead of the split GEMM Function
 
-        class LibBackend(net.HipBackend):
+        class LibBackend(step.be):
             linear = None
         step.be = LibBackend
     phases = {}
@@ -179,6 +184,7 @@ def main():
         ms_.get("num_device_alloc", -1), ms_.get("num_device_free", -1), ms_.get("num_alloc_retries", -1), steps + 2, torch.cuda.memory_reserved() / 2 ** 30))
     print("per step (ms) forward: %s | backward: %s" % (" ".join("%.0f" % (1e3 * t) for t in fw), " ".join("%.0f" % (1e3 * t) for t in bw)))
     gn = float(torch.sqrt(sum((p.grad.double() ** 2).sum() for p in model.parameters() if p.grad is not None)))
+    print("backend %s" % step.be.__name__)
     print("training step, ViT-H 1024^2, %d images / GPU, %.0f M trainable parameters, %d loss entries: forward %.1f ms, backward %.1f ms, total %.1f ms "
           "(%.2f images/s per GPU); loss %.3f, gradient norm %.3e, finite %s; peak memory %.1f GB"
           % (B, n_par / 1e6, len(losses), 1e3 * sum(fw) / len(fw), 1e3 * sum(bw) / len(bw), 1e3 * (sum(fw) + sum(bw)) / len(fw),
