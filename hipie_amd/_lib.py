@@ -41,6 +41,9 @@ SIGNATURES = {
     "hipie_add_layernorm": [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_f, c_i, c_i, c_i, c_p],
     "hipie_layernorm_backward": [c_p] * 8 + [c_l, c_l, c_i, c_f, c_p],
     "hipie_layernorm_backward_ws_bytes": [c_l, c_i],
+    "hipie_act_forward": [c_p, c_p, c_l, c_i, c_i, c_p],
+    "hipie_act_backward": [c_p] * 6 + [c_l, c_i, c_i, c_p],
+    "hipie_act_backward_ws_bytes": [c_l, c_i],
     "hipie_add_layernorm_sum": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_f, c_i, c_i, c_i, c_p],
     "hipie_add_layernorm_rows": [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_f, c_i, c_i, c_i, c_p, c_p, c_p],
     "hipie_batched_nms": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_i, c_p],
@@ -114,7 +117,7 @@ def load():
         fn.argtypes = argtypes
         fn.restype = (ctypes.c_char_p if name == "hipie_last_error" else
                       ctypes.c_int64 if name in ("hipie_bi_xattn_workspace", "hipie_mask_einsum_workspace", "hipie_msda_backward_workspace",
-                                                      "hipie_layernorm_backward_ws_bytes") else ctypes.c_int)
+                                                      "hipie_layernorm_backward_ws_bytes", "hipie_act_backward_ws_bytes") else ctypes.c_int)
     _lib = lib
     return lib
 

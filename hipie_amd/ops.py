@@ -734,6 +734,60 @@ def layernorm_backward(s, gy, weight, eps, gres=None, want_param_grads=True):
     return dx, dgamma, dbeta
 
 
+def _act_rows16(t, name):
+    """(t as dense fp32 rows on a 16-byte boundary, rows, N): a strided view or one at an odd storage offset is copied"""
+    if not t.is_cuda:
+        raise RuntimeError("Not implemented on the CPU (%s must be a CUDA/HIP tensor)" % name)
+    if t.dtype != torch.float32:
+        raise RuntimeError("%s must be torch.float32, got %s" % (name, t.dtype))
+    t = t.contiguous()
+    if t.data_ptr() % 16:
+        t = t.clone()
+    N = t.shape[-1] if t.dim() else 1
+    return t, (t.numel() // N if N else 0), N
+
+
+@_timed("act_fwd")
+def act_forward(u, act):
+    """a = act(u) on hipie_act_forward (fp32, last dimension % 4 == 0); act = ACT_GELU (the exact-erf formula of the GEMM epilogue, bit
+    for bit) | ACT_RELU.  The forward half of the training step's MLP node (functions.MlpFunction)."""
+    u, rows, N = _act_rows16(u, "u")
+    a = torch.empty_like(u)
+    rc = _lib.load().hipie_act_forward(u.data_ptr(), a.data_ptr(), rows, N, int(act), _stream())
+    _lib.check(rc, "hipie_act_forward")
+    return a
+
+
+@_timed("act_bwd")
+def act_backward(u, g, act, want_a=False, want_bias_grad=False, out=None):
+    """backward of a = act(u) (hipie_act_backward, fp32, one pass over u and g): g = d loss / d a ->
+    (du = g * act'(u),  a = act(u) recomputed with the bits of act_forward | None,  dbias = du summed over the rows, (N,) | None).
+    out: the buffer du is written into -- it may be g itself (in place); it is used when it is dense, 16-byte aligned fp32 of u's shape.
+    dbias is summed in a fixed order (bit-reproducible).  Nothing is cached: the workspace lives for the call."""
+    u, rows, N = _act_rows16(u, "u")
+    if g.shape != u.shape:
+        raise RuntimeError("act_backward: g %s must have the shape of u %s" % (tuple(g.shape), tuple(u.shape)))
+    g_in = g
+    g, _, _ = _act_rows16(g, "g")
+    if out is not None and not out.is_cuda:
+        raise RuntimeError("Not implemented on the CPU (out must be a CUDA/HIP tensor)")
+    if out is not None and out is g_in:
+        out = g                                             # in place on the operand the kernel reads (the dense copy, when one was made)
+    usable = (out is not None and out.dtype == torch.float32 and out.shape == u.shape and out.is_contiguous() and out.data_ptr() % 16 == 0
+              and out.data_ptr() != u.data_ptr())
+    du = out if usable else torch.empty_like(u)
+    a = torch.empty_like(u) if want_a else None
+    dbias = ws = None
+    lib = _lib.load()
+    if want_bias_grad:
+        dbias = torch.empty(N, dtype=torch.float32, device=u.device)
+        ws = torch.empty(int(lib.hipie_act_backward_ws_bytes(rows, N)), dtype=torch.uint8, device=u.device)
+    rc = lib.hipie_act_backward(u.data_ptr(), g.data_ptr(), du.data_ptr(), None if a is None else a.data_ptr(),
+                                None if dbias is None else dbias.data_ptr(), None if ws is None else ws.data_ptr(), rows, N, int(act), _stream())
+    _lib.check(rc, "hipie_act_backward")
+    return du, a, dbias
+
+
 @_timed("add_layernorm")
 def add_layernorm_sum(x, delta, weight, bias, eps, addend):
     """n = LayerNorm(x + delta) and n + addend, both in x's dtype, one launch (the encoder's post-norm + next `src + pos`)."""

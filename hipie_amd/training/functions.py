@@ -117,6 +117,73 @@ def split_linear(x, weight, bias, owner, key):
     return torch.nn.functional.linear(x, weight, bias)
 
 
+class MlpFunction(torch.autograd.Function):
+    """linear -> activation -> linear as ONE node of the graph: timm's Mlp of a ViT block (fc1 -> GELU -> fc2, backbone/vit.py:193-197) and the
+    FFN of an encoder layer (linear1 -> ReLU -> linear2, deformable_transformer_dino.py:384-394).
+        u = x . W1^T + b1     a = act(u)     y = a . W2^T + b2          the split GEMM of SplitLinearFunction, ops.act_forward between
+    Saved: x, u and the two weights.  a is NOT saved -- it is a pointwise function of u, and the backward's one pass over u and da
+    (ops.act_backward) writes it again, with the forward's bits, next to du = da * act'(u) (in place in da) and db1 = sum_m du:
+        da = dy . W2                    dW2 = dy^T . a      db2 = sum_m dy      (a dies here)
+        du, a, db1 = act_backward       dW1 = du^T . x      dx  = du . W1
+    act = ops.ACT_GELU | ops.ACT_RELU.  The HL8 copies of the weights are the ones SplitLinearFunction caches (on the weight, key "w")."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, act):
+        w1_hl8, _, _ = ops.split_weight(w1, "w", [w1], lambda: w1)
+        w2_hl8, _, _ = ops.split_weight(w2, "w", [w2], lambda: w2)
+        x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        u = ops.gemm(x2, w1_hl8, None if b1 is None else b1.detach().float().contiguous(), split=True, out_fmt=ops.F32, tag="train_fwd")
+        y = ops.gemm(ops.act_forward(u, act), w2_hl8, None if b2 is None else b2.detach().float().contiguous(), split=True, out_fmt=ops.F32,
+                     tag="train_fwd")
+        ctx.save_for_backward(x2, u, w1, w2)
+        ctx.act, ctx.lead, ctx.has_b1, ctx.has_b2 = int(act), x.shape[:-1], b1 is not None, b2 is not None
+        return y.view(*x.shape[:-1], w2.shape[0])
+
+    @staticmethod
+    def backward(ctx, gy):
+        x2, u, w1, w2 = ctx.saved_tensors
+        need_x, need_w1, need_b1, need_w2, need_b2 = ctx.needs_input_grad[:5]
+        need_b1, need_b2 = need_b1 and ctx.has_b1, need_b2 and ctx.has_b2
+        g2 = gy.reshape(-1, w2.shape[0]).float()
+        if g2.stride(-1) != 1:
+            g2 = g2.contiguous()
+        gx = gw1 = gb1 = gw2 = gb2 = du = a = None
+        if need_x or need_w1 or need_b1:
+            w2t_hl8, _, _ = ops.split_weight(w2, "w.T", [w2], lambda: w2.t().contiguous())
+            da = ops.gemm(g2, w2t_hl8, None, split=True, out_fmt=ops.F32, tag="train_dx")
+            du, a, gb1 = ops.act_backward(u, da, ctx.act, want_a=need_w2, want_bias_grad=need_b1, out=da)
+            del da
+        elif need_w2:
+            a = ops.act_forward(u, ctx.act)
+        if need_w2:
+            gw2 = _weight_grad(g2, a)
+        a = None
+        if need_b2:
+            gb2 = g2.sum(0)
+        if need_w1:
+            gw1 = _weight_grad(du, x2)
+        if need_x:
+            w1t_hl8, _, _ = ops.split_weight(w1, "w.T", [w1], lambda: w1.t().contiguous())
+            gx = ops.gemm(du, w1t_hl8, None, split=True, out_fmt=ops.F32, tag="train_dx").view(*ctx.lead, w1.shape[1])
+        return gx, gw1, gb1, gw2, gb2, None
+
+
+def _split_linear_ok(x, weight, rows):
+    """split_linear's own conditions"""
+    K, N = weight.shape[1], weight.shape[0]
+    return x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and K % 32 == 0 and N % 32 == 0 and rows >= 256
+
+
+def split_mlp(x, w1, b1, w2, b2, act):
+    """linear(act(linear(x, w1, b1)), w2, b2) as one node (MlpFunction) when BOTH linears are ones split_linear takes; any other shape runs
+    the three-node composition (split_linear -> library activation -> split_linear), so nothing is refused"""
+    rows = x.numel() // w1.shape[1] if w1.shape[1] else 0
+    if _split_linear_ok(x, w1, rows) and _split_linear_ok(x, w2, rows) and act in (ops.ACT_GELU, ops.ACT_RELU):
+        return MlpFunction.apply(x, w1, b1, w2, b2, act)
+    f = {ops.ACT_GELU: torch.nn.functional.gelu, ops.ACT_RELU: torch.nn.functional.relu}[act]
+    return split_linear(f(split_linear(x, w1, b1, w1, "w")), w2, b2, w2, "w")
+
+
 class FusedAttentionFunction(torch.autograd.Function):
     """softmax(q' k'^T) v with the decomposed rel-pos bias folded into q' / k' (net.vit_attention), forward and backward on
     hipie_attn_train_forward / _backward (csrc/attn_train.hip): no (heads, N, N) tensor in HBM.  q' (BH, N, <= 224), k' (BH, N, <= 224) whose

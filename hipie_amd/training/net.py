@@ -4,7 +4,8 @@ kernels have no backward.  What is hand-written HIP here is what has a backward 
 (hipie_msda_forward / hipie_msda_backward), the mask contraction and the CondInst dynamic mask head (training/functions.py); the dense
 linears, LayerNorm / GroupNorm, the softmax attentions and the convolutions run on the library kernels PyTorch-ROCm dispatches to, with
 torch.autograd providing their backward (opt-in, HipBackendNorms: the LayerNorms of the ViT blocks and of the encoder layers on
-hipie_add_layernorm / hipie_layernorm_backward).
+hipie_add_layernorm / hipie_layernorm_backward; opt-in, HipBackendMlp: their MLPs / FFNs as one node with the activation on
+hipie_act_forward / hipie_act_backward).
 
 Functional style over a dict ``sd`` of LIVE parameters (model.named_parameters() + buffers, reference key names), so gradients land in the
 model's own parameters.  Every function cites the reference code it follows.  Training-mode differences from the inference path:
@@ -90,6 +91,25 @@ class HipBackendNorms(HipBackend):
         """(s, y) = (x + delta, LayerNorm(s) * weight + bias); delta None: s = x (functions.AddLayerNormFunction)"""
         from .functions import add_layer_norm
         return add_layer_norm(x, delta, weight, bias, eps)
+
+
+class HipBackendMlp(HipBackend):
+    """HipBackend + the MLP of every ViT block and the FFN of every deformable encoder layer as ONE autograd node (functions.MlpFunction:
+    hipie_act_forward / hipie_act_backward between the split GEMMs; the activation is recomputed in the backward instead of saved).
+    Opt-in: TrainStep's default stays HipBackend."""
+
+    @staticmethod
+    def mlp(x, sd, p_fc1, p_fc2, act):
+        """linear(act(linear(x, p_fc1)), p_fc2); act = "gelu" | "relu" (functions.split_mlp: shapes the split GEMM does not take run the
+        three-node composition)"""
+        from .. import ops
+        from .functions import split_mlp
+        return split_mlp(x, sd[p_fc1 + "weight"], sd.get(p_fc1 + "bias"), sd[p_fc2 + "weight"], sd.get(p_fc2 + "bias"),
+                         {"gelu": ops.ACT_GELU, "relu": ops.ACT_RELU}[act])
+
+
+class HipBackendNormsMlp(HipBackendNorms, HipBackendMlp):
+    """both opt-in groups: the hand-written LayerNorm pair and the one-node MLP"""
 
 
 # ------------------------------------------------------------------------------------------------ small helpers
@@ -194,6 +214,14 @@ def _blin(x, sd, p, be):
     return f(x, sd, p) if f is not None else lin(x, sd, p)
 
 
+def _bmlp(x, sd, p_fc1, p_fc2, act, be):
+    """linear -> activation -> linear: the backend's one-node form when it has one (HipBackendMlp.mlp), else the three nodes"""
+    f = getattr(be, "mlp", None)
+    if f is not None:
+        return f(x, sd, p_fc1, p_fc2, act)
+    return _blin((F.gelu if act == "gelu" else F.relu)(_blin(x, sd, p_fc1, be)), sd, p_fc2, be)
+
+
 _KEY_AXES = {}
 FOLD_REL_POS = True
 
@@ -265,10 +293,10 @@ def vit_backbone(x, sd, p, cfg, be=None):
         if aln is None:
             x = x + h
             h = ln(x, sd, bp + "norm2.", 1e-6)
-            x = x + _blin(F.gelu(_blin(h, sd, bp + "mlp.fc1.", be)), sd, bp + "mlp.fc2.", be)
+            x = x + _bmlp(h, sd, bp + "mlp.fc1.", bp + "mlp.fc2.", "gelu", be)
         else:
             x, h = aln(x, h, sd[bp + "norm2.weight"], sd[bp + "norm2.bias"], 1e-6)
-            pending = _blin(F.gelu(_blin(h, sd, bp + "mlp.fc1.", be)), sd, bp + "mlp.fc2.", be)
+            pending = _bmlp(h, sd, bp + "mlp.fc1.", bp + "mlp.fc2.", "gelu", be)
             if i == cfg["vit_depth"] - 1:         # no norm follows the last block: a plain add
                 x = x + pending
     xp = x.permute(0, 3, 1, 2)
@@ -364,9 +392,9 @@ def encoder_layer(src, pos, refs, shapes, pad_mask, sd, p, be):
     aln = getattr(be, "add_layer_norm", None)
     if aln is not None:                             # HipBackendNorms: both post-norms with their residual adds, one node each
         _, src = aln(src, msda_module(src + pos, refs, src, shapes, pad_mask, sd, p + "self_attn.", be), sd[p + "norm1.weight"], sd[p + "norm1.bias"], 1e-5)
-        return aln(src, _blin(F.relu(_blin(src, sd, p + "linear1.", be)), sd, p + "linear2.", be), sd[p + "norm2.weight"], sd[p + "norm2.bias"], 1e-5)[1]
+        return aln(src, _bmlp(src, sd, p + "linear1.", p + "linear2.", "relu", be), sd[p + "norm2.weight"], sd[p + "norm2.bias"], 1e-5)[1]
     src = ln(src + msda_module(src + pos, refs, src, shapes, pad_mask, sd, p + "self_attn.", be), sd, p + "norm1.")
-    return ln(src + _blin(F.relu(_blin(src, sd, p + "linear1.", be)), sd, p + "linear2.", be), sd, p + "norm2.")
+    return ln(src + _bmlp(src, sd, p + "linear1.", p + "linear2.", "relu", be), sd, p + "norm2.")
 
 
 def mha(x_qk, x_v, sd, p, attn_mask=None, heads=8):

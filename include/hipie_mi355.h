@@ -293,6 +293,30 @@ int hipie_layernorm_backward(const float* s, const float* gy, const float* gres,
 int64_t hipie_layernorm_backward_ws_bytes(int64_t rows, int C);
 
 /*
+ * The pointwise activation between the two linears of an MLP, for the training step (fp32): forward, and a backward that produces the
+ * input gradient, the RECOMPUTED activation and the bias gradient of the first linear in one pass over u and g.
+ * Replaces: in the backward of timm's Mlp (fc1 -> nn.GELU() -> fc2, backbone/vit.py:193-197) and of the FFN of
+ *           DeformableTransformerEncoderLayer.forward (linear1 -> ReLU -> linear2, models/deformable_detr/deformable_transformer_dino.py:384-394):
+ *           the library's gelu_backward / threshold_backward, the separate row sum of the first linear's bias gradient, and the saved copy of
+ *           a = act(u) -- the graph keeps u alone.
+ *   act: 1 = exact-erf GELU (the branch-free formula of hipie_gemm's epilogue, bit for bit), 2 = ReLU -- hipie_gemm's numbering.
+ *   u, g, du, a: (rows, N) fp32, dense rows;  N % 4 == 0;  16-byte aligned buffers.
+ * hipie_act_forward:   a = act(u).
+ * hipie_act_backward:  du = g * act'(u);  du may alias g (not u).  GELU: act'(u) = Phi(u) + u phi(u), Phi and phi from the forward's own
+ *                      h(|u|) and exp2;  ReLU: act'(u) = (u > 0).
+ *                      a (or NULL) = act(u), the bits hipie_act_forward writes for the same u;  a aliases nothing.
+ *                      dbias (N) (or NULL) = sum_rows du: overwritten.  Summed without atomics in a fixed order (register partials per
+ *                      thread, one partial row per workgroup in `ws`, then a second kernel): bit-reproducible from call to call.
+ *                      ws: at least hipie_act_backward_ws_bytes(rows, N) bytes when dbias is given
+ *                          = min(ceil(rows / 4), max(1, 2048 / ceil(N / 1024))) partial rows x N floats.
+ * rows == 0 or N == 0: returns 0 without a launch; rows == 0 zero-fills dbias when given.
+ */
+int hipie_act_forward(const float* u, float* a, int64_t rows, int N, int act, void* stream);
+int hipie_act_backward(const float* u, const float* g, float* du, float* a, float* dbias, void* ws, int64_t rows, int N, int act,
+                       void* stream);
+int64_t hipie_act_backward_ws_bytes(int64_t rows, int N);
+
+/*
  * hipie_vit_attn with the decomposed relative-position bias computed INSIDE the kernel from the (re-interpolated) tables
  * (get_rel_pos + add_decomposed_rel_pos, hipie/backbone/utils.py:63-125): bias_w[q, kx] = q . Rw[qx - kx + gw - 1] and
  * bias_h[q, ky] = q . Rh[qy - ky + gh - 1] are two MFMA products per wave in the prologue, so neither hipie_vit_relpos nor

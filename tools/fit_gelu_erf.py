@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Constants of gm_gelu (hipie_amd/csrc/gemm.hip): the erfc form  erf(x) = 1 - P(t) exp(-x^2),  t = 1 / (1 + p x)  of Abramowitz & Stegun
+"""Constants of gm_gelu (hipie_amd/csrc/gelu.h): the erfc form  erf(x) = 1 - P(t) exp(-x^2),  t = 1 / (1 + p x)  of Abramowitz & Stegun
 7.1.26 with a sixth-degree P, fitted here (Lawson-weighted least squares -> minimax on [0, 6]), then re-expressed for
 Phi(x) = 0.5 (1 + erf(x / sqrt 2)) and checked in emulated fp32 against fp64.  CPU only (numpy / scipy)."""
 import numpy as np
