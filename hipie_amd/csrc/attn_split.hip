@@ -16,6 +16,7 @@
 // LDS by the whole workgroup (single buffer, two barriers per tile: these launches are 10 .. 50 us of latency, not throughput).
 #include "common.h"
 #include "mfma.h"
+#include "wave.h"
 
 namespace hipie {
 
@@ -28,13 +29,6 @@ struct ASParams {
   long q_sb, q_st, k_sb, k_st, v_sb, v_st;
   float scale_log2e;
 };
-
-__device__ __forceinline__ float as_xhalf_max(float x) {
-  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-  const unsigned int u = __builtin_bit_cast(unsigned int, x);
-  const u32x2 r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return fmaxf(__builtin_bit_cast(float, (unsigned int)r[0]), __builtin_bit_cast(float, (unsigned int)r[1]));
-}
 
 template <int HD>
 __global__ __launch_bounds__(256) void attn_split_kernel(const ASParams p) {
@@ -137,7 +131,7 @@ __global__ __launch_bounds__(256) void attn_split_kernel(const ASParams p) {
         if (qm && k0 + kk < p.Nk && qm[k0 + kk] == 0) S[blk][r] = -INFINITY;                 // this row may not see key k0 + kk
         mx = fmaxf(mx, S[blk][r]);
       }
-    mx = as_xhalf_max(mx);
+    mx = xhalf_max(mx);
     if (mx > m_run) {                                  // per-lane (= per query) rescale
       const float alpha = __builtin_amdgcn_exp2f(m_run - mx);      // m_run = -inf -> 0
       m_run = mx;

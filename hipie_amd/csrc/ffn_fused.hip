@@ -16,6 +16,7 @@
 // on this chip, ONE wave per SIMD saturates the power-limited matrix pipe as long as it has a hardware barrier and deep prefetch.
 #include "common.h"
 #include "mfma.h"
+#include "wave.h"
 
 namespace hipie {
 
@@ -24,14 +25,6 @@ struct FFParams {
   long ldx_b, ldw1_b, ldw2_b, ldo;      // row strides: X / W1 / W2 in bytes, out in floats
   int M;
 };
-
-__device__ __forceinline__ void ff_dma16(const char* sbase, unsigned int voff, unsigned int lds_dst) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  unsigned int keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-#endif
-}
 
 constexpr int FF_D = 256, FF_F = 2048, FF_C = 32;            // model width, hidden width, hidden units per chunk
 constexpr int FF_W1B = FF_C * FF_D * 4;                        // bytes of a W1 chunk tile (32 rows x 1 KB)
@@ -80,8 +73,8 @@ __global__ __launch_bounds__(256, 1) void ffn_fused_kernel(const FFParams p) {
   const unsigned int lds0 = (unsigned int)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) char*)smem);
   auto dma_chunk = [&](const int c, const int buf, const int q) {
     const int i = wave + 4 * q;
-    ff_dma16(p.W1 + (long)c * FF_C * p.ldw1_b, dv1[q], __builtin_amdgcn_readfirstlane(lds0 + (unsigned int)(buf * FF_BUF + 1024 * i)));
-    ff_dma16(p.W2 + (long)c * (FF_C * 4), dv2[q], __builtin_amdgcn_readfirstlane(lds0 + (unsigned int)(buf * FF_BUF + FF_W1B + 1024 * i)));
+    dma16(p.W1 + (long)c * FF_C * p.ldw1_b, dv1[q], __builtin_amdgcn_readfirstlane(lds0 + (unsigned int)(buf * FF_BUF + 1024 * i)));
+    dma16(p.W2 + (long)c * (FF_C * 4), dv2[q], __builtin_amdgcn_readfirstlane(lds0 + (unsigned int)(buf * FF_BUF + FF_W1B + 1024 * i)));
   };
 
   f32x16 acc[NB];
@@ -102,7 +95,7 @@ __global__ __launch_bounds__(256, 1) void ffn_fused_kernel(const FFParams p) {
   // extra live accumulator tile turns into v_accvgpr traffic (tools/bench_ffn_fused.py: 1.075 ms this form, 1.118 / 1.160 ms those).
   for (int c = 0; c < NCH; ++c) {
     const int buf = c & 1;
-    __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0): this wave's pieces of chunk c have landed
+    __builtin_amdgcn_s_waitcnt(vmcnt(0));        // this wave's pieces of chunk c have landed
     __syncthreads();                            // ... everybody's; all reads of chunk c - 1 (the other buffer) are done
     const char* bs = smem + buf * FF_BUF;
     const bool more = c + 1 < NCH;

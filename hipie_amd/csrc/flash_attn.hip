@@ -30,6 +30,7 @@
 #include <algorithm>
 
 #include "mfma.h"
+#include "wave.h"
 
 namespace hipie {
 
@@ -47,12 +48,6 @@ struct FAParams {
 };
 
 constexpr float kLog2e = 1.4426950408889634f;
-
-__device__ __forceinline__ float max3(float a, float b, float c) {
-  float d;
-  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-  return d;
-}
 
 constexpr float kDefer = 8.f;                 // log2 of the largest P the deferred running max lets through
 

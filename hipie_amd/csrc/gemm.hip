@@ -34,6 +34,7 @@
 #include "common.h"
 #include "gelu.h"        // gm_gelu: the exact-erf GELU of the epilogue (shared with act_bwd.hip)
 #include "mfma.h"
+#include "wave.h"
 
 namespace hipie {
 
@@ -72,16 +73,6 @@ struct GemmParams {
   int prio_mode;              // gemm2: 0 none, 1 blocks 256..511 at low priority (phase offset), 2 by dispatch-round parity
 };
 
-// LDS-DMA, 16 bytes per lane: LDS[m0 + 16 * lane] <- *(sbase + voff).  Inline asm (see vit_attn.hip: the builtin makes hipcc
-// drain vmcnt(0) before every later ds_read); completion is counted by hand -- vmcnt(0) before the stage barrier.
-__device__ __forceinline__ void gm_dma16(const char* sbase, unsigned int voff, unsigned int lds_dst) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  unsigned int keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-#endif
-}
-
 __device__ __forceinline__ unsigned int gm_pack2(float a, float b) {
   typedef _Float16 h2 __attribute__((ext_vector_type(2)));
   h2 v;
@@ -106,23 +97,7 @@ typedef _Float16 gm_h2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void gm_split2(float x0, float x1, unsigned int& H, unsigned int& L) {
   x0 = __builtin_amdgcn_fmed3f(x0, -65504.f, 65504.f);
   x1 = __builtin_amdgcn_fmed3f(x1, -65504.f, 65504.f);
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(HIPIE_NO_FMA_MIX)
-  // hi = fp16(x) for the pair in one v_cvt_pk_f16_f32; lo = fp16(x - hi) in ONE v_fma_mix{lo,hi}_f16 each (the fp16 hi is an fp16 source
-  // operand of the fma, x - hi is exact, one rounding): the same bits as `(f16)(x - (float)(f16)x)`, which costs a convert, a convert back
-  // and a subtract per value.  The asm operands are the register values themselves: nothing for the compiler to re-fold (see hl_split).
-  unsigned int h, l;
-  asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h) : "v"(x0), "v"(x1));
-  asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l) : "v"(h), "v"(x0));
-  asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l) : "v"(h), "v"(x1));
-  H = h;
-  L = l;
-#else
-  gm_h2 h, l;
-  h[0] = (f16_t)x0; h[1] = (f16_t)x1;
-  l[0] = (f16_t)(x0 - (float)h[0]); l[1] = (f16_t)(x1 - (float)h[1]);
-  H = __builtin_bit_cast(unsigned int, h);
-  L = __builtin_bit_cast(unsigned int, l);
-#endif
+  hl_split2(x0, x1, H, L);
 }
 
 // quads [G0, G0 + NG) of the block; rq = the residual quads (zeros when there is no residual); sb = this block's 32 bias values in LDS
@@ -197,7 +172,7 @@ __device__ __forceinline__ void gm_epi_vals(const float (&x)[NG][4], const int G
         gm_split2(v[g][2], v[g][3], H1, L1);
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(HIPIE_NO_FMA_MIX)
         // the split above is inline asm, which hipcc's hazard recogniser does not look into: v_permlane32_swap must not read a VGPR in the
-        // two wait states behind the VALU instruction that wrote it (see vs_settle in vit_attn_split.hip)
+        // two wait states behind the VALU instruction that wrote it (the rule of settle(), wave.h, for the four registers of this quad)
         asm volatile("s_nop 1" : "+v"(H0), "+v"(L0), "+v"(H1), "+v"(L1));
 #endif
         const u32x2 s0 = __builtin_amdgcn_permlane32_swap(H0, L0, false, false);    // lower: (H0 own, H0 of upper); upper: (L0 of lower, L0 own)
@@ -316,7 +291,7 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel(const GemmParams pin) {
       ko = ((long)(dy - 1) * p.conv_wp + (tap - 3 * dy - 1)) * p.lda_b + (long)r * 128;
     }
     const char* sb = (isa ? abase : wbase) + ko;
-    gm_dma16(sb, dvoff[i], __builtin_amdgcn_readfirstlane(lds0 + (unsigned int)(stage * STAGE + 1024 * (8 * i + wave))));
+    dma16(sb, dvoff[i], __builtin_amdgcn_readfirstlane(lds0 + (unsigned int)(stage * STAGE + 1024 * (8 * i + wave))));
   };
 
   // ---- fragment addresses: row = tile base (multiple of 32) + li, so the swizzle term is ((li >> 1) & 7) for every tile ----
@@ -345,7 +320,7 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel(const GemmParams pin) {
 #pragma unroll
     for (int i = 0; i < NI; ++i) dma(i, 0, 0);
   }
-  __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0)
+  __builtin_amdgcn_s_waitcnt(vmcnt(0));
   __syncthreads();
 
   for (int kt = 0; kt < nkt; ++kt) {
@@ -415,7 +390,7 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel(const GemmParams pin) {
         for (int i = s * PER; i < (s + 1) * PER && i < NI; ++i) dma(i, kt + 1, st ^ 1);
       }
     }
-    __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): this wave's DMA writes of stage t+1 have landed
+    __builtin_amdgcn_s_waitcnt(vmcnt(0));      // this wave's DMA writes of stage t+1 have landed
     __syncthreads();                          // ... and everybody's; all reads of stage t are done
   }
 
@@ -670,7 +645,7 @@ __global__ __launch_bounds__(256, 2) void gemm_small_kernel(const GemmParams p) 
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const bool isa = (8 * (4 * i + wave)) < BM;         // wave-uniform (BM % 8 == 0)
-      gm_dma16((isa ? abase : wbase) + (long)kt * 128, dvoff[i],
+      dma16((isa ? abase : wbase) + (long)kt * 128, dvoff[i],
                __builtin_amdgcn_readfirstlane(lds0 + (unsigned int)(slot * STAGE + 1024 * (4 * i + wave))));
     }
   };
@@ -691,8 +666,8 @@ __global__ __launch_bounds__(256, 2) void gemm_small_kernel(const GemmParams p) 
   if (nkt > 1) dma_stage(1, 1);
   int slot = 0;
   for (int kt = 0; kt < nkt; ++kt) {
-    if (kt + 1 < nkt) __builtin_amdgcn_s_waitcnt(0x0F70 | NI);      // stage kt landed; stage kt + 1 may still be in flight
-    else __builtin_amdgcn_s_waitcnt(0x0F70);
+    if (kt + 1 < nkt) __builtin_amdgcn_s_waitcnt(vmcnt(NI));      // stage kt landed; stage kt + 1 may still be in flight
+    else __builtin_amdgcn_s_waitcnt(vmcnt(0));
     __syncthreads();                                                // ... for every wave; all reads of stage kt - 1 are done
     if (kt + 2 < nkt) dma_stage(kt + 2, slot == 0 ? 2 : slot - 1);
     const char* xs = xrow + slot * STAGE;

@@ -129,7 +129,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f8x_kernel(const F8xParams fp) {
   const unsigned int lds0 = (unsigned int)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) char*)smem);
   auto dma = [&](const int i, const int kt, const int stage) {
     const bool isa = (8 * (8 * i + wave)) < BM;
-    gm_dma16((isa ? abase : wbase) + (long)kt * 128, dvoff[i],
+    dma16((isa ? abase : wbase) + (long)kt * 128, dvoff[i],
              __builtin_amdgcn_readfirstlane(lds0 + (unsigned int)(stage * STAGE + 1024 * (8 * i + wave))));
   };
 
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f8x_kernel(const F8xParams fp) {
   unsigned int wsc[NJ];
 #pragma unroll
   for (int j = 0; j < NJ; ++j) wsc[j] = fp.wsc[wsc_off[j]];
-  __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0)
+  __builtin_amdgcn_s_waitcnt(vmcnt(0));
   __syncthreads();
 
   for (int kt = 0; kt < nkt; ++kt) {
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f8x_kernel(const F8xParams fp) {
       __builtin_amdgcn_sched_barrier(0);       // one block's W fragments in flight at a time (hoisted together they spill)
 #endif
     }
-    __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): this wave's DMA writes of stage t+1 (and its scale loads) have landed
+    __builtin_amdgcn_s_waitcnt(vmcnt(0));      // this wave's DMA writes of stage t+1 (and its scale loads) have landed
 #pragma unroll
     for (int j = 0; j < NJ; ++j) wsc[j] = wsn[j];
     __syncthreads();                          // ... and everybody's; all reads of stage t are done

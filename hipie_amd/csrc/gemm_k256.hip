@@ -24,6 +24,7 @@
 
 #include "common.h"
 #include "mfma.h"
+#include "wave.h"
 
 namespace hipie {
 
@@ -32,14 +33,6 @@ struct TKParams {
   long ldx_b, ldw_b, ldo;               // row strides: X / W in bytes, out in floats
   int M, N;
 };
-
-__device__ __forceinline__ void tk_dma16(const char* sbase, unsigned int voff, unsigned int lds_dst) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  unsigned int keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-#endif
-}
 
 constexpr int TK_K = 256, TK_C = 32;                         // K, output features per chunk
 constexpr int TK_TILE = TK_C * TK_K * 4;                     // bytes of a weight chunk tile (32 rows x 1 KB of fp16 pairs)
@@ -68,7 +61,7 @@ __global__ __launch_bounds__(256, 2) void gemm_k256_kernel(const TKParams p) {
   const unsigned int lds0 = (unsigned int)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) char*)smem);
   auto dma_chunk = [&](const int c, const int buf, const int q) __attribute__((always_inline)) {
     const int i = wave + 4 * q;
-    tk_dma16(p.W + (long)c * TK_C * p.ldw_b, dv[q], __builtin_amdgcn_readfirstlane(lds0 + (unsigned int)(buf * TK_TILE + 1024 * i)));
+    dma16(p.W + (long)c * TK_C * p.ldw_b, dv[q], __builtin_amdgcn_readfirstlane(lds0 + (unsigned int)(buf * TK_TILE + 1024 * i)));
   };
 
   // ---- X fragments (B operand): lane (token li, half hi) holds k group 2 ks + hi of its row, both halves.  HL8 rows: 16 bytes of
@@ -88,10 +81,10 @@ __global__ __launch_bounds__(256, 2) void gemm_k256_kernel(const TKParams p) {
     }
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
-      __builtin_amdgcn_s_waitcnt(0xC07F);        // lgkmcnt(0): the fragment reads of the first half are done before it is overwritten
+      __builtin_amdgcn_s_waitcnt(lgkmcnt0);        // the fragment reads of the first half are done before it is overwritten
 #pragma unroll
-      for (int j = 0; j < 16; ++j) tk_dma16(p.X + 512 * half, xv[j], __builtin_amdgcn_readfirstlane(xslice + 1024 * j));
-      __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0): landed (only this wave reads this slice)
+      for (int j = 0; j < 16; ++j) dma16(p.X + 512 * half, xv[j], __builtin_amdgcn_readfirstlane(xslice + 1024 * j));
+      __builtin_amdgcn_s_waitcnt(vmcnt(0));        // landed (only this wave reads this slice)
 #pragma unroll
       for (int ksl = 0; ksl < KS / 2; ++ksl) {
         const int ks = half * (KS / 2) + ksl;
@@ -114,7 +107,7 @@ __global__ __launch_bounds__(256, 2) void gemm_k256_kernel(const TKParams p) {
         }
       }
     }
-    __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0)
+    __builtin_amdgcn_s_waitcnt(lgkmcnt0);
     __syncthreads();                              // every wave has its fragments: the slices become the weight buffers
   }
 #pragma unroll
@@ -128,7 +121,7 @@ __global__ __launch_bounds__(256, 2) void gemm_k256_kernel(const TKParams p) {
 
   for (int c = 0; c < nch; ++c) {
     const int buf = c & 1;
-    __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0): this wave's pieces of chunk c have landed (and the stores of chunk c - 2)
+    __builtin_amdgcn_s_waitcnt(vmcnt(0));        // this wave's pieces of chunk c have landed (and the stores of chunk c - 2)
     __syncthreads();                            // ... everybody's; all reads of chunk c - 1 (the other buffer) are done
     if (c > 0 && m < p.M) {
 #pragma unroll

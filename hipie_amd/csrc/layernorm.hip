@@ -8,56 +8,17 @@
 // vector loads), statistics are fp32 wave reductions (two-pass: mean, then centred variance -- the same arithmetic as
 // torch's layer_norm), and both outputs are written once.  Bytes per row: C * (|x| + |delta| + |res| + |norm|).
 #include "common.h"
+#include "wave.h"
 
 namespace hipie {
-
-template <typename T> struct V4 {
-  static __device__ __forceinline__ void ld(const T* p, float (&v)[4]);
-  static __device__ __forceinline__ void st(T* p, const float (&v)[4]);
-};
-template <> struct V4<float> {
-  static __device__ __forceinline__ void ld(const float* p, float (&v)[4]) {
-    const float4 r = *reinterpret_cast<const float4*>(p);
-    v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
-  }
-  static __device__ __forceinline__ void st(float* p, const float (&v)[4]) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  }
-};
-template <> struct V4<bf16_t> {
-  static __device__ __forceinline__ void ld(const bf16_t* p, float (&v)[4]) {
-    const bf16x4 r = *reinterpret_cast<const bf16x4*>(p);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = (float)r[i];
-  }
-  static __device__ __forceinline__ void st(bf16_t* p, const float (&v)[4]) {
-    bf16x4 r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) r[i] = (bf16_t)v[i];
-    *reinterpret_cast<bf16x4*>(p) = r;
-  }
-};
-template <> struct V4<f16_t> {
-  static __device__ __forceinline__ void ld(const f16_t* p, float (&v)[4]) {
-    const f16x4 r = *reinterpret_cast<const f16x4*>(p);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = (float)r[i];
-  }
-  static __device__ __forceinline__ void st(f16_t* p, const float (&v)[4]) {
-    f16x4 r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) r[i] = (f16_t)v[i];
-    *reinterpret_cast<f16x4*>(p) = r;
-  }
-};
 
 // HIPIE_HL8 as an OUTPUT (or addend) type of these kernels.  An HL8 row of C values occupies 4 C bytes like an fp32 row, so the kernels'
 // element indexing (row * C + c, 4-byte elements) lands on the right row; inside the row the 4 consecutive values of a lane (c % 8 is 0
 // or 4) live at bytes 32 (c / 8) + 2 (c % 8) (hi) and + 16 (lo).  With p = base + 4 c that is p / p + 16 for c % 8 == 0 and p - 8 / p + 8 for
 // c % 8 == 4 (bit 4 of p: the rows are 32-byte aligned because C % 8 == 0 and torch allocations are).
 struct hl8_t { unsigned int u; };
-template <> struct V4<hl8_t> {
-  static __device__ __forceinline__ void ld(const hl8_t* p, float (&v)[4]) {
+template <> struct Vec4<hl8_t> {
+  static __device__ __forceinline__ void load(const hl8_t* p, float (&v)[4]) {
     const char* q = reinterpret_cast<const char*>(p);
     const bool second = (reinterpret_cast<uintptr_t>(q) & 16) != 0;
     const f16x4 h = *reinterpret_cast<const f16x4*>(second ? q - 8 : q);
@@ -65,7 +26,7 @@ template <> struct V4<hl8_t> {
 #pragma unroll
     for (int i = 0; i < 4; ++i) v[i] = (float)h[i] + (float)l[i];
   }
-  static __device__ __forceinline__ void st(hl8_t* p, const float (&v)[4]) {
+  static __device__ __forceinline__ void store(hl8_t* p, const float (&v)[4]) {
     char* q = reinterpret_cast<char*>(p);
     const bool second = (reinterpret_cast<uintptr_t>(q) & 16) != 0;
     f16x4 h, l;
@@ -82,9 +43,6 @@ template <> struct V4<hl8_t> {
 };
 
 constexpr int LN_MAXV = 8;     // up to 8 x 4 elements per lane: C <= 2048
-// row maps of the call being dispatched (host-side plumbing through the dtype switch; set and cleared by the entry points)
-static thread_local const int32_t* g_delta_row = nullptr;
-static thread_local const int32_t* g_out_src = nullptr;
 
 template <typename Tx, typename Td, typename Tn>
 __global__ __launch_bounds__(256) void add_layernorm_kernel(const Tx* __restrict__ x, const Td* __restrict__ delta,
@@ -105,7 +63,7 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const Tx* __restrict
   if (row < 0) {
     const float z[4] = {0.f, 0.f, 0.f, 0.f};
     for (int i = 0; i <= nv; ++i)
-      if ((i < nv) || (lane < tail)) V4<Tn>::st(norm_out + orow * C + i * 256 + lane * 4, z);
+      if ((i < nv) || (lane < tail)) Vec4<Tn>::store(norm_out + orow * C + i * 256 + lane * 4, z);
     return;
   }
   const long drow = delta_row ? (long)delta_row[row] : row;
@@ -117,14 +75,14 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const Tx* __restrict
     const bool on = (i < nv) || (i == nv && lane < tail);
     if (on) {
       const int c = i * 256 + lane * 4;
-      V4<Tx>::ld(xr + c, v[i]);
+      Vec4<Tx>::load(xr + c, v[i]);
       if (delta != nullptr) {
         float d[4];
-        V4<Td>::ld(delta + drow * C + c, d);
+        Vec4<Td>::load(delta + drow * C + c, d);
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[i][e] += d[e];
       }
-      if (res_out != nullptr) V4<Tx>::st(res_out + row * C + c, v[i]);
+      if (res_out != nullptr) Vec4<Tx>::store(res_out + row * C + c, v[i]);
 #pragma unroll
       for (int e = 0; e < 4; ++e) sum += v[i][e];
     } else {
@@ -159,51 +117,68 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const Tx* __restrict
       o[1] = (v[i][1] - mean) * rstd * g.y + b.y;
       o[2] = (v[i][2] - mean) * rstd * g.z + b.z;
       o[3] = (v[i][3] - mean) * rstd * g.w + b.w;
-      V4<Tn>::st(norm_out + orow * C + c, o);
+      Vec4<Tn>::store(norm_out + orow * C + c, o);
       if (sum_out != nullptr) {               // the normalised row plus a second addend (e.g. the position embedding of the next query)
         float a[4];
-        V4<Tn>::ld(addend + orow * C + c, a);
+        Vec4<Tn>::load(addend + orow * C + c, a);
 #pragma unroll
         for (int e = 0; e < 4; ++e) a[e] += o[e];
-        V4<Tn>::st(sum_out + orow * C + c, a);
+        Vec4<Tn>::store(sum_out + orow * C + c, a);
       }
     }
   }
 }
 
-static thread_local const void* g_ln_addend = nullptr;     // optional extra output of the call being dispatched (as the row maps)
-static thread_local void* g_ln_sum_out = nullptr;
+// one call of add_layernorm_kernel, as the three entry points fill it in: what all of them take, then the optional arguments (null = absent)
+struct LnArgs {
+  const void* x; const void* delta; const float* gamma; const float* beta; void* res_out; void* norm_out;
+  long rows; int C; float eps;
+  int x_dtype, delta_dtype, norm_dtype;
+  hipStream_t stream;
+  const int32_t* delta_row = nullptr; const int32_t* out_src = nullptr;       // row maps (see the kernel)
+  const void* addend = nullptr; void* sum_out = nullptr;                      // second output: norm_out + addend
+};
 
 template <typename Tx, typename Td, typename Tn>
-static int launch_ln(const void* x, const void* d, const float* g, const float* b, void* r, void* n, long rows, int C,
-                     float eps, hipStream_t st) {
-  hipLaunchKernelGGL((add_layernorm_kernel<Tx, Td, Tn>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, (const Tx*)x,
-                     (const Td*)d, g, b, (Tx*)r, (Tn*)n, rows, C, eps, g_delta_row, g_out_src, (const Tn*)g_ln_addend, (Tn*)g_ln_sum_out);
+static int launch_ln(const LnArgs& a) {
+  hipLaunchKernelGGL((add_layernorm_kernel<Tx, Td, Tn>), dim3((unsigned)((a.rows + 3) / 4)), dim3(256), 0, a.stream, (const Tx*)a.x,
+                     (const Td*)a.delta, a.gamma, a.beta, (Tx*)a.res_out, (Tn*)a.norm_out, a.rows, a.C, a.eps, a.delta_row, a.out_src,
+                     (const Tn*)a.addend, (Tn*)a.sum_out);
   return check_launch("add_layernorm");
 }
 
 template <typename Tx, typename Td>
-static int ln_out(int nd, const void* x, const void* d, const float* g, const float* b, void* r, void* n, long rows, int C,
-                  float eps, hipStream_t st) {
-  switch (nd) {
-    case HIPIE_F32: return launch_ln<Tx, Td, float>(x, d, g, b, r, n, rows, C, eps, st);
-    case HIPIE_F16: return launch_ln<Tx, Td, f16_t>(x, d, g, b, r, n, rows, C, eps, st);
-    case HIPIE_BF16: return launch_ln<Tx, Td, bf16_t>(x, d, g, b, r, n, rows, C, eps, st);
+static int ln_out(const LnArgs& a) {
+  switch (a.norm_dtype) {
+    case HIPIE_F32: return launch_ln<Tx, Td, float>(a);
+    case HIPIE_F16: return launch_ln<Tx, Td, f16_t>(a);
+    case HIPIE_BF16: return launch_ln<Tx, Td, bf16_t>(a);
     case HIPIE_HL8:
-      if (C % 8 != 0 || (reinterpret_cast<uintptr_t>(n) & 31) != 0) return set_err(HIPIE_EINVAL, "add_layernorm: HL8 output needs C %% 8 == 0 and a 32-byte aligned buffer");
-      return launch_ln<Tx, Td, hl8_t>(x, d, g, b, r, n, rows, C, eps, st);
-    default: return set_err(HIPIE_EINVAL, "add_layernorm: bad norm dtype %d", nd);
+      if (a.C % 8 != 0 || (reinterpret_cast<uintptr_t>(a.norm_out) & 31) != 0) return set_err(HIPIE_EINVAL, "add_layernorm: HL8 output needs C %% 8 == 0 and a 32-byte aligned buffer");
+      return launch_ln<Tx, Td, hl8_t>(a);
+    default: return set_err(HIPIE_EINVAL, "add_layernorm: bad norm dtype %d", a.norm_dtype);
   }
 }
 
 template <typename Tx>
-static int ln_delta(int dd, int nd, const void* x, const void* d, const float* g, const float* b, void* r, void* n,
-                    long rows, int C, float eps, hipStream_t st) {
-  switch (dd) {
-    case HIPIE_F32: return ln_out<Tx, float>(nd, x, d, g, b, r, n, rows, C, eps, st);
-    case HIPIE_F16: return ln_out<Tx, f16_t>(nd, x, d, g, b, r, n, rows, C, eps, st);
-    case HIPIE_BF16: return ln_out<Tx, bf16_t>(nd, x, d, g, b, r, n, rows, C, eps, st);
-    default: return set_err(HIPIE_EINVAL, "add_layernorm: bad delta dtype %d", dd);
+static int ln_delta(const LnArgs& a) {
+  switch (a.delta_dtype) {
+    case HIPIE_F32: return ln_out<Tx, float>(a);
+    case HIPIE_F16: return ln_out<Tx, f16_t>(a);
+    case HIPIE_BF16: return ln_out<Tx, bf16_t>(a);
+    default: return set_err(HIPIE_EINVAL, "add_layernorm: bad delta dtype %d", a.delta_dtype);
+  }
+}
+
+static int add_layernorm(const LnArgs& a) {
+  HIPIE_REQUIRE(a.x && a.gamma && a.beta && a.norm_out, "add_layernorm: null pointer");
+  HIPIE_REQUIRE(a.rows >= 0 && a.C > 0 && a.C % 4 == 0 && a.C <= LN_MAXV * 256, "add_layernorm: C=%d must be a multiple of 4 and <= %d", a.C, LN_MAXV * 256);
+  if (a.rows == 0) return HIPIE_OK;
+  switch (a.x_dtype) {
+    case HIPIE_F32: return ln_delta<float>(a);
+    case HIPIE_F16: return ln_delta<f16_t>(a);
+    case HIPIE_BF16: return ln_delta<bf16_t>(a);
+    default: return set_err(HIPIE_EINVAL, "add_layernorm: bad x dtype %d", a.x_dtype);
   }
 }
 
@@ -230,8 +205,8 @@ __global__ __launch_bounds__(256) void add_layernorm_dec_kernel(const float* __r
     if (on) {
       const long c = row * C + i * 256 + lane * 4;
       float d[4];
-      V4<float>::ld(x + c, v[i]);
-      V4<Td>::ld(delta + c, d);
+      Vec4<float>::load(x + c, v[i]);
+      Vec4<Td>::load(delta + c, d);
 #pragma unroll
       for (int e = 0; e < 4; ++e) { v[i][e] += d[e]; sum += v[i][e]; }
     } else {
@@ -267,14 +242,14 @@ __global__ __launch_bounds__(256) void add_layernorm_dec_kernel(const float* __r
       o[1] = (v[i][1] - mean) * rstd * g.y + b.y;
       o[2] = (v[i][2] - mean) * rstd * g.z + b.z;
       o[3] = (v[i][3] - mean) * rstd * g.w + b.w;
-      V4<float>::st(norm_out + c, o);
-      if (norm16 != nullptr) V4<Ta>::st(norm16 + c, o);
+      Vec4<float>::store(norm_out + c, o);
+      if (norm16 != nullptr) Vec4<Ta>::store(norm16 + c, o);
       if (sum16 != nullptr) {
         float a[4];
-        V4<Ta>::ld(addend + c, a);
+        Vec4<Ta>::load(addend + c, a);
 #pragma unroll
         for (int e = 0; e < 4; ++e) a[e] += o[e];
-        V4<Ta>::st(sum16 + c, a);
+        Vec4<Ta>::store(sum16 + c, a);
       }
     }
   }
@@ -294,42 +269,29 @@ __global__ __launch_bounds__(256) void add_cast_kernel(const float* __restrict__
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n4) return;
   float x[4], y[4];
-  V4<float>::ld(a + 4 * i, x);
-  V4<Ta>::ld(b + 4 * i, y);
+  Vec4<float>::load(a + 4 * i, x);
+  Vec4<Ta>::load(b + 4 * i, y);
 #pragma unroll
   for (int e = 0; e < 4; ++e) x[e] += y[e];
-  V4<Ta>::st(out + 4 * i, x);
+  Vec4<Ta>::store(out + 4 * i, x);
 }
 
 }  // namespace hipie
+
+extern "C" int hipie_add_layernorm(const void* x, const void* delta, const float* gamma, const float* beta, void* res_out,
+                                   void* norm_out, int64_t rows, int C, float eps, int x_dtype, int delta_dtype,
+                                   int norm_dtype, void* stream) {
+  return hipie::add_layernorm({x, delta, gamma, beta, res_out, norm_out, rows, C, eps, x_dtype, delta_dtype, norm_dtype, (hipStream_t)stream});
+}
 
 extern "C" int hipie_add_layernorm_rows(const void* x, const void* delta, const float* gamma, const float* beta,
                                         void* res_out, void* norm_out, int64_t out_rows, int C, float eps, int x_dtype,
                                         int delta_dtype, int norm_dtype, const int32_t* delta_row, const int32_t* out_src,
                                         void* stream) {
-  hipie::g_delta_row = delta_row;
-  hipie::g_out_src = out_src;
-  const int rc = hipie_add_layernorm(x, delta, gamma, beta, res_out, norm_out, out_rows, C, eps, x_dtype, delta_dtype,
-                                     norm_dtype, stream);
-  hipie::g_delta_row = nullptr;
-  hipie::g_out_src = nullptr;
-  return rc;
-}
-
-extern "C" int hipie_add_layernorm(const void* x, const void* delta, const float* gamma, const float* beta, void* res_out,
-                                   void* norm_out, int64_t rows, int C, float eps, int x_dtype, int delta_dtype,
-                                   int norm_dtype, void* stream) {
-  using namespace hipie;
-  HIPIE_REQUIRE(x && gamma && beta && norm_out, "add_layernorm: null pointer");
-  HIPIE_REQUIRE(rows >= 0 && C > 0 && C % 4 == 0 && C <= LN_MAXV * 256, "add_layernorm: C=%d must be a multiple of 4 and <= %d", C, LN_MAXV * 256);
-  if (rows == 0) return HIPIE_OK;
-  hipStream_t st = (hipStream_t)stream;
-  switch (x_dtype) {
-    case HIPIE_F32: return ln_delta<float>(delta_dtype, norm_dtype, x, delta, gamma, beta, res_out, norm_out, rows, C, eps, st);
-    case HIPIE_F16: return ln_delta<f16_t>(delta_dtype, norm_dtype, x, delta, gamma, beta, res_out, norm_out, rows, C, eps, st);
-    case HIPIE_BF16: return ln_delta<bf16_t>(delta_dtype, norm_dtype, x, delta, gamma, beta, res_out, norm_out, rows, C, eps, st);
-    default: return set_err(HIPIE_EINVAL, "add_layernorm: bad x dtype %d", x_dtype);
-  }
+  hipie::LnArgs a = {x, delta, gamma, beta, res_out, norm_out, out_rows, C, eps, x_dtype, delta_dtype, norm_dtype, (hipStream_t)stream};
+  a.delta_row = delta_row;
+  a.out_src = out_src;
+  return hipie::add_layernorm(a);
 }
 
 extern "C" int hipie_add_layernorm_dec(const float* x, const void* delta, const float* gamma, const float* beta, float* norm_out,
@@ -383,10 +345,8 @@ extern "C" int hipie_add_layernorm_sum(const void* x, const void* delta, const f
                                        int x_dtype, int delta_dtype, int norm_dtype, void* stream) {
   using namespace hipie;
   HIPIE_REQUIRE((addend == nullptr) == (sum_out == nullptr), "add_layernorm_sum: addend and sum_out go together");
-  g_ln_addend = addend;
-  g_ln_sum_out = sum_out;
-  const int rc = hipie_add_layernorm(x, delta, gamma, beta, res_out, norm_out, rows, C, eps, x_dtype, delta_dtype, norm_dtype, stream);
-  g_ln_addend = nullptr;
-  g_ln_sum_out = nullptr;
-  return rc;
+  LnArgs a = {x, delta, gamma, beta, res_out, norm_out, rows, C, eps, x_dtype, delta_dtype, norm_dtype, (hipStream_t)stream};
+  a.addend = addend;
+  a.sum_out = sum_out;
+  return add_layernorm(a);
 }

@@ -32,6 +32,7 @@
 
 #include "common.h"
 #include "mfma.h"
+#include "wave.h"
 
 namespace hipie {
 
@@ -275,14 +276,6 @@ constexpr int MD_PART = ME_QB * 32 * MD_ROW;              // 10 x 1 KB
 constexpr int MD_CHUNK = 2 * MD_PART;                     // hi + lo: the image of one K chunk of one pass of one batch item
 constexpr int MD_PERIOD = 4;                              // feature register sets (the K loop runs in multiples of this)
 
-__device__ __forceinline__ void me_dma16(const char* sbase, unsigned int voff, unsigned int lds_dst) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  unsigned int keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-#endif
-}
-constexpr int me_vmcnt(int n) { return 0x0F70 | (n & 15) | ((n >> 4) << 14); }   // s_waitcnt vmcnt(n) only (gfx9 encoding)
 
 // workspace image: [batch][pass][chunk 0 .. nk4)[part][320 rows][2 units of 8 bf16, swizzled]; rows past Q and chunks past C / 16 = 0
 __global__ __launch_bounds__(256) void me_split_embed_kernel(const float* __restrict__ embed, char* __restrict__ ws, int Q, int C,
@@ -355,7 +348,7 @@ __global__ __launch_bounds__(MX_WAVES * 64, 2) void mask_einsum_dma_kernel(const
 #pragma unroll
       for (int j = 0; j < DPW; ++j) {               // NDMA is not a multiple of 4: the last round repeats the last piece (same bytes,
         const int i = min(wave + MX_WAVES * j, NDMA - 1);   // same place) rather than branch -- every wave issues exactly DPW
-        me_dma16(src + 1024 * i, dvoff, __builtin_amdgcn_readfirstlane(dst + 1024 * i));
+        dma16(src + 1024 * i, dvoff, __builtin_amdgcn_readfirstlane(dst + 1024 * i));
       }
     };
     f32x16 acc[ME_QB];
@@ -378,7 +371,7 @@ __global__ __launch_bounds__(MX_WAVES * 64, 2) void mask_einsum_dma_kernel(const
 #pragma unroll
       for (int j = 0; j < 8; ++j) f2[j] = Fl[(long)(c2 + j) * P];
     }
-    __builtin_amdgcn_s_waitcnt(me_vmcnt(24));       // the DMA pieces are older than the 24 feature loads (vmcnt counts in order)
+    __builtin_amdgcn_s_waitcnt(vmcnt(24));       // the DMA pieces are older than the 24 feature loads (vmcnt counts in order)
     __syncthreads();
 
     // One K-chunk: `cur` holds its features (loaded three steps ago), `nxt3` receives those of chunk k + 3; the image of chunk
@@ -412,7 +405,7 @@ __global__ __launch_bounds__(MX_WAVES * 64, 2) void mask_einsum_dma_kernel(const
         acc[qb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[qb], 0, 0, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_waitcnt(me_vmcnt(16 + DPW));   // this wave's pieces of chunk k + 1 have landed ...
+      __builtin_amdgcn_s_waitcnt(vmcnt(16 + DPW));   // this wave's pieces of chunk k + 1 have landed ...
       __syncthreads();                              // ... everybody's; all reads of chunk k are done
     };
     // four steps per trip, the feature sets taking turns by name (a register rotation would wait for the loads it copies); the
@@ -434,7 +427,7 @@ __global__ __launch_bounds__(MX_WAVES * 64, 2) void mask_einsum_dma_kernel(const
         }
       }
     }
-    __builtin_amdgcn_s_waitcnt(me_vmcnt(0));        // the clamped DMA of the last step targets the buffer the next pass fills
+    __builtin_amdgcn_s_waitcnt(vmcnt(0));        // the clamped DMA of the last step targets the buffer the next pass fills
     __syncthreads();                                // rbs / the LDS tile are rewritten by the next pass
   }
 }

@@ -24,42 +24,9 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "wave.h"
 
 namespace hipie {
-
-template <typename T> struct Vec4;
-template <> struct Vec4<float> {
-  typedef float4 raw;
-  static __device__ __forceinline__ void load(const float* p, float (&v)[4]) {
-    float4 r = *reinterpret_cast<const float4*>(p);
-    v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
-  }
-  static __device__ __forceinline__ void store(float* p, const float (&v)[4]) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  }
-};
-template <> struct Vec4<bf16_t> {
-  static __device__ __forceinline__ void load(const bf16_t* p, float (&v)[4]) {
-    bf16x4 r = *reinterpret_cast<const bf16x4*>(p);
-    for (int i = 0; i < 4; ++i) v[i] = (float)r[i];
-  }
-  static __device__ __forceinline__ void store(bf16_t* p, const float (&v)[4]) {
-    bf16x4 r;
-    for (int i = 0; i < 4; ++i) r[i] = (bf16_t)v[i];
-    *reinterpret_cast<bf16x4*>(p) = r;
-  }
-};
-template <> struct Vec4<f16_t> {
-  static __device__ __forceinline__ void load(const f16_t* p, float (&v)[4]) {
-    f16x4 r = *reinterpret_cast<const f16x4*>(p);
-    for (int i = 0; i < 4; ++i) v[i] = (float)r[i];
-  }
-  static __device__ __forceinline__ void store(f16_t* p, const float (&v)[4]) {
-    f16x4 r;
-    for (int i = 0; i < 4; ++i) r[i] = (f16_t)v[i];
-    *reinterpret_cast<f16x4*>(p) = r;
-  }
-};
 
 constexpr int kMaxLP = 32;  // L*P supported by the fused softmax (reference geometry: 4*4 = 16)
 
@@ -309,10 +276,6 @@ __global__ __launch_bounds__(256) void msda_generic_kernel(const T* __restrict__
   out[idx] = elem<T>::from_f32(col);
 }
 
-// value row stride of the call being dispatched (host-side plumbing through the dtype switch; 0 = dense M * D)
-static thread_local long g_value_row = 0;
-
-
 // double instantiation of the reference op (AT_DISPATCH_FLOATING_TYPES, ms_deform_attn_cuda.cu:56): one thread per output element,
 // every quantity in f64 in the reference's operation order (ms_deform_attn_im2col_bilinear, ms_deform_im2col_cuda.cuh:21-73, 237-299).
 // Not on the product path -- it completes the plugin boundary (ops/test.py checks the op in double).
@@ -353,13 +316,22 @@ __global__ __launch_bounds__(256) void msda_f64_kernel(const double* __restrict_
   out[idx] = col;
 }
 
+// one call of the forward kernels, as the entry points fill it in (a / w: sampling locations + attention weights, or, FUSED, offsets + logits)
+struct MsdaArgs {
+  const void* value; const int64_t* shapes; const int64_t* lstart; const void* a; const void* w; const float* ref; void* out;
+  int B, S, M, D, L, Lq, P, ref_dim;
+  int dtype, aux_dtype;
+  long off_stride, w_stride;
+  long value_row;               // elements from one pixel's channels to the next pixel's; 0 = dense (M * D)
+  hipStream_t stream;
+};
+
 template <typename T, typename A, bool FUSED>
-static int launch_msda(const void* value, const int64_t* shapes, const int64_t* lstart, const void* a, const void* w,
-                       const float* ref, void* out, int B, int S, int M, int D, int L, int Lq, int P, int ref_dim,
-                       long off_stride, long w_stride, hipStream_t st) {
+static int launch_msda(const MsdaArgs& p) {
+  const int B = p.B, S = p.S, M = p.M, D = p.D, L = p.L, Lq = p.Lq, P = p.P;
   const long groups = (long)B * Lq * M;
   if (groups == 0) return HIPIE_OK;
-  const long vrow = g_value_row > 0 ? g_value_row : (long)M * D;
+  const long vrow = p.value_row > 0 ? p.value_row : (long)M * D;
   if (D == 32) {
     // group -> workgroup map (see the kernel): tiles of the pyramid when the queries are its pixels, else runs of 32 queries of
     // one head; HIPIE_MSDA_MAP=0 restores the heads-fastest order (A/B timing: tools/bench_msda.py)
@@ -368,51 +340,48 @@ static int launch_msda(const void* value, const int64_t* shapes, const int64_t* 
     const long blocks = map == 0 ? (groups + 31) / 32 : (((long)B * Lq + 31) / 32) * M;
     const size_t lds = (size_t)32 * (L * P * 8 + 4) * sizeof(float);
     // unroll 2 of the record loop: 0.467 ms vs 0.480 (1, 4, 8) on the bs-8 encoder geometry (tools/bench_msda.py)
-    hipLaunchKernelGGL((msda_d32_kernel<T, A, FUSED, 2>), dim3((unsigned)blocks), dim3(256), lds, st, (const T*)value, shapes,
-                       lstart, (const A*)a, (const A*)w, ref, (T*)out, S, M, L, Lq, P, ref_dim, groups, off_stride, w_stride, vrow, map);
+    hipLaunchKernelGGL((msda_d32_kernel<T, A, FUSED, 2>), dim3((unsigned)blocks), dim3(256), lds, p.stream, (const T*)p.value, p.shapes,
+                       p.lstart, (const A*)p.a, (const A*)p.w, p.ref, (T*)p.out, S, M, L, Lq, P, p.ref_dim, groups, p.off_stride, p.w_stride,
+                       vrow, map);
   } else {
     const long n = groups * D;
     const long blocks = (n + 255) / 256;
-    hipLaunchKernelGGL((msda_generic_kernel<T, A, FUSED>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)value,
-                       shapes, lstart, (const A*)a, (const A*)w, ref, (T*)out, S, M, D, L, Lq, P, ref_dim, n, off_stride, w_stride, vrow);
+    hipLaunchKernelGGL((msda_generic_kernel<T, A, FUSED>), dim3((unsigned)blocks), dim3(256), 0, p.stream, (const T*)p.value, p.shapes,
+                       p.lstart, (const A*)p.a, (const A*)p.w, p.ref, (T*)p.out, S, M, D, L, Lq, P, p.ref_dim, n, p.off_stride, p.w_stride,
+                       vrow);
   }
   return check_launch("msda");
 }
 
 template <typename T, bool FUSED>
-static int dispatch_aux(int aux_dtype, const void* value, const int64_t* shapes, const int64_t* lstart, const void* a,
-                        const void* w, const float* ref, void* out, int B, int S, int M, int D, int L, int Lq, int P,
-                        int ref_dim, long off_stride, long w_stride, hipStream_t st) {
-  switch (aux_dtype) {
-    case HIPIE_F32: return launch_msda<T, float, FUSED>(value, shapes, lstart, a, w, ref, out, B, S, M, D, L, Lq, P, ref_dim, off_stride, w_stride, st);
-    case HIPIE_F16: return launch_msda<T, f16_t, FUSED>(value, shapes, lstart, a, w, ref, out, B, S, M, D, L, Lq, P, ref_dim, off_stride, w_stride, st);
-    case HIPIE_BF16: return launch_msda<T, bf16_t, FUSED>(value, shapes, lstart, a, w, ref, out, B, S, M, D, L, Lq, P, ref_dim, off_stride, w_stride, st);
-    default: return set_err(HIPIE_EINVAL, "msda: unsupported aux dtype %d", aux_dtype);
+static int dispatch_aux(const MsdaArgs& p) {
+  switch (p.aux_dtype) {
+    case HIPIE_F32: return launch_msda<T, float, FUSED>(p);
+    case HIPIE_F16: return launch_msda<T, f16_t, FUSED>(p);
+    case HIPIE_BF16: return launch_msda<T, bf16_t, FUSED>(p);
+    default: return set_err(HIPIE_EINVAL, "msda: unsupported aux dtype %d", p.aux_dtype);
   }
 }
 
-
 template <bool FUSED>
-static int dispatch_msda(const void* value, const int64_t* shapes, const int64_t* lstart, const void* a, const void* w,
-                         const float* ref, void* out, int B, int S, int M, int D, int L, int Lq, int P, int ref_dim,
-                         int dtype, int aux_dtype, long off_stride, long w_stride, void* stream) {
+static int dispatch_msda(const MsdaArgs& p) {
+  const int B = p.B, S = p.S, M = p.M, D = p.D, L = p.L, Lq = p.Lq, P = p.P;
   HIPIE_REQUIRE(B >= 0 && S > 0 && M > 0 && D > 0 && L > 0 && Lq >= 0 && P > 0, "msda: bad shape B=%d S=%d M=%d D=%d L=%d Lq=%d P=%d", B, S, M, D, L, Lq, P);
   if (B == 0 || Lq == 0) return HIPIE_OK;              // no queries: nothing to write (pointers of empty tensors may be null)
-  HIPIE_REQUIRE(value && shapes && lstart && a && w && out, "msda: null pointer");
+  HIPIE_REQUIRE(p.value && p.shapes && p.lstart && p.a && p.w && p.out, "msda: null pointer");
   HIPIE_REQUIRE((long)B * S * M * D < (1L << 40), "msda: tensor too large");
-  HIPIE_REQUIRE(off_stride >= (long)M * L * P * 2 && w_stride >= (long)M * L * P, "msda: row strides too small");
-  HIPIE_REQUIRE((long)S * (g_value_row > 0 ? g_value_row : (long)M * D) < (1L << 31), "msda: one image's value block exceeds the 32-bit sample offsets");
-  HIPIE_REQUIRE(g_value_row == 0 || (g_value_row >= (long)M * D && g_value_row % 8 == 0), "msda: value row stride %ld < M*D or not a multiple of 8", g_value_row);
+  HIPIE_REQUIRE(p.off_stride >= (long)M * L * P * 2 && p.w_stride >= (long)M * L * P, "msda: row strides too small");
+  HIPIE_REQUIRE((long)S * (p.value_row > 0 ? p.value_row : (long)M * D) < (1L << 31), "msda: one image's value block exceeds the 32-bit sample offsets");
+  HIPIE_REQUIRE(p.value_row == 0 || (p.value_row >= (long)M * D && p.value_row % 8 == 0), "msda: value row stride %ld < M*D or not a multiple of 8", p.value_row);
   if (FUSED) {
-    HIPIE_REQUIRE(ref != nullptr && (ref_dim == 2 || ref_dim == 4), "msda_fused: ref_dim must be 2 or 4 (got %d)", ref_dim);
+    HIPIE_REQUIRE(p.ref != nullptr && (p.ref_dim == 2 || p.ref_dim == 4), "msda_fused: ref_dim must be 2 or 4 (got %d)", p.ref_dim);
     HIPIE_REQUIRE(L * P <= kMaxLP, "msda_fused: L*P=%d > %d", L * P, kMaxLP);
   }
-  hipStream_t st = (hipStream_t)stream;
-  switch (dtype) {
-    case HIPIE_F32: return dispatch_aux<float, FUSED>(aux_dtype, value, shapes, lstart, a, w, ref, out, B, S, M, D, L, Lq, P, ref_dim, off_stride, w_stride, st);
-    case HIPIE_F16: return dispatch_aux<f16_t, FUSED>(aux_dtype, value, shapes, lstart, a, w, ref, out, B, S, M, D, L, Lq, P, ref_dim, off_stride, w_stride, st);
-    case HIPIE_BF16: return dispatch_aux<bf16_t, FUSED>(aux_dtype, value, shapes, lstart, a, w, ref, out, B, S, M, D, L, Lq, P, ref_dim, off_stride, w_stride, st);
-    default: return set_err(HIPIE_EINVAL, "msda: unsupported dtype %d", dtype);
+  switch (p.dtype) {
+    case HIPIE_F32: return dispatch_aux<float, FUSED>(p);
+    case HIPIE_F16: return dispatch_aux<f16_t, FUSED>(p);
+    case HIPIE_BF16: return dispatch_aux<bf16_t, FUSED>(p);
+    default: return set_err(HIPIE_EINVAL, "msda: unsupported dtype %d", p.dtype);
   }
 }
 
@@ -435,16 +404,16 @@ extern "C" int hipie_msda_forward(const void* value, const int64_t* spatial_shap
                                   int D, int L, int Lq, int P, int value_dtype, void* stream) {
   if (value_dtype == HIPIE_F64)
     return msda_forward_f64(value, spatial_shapes, level_start, sampling_loc, attn_weight, out, B, S, M, D, L, Lq, P, stream);
-  return hipie::dispatch_msda<false>(value, spatial_shapes, level_start, sampling_loc, attn_weight, nullptr, out, B, S,
-                                     M, D, L, Lq, P, 2, value_dtype, HIPIE_F32, (long)M * L * P * 2, (long)M * L * P, stream);
+  return hipie::dispatch_msda<false>({value, spatial_shapes, level_start, sampling_loc, attn_weight, nullptr, out, B, S, M, D, L, Lq, P, 2,
+                                      value_dtype, HIPIE_F32, (long)M * L * P * 2, (long)M * L * P, 0, (hipStream_t)stream});
 }
 
 extern "C" int hipie_msda_fused_forward(const void* value, const int64_t* spatial_shapes, const int64_t* level_start,
                                         const float* ref, const void* offsets, const void* logits, void* out, int B,
                                         int S, int M, int D, int L, int Lq, int P, int ref_dim, int value_dtype,
                                         int aux_dtype, int64_t off_row_stride, int64_t logit_row_stride, void* stream) {
-  return hipie::dispatch_msda<true>(value, spatial_shapes, level_start, offsets, logits, ref, out, B, S, M, D, L, Lq, P,
-                                    ref_dim, value_dtype, aux_dtype, off_row_stride, logit_row_stride, stream);
+  return hipie::dispatch_msda<true>({value, spatial_shapes, level_start, offsets, logits, ref, out, B, S, M, D, L, Lq, P, ref_dim, value_dtype,
+                                     aux_dtype, off_row_stride, logit_row_stride, 0, (hipStream_t)stream});
 }
 
 extern "C" int hipie_msda_fused_forward_strided(const void* value, int64_t value_row_stride, const int64_t* spatial_shapes,
@@ -452,9 +421,6 @@ extern "C" int hipie_msda_fused_forward_strided(const void* value, int64_t value
                                                 const void* logits, void* out, int B, int S, int M, int D, int L, int Lq, int P,
                                                 int ref_dim, int value_dtype, int aux_dtype, int64_t off_row_stride,
                                                 int64_t logit_row_stride, void* stream) {
-  hipie::g_value_row = value_row_stride;
-  const int rc = hipie::dispatch_msda<true>(value, spatial_shapes, level_start, offsets, logits, ref, out, B, S, M, D, L, Lq, P,
-                                            ref_dim, value_dtype, aux_dtype, off_row_stride, logit_row_stride, stream);
-  hipie::g_value_row = 0;
-  return rc;
+  return hipie::dispatch_msda<true>({value, spatial_shapes, level_start, offsets, logits, ref, out, B, S, M, D, L, Lq, P, ref_dim, value_dtype,
+                                     aux_dtype, off_row_stride, logit_row_stride, value_row_stride, (hipStream_t)stream});
 }

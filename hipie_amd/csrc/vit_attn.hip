@@ -23,6 +23,7 @@
 
 #include "common.h"
 #include "mfma.h"
+#include "wave.h"
 
 namespace hipie {
 
@@ -37,12 +38,6 @@ struct VAParams {
   int nqt, swz, prio;
 };
 
-__device__ __forceinline__ float va_max3(float a, float b, float c) {
-  float d;
-  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-  return d;
-}
-
 // keep a value alive without cost (timing ablations): an asm statement with a "v" operand must live in a __device__ function
 // -- inside the __global__ body the host pass rejects the constraint and silently drops the kernel stub
 template <typename V> __host__ __device__ __forceinline__ void va_keep(V v) {
@@ -56,15 +51,6 @@ __host__ __device__ __forceinline__ void va_pin(float& x) {
 #if defined(__HIP_DEVICE_COMPILE__)
   asm volatile("" : "+v"(x));
 #endif
-}
-
-// max over the two 32-lane halves (lane l <-> l ^ 32) without LDS: v_permlane32_swap exchanges the upper half of its first
-// operand with the lower half of its second
-__device__ __forceinline__ float va_xhalf_max(float x) {
-  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-  const unsigned int u = __builtin_bit_cast(unsigned int, x);
-  const u32x2 r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return fmaxf(__builtin_bit_cast(float, (unsigned int)r[0]), __builtin_bit_cast(float, (unsigned int)r[1]));
 }
 
 // T: bf16_t | f16_t;  HD: head dim (64 | 80);  NB: 32-slot key blocks per tile;  FAST: deferred max + MFMA row sums;
@@ -300,8 +286,8 @@ __global__ __launch_bounds__(WAVES * 64, 2) void vit_attn_kernel(const VAParams 
 #pragma unroll
       for (int blk = 0; blk < NB; ++blk)
 #pragma unroll
-        for (int r = 0; r < 16; r += 2) mx = va_max3(mx, S[blk][r], S[blk][r + 1]);
-      mx = va_xhalf_max(mx);
+        for (int r = 0; r < 16; r += 2) mx = max3(mx, S[blk][r], S[blk][r + 1]);
+      mx = xhalf_max(mx);
     }
     mx += (R > 1 ? 0.f : bh0);
     // the reference point m_run only moves when some row's maximum grew by more than 2^DEFER (FAST) / at all (exact)
@@ -445,17 +431,6 @@ static int launch_va(VAParams& p, hipStream_t st) {
 //   * K ring 3 deep, V ring 2 deep; the first K fragments of the next tile are fetched before the tile barrier.
 __device__ __attribute__((aligned(32))) const unsigned short g_va_pad_bf16[16] = {0x3F80, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};     // [1.0, 0 x 7 | 0 x 8]
 __device__ __attribute__((aligned(32))) const unsigned short g_va_pad_f16[16] = {0x3C00, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-
-// LDS-DMA of 16 bytes per lane: LDS[lds_dst + 16 * lane] <- *gsrc.  Inline asm on purpose: the compiler tracks the builtin form as
-// an LDS write and puts s_waitcnt vmcnt(0) in front of every later ds_read (a full L2 round trip per DMA, measured); here the
-// completion is counted by hand -- vmcnt(0) before the tile barrier.  M0 carries the wave-uniform LDS byte address.
-__device__ __forceinline__ void va_dma16(const void* gsrc, unsigned int lds_dst) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  unsigned int keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-#endif
-}
 
 template <typename T> __device__ __forceinline__ unsigned int va_bits16(T x) { return (unsigned int)__builtin_bit_cast(unsigned short, x); }
 
@@ -612,7 +587,7 @@ __global__ __launch_bounds__(512, 2) void vit_attn_sp_kernel(const VAParams p) {
       if (tt < 0) continue;
       const unsigned int dst = lds0 + (isk ? (unsigned int)(ks_ * KBUF * sizeof(T)) + 1024u * j
                                              : (unsigned int)((3 * KBUF + vs_ * VBUF) * sizeof(T)) + 1024u * (j - KBLK));
-      va_dma16(dsrc[r] + (long)tt * dstep[r], __builtin_amdgcn_readfirstlane(dst));
+      dma16_off(dsrc[r] + (long)tt * dstep[r], __builtin_amdgcn_readfirstlane(dst));
     }
   };
 
@@ -639,7 +614,7 @@ __global__ __launch_bounds__(512, 2) void vit_attn_sp_kernel(const VAParams p) {
   dma_tiles(0, 0, 0, 0);
   dma_tiles(nt > 1 ? 1 : -1, 1, -1, 0);
   dma_tiles(nt > 2 ? 2 : -1, 2, -1, 0);
-  __builtin_amdgcn_s_waitcnt(0x0F70);       // vmcnt(0): this wave's DMA writes have landed
+  __builtin_amdgcn_s_waitcnt(vmcnt(0));       // this wave's DMA writes have landed
   __syncthreads();
 
   f32x16 SA[NB], SB[NB];
@@ -662,7 +637,7 @@ __global__ __launch_bounds__(512, 2) void vit_attn_sp_kernel(const VAParams p) {
     for (int blk = 0; blk < NB; ++blk)
 #pragma unroll
       for (int r = 0; r < 16; r += 2) mx = __builtin_fmaxf(__builtin_fmaxf(mx, SA[blk][r]), SA[blk][r + 1]);
-    mx = va_xhalf_max(mx);
+    mx = xhalf_max(mx);
     m_run = __builtin_ceilf(mx * 16.f) * 0.0625f;
 #pragma unroll
     for (int blk = 0; blk < NB; ++blk)
@@ -810,14 +785,14 @@ __global__ __launch_bounds__(512, 2) void vit_attn_sp_kernel(const VAParams p) {
     }
 #undef SP_PUNIT
     const long long c2 = (ABL >= 8) ? clock64() : 0;
-    __builtin_amdgcn_s_waitcnt(0x0F70);       // vmcnt(0): this wave's DMA writes of the iteration have landed
+    __builtin_amdgcn_s_waitcnt(vmcnt(0));       // this wave's DMA writes of the iteration have landed
     __syncthreads();
     const long long c3 = (ABL >= 8) ? clock64() : 0;
     if (ABL >= 8) { dbg[0] += c1 - c0; dbg[1] += c2 - c1; dbg[2] += c3 - c2; dbg[3] += grow_any ? 1 : 0; }
 
     // ================= reference update (cold unless a score left the window) =================
     if (grow_any) {
-      const float mx = va_xhalf_max(mxp[0]);                          // row maximum of S_next relative to m_run
+      const float mx = xhalf_max(mxp[0]);                          // row maximum of S_next relative to m_run
       const float dlt = __builtin_ceilf(fmaxf(mx, 0.f) * 16.f) * 0.0625f;      // new reference = m_run + dlt, on the 1/16 grid
       const float alpha = __builtin_amdgcn_exp2f(-dlt);
       m_run += dlt;

@@ -22,6 +22,7 @@
 
 #include "common.h"
 #include "mfma.h"
+#include "wave.h"
 
 #ifndef HIPIE_VS_TAIL
 #define HIPIE_VS_TAIL 1        // 0: hd 80 as three 32-row blocks with a ones column (the round-4 form), for A/B timing builds only
@@ -46,73 +47,6 @@ struct VSParams {
   int tr, kwm;
   long krs, kts;                // fp16 elements between consecutive key slots of a tile / between consecutive tiles
 };
-
-__device__ __forceinline__ float vs_max3(float a, float b, float c) {
-  float d;
-  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-  return d;
-}
-
-__device__ __forceinline__ float vs_xhalf_max(float x) {
-  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-  const unsigned int u = __builtin_bit_cast(unsigned int, x);
-  const u32x2 r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return fmaxf(__builtin_bit_cast(float, (unsigned int)r[0]), __builtin_bit_cast(float, (unsigned int)r[1]));
-}
-
-// two probabilities -> one VGPR of fp16 hi halves and one of lo halves, lo = fp16(p - hi) from ONE instruction each: v_fma_mix{lo,hi}_f16
-// forms p - hi exactly (the fp16 hi enters as an fp16 source operand) and rounds once.  The C++ form `(T)(pv - (float)(T)pv)` costs a
-// v_cvt_f16_f32, a v_cvt_f32_f16 and a v_sub_f32 per VALUE on top of the two packs: 4 instead of 1.5 VALU per probability, 80 of the
-// ~230 VALU instructions a wave issues per 64-key tile of the global-attention instance.
-__device__ __forceinline__ void vs_split2(const float a, const float b, unsigned int& H, unsigned int& L) {
-#if defined(__HIP_DEVICE_COMPILE__) && defined(HIPIE_NO_FMA_MIX)
-  typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-  h2v h, l;
-  h[0] = (f16_t)a; h[1] = (f16_t)b;
-  l[0] = (f16_t)(a - (float)h[0]); l[1] = (f16_t)(b - (float)h[1]);
-  H = __builtin_bit_cast(unsigned int, h);
-  L = __builtin_bit_cast(unsigned int, l);
-#elif defined(__HIP_DEVICE_COMPILE__)
-  unsigned int h, l;
-  asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h) : "v"(a), "v"(b));
-  asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l) : "v"(h), "v"(a));
-  asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l) : "v"(h), "v"(b));
-  H = h;
-  L = l;
-#endif
-}
-
-// hipcc's hazard recogniser does not look inside inline asm: a VGPR written by the statements above and read by the NEXT instruction as an
-// MFMA operand or by v_permlane*_swap is read too early (gfx950 needs 2 wait states there; round 5: the a22 error of the full-depth
-// fixture went from 5e-5 to 1e-3 -- isolated stale fragments -- until this was added; tools/split_form_check.py shows the split itself
-// is bit-identical to the C++ form).  One s_nop behind a block of splits, tied to every register the block wrote.
-__device__ __forceinline__ void vs_settle(unsigned int (&h)[4], unsigned int (&l)[4]) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("s_nop 1" : "+v"(h[0]), "+v"(h[1]), "+v"(h[2]), "+v"(h[3]), "+v"(l[0]), "+v"(l[1]), "+v"(l[2]), "+v"(l[3]));
-#endif
-}
-
-// The other direction: the probabilities come out of v_exp_f32, and on gfx950 a transcendental result needs one wait state before a
-// non-transcendental VALU instruction reads it.  hipcc inserts it for instructions it can see -- not for the asm statements of vs_split2.
-// Where the scheduler happened to put something between the two nothing showed; in the 96-slot instance with the 16-row tail it did not,
-// and the splits read stale registers (garbage outputs, round 5).  One s_nop behind the block of exps, tied to all of them.
-__device__ __forceinline__ void vs_exp_settle(float (&pv)[8]) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("s_nop 0" : "+v"(pv[0]), "+v"(pv[1]), "+v"(pv[2]), "+v"(pv[3]), "+v"(pv[4]), "+v"(pv[5]), "+v"(pv[6]), "+v"(pv[7]));
-#endif
-}
-
-// LDS-DMA of 16 bytes per lane: LDS[lds_dst + 16 * lane] <- *(sbase + voff) for the lanes of `mask` (see gemm.hip / vit_attn.hip for the
-// inline-asm form).  The lane mask (a tile's row-padding chunks are neither fetched nor written) is applied inside the statement --
-// s_and_saveexec / s_mov exec around the load, no branch -- and M0 is simply overwritten (nothing else in this kernel uses it): 5 scalar
-// instructions per DMA where the compiler's own predication + an M0 save / restore took 12.
-__device__ __forceinline__ void vs_dma16(const char* sbase, unsigned int voff, unsigned int lds_dst, unsigned long long mask) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  unsigned long long save;
-  asm volatile("s_and_saveexec_b64 %0, %4\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b64 exec, %0"
-               : "=&s"(save) : "v"(voff), "s"(sbase), "s"(lds_dst), "s"(mask) : "memory", "m0");
-#endif
-}
 
 // HD: head dim (80 | 64);  NB: 32-slot key blocks per tile;  R: key rows of the token grid per tile;  KW: compile-time grid width when R > 1
 // BHC: 0 = the bias_h of every key row is computed up front ([kh][queries] floats of LDS); > 0 = it is recomputed per chunk of BHC
@@ -142,7 +76,7 @@ __global__ __launch_bounds__(WAVES * 64, (NB >= 3 ? 1 : 2)) void vit_attn_split_
   // pipe is the power-limited resource of this kernel: time follows the MFMA work issued, not the instruction count).  The tail's B operand
   // needs a lane's 16 queries x 4 k-groups where the S^T layout has 32 queries x 2 halves: two v_permlane16_swap per VGPR re-deal the two
   // 16-key steps of a 32-key block into the fragments of queries 0-15 (X) and 16-31 (Y); see the PV loop.
-  // (all instances; the 96-slot one of the 84 x 84 grid gave garbage with it until vs_exp_settle: its splits read v_exp_f32 results early)
+  // (all instances; the 96-slot one of the 84 x 84 grid gave garbage with it until exp_settle: its splits read v_exp_f32 results early)
   constexpr bool TAIL = (HD % 32 == 16) && (HIPIE_VS_TAIL != 0) && NB <= HIPIE_VS_TAIL_MAXNB;
   constexpr int DBB = TAIL ? HD / 32 : DB;     // full 32-row d blocks that run on the 32x32x16 MFMA
   constexpr bool ONES = (DB * 32 > HD) && !TAIL;
@@ -301,7 +235,7 @@ __global__ __launch_bounds__(WAVES * 64, (NB >= 3 ? 1 : 2)) void vit_attn_split_
     const bool last_ragged = ragged && (t == nt - 1);
     const unsigned int vo = last_ragged ? dma_voff(r, p.N - t * nkt - 1) : dvoff[r];
     const unsigned int ldst = __builtin_amdgcn_readfirstlane(lds0 + (unsigned int)(buf * BUF * (int)sizeof(T) + 1024 * j));
-    vs_dma16(kbase0 + (long)t * tile_bytes, vo, ldst, dmask[r]);
+    dma16_masked(kbase0 + (long)t * tile_bytes, vo, ldst, dmask[r]);
   };
 
   // row padding of the V planes of both buffers (the prologue's staging area overlapped them): zeros, and 1.0 in column HD of V_hi
@@ -329,7 +263,7 @@ __global__ __launch_bounds__(WAVES * 64, (NB >= 3 ? 1 : 2)) void vit_attn_split_
 
 #pragma unroll
   for (int r = 0; r < NDMA; ++r) dma_tile(0, 0, r);
-  __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0)
+  __builtin_amdgcn_s_waitcnt(vmcnt(0));
   __syncthreads();
 
   const int l16 = lane & 15, g1 = (lane >> 4) & 1;
@@ -407,14 +341,14 @@ __global__ __launch_bounds__(WAVES * 64, (NB >= 3 ? 1 : 2)) void vit_attn_split_
     for (int blk = 0; blk < NB; ++blk)
 #pragma unroll
       for (int r = 0; r < 16; r += 8) {
-        mx = vs_max3(mx, S[blk][r], S[blk][r + 1]);
-        mxb = vs_max3(mxb, S[blk][r + 2], S[blk][r + 3]);
-        mxc = vs_max3(mxc, S[blk][r + 4], S[blk][r + 5]);
-        mxd = vs_max3(mxd, S[blk][r + 6], S[blk][r + 7]);
+        mx = max3(mx, S[blk][r], S[blk][r + 1]);
+        mxb = max3(mxb, S[blk][r + 2], S[blk][r + 3]);
+        mxc = max3(mxc, S[blk][r + 4], S[blk][r + 5]);
+        mxd = max3(mxd, S[blk][r + 6], S[blk][r + 7]);
       }
-    mx = vs_max3(mx, mxb, mxc);
-    mx = vs_max3(mx, mxd, mxd);
-    mx = vs_xhalf_max(mx);
+    mx = max3(mx, mxb, mxc);
+    mx = max3(mx, mxd, mxd);
+    mx = xhalf_max(mx);
     mx += (R > 1 ? 0.f : bh0);
     // LAZY running maximum: the reference point only moves when some row's maximum grew by more than 2^VS_LAZY (log2 domain), so
     // probabilities may reach 2^VS_LAZY instead of 1 -- fp16 holds them at the same relative precision, the sums are fp32 -- and the
@@ -449,13 +383,13 @@ __global__ __launch_bounds__(WAVES * 64, (NB >= 3 ? 1 : 2)) void vit_attn_split_
         float pv[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) pv[j] = __builtin_amdgcn_exp2f(S[blk][8 * st + j] + off);
-        vs_exp_settle(pv);
+        exp_settle(pv);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           l_run += pv[2 * j] + pv[2 * j + 1];  // fp32 row sums of the unrounded probabilities (no spare O^T row for a ones column here)
-          vs_split2(pv[2 * j], pv[2 * j + 1], hh[j], ll[j]);
+          hl_split2(pv[2 * j], pv[2 * j + 1], hh[j], ll[j]);
         }
-        vs_settle(hh, ll);
+        settle(hh, ll);
 #pragma unroll
         for (int j = 0; j < 4; ++j) { Hh[j] = hh[j]; Ll[j] = ll[j]; }
       };
@@ -528,13 +462,13 @@ __global__ __launch_bounds__(WAVES * 64, (NB >= 3 ? 1 : 2)) void vit_attn_split_
       float pv[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) pv[j] = __builtin_amdgcn_exp2f(S[0][j] + off);
-      vs_exp_settle(pv);
+      exp_settle(pv);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (!ONES) l_run += pv[2 * j] + pv[2 * j + 1];
-        vs_split2(pv[2 * j], pv[2 * j + 1], hh[j], ll[j]);
+        hl_split2(pv[2 * j], pv[2 * j + 1], hh[j], ll[j]);
       }
-      vs_settle(hh, ll);
+      settle(hh, ll);
       pf = __builtin_bit_cast(frag, (u32x4){hh[0], hh[1], hh[2], hh[3]});
       pfl = __builtin_bit_cast(frag, (u32x4){ll[0], ll[1], ll[2], ll[3]});
     }
@@ -561,13 +495,13 @@ __global__ __launch_bounds__(WAVES * 64, (NB >= 3 ? 1 : 2)) void vit_attn_split_
           float pv[8];
 #pragma unroll
           for (int j = 0; j < 8; ++j) pv[j] = __builtin_amdgcn_exp2f(S[nb_][8 * ns_ + j] + off);
-          vs_exp_settle(pv);
+          exp_settle(pv);
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             if (!ONES) l_run += pv[2 * j] + pv[2 * j + 1];
-            vs_split2(pv[2 * j], pv[2 * j + 1], hh[j], ll[j]);
+            hl_split2(pv[2 * j], pv[2 * j + 1], hh[j], ll[j]);
           }
-          vs_settle(hh, ll);
+          settle(hh, ll);
           pn = __builtin_bit_cast(frag, (u32x4){hh[0], hh[1], hh[2], hh[3]});
           pnl = __builtin_bit_cast(frag, (u32x4){ll[0], ll[1], ll[2], ll[3]});
         }
@@ -586,7 +520,7 @@ __global__ __launch_bounds__(WAVES * 64, (NB >= 3 ? 1 : 2)) void vit_attn_split_
 
     }
 
-    __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): this wave's DMA writes of tile t + 1 have landed
+    __builtin_amdgcn_s_waitcnt(vmcnt(0));      // this wave's DMA writes of tile t + 1 have landed
     __syncthreads();                          // ... and everybody's; all reads of tile t are done
   }
 

@@ -849,6 +849,33 @@ def test_add_layernorm_sum(dt):
     assert torch.equal(n, ops.add_layernorm(x, d, w, b, 1e-5, dt, want_res=False)[1])
 
 
+def test_add_layernorm_optional_arguments_do_not_carry_over():
+    """the row maps of hipie_add_layernorm_rows and the addend of hipie_add_layernorm_sum belong to their own call: the plain call
+    after them gives, bit for bit, what it gave before them (tolerances of the mapped / summed results as in test_add_layernorm)."""
+    import torch.nn.functional as F
+    from hipie_amd import ops
+    C, rows = 160, 37
+    gen = torch.Generator().manual_seed(5)
+    x = (torch.randn(rows, C, generator=gen) * 3).to(DEV)
+    d = torch.randn(rows, C, generator=gen).to(DEV)
+    pos = torch.randn(rows, C, generator=gen).to(DEV)
+    w = (1 + 0.1 * torch.randn(C, generator=gen)).to(DEV)
+    b = (0.1 * torch.randn(C, generator=gen)).to(DEV)
+    want = F.layer_norm((x + d).cpu(), (C,), w.cpu(), b.cpu(), 1e-6)
+    before = ops.add_layernorm(x, d, w, b, 1e-6, torch.float32)[1].clone()
+    assert rel_err(before.cpu(), want) < 2e-6
+    perm = torch.randperm(rows, generator=gen)
+    out_src = torch.cat((perm[:5], torch.tensor([-1]), perm[5:])).to(torch.int32)       # every row once, one padding row
+    res, mapped = ops.add_layernorm(x, d, w, b, 1e-6, torch.float32, out_src=out_src.to(DEV))
+    want_mapped = torch.cat((want[perm[:5]], torch.zeros(1, C), want[perm[5:]]))
+    assert rel_err(res.cpu(), (x + d).cpu()) < 1e-6 and rel_err(mapped.cpu(), want_mapped) < 2e-6
+    assert (mapped[5] == 0).all()
+    n, s = ops.add_layernorm_sum(x, d, w, b, 1e-6, pos)
+    assert rel_err(n.cpu(), want) < 2e-6 and rel_err(s.cpu(), want + pos.cpu()) < 2e-6
+    after = ops.add_layernorm(x, d, w, b, 1e-6, torch.float32)[1]
+    assert torch.equal(after, before)
+
+
 @pytest.mark.parametrize("dt,tol", [(torch.float32, 5e-6), (torch.float16, 2e-3)])
 def test_decoder_heads_fused(dt, tol):
     """hipie_ref_point_mlp / hipie_box_head against the chains they replace: get_sine_pos_embed -> ref_point_head (oracle's
@@ -1030,6 +1057,30 @@ def test_msda_fused_tiny_dense_heads():
     lsi = torch.cat((shapes.new_zeros((1,)), shapes.prod(1).cumsum(0)[:-1]))
     got = ops.msda_fused(value.to(DEV), shapes.to(DEV), lsi.to(DEV), ref.to(DEV), off.to(DEV), logits.to(DEV))
     assert rel_err(got.cpu(), want) < 2e-5
+
+
+def test_msda_fused_value_stride_does_not_carry_over():
+    """the value row stride of a strided call belongs to that call: a dense call after it gives, bit for bit, what it gave before it,
+    and the strided call (value = a column block of a tensor twice as wide) what the dense one gives on a contiguous copy."""
+    from hipie_amd import ops
+    gen = torch.Generator().manual_seed(13)
+    B, M, D, L, P, Lq = 1, 2, 32, 2, 2, 8
+    shapes = torch.tensor([(4, 4), (2, 2)], dtype=torch.long)
+    S = int(shapes.prod(1).sum())
+    value = torch.rand(B, S, M, D, generator=gen).to(DEV)
+    wide = torch.rand(B, S, 2 * M * D, generator=gen).to(DEV)
+    block = wide[..., M * D:].unflatten(-1, (M, D))                  # row stride 2 * M * D
+    assert not block.is_contiguous() and block.stride(1) == 2 * M * D
+    ref = torch.rand(B, Lq, L, 2, generator=gen).to(DEV)
+    off = torch.randn(B, Lq, M, L, P, 2, generator=gen).to(DEV)
+    logits = torch.randn(B, Lq, M, L * P, generator=gen).to(DEV)
+    ss, ls = shapes.to(DEV), _lsi(shapes).to(DEV)
+    before = ops.msda_fused(value, ss, ls, ref, off, logits).clone()
+    strided = ops.msda_fused(block, ss, ls, ref, off, logits)
+    after = ops.msda_fused(value, ss, ls, ref, off, logits)
+    assert torch.equal(after, before)
+    assert torch.equal(strided, ops.msda_fused(block.contiguous(), ss, ls, ref, off, logits))
+    assert not torch.equal(strided, before)                          # different values: a carried-over stride would show
 
 
 def test_hl8_saturates_instead_of_nan():

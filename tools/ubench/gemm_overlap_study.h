@@ -92,10 +92,10 @@ __global__ __launch_bounds__(256, 2) void gemm2_kernel(const GemmParams pin) {
   const int nd = 4 + (NWI - 1) + (w_last ? 1 : 0);                // DMA instructions per step of this wave
 
   auto dma_a = [&](const int i, const int kt, const int slot) {
-    gm_dma16(abase + (long)kt * 64, dvA[i], __builtin_amdgcn_readfirstlane(lds0 + (unsigned int)(slot * STAGE + 1024 * (4 * wave + i))));
+    dma16(abase + (long)kt * 64, dvA[i], __builtin_amdgcn_readfirstlane(lds0 + (unsigned int)(slot * STAGE + 1024 * (4 * wave + i))));
   };
   auto dma_w = [&](const int i, const int kt, const int slot) {
-    gm_dma16(wbase + (long)kt * 64, dvW[i], __builtin_amdgcn_readfirstlane(lds0 + (unsigned int)(slot * STAGE + BM * 64 + 1024 * (4 * i + wave))));
+    dma16(wbase + (long)kt * 64, dvW[i], __builtin_amdgcn_readfirstlane(lds0 + (unsigned int)(slot * STAGE + BM * 64 + 1024 * (4 * i + wave))));
   };
   auto dma_step = [&](const int kt, const int slot) {
 #pragma unroll
@@ -105,9 +105,9 @@ __global__ __launch_bounds__(256, 2) void gemm2_kernel(const GemmParams pin) {
       if (i + 1 < NWI || w_last) dma_w(i, kt, slot);
   };
   auto wait_keep = [&](const bool keep) {       // wait until at most this step's own DMA instructions (issued last) are in flight
-    if (!keep) __builtin_amdgcn_s_waitcnt(0x0F70);
-    else if (w_last) __builtin_amdgcn_s_waitcnt(0x0F70 | (4 + NWI));
-    else __builtin_amdgcn_s_waitcnt(0x0F70 | (4 + NWI - 1));
+    if (!keep) __builtin_amdgcn_s_waitcnt(vmcnt(0));
+    else if (w_last) __builtin_amdgcn_s_waitcnt(vmcnt(4 + NWI));
+    else __builtin_amdgcn_s_waitcnt(vmcnt(4 + NWI - 1));
   };
 
   // ---- fragment addresses ----
@@ -323,11 +323,11 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(const GemmParams p) {
     for (int k = 0; k < NWI; ++k) dvW[k] = (unsigned int)((long)min(16 * (4 * k + wv) + rl, p.N - 1 - n0) * p.ldw_b + cch);
   };
   auto dma_a = [&](const int k) {
-    gm_dma16(fa + (long)f_k * 64, dvA[k], __builtin_amdgcn_readfirstlane(lds0 + (unsigned int)(f_slot * STAGE + 1024 * (4 * wv + k))));
+    dma16(fa + (long)f_k * 64, dvA[k], __builtin_amdgcn_readfirstlane(lds0 + (unsigned int)(f_slot * STAGE + 1024 * (4 * wv + k))));
   };
   auto dma_w = [&](const int k) {
     if (k + 1 < NWI || w_last)
-      gm_dma16(fw + (long)f_k * 64, dvW[k], __builtin_amdgcn_readfirstlane(lds0 + (unsigned int)(f_slot * STAGE + BM * 64 + 1024 * (4 * k + wv))));
+      dma16(fw + (long)f_k * 64, dvW[k], __builtin_amdgcn_readfirstlane(lds0 + (unsigned int)(f_slot * STAGE + BM * 64 + 1024 * (4 * k + wv))));
   };
   auto fetch_advance = [&]() {
     f_slot = f_slot == 2 ? 0 : f_slot + 1;
@@ -337,9 +337,9 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(const GemmParams p) {
     }
   };
   auto wait_keep = [&](const bool keep) {       // at most the DMA instructions issued in this step stay in flight
-    if (!keep) __builtin_amdgcn_s_waitcnt(0x0F70);
-    else if (w_last) __builtin_amdgcn_s_waitcnt(0x0F70 | (4 + NWI));
-    else __builtin_amdgcn_s_waitcnt(0x0F70 | (4 + NWI - 1));
+    if (!keep) __builtin_amdgcn_s_waitcnt(vmcnt(0));
+    else if (w_last) __builtin_amdgcn_s_waitcnt(vmcnt(4 + NWI));
+    else __builtin_amdgcn_s_waitcnt(vmcnt(4 + NWI - 1));
   };
 
   const int swz = (li >> 2) & 3;
@@ -368,7 +368,7 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(const GemmParams p) {
     }
   }
   if (tid < 2) gcnt[4 * tid] = 0u;
-  __builtin_amdgcn_s_waitcnt(0x0F70);
+  __builtin_amdgcn_s_waitcnt(vmcnt(0));
   __syncthreads();                             // the only workgroup barrier: counters zeroed, everybody's first two k steps landed
 
   // ---- group barrier: monotonic LDS counter, 4 arrivals per epoch ----
@@ -490,7 +490,7 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(const GemmParams p) {
       }
     };
     load_res(0, rq);
-    __builtin_amdgcn_s_waitcnt(0xC07F);        // lgkmcnt(0): this wave's bias values are in LDS
+    __builtin_amdgcn_s_waitcnt(lgkmcnt0);        // this wave's bias values are in LDS
     gbar();
     if (p.prio_mode == 1) __builtin_amdgcn_s_setprio(3);
     else if (p.prio_mode == 2) __builtin_amdgcn_s_setprio(1);
@@ -586,11 +586,11 @@ __global__ __launch_bounds__(256, 2) void gemm4_kernel(const GemmParams p) {
     for (int k = 0; k < NWI; ++k) dvW[k] = (unsigned int)((long)min(16 * (4 * k + wv) + rl, p.N - 1 - n0) * p.ldw_b + cch);
   };
   auto dma_a = [&](const int k) {
-    gm_dma16(fa + (long)f_k * 64, dvA[k], __builtin_amdgcn_readfirstlane(lds0 + (unsigned int)(f_slot * STAGE + 1024 * (4 * wv + k))));
+    dma16(fa + (long)f_k * 64, dvA[k], __builtin_amdgcn_readfirstlane(lds0 + (unsigned int)(f_slot * STAGE + 1024 * (4 * wv + k))));
   };
   auto dma_w = [&](const int k) {
     if (k + 1 < NWI || w_last)
-      gm_dma16(fw + (long)f_k * 64, dvW[k], __builtin_amdgcn_readfirstlane(lds0 + (unsigned int)(f_slot * STAGE + BM * 64 + 1024 * (4 * k + wv))));
+      dma16(fw + (long)f_k * 64, dvW[k], __builtin_amdgcn_readfirstlane(lds0 + (unsigned int)(f_slot * STAGE + BM * 64 + 1024 * (4 * k + wv))));
   };
   auto fetch_advance = [&]() {
     f_slot = f_slot == 2 ? 0 : f_slot + 1;
@@ -600,9 +600,9 @@ __global__ __launch_bounds__(256, 2) void gemm4_kernel(const GemmParams p) {
     }
   };
   auto wait_keep = [&](const bool keep) {       // at most the DMA instructions issued in this step stay in flight
-    if (!keep) __builtin_amdgcn_s_waitcnt(0x0F70);
-    else if (w_last) __builtin_amdgcn_s_waitcnt(0x0F70 | (4 + NWI));
-    else __builtin_amdgcn_s_waitcnt(0x0F70 | (4 + NWI - 1));
+    if (!keep) __builtin_amdgcn_s_waitcnt(vmcnt(0));
+    else if (w_last) __builtin_amdgcn_s_waitcnt(vmcnt(4 + NWI));
+    else __builtin_amdgcn_s_waitcnt(vmcnt(4 + NWI - 1));
   };
 
   const int swz = (li >> 2) & 3;
@@ -642,7 +642,7 @@ __global__ __launch_bounds__(256, 2) void gemm4_kernel(const GemmParams p) {
     if (p.variant == 12) sflag[0] = (blockIdx.x >> 3) & 1u;
 #endif
   }
-  __builtin_amdgcn_s_waitcnt(0x0F70);
+  __builtin_amdgcn_s_waitcnt(vmcnt(0));
   __syncthreads();                             // everybody's first two k steps landed; the slot is known
 #ifdef HIPIE_GEMM_VARIANTS
   if (sflag[0] == 1u && nt > 0 && p.variant != 7) {
@@ -751,7 +751,7 @@ __global__ __launch_bounds__(256, 2) void gemm4_kernel(const GemmParams p) {
       }
     };
     load_res(0, rq);
-    __builtin_amdgcn_s_waitcnt(0xC07F);        // lgkmcnt(0): this wave's bias values are in LDS
+    __builtin_amdgcn_s_waitcnt(lgkmcnt0);        // this wave's bias values are in LDS
     gbar();
     if (p.prio_mode == 1) __builtin_amdgcn_s_setprio(3);
     else if (p.prio_mode == 2) __builtin_amdgcn_s_setprio(1);
