@@ -468,11 +468,8 @@ extern "C" int hipie_attn_train_forward(const void* q_hi, const void* q_lo, cons
                                         void* out, void* lse, int BH, int N, void* stream) {
   HIPIE_REQUIRE(q_hi && q_lo && k_hi && k_lo && v_hi && v_lo && out && lse, "attn_train_forward: null pointer");
   HIPIE_REQUIRE(BH > 0 && N > 0 && N % 128 == 0 && (long)BH * (N / 128) < (1L << 31), "attn_train_forward: BH=%d N=%d (N a multiple of 128)", BH, N);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)attn_train_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAtFwdLds);
-    attr = true;
-  }
+  static LdsLimit limit;
+  limit.raise((const void*)attn_train_fwd_kernel, kAtFwdLds);
   hipLaunchKernelGGL(attn_train_fwd_kernel, dim3((unsigned)((N / AT_WG_ROWS) * BH)), dim3(AT_THREADS), kAtFwdLds, (hipStream_t)stream, (const f16_t*)q_hi,
                      (const f16_t*)q_lo, (const f16_t*)k_hi, (const f16_t*)k_lo, (const f16_t*)v_hi, (const f16_t*)v_lo, (float*)out, (float*)lse, N, BH);
   return check_launch("attn_train_forward");
@@ -484,12 +481,9 @@ extern "C" int hipie_attn_train_backward(const void* q_hi, const void* q_lo, con
   HIPIE_REQUIRE(q_hi && q_lo && k_hi && k_lo && v_hi && v_lo && do_hi && do_lo && lse && delta && dq && dk && dv, "attn_train_backward: null pointer");
   HIPIE_REQUIRE(BH > 0 && N > 0 && N % 128 == 0 && (long)BH * (N / 128) < (1L << 31), "attn_train_backward: BH=%d N=%d (N a multiple of 128)", BH, N);
   static_assert(kAtBwdKvLds <= 160 * 1024 && kAtBwdQLds <= 160 * 1024, "LDS budget");
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)attn_train_bwd_kv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAtBwdKvLds);
-    (void)hipFuncSetAttribute((const void*)attn_train_bwd_q_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAtBwdQLds);
-    attr = true;
-  }
+  static LdsLimit limit[2];
+  limit[0].raise((const void*)attn_train_bwd_kv_kernel, kAtBwdKvLds);
+  limit[1].raise((const void*)attn_train_bwd_q_kernel, kAtBwdQLds);
   const dim3 grid((unsigned)((N / AT_WG_ROWS) * BH)), block(AT_THREADS);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(attn_train_bwd_kv_kernel, grid, block, kAtBwdKvLds, st, (const f16_t*)q_hi, (const f16_t*)q_lo, (const f16_t*)k_hi,

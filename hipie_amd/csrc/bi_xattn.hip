@@ -213,13 +213,8 @@ template <typename T, int NKB>
 static int launch_i2t(XAParams& p, hipStream_t st) {
   const size_t lds = (size_t)(NKB * 32 * XA_KSTR + 2 * 32 * XA_VSTR) * sizeof(T) + (size_t)NKB * 32 * sizeof(float);
   auto kern = xattn_i2t_kernel<T, NKB>;
-  static size_t lds_set[64] = {0};
-  int dev = -1;
-  (void)hipGetDevice(&dev);
-  if (lds > 64 * 1024 && (dev < 0 || dev >= 64 || lds > lds_set[dev])) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (dev >= 0 && dev < 64) lds_set[dev] = lds;
-  }
+  static LdsLimit limit;               // per instantiation; nothing to do up to the default 64 KiB
+  limit.raise((const void*)kern, lds, 64 * 1024);
   const int nqt = (p.Nv + 255) / 256;
   dim3 grid((nqt + XA_QT - 1) / XA_QT, p.B * p.H);
   hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, p);
@@ -417,13 +412,8 @@ template <typename T, int NKB>
 static int launch_t2i(XTParams& p, hipStream_t st) {
   const size_t lds = (size_t)3 * (32 * XA_KSTR + 32 * XA_VSTR) * sizeof(T);
   auto kern = xattn_t2i_kernel<T, NKB>;
-  static size_t lds_set[64] = {0};
-  int dev = -1;
-  (void)hipGetDevice(&dev);
-  if (lds > 64 * 1024 && (dev < 0 || dev >= 64 || lds > lds_set[dev])) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (dev >= 0 && dev < 64) lds_set[dev] = lds;
-  }
+  static LdsLimit limit;               // per instantiation; nothing to do up to the default 64 KiB
+  limit.raise((const void*)kern, lds, 64 * 1024);
   hipLaunchKernelGGL(kern, dim3(p.SP, p.B * p.H), dim3(512), lds, st, p);
   int rc = check_launch("bi_xattn_t2i");
   if (rc != HIPIE_OK) return rc;

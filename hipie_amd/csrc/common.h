@@ -32,6 +32,30 @@ int check_launch(const char* what);
     if (!(cond)) return ::hipie::set_err(HIPIE_EINVAL, __VA_ARGS__); \
   } while (0)
 
+// a check that has set the error itself (returns 0 or the code): pass the refusal on
+#define HIPIE_TRY(call)                  \
+  do {                                   \
+    if (const int rc_ = (call)) return rc_; \
+  } while (0)
+
+// ---- dynamic-LDS limit (host) ----------------------------------------------------------------------
+// A kernel that takes more dynamic LDS than the default 64 KiB needs hipFuncAttributeMaxDynamicSharedMemorySize raised, on every device
+// it runs on.  One `static LdsLimit` per kernel at its launch site remembers what each device has been given and calls the runtime only
+// when a launch needs more: the call is not a stream operation, so after a kernel's first launch it stays out of graph capture.
+// `floor`: what needs no call at all (kernels whose LDS size varies pass the default limit).  A device index outside 0..63 is always set.
+struct LdsLimit {
+  size_t seen[64];                       // per device; zero-initialised (static storage)
+  void raise(const void* kernel, size_t lds, size_t floor = 0) {
+    if (lds <= floor) return;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const bool known = dev >= 0 && dev < 64;
+    if (known && lds <= seen[dev]) return;
+    (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (known) seen[dev] = lds;
+  }
+};
+
 // ---- 16-bit <-> f32 ---------------------------------------------------------------------------------
 template <typename T> struct elem;
 template <> struct elem<float> {

@@ -180,13 +180,8 @@ extern "C" int hipie_ffn_fused(const void* x, int64_t ldx, const void* w1, const
   p.ldx_b = ldx * 2; p.ldw1_b = (long)2 * D * 2; p.ldw2_b = (long)2 * F * 2; p.ldo = ldo;
   p.M = M;
   const size_t lds = (size_t)2 * FF_BUF + FF_F * sizeof(float);
-  static bool lds_set[64] = {false};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !lds_set[dev]) {
-    (void)hipFuncSetAttribute((const void*)ffn_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (dev >= 0 && dev < 64) lds_set[dev] = true;
-  }
+  static LdsLimit limit;
+  limit.raise((const void*)ffn_fused_kernel, lds);
   hipLaunchKernelGGL(ffn_fused_kernel, dim3((unsigned)((M + 127) / 128)), dim3(256), lds, (hipStream_t)stream, p);
   return check_launch("ffn_fused");
 }

@@ -1,4 +1,4 @@
-// gelu.h -- the exact-erf GELU of the library, shared by the GEMM epilogue (gemm.hip) and the activation kernels of the training step
+// gelu.h -- the exact-erf GELU of the library, shared by the GEMM epilogue (gemm_tile.h) and the activation kernels of the training step
 // (act_bwd.hip): ONE formula, so that an activation recomputed in the backward has the bits of the one the forward produced.
 #pragma once
 #include "common.h"

@@ -2,7 +2,7 @@
 //
 //     out = epilogue( W_hi . X_hi  +  q8(W_lo) . q8(X_hi)  +  q8(W_hi) . q8(X_lo) )            fp32 accumulation
 //
-// hipie_gemm forms an fp32-class product from three fp16 MFMAs (gemm.hip).  The two cross terms are 2^-11 of the main term, so their
+// hipie_gemm forms an fp32-class product from three fp16 MFMAs (gemm_tile.h).  The two cross terms are 2^-11 of the main term, so their
 // operands need ~5 bits: here they are e4m3 with one power-of-two (E8M0) scale per 32 k-elements (q8, hipie_amd/fp8x.py has the exact rule)
 // and run on v_mfma_scale_f32_32x32x64_f8f6f4, which takes e4m3 at twice the fp16 rate.  Per (feature block, token tile) and 32-element k
 // stage: two v_mfma_f32_32x32x16_f16 for W_hi . X_hi and ONE scaled MFMA for both cross terms, concatenated along its K = 64:
@@ -21,9 +21,8 @@
 //   W  the f8x weight format: every 32-element k slice of a row is 128 bytes like an HL8 slice, hi fp16 [64 B] then 64 B of e4m3 in the lane
 //      order above: [q8(lo) g0 g2 | q8(hi) g0 g2 | q8(lo) g1 g3 | q8(hi) g1 g3] (8 bytes per 8-group g), and a side tensor (N, K/32, 2) of
 //      E8M0 scales [lo, hi].  Stage size, LDS-DMA and swizzle are gemm_kernel's.
-// The tile (256 x 256, 8 waves, 2 LDS stages of 128-byte k32 rows, XCD tile order) and the epilogue (gm_epi_quads) are gemm.hip's.
-#define HIPIE_GEMM_INCLUDED_TU
-#include "gemm.hip"
+// The tile (256 x 256, 8 waves, 2 LDS stages of 128-byte k32 rows, XCD tile order) and the epilogue (gm_epi_quads) are gemm_tile.h's.
+#include "gemm_tile.h"
 
 namespace hipie {
 
@@ -70,7 +69,7 @@ __device__ __forceinline__ void f8x_cvt16(const unsigned int (&v)[8], const floa
 
 struct F8xParams {
   GemmParams g;
-  const unsigned char* wsc;   // (N, K/32, 2) E8M0 scales of W's [lo, hi] e4m3 parts
+  const unsigned char* wsc = nullptr;   // (N, K/32, 2) E8M0 scales of W's [lo, hi] e4m3 parts
 };
 
 template <int BN>
@@ -280,13 +279,8 @@ static int launch_gemm_f8x(F8xParams& fp, hipStream_t st) {
   p.tiles_n = (p.N + BN - 1) / BN;
   p.group_m = p.tiles_n > 4 ? 8 : 0;            // launch_gemm's tile order
   auto kern = gemm_f8x_kernel<BN>;
-  static bool lds_set[64] = {false};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !lds_set[dev]) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (dev >= 0 && dev < 64) lds_set[dev] = true;
-  }
+  static LdsLimit limit;
+  limit.raise((const void*)kern, lds);
   hipLaunchKernelGGL(kern, dim3((unsigned)(p.tiles_m * p.tiles_n)), dim3(512), lds, st, fp);
   return check_launch("gemm_f8x");
 }
@@ -335,23 +329,15 @@ extern "C" int hipie_gemm_f8x(const void* A, int64_t lda, const void* W, int64_t
   HIPIE_REQUIRE(out_fmt == HIPIE_F32 || out_fmt == HIPIE_F16 || out_fmt == HIPIE_HL8, "gemm_f8x: output format %d", out_fmt);
   HIPIE_REQUIRE(act >= 0 && act <= 3, "gemm_f8x: activation %d (0 none, 1 gelu, 2 relu, 3 quick-gelu)", act);
   HIPIE_REQUIRE(M > 0 && N > 0 && K > 0 && N % 8 == 0 && K % 32 == 0, "gemm_f8x: M=%d N=%d K=%d (N %% 8, K %% 32)", M, N, K);
-  HIPIE_REQUIRE(lda >= 2 * K && ldw >= 2 * K && lda % 8 == 0 && ldw % 8 == 0, "gemm_f8x: operand row strides %ld / %ld (>= %d, multiples of 8)",
-                (long)lda, (long)ldw, 2 * K);
-  HIPIE_REQUIRE((long)256 * lda * 2 < (1L << 31) && (long)320 * ldw * 2 < (1L << 31), "gemm_f8x: row stride too large");
-  const int opr = out_fmt == HIPIE_HL8 ? 2 * N : N;
-  HIPIE_REQUIRE(ldo >= opr && ldo % 4 == 0, "gemm_f8x: output row stride %ld (>= %d)", (long)ldo, opr);
-  HIPIE_REQUIRE(resid == nullptr || (ldr >= N && ldr % 4 == 0), "gemm_f8x: residual row stride %ld", (long)ldr);
-  HIPIE_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)W % 16) == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)bias % 16) == 0 &&
-                ((uintptr_t)resid % 16) == 0, "gemm_f8x: pointers must be 16-byte aligned");
+  HIPIE_TRY(gm_check_operands("gemm_f8x", lda, ldw, 2 * K, 320));
+  HIPIE_TRY(gm_check_out("gemm_f8x", ldo, out_fmt, N));
+  HIPIE_TRY(gm_check_resid("gemm_f8x", resid, ldr, N));
+  HIPIE_TRY(gm_check_aligned("gemm_f8x", {A, W, out, bias, resid}));
   F8xParams fp;
   GemmParams& p = fp.g;
-  p.A = (const char*)A; p.W = (const char*)W; p.bias = bias; p.resid = resid; p.out = (char*)out; p.out_row = out_row; p.a_row = nullptr;
-  p.lda_b = lda * 2; p.ldw_b = ldw * 2; p.ldr = ldr; p.ldo = ldo;
-  p.M = M; p.N = N; p.K = K; p.nkt = K / 32;
+  gm_set_operands(p, A, lda, W, ldw, M, N, K);
+  p.bias = bias; p.resid = resid; p.ldr = ldr; p.out = (char*)out; p.ldo = ldo; p.out_row = out_row;
   p.out_fmt = out_fmt; p.act = act; p.alpha = alpha; p.oscale = oscale;
-  p.nbi = 1; p.a_bo = p.a_bi = p.w_bo = p.w_bi = p.o_bo = p.o_bi = 0;
-  p.conv_kpt = 0; p.conv_wp = 0; p.softmax = 0; p.sm_L = 0; p.sm_clamp = 0.f; p.sm_mask = nullptr;
-  p.prio_mode = 0; p.variant = 0;
   fp.wsc = (const unsigned char*)w_scale;
   hipStream_t st = (hipStream_t)stream;
   // the 256-column tile for every N: the 320-column one needs ~40 registers more than the 256 a wave has at two waves per SIMD (X's q8 operands,

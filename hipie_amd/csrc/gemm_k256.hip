@@ -170,14 +170,9 @@ int launch_gemm_k256(const void* X, long ldx_b, int x_f32, const void* W, long l
   p.ldx_b = ldx_b; p.ldw_b = ldw_b; p.ldo = ldo;
   p.M = M; p.N = N;
   const size_t lds = (size_t)2 * TK_TILE;
-  static bool lds_set[64] = {false};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !lds_set[dev]) {
-    (void)hipFuncSetAttribute((const void*)gemm_k256_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)gemm_k256_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (dev >= 0 && dev < 64) lds_set[dev] = true;
-  }
+  static LdsLimit limit[2];
+  limit[0].raise((const void*)gemm_k256_kernel<true>, lds);
+  limit[1].raise((const void*)gemm_k256_kernel<false>, lds);
   const dim3 grid((unsigned)((M + 127) / 128));
   if (x_f32) hipLaunchKernelGGL(gemm_k256_kernel<true>, grid, dim3(256), lds, st, p);
   else hipLaunchKernelGGL(gemm_k256_kernel<false>, grid, dim3(256), lds, st, p);

@@ -237,7 +237,8 @@ static int launch_gn(const void* x, const float* prebias, const float* gamma, co
     if (nhwc == 2) {                         // channels-last in, NCHW out
       const size_t lds = (size_t)C * (GN_TP + 1) * sizeof(float);
       auto kern = gn_apply_nhwc_to_nchw_kernel<T, OutT>;
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      static LdsLimit limit;
+      limit.raise((const void*)kern, lds);
       hipLaunchKernelGGL(kern, dim3(HW / GN_TP, B), dim3(256), lds, st, (const T*)x, prebias, part, gamma, beta, (OutT*)out, HW, G, nchunk,
                          eps, relu);
       return check_launch("group_norm");

@@ -450,12 +450,9 @@ static int launch_msda_bwd_gather(const void* value, const int64_t* shapes, cons
   BwdRec* recs = (BwdRec*)(ws + w.recs);
   const dim3 block(256), bin_grid((unsigned)(B * M * w.K)), bin_block(1024);
   const size_t lds = (size_t)S * 4;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)msda_bwd_bin_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)msda_bwd_bin_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
+  static LdsLimit limit[2];              // the whole 160 KiB once, whatever this call's S needs
+  limit[0].raise((const void*)msda_bwd_bin_kernel<false>, 160 * 1024);
+  limit[1].raise((const void*)msda_bwd_bin_kernel<true>, 160 * 1024);
   hipLaunchKernelGGL((msda_bwd_bin_kernel<false>), bin_grid, bin_block, lds, st, shapes, lstart, (const float*)loc, (const float*)attn, bins,
                      recs, S, M, L, Lq, P, w.K);
   hipLaunchKernelGGL(msda_bwd_scan_totals_kernel, dim3((unsigned)w.nblocks), block, 0, st, bins, totals, w.nbins, S, w.K);

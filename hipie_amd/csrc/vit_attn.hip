@@ -394,15 +394,8 @@ static int launch_va(VAParams& p, hipStream_t st) {
   p.swz = ((p.B * p.H) % 8 == 0) ? 1 : 0;
   const unsigned grid = (unsigned)(p.nqt * p.B * p.H);
   auto kern = vit_attn_kernel<T, HD, NB, WAVES, FAST, R, KW, ABL>;
-  if (lds > 64 * 1024) {     // the dynamic-LDS limit is a per-device attribute of the function (not a stream operation)
-    static size_t lds_set[64] = {0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || lds > lds_set[dev]) {
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (dev >= 0 && dev < 64) lds_set[dev] = lds;
-    }
-  }
+  static LdsLimit limit;               // per instantiation; nothing to do up to the default 64 KiB
+  limit.raise((const void*)kern, lds, 64 * 1024);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, st, p);
   return check_launch("vit_attn");
 }
@@ -864,15 +857,8 @@ static int launch_sp(VAParams& p, hipStream_t st) {
   const unsigned grid = (unsigned)(p.nqt * p.B * p.H);
   { static int prio = -1; if (prio < 0) { const char* e = study_env("HIPIE_VA_PRIO"); prio = e ? atoi(e) : 1; } p.prio = prio; }
   auto kern = vit_attn_sp_kernel<T, HD, NB, FAST, ABL>;
-  if (lds > 64 * 1024) {
-    static size_t lds_set[64] = {0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || lds > lds_set[dev]) {
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (dev >= 0 && dev < 64) lds_set[dev] = lds;
-    }
-  }
+  static LdsLimit limit;               // per instantiation; nothing to do up to the default 64 KiB
+  limit.raise((const void*)kern, lds, 64 * 1024);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, st, p);
   return check_launch("vit_attn(sp)");
 }
