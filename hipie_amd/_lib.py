@@ -83,6 +83,8 @@ SIGNATURES = {
     "hipie_attn_train_forward": [c_p] * 8 + [c_i, c_i, c_p],
     "hipie_to_f16_pair": [c_p, c_l, c_p, c_p, c_l, c_i, c_i, c_p, c_p],
     "hipie_attn_train_backward": [c_p] * 13 + [c_i, c_i, c_p],
+    "hipie_attn_train_win_forward": [c_p] * 8 + [c_i, c_i, c_p],
+    "hipie_attn_train_win_backward": [c_p] * 13 + [c_i, c_i, c_p],
     "hipie_selftest": [c_i, c_p, c_p, c_p, c_p],
 }
 

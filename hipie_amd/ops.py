@@ -1198,6 +1198,62 @@ def attn_train_backward(q_pair, k_pair, v96_pair, do96_pair, lse, delta):
     return dq, dk, dv
 
 
+def _win_planes(who, planes):
+    for t in planes:
+        if not t.is_cuda or t.dtype != torch.float16 or not t.is_contiguous():
+            raise RuntimeError("%s: contiguous fp16 device planes" % who)
+
+
+@_timed("attn_train_win_fwd")
+def attn_train_win_forward(q_pair, k_pair, v_pair):
+    """hipie_attn_train_win_forward (the windowed blocks: one (window, head) item of N <= 256 tokens per workgroup, no row padding): q', k'
+    (BH, N, 128) and v (BH, N, 80) as fp16 pairs (f16_pair) -> (out (BH, N, 80) f32, lse (BH, N) f32)"""
+    lib = _lib.load()
+    qh, ql = q_pair
+    kh, kl = k_pair
+    vh, vl = v_pair
+    _win_planes("attn_train_win_forward", (qh, ql, kh, kl, vh, vl))
+    if qh.dim() != 3 or qh.shape[-1] != 128 or kh.shape != qh.shape or ql.shape != qh.shape or kl.shape != qh.shape \
+            or tuple(vh.shape) != (qh.shape[0], qh.shape[1], 80) or vl.shape != vh.shape or not 1 <= qh.shape[1] <= 256 or qh.shape[0] < 1:
+        raise RuntimeError("attn_train_win_forward: q', k' (BH, N, 128), v (BH, N, 80) pairs with 1 <= N <= 256, got %s / %s / %s"
+                           % (tuple(qh.shape), tuple(kh.shape), tuple(vh.shape)))
+    BH, N, _ = qh.shape
+    out = torch.empty(BH, N, 80, dtype=torch.float32, device=qh.device)
+    lse = torch.empty(BH, N, dtype=torch.float32, device=qh.device)
+    rc = lib.hipie_attn_train_win_forward(qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(), vh.data_ptr(), vl.data_ptr(), out.data_ptr(),
+                                          lse.data_ptr(), BH, N, _stream())
+    _lib.check(rc, "hipie_attn_train_win_forward")
+    return out, lse
+
+
+@_timed("attn_train_win_bwd")
+def attn_train_win_backward(q_pair, k_pair, v96_pair, do96_pair, lse, delta):
+    """hipie_attn_train_win_backward: the forward's q', k' pairs, v and dO as (BH, N, 96) pairs (f16_pair(.., 96); dO scaled into fp16's range by
+    the caller), lse, delta = rowsum(dO * out) -> (dq' (BH, N, 128), dk (BH, N, 80), dv (BH, N, 80)) fp32, in the scale of the dO given"""
+    lib = _lib.load()
+    qh, ql = q_pair
+    kh, kl = k_pair
+    vh, vl = v96_pair
+    dh, dl = do96_pair
+    _win_planes("attn_train_win_backward", (qh, ql, kh, kl, vh, vl, dh, dl))
+    if qh.dim() != 3 or qh.shape[-1] != 128 or kh.shape != qh.shape or ql.shape != qh.shape or kl.shape != qh.shape \
+            or not 1 <= qh.shape[1] <= 256 or qh.shape[0] < 1:
+        raise RuntimeError("attn_train_win_backward: q', k' (BH, N, 128) pairs with 1 <= N <= 256, got %s / %s" % (tuple(qh.shape), tuple(kh.shape)))
+    BH, N, _ = qh.shape
+    if any(tuple(t.shape) != (BH, N, 96) for t in (vh, vl, dh, dl)) or tuple(lse.shape) != (BH, N) or tuple(delta.shape) != (BH, N) \
+            or not lse.is_cuda or not delta.is_cuda:
+        raise RuntimeError("attn_train_win_backward: v / dO as (BH, N, 96) pairs, lse / delta (BH, N) on the device")
+    lse, delta = lse.float().contiguous(), delta.float().contiguous()
+    dq = torch.empty(BH, N, 128, dtype=torch.float32, device=qh.device)
+    dk = torch.empty(BH, N, 80, dtype=torch.float32, device=qh.device)
+    dv = torch.empty(BH, N, 80, dtype=torch.float32, device=qh.device)
+    rc = lib.hipie_attn_train_win_backward(qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(), vh.data_ptr(), vl.data_ptr(), dh.data_ptr(),
+                                           dl.data_ptr(), lse.data_ptr(), delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), BH, N,
+                                           _stream())
+    _lib.check(rc, "hipie_attn_train_win_backward")
+    return dq, dk, dv
+
+
 @_timed("fill_rows")
 def fill_rows(dst, rows, src_row):
     """dst[rows[i]] = src_row for every i (hipie_fill_rows): dst (R, W) contiguous device tensor, rows int32 (n,), src_row (W,) of dst's

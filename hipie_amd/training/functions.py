@@ -241,6 +241,53 @@ def fused_attention(qa, ka, v):
     return FusedAttentionFunction.apply(qa_p, ka_p, pad(v, (0, 0, 0, Np - N)))[:, :N]
 
 
+class WindowAttentionFunction(torch.autograd.Function):
+    """FusedAttentionFunction for the WINDOWED blocks: softmax(q' k'^T) v over items of N <= 256 tokens (one (window, head) each, no row
+    padding) on hipie_attn_train_win_forward / _backward (csrc/attn_train_win.hip).  q', k' (BH, N, <= 128) whose columns from 80 on are
+    CONSTANT in k' (the key-axis indicators: they get a zero gradient), v (BH, N, 80).  Saved for the backward: the fp16 pairs of q' and k',
+    v, the output and the log-sum-exp row.
+    A ONE-token item is the closed form, not a launch: a softmax over one key is the identity, so out = v, dq' = 0, dk' = 0 and dv = dO hold
+    exactly, whereas the kernels (which take v and dO as fp16 pairs: 22 of fp32's 24 significant bits) reach them to ~2e-7 only.  The
+    kernels themselves take N = 1 (tests/test_gpu_attn_train_win.py runs them there through the ops)."""
+
+    @staticmethod
+    def forward(ctx, qa, ka, v):
+        ctx.single = qa.shape[1] == 1
+        if ctx.single:
+            ctx.shapes = (qa.shape, ka.shape)
+            return v.clone()
+        qp, kp = ops.f16_pair(qa, 128), ops.f16_pair(ka, 128)
+        out, lse = ops.attn_train_win_forward(qp, kp, ops.f16_pair(v))
+        ctx.save_for_backward(qp[0], qp[1], kp[0], kp[1], v, out, lse)
+        ctx.cols = (qa.shape[-1], ka.shape[-1])
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        if ctx.single:
+            return go.new_zeros(ctx.shapes[0]), go.new_zeros(ctx.shapes[1]), go
+        qh, ql, kh, kl, v, out, lse = ctx.saved_tensors
+        go = go.float().contiguous()
+        # as FusedAttentionFunction.backward: dO scaled by a power of two (a device scalar: no host wait) so that its largest entry is in [8, 16)
+        scale = torch.exp2(torch.floor(torch.log2(16.0 / go.abs().amax().clamp_min(1e-30))))
+        delta = (go * out).sum(-1) * scale
+        dq, dk, dv = ops.attn_train_win_backward((qh, ql), (kh, kl), ops.f16_pair(v, 96), ops.f16_pair(go, 96, scale), lse, delta)
+        inv = 1.0 / scale
+        cq, ck = ctx.cols
+        return dq[..., :cq] * inv, torch.nn.functional.pad(dk * inv, (0, ck - 80)), dv * inv
+
+
+def window_attention_ok(qa, ka, v):
+    """operands WindowAttentionFunction takes: device fp32, head width 80, at most 128 operand columns, items of at most 256 tokens"""
+    return (qa.dim() == 3 and qa.is_cuda and qa.dtype == torch.float32 and v.shape[-1] == 80 and 80 <= qa.shape[-1] <= 128
+            and ka.shape[-1] == qa.shape[-1] and 1 <= qa.shape[1] <= 256 and qa.shape[0] >= 1)
+
+
+def window_attention(qa, ka, v):
+    """softmax(q' k'^T) v of the windowed ViT blocks on the short-sequence fused kernels, or None when the operands are not covered"""
+    return WindowAttentionFunction.apply(qa, ka, v) if window_attention_ok(qa, ka, v) else None
+
+
 class AddLayerNormFunction(torch.autograd.Function):
     """s = x + delta;  y = LayerNorm(s) * weight + bias  -> (s, y): a residual add and the LayerNorm that follows it (Block.forward,
     backbone/vit.py:212-230; the post-norms of DeformableTransformerEncoderLayer.forward, deformable_transformer_dino.py:384-394) as one

@@ -5,7 +5,8 @@ kernels have no backward.  What is hand-written HIP here is what has a backward 
 linears, LayerNorm / GroupNorm, the softmax attentions and the convolutions run on the library kernels PyTorch-ROCm dispatches to, with
 torch.autograd providing their backward (opt-in, HipBackendNorms: the LayerNorms of the ViT blocks and of the encoder layers on
 hipie_add_layernorm / hipie_layernorm_backward; opt-in, HipBackendMlp: their MLPs / FFNs as one node with the activation on
-hipie_act_forward / hipie_act_backward).
+hipie_act_forward / hipie_act_backward; opt-in, HipBackendWindows: the attention of the windowed ViT blocks on
+hipie_attn_train_win_forward / _backward).
 
 Functional style over a dict ``sd`` of LIVE parameters (model.named_parameters() + buffers, reference key names), so gradients land in the
 model's own parameters.  Every function cites the reference code it follows.  Training-mode differences from the inference path:
@@ -110,6 +111,23 @@ class HipBackendMlp(HipBackend):
 
 class HipBackendNormsMlp(HipBackendNorms, HipBackendMlp):
     """both opt-in groups: the hand-written LayerNorm pair and the one-node MLP"""
+
+
+class HipBackendWindows(HipBackend):
+    """HipBackend + the attention of the WINDOWED ViT blocks (196-token windows) on the short-sequence instance of the fused split-fp16
+    kernels (functions.WindowAttentionFunction, csrc/attn_train_win.hip): no (windows x heads, 196, 196) tensor in HBM, forward or backward.
+    Opt-in: TrainStep's default stays HipBackend."""
+
+    @staticmethod
+    def window_attention(qa, ka, v):
+        """softmax(q' k'^T) v for items of at most 256 tokens (head width 80, <= 128 operand columns), else None: the materialised
+        formulation runs.  Asked only where fused_attention declined."""
+        from .functions import window_attention
+        return window_attention(qa, ka, v)
+
+
+class HipBackendAll(HipBackendNorms, HipBackendMlp, HipBackendWindows):
+    """the three opt-in groups: the hand-written LayerNorm pair, the one-node MLP and the fused windowed attention"""
 
 
 # ------------------------------------------------------------------------------------------------ small helpers
@@ -255,12 +273,15 @@ def vit_attention(x, sd, p, heads, be=None):
     if FOLD_REL_POS:
         qa = torch.cat((q * hd ** -0.5, rel_h, rel_w), -1)
         ka = torch.cat((k, _key_axis_indicators(H, W, k.device, k.dtype).expand(B * heads, -1, -1)), -1)
-        fused = getattr(be, "fused_attention", None)
+        fused, windows = getattr(be, "fused_attention", None), getattr(be, "window_attention", None)
+        o = None
         if fused is not None:
             o = fused(qa, ka, v)                      # HipBackend: forward + backward without the (heads, HW, HW) tensors (csrc/attn_train.hip)
-            if o is not None:
-                o = o.view(B, heads, H, W, -1).permute(0, 2, 3, 1, 4).reshape(B, H, W, -1)
-                return _blin(o, sd, p + "proj.", be)
+        if o is None and windows is not None:
+            o = windows(qa, ka, v)                    # HipBackendWindows: the short items fused_attention leaves out (csrc/attn_train_win.hip)
+        if o is not None:
+            o = o.view(B, heads, H, W, -1).permute(0, 2, 3, 1, 4).reshape(B, H, W, -1)
+            return _blin(o, sd, p + "proj.", be)
         attn = qa @ ka.transpose(-2, -1)
     else:
         attn = (q * hd ** -0.5) @ k.transpose(-2, -1)

@@ -573,6 +573,21 @@ int hipie_attn_train_backward(const void* q_hi, const void* q_lo, const void* k_
                               const void* do_hi, const void* do_lo, const void* lse, const void* delta, void* dq, void* dk, void* dv,
                               int BH, int N, void* stream);
 
+/* The short-sequence instance of the two entries above (csrc/attn_train_win.hip): the attention of the WINDOWED ViT blocks of the training
+ * step -- Attention.forward, hipie/backbone/vit.py:69-80, with add_decomposed_rel_pos (hipie/backbone/utils.py:96-125) folded into the operands
+ * -- over items of N tokens, 1 <= N <= 256, one (window, head) each, dense in memory (no row padding), one workgroup per item.
+ *   q', k' (BH, N, 128) pairs (a 14 x 14 window has 80 + 14 + 14 live columns, the rest zero); v (BH, N, 80) pair; same arithmetic as above.
+ *   forward:   -> out (BH, N, 80) f32, lse (BH, N) f32
+ *   backward:  v and dO (scaled by the caller into fp16's range) as (BH, N, 96) pairs, lse, delta (BH, N) f32 = rowsum(dO * out)
+ *              -> dq' (BH, N, 128) f32, dk (BH, N, 80) f32, dv (BH, N, 80) f32
+ * Rows beyond N exist only inside the kernels: keys >= N get probability exactly 0 (masked by index), rows >= N are neither read as data nor
+ * written.  HIPIE_EINVAL without a launch for N < 1, N > 256, BH < 1 or a null pointer. */
+int hipie_attn_train_win_forward(const void* q_hi, const void* q_lo, const void* k_hi, const void* k_lo, const void* v_hi, const void* v_lo,
+                                 void* out, void* lse, int BH, int N, void* stream);
+int hipie_attn_train_win_backward(const void* q_hi, const void* q_lo, const void* k_hi, const void* k_lo, const void* v_hi, const void* v_lo,
+                                  const void* do_hi, const void* do_lo, const void* lse, const void* delta, void* dq, void* dk, void* dv,
+                                  int BH, int N, void* stream);
+
 /* dst + rows[i] * ld_bytes <- the row_bytes bytes at src_row, for i < n_rows (negative entries are skipped): one constant row into a
  * listed set of rows.  Used to write the HL8 qkv BIAS row into the padding rows of a window-layout qkv buffer -- the qkv of a padding token
  * of window_partition is the bias, its LayerNorm output being zero (hipie/backbone/utils.py:29-37, vit.py:67-71).  16-byte units. */
