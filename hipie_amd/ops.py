@@ -1151,107 +1151,78 @@ def f16_pair(x, cols=None, scale=None):
                        % (x.dtype, tuple(x.shape), x.device, Cp))
 
 
+# the two instances of the fused training attention (csrc/attn_train_tile.h): (entry-point stem, operand columns, rule on N, its wording)
+_ATTN_TRAIN = ("attn_train", 224, lambda N: N >= 128 and N % 128 == 0, "N % 128 == 0")
+_ATTN_TRAIN_WIN = ("attn_train_win", 128, lambda N: 1 <= N <= 256, "1 <= N <= 256")
+
+
+def _attn_train_operands(who, inst, pairs, widths):
+    """the checks both directions share: every plane a contiguous fp16 device tensor, lo planes shaped like their hi planes, q' / k'
+    (BH, N, cols) with N as the instance takes it, the remaining pairs (BH, N, widths[i]) -> (the planes in entry order, BH, N)"""
+    _, cols, n_ok, rule = inst
+    planes = [t for pair in pairs for t in pair]
+    for t in planes:
+        if not t.is_cuda or t.dtype != torch.float16 or not t.is_contiguous():
+            raise RuntimeError("%s: contiguous fp16 device planes" % who)
+    qh, kh = pairs[0][0], pairs[1][0]
+    if qh.dim() != 3 or qh.shape[-1] != cols or kh.shape != qh.shape or not n_ok(qh.shape[1]) or qh.shape[0] < 1 \
+            or any(lo.shape != hi.shape for hi, lo in pairs) \
+            or any(tuple(pair[0].shape) != (qh.shape[0], qh.shape[1], w) for pair, w in zip(pairs[2:], widths)):
+        raise RuntimeError("%s: q', k' (BH, N, %d) and %s pairs with %s, got %s"
+                           % (who, cols, " / ".join("(BH, N, %d)" % w for w in widths), rule, " / ".join(str(tuple(pair[0].shape)) for pair in pairs)))
+    return planes, qh.shape[0], qh.shape[1]
+
+
+def _attn_train_forward(inst, q_pair, k_pair, v_pair):
+    who = inst[0] + "_forward"
+    planes, BH, N = _attn_train_operands(who, inst, (q_pair, k_pair, v_pair), (80,))
+    out = torch.empty(BH, N, 80, dtype=torch.float32, device=planes[0].device)
+    lse = torch.empty(BH, N, dtype=torch.float32, device=planes[0].device)
+    rc = getattr(_lib.load(), "hipie_" + who)(*[t.data_ptr() for t in planes], out.data_ptr(), lse.data_ptr(), BH, N, _stream())
+    _lib.check(rc, "hipie_" + who)
+    return out, lse
+
+
+def _attn_train_backward(inst, q_pair, k_pair, v96_pair, do96_pair, lse, delta):
+    who = inst[0] + "_backward"
+    planes, BH, N = _attn_train_operands(who, inst, (q_pair, k_pair, v96_pair, do96_pair), (96, 96))
+    if tuple(lse.shape) != (BH, N) or tuple(delta.shape) != (BH, N) or not lse.is_cuda or not delta.is_cuda:
+        raise RuntimeError("%s: lse / delta (BH, N) on the device" % who)
+    lse, delta = lse.float().contiguous(), delta.float().contiguous()
+    dq = torch.empty(BH, N, inst[1], dtype=torch.float32, device=planes[0].device)
+    dk = torch.empty(BH, N, 80, dtype=torch.float32, device=planes[0].device)
+    dv = torch.empty(BH, N, 80, dtype=torch.float32, device=planes[0].device)
+    rc = getattr(_lib.load(), "hipie_" + who)(*[t.data_ptr() for t in planes], lse.data_ptr(), delta.data_ptr(), dq.data_ptr(), dk.data_ptr(),
+                                              dv.data_ptr(), BH, N, _stream())
+    _lib.check(rc, "hipie_" + who)
+    return dq, dk, dv
+
+
 @_timed("attn_train_fwd")
 def attn_train_forward(q_pair, k_pair, v_pair):
     """hipie_attn_train_forward: q', k' (BH, N, 224) and v (BH, N, 80) as fp16 pairs (f16_pair) -> (out (BH, N, 80) f32, lse (BH, N) f32)"""
-    lib = _lib.load()
-    qh, ql = q_pair
-    kh, kl = k_pair
-    vh, vl = v_pair
-    BH, N, DQ = qh.shape
-    if DQ != 224 or kh.shape != qh.shape or tuple(vh.shape) != (BH, N, 80) or N % 128 or not qh.is_cuda:
-        raise RuntimeError("attn_train_forward: q', k' (BH, N, 224), v (BH, N, 80) device pairs with N %% 128 == 0, got %s / %s / %s"
-                           % (tuple(qh.shape), tuple(kh.shape), tuple(vh.shape)))
-    for t in (qh, ql, kh, kl, vh, vl):
-        if t.dtype != torch.float16 or not t.is_contiguous():
-            raise RuntimeError("attn_train_forward: contiguous fp16 planes")
-    out = torch.empty(BH, N, 80, dtype=torch.float32, device=qh.device)
-    lse = torch.empty(BH, N, dtype=torch.float32, device=qh.device)
-    rc = lib.hipie_attn_train_forward(qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(), vh.data_ptr(), vl.data_ptr(), out.data_ptr(),
-                                      lse.data_ptr(), BH, N, _stream())
-    _lib.check(rc, "hipie_attn_train_forward")
-    return out, lse
+    return _attn_train_forward(_ATTN_TRAIN, q_pair, k_pair, v_pair)
 
 
 @_timed("attn_train_bwd")
 def attn_train_backward(q_pair, k_pair, v96_pair, do96_pair, lse, delta):
     """hipie_attn_train_backward: the forward's q', k' pairs, v and dO as (BH, N, 96) pairs (f16_pair(.., 96); dO scaled into fp16's range by the
     caller), lse, delta = rowsum(dO * out) -> (dq' (BH, N, 224), dk (BH, N, 80), dv (BH, N, 80)) fp32, in the scale of the dO given"""
-    lib = _lib.load()
-    qh, ql = q_pair
-    kh, kl = k_pair
-    vh, vl = v96_pair
-    dh, dl = do96_pair
-    BH, N, _ = qh.shape
-    if tuple(vh.shape) != (BH, N, 96) or tuple(dh.shape) != (BH, N, 96) or tuple(lse.shape) != (BH, N) or tuple(delta.shape) != (BH, N):
-        raise RuntimeError("attn_train_backward: v / dO as (BH, N, 96) pairs, lse / delta (BH, N)")
-    for t in (qh, ql, kh, kl, vh, vl, dh, dl):
-        if t.dtype != torch.float16 or not t.is_contiguous() or not t.is_cuda:
-            raise RuntimeError("attn_train_backward: contiguous fp16 device planes")
-    lse, delta = lse.float().contiguous(), delta.float().contiguous()
-    dq = torch.empty(BH, N, 224, dtype=torch.float32, device=qh.device)
-    dk = torch.empty(BH, N, 80, dtype=torch.float32, device=qh.device)
-    dv = torch.empty(BH, N, 80, dtype=torch.float32, device=qh.device)
-    rc = lib.hipie_attn_train_backward(qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(), vh.data_ptr(), vl.data_ptr(), dh.data_ptr(),
-                                       dl.data_ptr(), lse.data_ptr(), delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), BH, N, _stream())
-    _lib.check(rc, "hipie_attn_train_backward")
-    return dq, dk, dv
-
-
-def _win_planes(who, planes):
-    for t in planes:
-        if not t.is_cuda or t.dtype != torch.float16 or not t.is_contiguous():
-            raise RuntimeError("%s: contiguous fp16 device planes" % who)
+    return _attn_train_backward(_ATTN_TRAIN, q_pair, k_pair, v96_pair, do96_pair, lse, delta)
 
 
 @_timed("attn_train_win_fwd")
 def attn_train_win_forward(q_pair, k_pair, v_pair):
     """hipie_attn_train_win_forward (the windowed blocks: one (window, head) item of N <= 256 tokens per workgroup, no row padding): q', k'
     (BH, N, 128) and v (BH, N, 80) as fp16 pairs (f16_pair) -> (out (BH, N, 80) f32, lse (BH, N) f32)"""
-    lib = _lib.load()
-    qh, ql = q_pair
-    kh, kl = k_pair
-    vh, vl = v_pair
-    _win_planes("attn_train_win_forward", (qh, ql, kh, kl, vh, vl))
-    if qh.dim() != 3 or qh.shape[-1] != 128 or kh.shape != qh.shape or ql.shape != qh.shape or kl.shape != qh.shape \
-            or tuple(vh.shape) != (qh.shape[0], qh.shape[1], 80) or vl.shape != vh.shape or not 1 <= qh.shape[1] <= 256 or qh.shape[0] < 1:
-        raise RuntimeError("attn_train_win_forward: q', k' (BH, N, 128), v (BH, N, 80) pairs with 1 <= N <= 256, got %s / %s / %s"
-                           % (tuple(qh.shape), tuple(kh.shape), tuple(vh.shape)))
-    BH, N, _ = qh.shape
-    out = torch.empty(BH, N, 80, dtype=torch.float32, device=qh.device)
-    lse = torch.empty(BH, N, dtype=torch.float32, device=qh.device)
-    rc = lib.hipie_attn_train_win_forward(qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(), vh.data_ptr(), vl.data_ptr(), out.data_ptr(),
-                                          lse.data_ptr(), BH, N, _stream())
-    _lib.check(rc, "hipie_attn_train_win_forward")
-    return out, lse
+    return _attn_train_forward(_ATTN_TRAIN_WIN, q_pair, k_pair, v_pair)
 
 
 @_timed("attn_train_win_bwd")
 def attn_train_win_backward(q_pair, k_pair, v96_pair, do96_pair, lse, delta):
     """hipie_attn_train_win_backward: the forward's q', k' pairs, v and dO as (BH, N, 96) pairs (f16_pair(.., 96); dO scaled into fp16's range by
     the caller), lse, delta = rowsum(dO * out) -> (dq' (BH, N, 128), dk (BH, N, 80), dv (BH, N, 80)) fp32, in the scale of the dO given"""
-    lib = _lib.load()
-    qh, ql = q_pair
-    kh, kl = k_pair
-    vh, vl = v96_pair
-    dh, dl = do96_pair
-    _win_planes("attn_train_win_backward", (qh, ql, kh, kl, vh, vl, dh, dl))
-    if qh.dim() != 3 or qh.shape[-1] != 128 or kh.shape != qh.shape or ql.shape != qh.shape or kl.shape != qh.shape \
-            or not 1 <= qh.shape[1] <= 256 or qh.shape[0] < 1:
-        raise RuntimeError("attn_train_win_backward: q', k' (BH, N, 128) pairs with 1 <= N <= 256, got %s / %s" % (tuple(qh.shape), tuple(kh.shape)))
-    BH, N, _ = qh.shape
-    if any(tuple(t.shape) != (BH, N, 96) for t in (vh, vl, dh, dl)) or tuple(lse.shape) != (BH, N) or tuple(delta.shape) != (BH, N) \
-            or not lse.is_cuda or not delta.is_cuda:
-        raise RuntimeError("attn_train_win_backward: v / dO as (BH, N, 96) pairs, lse / delta (BH, N) on the device")
-    lse, delta = lse.float().contiguous(), delta.float().contiguous()
-    dq = torch.empty(BH, N, 128, dtype=torch.float32, device=qh.device)
-    dk = torch.empty(BH, N, 80, dtype=torch.float32, device=qh.device)
-    dv = torch.empty(BH, N, 80, dtype=torch.float32, device=qh.device)
-    rc = lib.hipie_attn_train_win_backward(qh.data_ptr(), ql.data_ptr(), kh.data_ptr(), kl.data_ptr(), vh.data_ptr(), vl.data_ptr(), dh.data_ptr(),
-                                           dl.data_ptr(), lse.data_ptr(), delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), BH, N,
-                                           _stream())
-    _lib.check(rc, "hipie_attn_train_win_backward")
-    return dq, dk, dv
+    return _attn_train_backward(_ATTN_TRAIN_WIN, q_pair, k_pair, v96_pair, do96_pair, lse, delta)
 
 
 @_timed("fill_rows")

@@ -184,6 +184,29 @@ def split_mlp(x, w1, b1, w2, b2, act):
     return split_linear(f(split_linear(x, w1, b1, w1, "w")), w2, b2, w2, "w")
 
 
+def _attention_forward(ctx, qa, ka, v, cols, forward_op):
+    """the forward of FusedAttentionFunction / WindowAttentionFunction: q', k' padded to `cols` operand columns"""
+    qp, kp = ops.f16_pair(qa, cols), ops.f16_pair(ka, cols)
+    out, lse = forward_op(qp, kp, ops.f16_pair(v))
+    ctx.save_for_backward(qp[0], qp[1], kp[0], kp[1], v, out, lse)
+    ctx.cols = (qa.shape[-1], ka.shape[-1])
+    return out
+
+
+def _attention_backward(ctx, go, backward_op):
+    """their backward"""
+    qh, ql, kh, kl, v, out, lse = ctx.saved_tensors
+    go = go.float().contiguous()
+    # dO enters the kernels as fp16 pairs: scaled by a power of two so that its largest entry sits in [8, 16) (a device scalar: no host
+    # wait) -- high enough for the pairs of dO and dS = P (dP - delta) to be normal fp16 numbers, low enough for |dP| <= 16 * 80 * max|v|
+    scale = torch.exp2(torch.floor(torch.log2(16.0 / go.abs().amax().clamp_min(1e-30))))
+    delta = (go * out).sum(-1) * scale
+    dq, dk, dv = backward_op((qh, ql), (kh, kl), ops.f16_pair(v, 96), ops.f16_pair(go, 96, scale), lse, delta)
+    inv = 1.0 / scale
+    cq, ck = ctx.cols
+    return dq[..., :cq] * inv, torch.nn.functional.pad(dk * inv, (0, ck - 80)), dv * inv
+
+
 class FusedAttentionFunction(torch.autograd.Function):
     """softmax(q' k'^T) v with the decomposed rel-pos bias folded into q' / k' (net.vit_attention), forward and backward on
     hipie_attn_train_forward / _backward (csrc/attn_train.hip): no (heads, N, N) tensor in HBM.  q' (BH, N, <= 224), k' (BH, N, <= 224) whose
@@ -192,24 +215,11 @@ class FusedAttentionFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qa, ka, v):
-        qp, kp = ops.f16_pair(qa, 224), ops.f16_pair(ka, 224)
-        out, lse = ops.attn_train_forward(qp, kp, ops.f16_pair(v))
-        ctx.save_for_backward(qp[0], qp[1], kp[0], kp[1], v, out, lse)
-        ctx.cols = (qa.shape[-1], ka.shape[-1])
-        return out
+        return _attention_forward(ctx, qa, ka, v, 224, ops.attn_train_forward)
 
     @staticmethod
     def backward(ctx, go):
-        qh, ql, kh, kl, v, out, lse = ctx.saved_tensors
-        go = go.float().contiguous()
-        # dO enters the kernels as fp16 pairs: scaled by a power of two so that its largest entry sits in [8, 16) (a device scalar: no host
-        # wait) -- high enough for the pairs of dO and dS = P (dP - delta) to be normal fp16 numbers, low enough for |dP| <= 16 * 80 * max|v|
-        scale = torch.exp2(torch.floor(torch.log2(16.0 / go.abs().amax().clamp_min(1e-30))))
-        delta = (go * out).sum(-1) * scale
-        dq, dk, dv = ops.attn_train_backward((qh, ql), (kh, kl), ops.f16_pair(v, 96), ops.f16_pair(go, 96, scale), lse, delta)
-        inv = 1.0 / scale
-        cq, ck = ctx.cols
-        return dq[..., :cq] * inv, torch.nn.functional.pad(dk * inv, (0, ck - 80)), dv * inv
+        return _attention_backward(ctx, go, ops.attn_train_backward)
 
 
 def fused_attention_ok(qa, ka, v):
@@ -256,25 +266,13 @@ class WindowAttentionFunction(torch.autograd.Function):
         if ctx.single:
             ctx.shapes = (qa.shape, ka.shape)
             return v.clone()
-        qp, kp = ops.f16_pair(qa, 128), ops.f16_pair(ka, 128)
-        out, lse = ops.attn_train_win_forward(qp, kp, ops.f16_pair(v))
-        ctx.save_for_backward(qp[0], qp[1], kp[0], kp[1], v, out, lse)
-        ctx.cols = (qa.shape[-1], ka.shape[-1])
-        return out
+        return _attention_forward(ctx, qa, ka, v, 128, ops.attn_train_win_forward)
 
     @staticmethod
     def backward(ctx, go):
         if ctx.single:
             return go.new_zeros(ctx.shapes[0]), go.new_zeros(ctx.shapes[1]), go
-        qh, ql, kh, kl, v, out, lse = ctx.saved_tensors
-        go = go.float().contiguous()
-        # as FusedAttentionFunction.backward: dO scaled by a power of two (a device scalar: no host wait) so that its largest entry is in [8, 16)
-        scale = torch.exp2(torch.floor(torch.log2(16.0 / go.abs().amax().clamp_min(1e-30))))
-        delta = (go * out).sum(-1) * scale
-        dq, dk, dv = ops.attn_train_win_backward((qh, ql), (kh, kl), ops.f16_pair(v, 96), ops.f16_pair(go, 96, scale), lse, delta)
-        inv = 1.0 / scale
-        cq, ck = ctx.cols
-        return dq[..., :cq] * inv, torch.nn.functional.pad(dk * inv, (0, ck - 80)), dv * inv
+        return _attention_backward(ctx, go, ops.attn_train_win_backward)
 
 
 def window_attention_ok(qa, ka, v):

@@ -573,7 +573,8 @@ int hipie_attn_train_backward(const void* q_hi, const void* q_lo, const void* k_
                               const void* do_hi, const void* do_lo, const void* lse, const void* delta, void* dq, void* dk, void* dv,
                               int BH, int N, void* stream);
 
-/* The short-sequence instance of the two entries above (csrc/attn_train_win.hip): the attention of the WINDOWED ViT blocks of the training
+/* The short-sequence instance of the two entries above (csrc/attn_train_win.hip; the same kernels, csrc/attn_train_tile.h, built for 128
+ * operand columns, two tiles per wave and ragged items): the attention of the WINDOWED ViT blocks of the training
  * step -- Attention.forward, hipie/backbone/vit.py:69-80, with add_decomposed_rel_pos (hipie/backbone/utils.py:96-125) folded into the operands
  * -- over items of N tokens, 1 <= N <= 256, one (window, head) each, dense in memory (no row padding), one workgroup per item.
  *   q', k' (BH, N, 128) pairs (a 14 x 14 window has 80 + 14 + 14 live columns, the rest zero); v (BH, N, 80) pair; same arithmetic as above.

@@ -27,7 +27,7 @@ def _operands(BH, H, W, seed):
 
 
 @gpu
-@pytest.mark.parametrize("BH,H,W", [(3, 16, 16), (2, 32, 32), (1, 8, 16), (5, 64, 64)])
+@pytest.mark.parametrize("BH,H,W", [(3, 16, 16), (2, 32, 32), (1, 8, 16), (5, 64, 64), (16, 16, 16)])   # BH = 16: the XCD-placed branch of the item locator
 def test_attn_train_forward_vs_materialised(BH, H, W):
     from hipie_amd import ops
     qa, ka, v = _operands(BH, H, W, BH * 100 + H)
@@ -41,7 +41,7 @@ def test_attn_train_forward_vs_materialised(BH, H, W):
 
 
 @gpu
-@pytest.mark.parametrize("BH,H,W,gscale", [(3, 16, 16, 1.0), (2, 32, 32, 1e-4), (1, 8, 16, 30.0), (2, 64, 64, 1e-2)])
+@pytest.mark.parametrize("BH,H,W,gscale", [(3, 16, 16, 1.0), (2, 32, 32, 1e-4), (1, 8, 16, 30.0), (2, 64, 64, 1e-2), (16, 16, 16, 1.0)])
 def test_attn_train_function_gradients_vs_autograd_in_double(BH, H, W, gscale):
     """FusedAttentionFunction (forward + both backward kernels) against torch.autograd of the materialised formulation in double: d q'
     (whose columns 80.. are d rel_h | d rel_w), d k (the first 80 columns of k'; the indicator columns are constants), d v; upstream

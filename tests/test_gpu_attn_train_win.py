@@ -25,8 +25,10 @@ def _grad_enabled():
 
 # (BH, H, W, upstream gradient scale): 196 = the workload's item (28 masked keys in the last 32-key tile, a partial last query tile); 16 = a
 # single key tile, half of it masked; 63 = one short of a tile boundary; 256 = the largest item, no masking, odd BH, 112 columns; 192 = a
-# non-square grid, BH no multiple of 8, 112 columns.  BH >= 2: a store past an item's last row lands in the next item.
-SHAPES = [(3, 14, 14, 1.0), (2, 4, 4, 1e-4), (2, 7, 9, 30.0), (5, 16, 16, 1e-4), (9, 8, 24, 30.0)]
+# non-square grid, BH no multiple of 8, 112 columns.  BH >= 2: a store past an item's last row lands in the next item.  128 | 129 and
+# 224 | 225: the last full item and the first item on each side of the 4 -> 7 and 7 -> 8 wave selection.
+SHAPES = [(3, 14, 14, 1.0), (2, 4, 4, 1e-4), (2, 7, 9, 30.0), (5, 16, 16, 1e-4), (9, 8, 24, 30.0),
+          (2, 8, 16, 1.0), (2, 3, 43, 30.0), (2, 14, 16, 1e-4), (2, 15, 15, 1.0)]
 _REF = {}
 
 
