@@ -44,6 +44,12 @@ SIGNATURES = {
     "hipie_act_forward": [c_p, c_p, c_l, c_i, c_i, c_p],
     "hipie_act_backward": [c_p] * 6 + [c_l, c_i, c_i, c_p],
     "hipie_act_backward_ws_bytes": [c_l, c_i],
+    "hipie_point_mask_loss_forward": [c_p] * 8 + [c_l, c_l, c_i, c_i, c_l, c_i, c_i, c_i, c_i, c_f, c_f, c_p],
+    "hipie_point_mask_loss_ws_bytes": [c_l, c_i],
+    "hipie_point_mask_loss_backward": [c_p] * 8 + [c_l, c_i, c_i, c_l, c_i, c_i, c_i, c_i, c_f, c_f, c_p],
+    "hipie_token_focal_forward": [c_p] * 5 + [c_l, c_i, c_i, c_i, c_f, c_f, c_p],
+    "hipie_token_focal_ws_bytes": [c_l],
+    "hipie_token_focal_backward": [c_p] * 5 + [c_i, c_i, c_i, c_f, c_f, c_p],
     "hipie_add_layernorm_sum": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_f, c_i, c_i, c_i, c_p],
     "hipie_add_layernorm_rows": [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_f, c_i, c_i, c_i, c_p, c_p, c_p],
     "hipie_batched_nms": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_i, c_p],
@@ -119,7 +125,8 @@ def load():
         fn.argtypes = argtypes
         fn.restype = (ctypes.c_char_p if name == "hipie_last_error" else
                       ctypes.c_int64 if name in ("hipie_bi_xattn_workspace", "hipie_mask_einsum_workspace", "hipie_msda_backward_workspace",
-                                                      "hipie_layernorm_backward_ws_bytes", "hipie_act_backward_ws_bytes") else ctypes.c_int)
+                                                      "hipie_layernorm_backward_ws_bytes", "hipie_act_backward_ws_bytes", "hipie_point_mask_loss_ws_bytes",
+                                                      "hipie_token_focal_ws_bytes") else ctypes.c_int)
     _lib = lib
     return lib
 

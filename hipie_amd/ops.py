@@ -788,6 +788,107 @@ def act_backward(u, g, act, want_a=False, want_bias_grad=False, out=None):
     return du, a, dbias
 
 
+def _loss_f32(t, name):
+    """t as a dense fp32 device tensor (a strided view is copied)"""
+    if not t.is_cuda:
+        raise RuntimeError("Not implemented on the CPU (%s must be a CUDA/HIP tensor)" % name)
+    if t.dtype != torch.float32:
+        raise RuntimeError("%s must be torch.float32, got %s" % (name, t.dtype))
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _point_loss_operands(src, tgt, tgt_index, pts):
+    src, tgt, pts = _loss_f32(src, "src"), _loss_f32(tgt, "tgt"), _loss_f32(pts, "pts")
+    if not tgt_index.is_cuda:
+        raise RuntimeError("Not implemented on the CPU (tgt_index must be a CUDA/HIP tensor)")
+    if tgt_index.dtype != torch.int64:
+        raise RuntimeError("tgt_index must be torch.int64, got %s" % tgt_index.dtype)
+    if src.dim() != 3 or tgt.dim() != 3 or pts.dim() != 3 or pts.shape[0] != src.shape[0] or pts.shape[2] != 2 or tgt_index.shape != src.shape[:1]:
+        raise RuntimeError("point_mask_loss: src (N,H,W), tgt (T,Ht,Wt), tgt_index (N,), pts (N,P,2); got %s %s %s %s"
+                           % (tuple(src.shape), tuple(tgt.shape), tuple(tgt_index.shape), tuple(pts.shape)))
+    return src, tgt, tgt_index.contiguous(), pts
+
+
+@_timed("point_loss_fwd")
+def point_mask_loss_forward(src, tgt, tgt_index, pts, mode, alpha=-1.0):
+    """the point-sampled mask losses of one criterion call (hipie_point_mask_loss_forward, fp32): src (N,H,W) logits, tgt (T,Ht,Wt) ALL
+    target masks, tgt_index (N,) int64 rows of tgt, pts (N,P,2) (x, y) in [0,1]^2; mode 0 = sigmoid CE, 1 = focal (gamma 2, alpha) ->
+    (lmask (N,), ldice (N,), sums (N,3) for point_mask_loss_backward).  Bit-reproducible; the workspace lives for the call."""
+    src, tgt, tgt_index, pts = _point_loss_operands(src, tgt, tgt_index, pts)
+    lib = _lib.load()
+    N, P = src.shape[0], pts.shape[1]
+    lmask, ldice, sums = src.new_empty(N), src.new_empty(N), src.new_empty(N, 3)
+    ws_bytes = int(lib.hipie_point_mask_loss_ws_bytes(N, P))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=src.device)
+    rc = lib.hipie_point_mask_loss_forward(src.data_ptr(), tgt.data_ptr(), tgt_index.data_ptr(), pts.data_ptr(), lmask.data_ptr(), ldice.data_ptr(),
+                                           sums.data_ptr(), ws.data_ptr(), ws_bytes, N, src.shape[1], src.shape[2], tgt.shape[0], tgt.shape[1],
+                                           tgt.shape[2], P, int(mode), float(alpha), 2.0, _stream())
+    _lib.check(rc, "hipie_point_mask_loss_forward")
+    return lmask, ldice, sums
+
+
+@_timed("point_loss_bwd")
+def point_mask_loss_backward(src, tgt, tgt_index, pts, sums, g_mask, g_dice, mode, alpha=-1.0):
+    """d_src (N,H,W) of point_mask_loss_forward for the gradients g_mask (N,), g_dice (N,) of its two outputs
+    (hipie_point_mask_loss_backward): the samples are recomputed, the corners accumulated with fp32 atomics (not bit-reproducible)."""
+    src, tgt, tgt_index, pts = _point_loss_operands(src, tgt, tgt_index, pts)
+    sums, g_mask, g_dice = _loss_f32(sums, "sums"), _loss_f32(g_mask, "g_mask"), _loss_f32(g_dice, "g_dice")
+    N = src.shape[0]
+    if sums.shape != (N, 3) or g_mask.shape != (N,) or g_dice.shape != (N,):
+        raise RuntimeError("point_mask_loss_backward: sums (N,3), g_mask (N,), g_dice (N,) for N=%d" % N)
+    d_src = torch.empty_like(src)
+    rc = _lib.load().hipie_point_mask_loss_backward(src.data_ptr(), tgt.data_ptr(), tgt_index.data_ptr(), pts.data_ptr(), sums.data_ptr(),
+                                                    g_mask.data_ptr(), g_dice.data_ptr(), d_src.data_ptr(), N, src.shape[1], src.shape[2],
+                                                    tgt.shape[0], tgt.shape[1], tgt.shape[2], pts.shape[1], int(mode), float(alpha), 2.0, _stream())
+    _lib.check(rc, "hipie_point_mask_loss_backward")
+    return d_src
+
+
+def _token_focal_operands(logits, onehot, keep):
+    logits, onehot = _loss_f32(logits, "logits"), _loss_f32(onehot, "onehot")
+    if logits.dim() != 3 or onehot.shape != logits.shape:
+        raise RuntimeError("token_focal: logits and onehot (B,Q,T); got %s %s" % (tuple(logits.shape), tuple(onehot.shape)))
+    if keep is not None:
+        if not keep.is_cuda:
+            raise RuntimeError("Not implemented on the CPU (keep must be a CUDA/HIP tensor)")
+        if keep.shape != (logits.shape[0], logits.shape[2]):
+            raise RuntimeError("token_focal: keep %s must be (B,T) of logits %s" % (tuple(keep.shape), tuple(logits.shape)))
+        keep = (keep if keep.dtype in (torch.uint8, torch.bool) else keep > 0).contiguous()           # one byte per token either way
+    return logits, onehot, keep
+
+
+@_timed("token_focal_fwd")
+def token_focal_forward(logits, onehot, keep=None, alpha=0.25):
+    """sum over (b, q, t) with keep[b, t] != 0 of the binary focal loss (gamma 2) of logits (B,Q,T) against onehot (B,Q,T)
+    (hipie_token_focal_forward, fp32) -> 0-d tensor.  keep (B,T) or None.  Bit-reproducible, no host wait."""
+    logits, onehot, keep = _token_focal_operands(logits, onehot, keep)
+    lib = _lib.load()
+    B, Q, T = logits.shape
+    out = logits.new_zeros(())
+    ws_bytes = int(lib.hipie_token_focal_ws_bytes(logits.numel()))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=logits.device)
+    rc = lib.hipie_token_focal_forward(logits.data_ptr(), onehot.data_ptr(), None if keep is None else keep.data_ptr(), out.data_ptr(),
+                                       ws.data_ptr(), ws_bytes, B, Q, T, float(alpha), 2.0, _stream())
+    _lib.check(rc, "hipie_token_focal_forward")
+    return out
+
+
+@_timed("token_focal_bwd")
+def token_focal_backward(logits, onehot, keep, g, alpha=0.25):
+    """dlogits (B,Q,T) = g * d focal / d logits at kept tokens, exactly 0 at dropped ones (hipie_token_focal_backward); g: 0-d DEVICE
+    tensor, the gradient of token_focal_forward's output."""
+    logits, onehot, keep = _token_focal_operands(logits, onehot, keep)
+    g = _loss_f32(g, "g")
+    if g.numel() != 1:
+        raise RuntimeError("token_focal_backward: g must hold one value, got %s" % (tuple(g.shape),))
+    B, Q, T = logits.shape
+    dlogits = torch.empty_like(logits)
+    rc = _lib.load().hipie_token_focal_backward(logits.data_ptr(), onehot.data_ptr(), None if keep is None else keep.data_ptr(), g.data_ptr(),
+                                                dlogits.data_ptr(), B, Q, T, float(alpha), 2.0, _stream())
+    _lib.check(rc, "hipie_token_focal_backward")
+    return dlogits
+
+
 @_timed("add_layernorm")
 def add_layernorm_sum(x, delta, weight, bias, eps, addend):
     """n = LayerNorm(x + delta) and n + addend, both in x's dtype, one launch (the encoder's post-norm + next `src + pos`)."""

@@ -10,7 +10,14 @@ What is NOT restated: the BoxInst projection / pairwise-colour terms (`loss_mask
 in every shipped config) and the tracking `loss_reid` (:598-634, video models: SURVEY section 8 "out").  With OTA matching (matcher.forward_ota)
 the reference normalises by the number of matched pairs instead of targets (`num_boxes = len(idx[0]) if self.ota`): pass ota=True.
 The cross-rank mean of the target count (`all_reduce(num_boxes) / world_size`) is applied when torch.distributed is initialised, as
-in the reference.  Random point coordinates come from ``draw(shape, device)`` (default torch.rand), in the reference's order."""
+in the reference.  Random point coordinates come from ``draw(shape, device)`` (default torch.rand), in the reference's order.
+
+``ops`` (both criteria, default None: the torch code below, unchanged): an object with
+    point_mask_loss(src (N,H,W), tgt_maps (T,Ht,Wt), tgt_index (N,), pts (N,P,2), mode, alpha) -> (lmask (N,), ldice (N,))
+    token_focal_sum(logits, onehot, text_mask, alpha) -> scalar
+(net.HipBackendLosses: functions.PointMaskLossFunction / TokenFocalFunction on csrc/point_loss.hip).  With it the point-sampled mask losses
+hand over ALL padded targets and the flat index of the matched ones -- the targets are not gathered -- and the token focal loss drops the pad
+tokens inside the kernel instead of by boolean indexing (a host wait).  The random draws and their order do not change."""
 import copy
 
 import torch
@@ -115,8 +122,10 @@ class DetCriterion(nn.Module):
     passed as `indices_per_layer` (last entry = last layer)."""
 
     def __init__(self, matcher, losses, focal_alpha=0.25, mask_out_stride=4, point_sample_masks=True, panoptic_box_loss=True,
-                 still_cls_for_encoder=False, num_points=112 * 112, oversample_ratio=3.0, importance_sample_ratio=0.75, draw=None, ota=False):
+                 still_cls_for_encoder=False, num_points=112 * 112, oversample_ratio=3.0, importance_sample_ratio=0.75, draw=None, ota=False,
+                 ops=None):
         super().__init__()
+        self.ops = ops
         self.ota = ota                                     # one-to-many assignments: every loss is per MATCHED PAIR (deformable_detr.py:362, 430, 481)
         self.matcher, self.losses = matcher, tuple(losses)
         self.focal_alpha, self.mask_out_stride = focal_alpha, mask_out_stride
@@ -134,6 +143,8 @@ class DetCriterion(nn.Module):
         if count == 0:
             return {"loss_ce": logits.sum() * 0.0}
         onehot = _positive_onehot(logits, targets, indices)
+        if self.ops is not None:
+            return {"loss_ce": self.ops.token_focal_sum(logits, onehot, out["text_masks"], self.focal_alpha) / count}
         return {"loss_ce": token_focal_loss(logits, onehot, out["text_masks"], self.focal_alpha) / count}
 
     def loss_boxes(self, out, targets, indices, count):
@@ -180,11 +191,21 @@ class DetCriterion(nn.Module):
             return {"loss_mask": src * 0.0, "loss_dice": src * 0.0}
         frames = src.shape[1]
         tm = self.target_masks(targets, src)
-        tm = tm.reshape(len(targets), -1, frames, tm.shape[-2], tm.shape[-1])[_perm(indices, 1)]
+        tm = tm.reshape(len(targets), -1, frames, tm.shape[-2], tm.shape[-1])
+        matched = _perm(indices, 1)
+        fused = self.ops is not None and frames == 1 and self.point_sample_masks
+        if not fused:
+            tm = tm[matched]
         if self.ota:
             count = src.shape[0]
-        if len(tm) == 0:
+        if len(matched[0]) == 0:
             return {"loss_mask": src.sum() * 0.0, "loss_dice": src.sum() * 0.0}
+        if fused:                                           # the targets stay where they are: the kernel reads row `flat` of (B * max n, h, w)
+            with torch.no_grad():
+                pts = uncertain_points(src, self.num_points, self.oversample_ratio, self.importance_sample_ratio, self.draw)
+            flat = (matched[0] * tm.shape[1] + matched[1]).to(src.device)
+            lmask, ldice = self.ops.point_mask_loss(src[:, 0], tm.flatten(0, 2), flat, pts, 1, 0.25)      # dense_focal_loss's default alpha
+            return {"loss_mask": lmask.sum() / count, "loss_dice": ldice.sum() / count}
         if self.point_sample_masks:
             with torch.no_grad():
                 pts = uncertain_points(src, self.num_points, self.oversample_ratio, self.importance_sample_ratio, self.draw)
@@ -247,8 +268,10 @@ class MaskCriterion(nn.Module):
     dn: "no" | "standard" | "seg" with dn_losses the families applied to the de-noising part (maskdino/criterion.py:136-166)."""
 
     def __init__(self, num_classes, matcher, losses, vl_loss=False, num_points=112 * 112, oversample_ratio=3.0, importance_sample_ratio=0.75,
-                 dn="no", dn_losses=(), panoptic_on=False, focal_alpha=0.25, draw=None):
+                 dn="no", dn_losses=(), panoptic_on=False, focal_alpha=0.25, draw=None, ops=None):
         super().__init__()
+        self.ops = ops
+        self._padded = None                                # (targets, their padded masks) of the forward in flight, `ops` path only
         self.num_classes, self.matcher, self.losses = num_classes, matcher, tuple(losses)
         self.vl_loss, self.dn, self.dn_losses_names, self.panoptic_on, self.focal_alpha = vl_loss, dn, tuple(dn_losses), panoptic_on, focal_alpha
         self.num_points, self.oversample_ratio, self.importance_sample_ratio = num_points, oversample_ratio, importance_sample_ratio
@@ -260,6 +283,8 @@ class MaskCriterion(nn.Module):
             if count == 0:
                 return {"loss_ce": logits.sum() * 0.0}
             onehot = _positive_onehot(logits, targets, indices).detach()
+            if self.ops is not None:
+                return {"loss_ce": self.ops.token_focal_sum(logits, onehot, out["text_masks"].detach(), self.focal_alpha) / count}
             return {"loss_ce": token_focal_loss(logits, onehot, out["text_masks"].detach(), self.focal_alpha) / count}
         onehot = torch.zeros_like(logits)                  # :186-207: unmatched queries are all-zero rows ("no object")
         bi, si = _perm(indices, 0)
@@ -281,12 +306,27 @@ class MaskCriterion(nn.Module):
     def loss_masks(self, out, targets, indices, count):
         """:286-336"""
         src = out["pred_masks"][_perm(indices, 0)][:, None]
+        if self.ops is not None and len(src):               # the targets stay where they are: the kernel reads row `flat` of (B * max n, H, W)
+            tm = self._padded_targets(targets, src)
+            with torch.no_grad():
+                pts = uncertain_points(src, self.num_points, self.oversample_ratio, self.importance_sample_ratio, self.draw)
+            bi, ti = _perm(indices, 1)
+            lmask, ldice = self.ops.point_mask_loss(src[:, 0], tm.flatten(0, 1), (bi * tm.shape[1] + ti).to(src.device), pts, 0, -1.0)
+            return {"loss_mask": lmask.sum() / count, "loss_dice": ldice.sum() / count}
         tm = _pad_masks([t["masks"] for t in targets]).to(src)[_perm(indices, 1)][:, None]
         with torch.no_grad():
             pts = uncertain_points(src, self.num_points, self.oversample_ratio, self.importance_sample_ratio, self.draw)
             lab = point_sample(tm, pts)[:, 0]
         lg = point_sample(src, pts)[:, 0]
         return {"loss_mask": sigmoid_ce_loss(lg, lab, count), "loss_dice": dice_loss(lg, lab, count)}
+
+    def _padded_targets(self, targets, like):
+        """the padded (B, max n, H, W) targets of the `ops` path, built ONCE per forward: every layer and de-noising part indexes the same
+        tensor (each fused node keeps its targets until the backward; a tensor per call would be ~64 MB each at 2 x 8 masks of 1024^2)"""
+        hit = self._padded
+        if hit is None or hit[0] is not targets or hit[1].dtype != like.dtype or hit[1].device != like.device:
+            hit = self._padded = (targets, _pad_masks([t["masks"] for t in targets]).to(like))
+        return hit[1]
 
     def _one(self, name, out, targets, indices, count):
         return {"labels": self.loss_labels, "masks": self.loss_masks, "boxes": self.loss_boxes}[name](out, targets, indices, count)
@@ -332,4 +372,5 @@ class MaskCriterion(nn.Module):
             iidx = self._match(outputs["interm_outputs"], targets)
             for name in self.losses:
                 losses.update({k + "_interm": v for k, v in self._one(name, outputs["interm_outputs"], targets, iidx, count).items()})
+        self._padded = None                                # the graph holds what it needs
         return losses

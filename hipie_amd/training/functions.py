@@ -319,3 +319,60 @@ class AddLayerNormFunction(torch.autograd.Function):
 def add_layer_norm(x, delta, weight, bias, eps):
     """(s, y) = (x + delta, LayerNorm(x + delta)) with a hand-written backward (AddLayerNormFunction); delta=None: s is x"""
     return AddLayerNormFunction.apply(x, delta, weight, bias, eps)
+
+
+class PointMaskLossFunction(torch.autograd.Function):
+    """the point-sampled mask losses of ONE criterion call as one node (criterion.loss_masks: point_sample of the predictions and of the
+    targets, focal / sigmoid-CE + dice): src (N,H,W) logits, tgt_maps (T,Ht,Wt) ALL padded targets -- indexed by tgt_index (N,) inside the
+    kernel, never gathered --, pts (N,P,2) -> (lmask (N,), ldice (N,)), the caller forms sum / count.  forward = ops.point_mask_loss_forward,
+    backward = ops.point_mask_loss_backward.  Saved: the four inputs (dense: a strided view is copied once, before it is saved) and the
+    (N,3) sums; the samples are recomputed -- nothing of N x P or N x Ht x Wt elements is kept.  Gradient for src only."""
+
+    @staticmethod
+    def forward(ctx, src, tgt_maps, tgt_index, pts, mode, alpha):
+        # dense copies are made HERE, once: a strided view (the targets sub-sampled at the mask stride) would otherwise be copied by the
+        # forward and again by the backward, and saving it would pin the storage it is a view of
+        src, tgt_maps, tgt_index, pts = src.contiguous(), tgt_maps.contiguous(), tgt_index.contiguous(), pts.contiguous()
+        lmask, ldice, sums = ops.point_mask_loss_forward(src, tgt_maps, tgt_index, pts, mode, alpha)
+        ctx.save_for_backward(src, tgt_maps, tgt_index, pts, sums)
+        ctx.mode, ctx.alpha = int(mode), float(alpha)
+        return lmask, ldice
+
+    @staticmethod
+    def backward(ctx, g_mask, g_dice):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        src, tgt_maps, tgt_index, pts, sums = ctx.saved_tensors
+        d_src = ops.point_mask_loss_backward(src, tgt_maps, tgt_index, pts, sums, g_mask.float().contiguous(), g_dice.float().contiguous(), ctx.mode,
+                                             ctx.alpha)
+        return (d_src,) + (None,) * 5
+
+
+def point_mask_loss(src, tgt_maps, tgt_index, pts, mode, alpha=-1.0):
+    """(lmask (N,), ldice (N,)) on hipie_point_mask_loss_forward / _backward; mode 0 = sigmoid CE, 1 = focal (gamma 2, alpha; alpha < 0: none)"""
+    return PointMaskLossFunction.apply(src, tgt_maps, tgt_index, pts, mode, alpha)
+
+
+class TokenFocalFunction(torch.autograd.Function):
+    """criterion.token_focal_loss as one node: the sum over (image, query, token) of the binary focal loss (gamma 2) of logits (B,Q,T)
+    against onehot, pad tokens (text_mask (B,T) == 0) left out INSIDE the kernel -- no boolean indexing, so no host wait.
+    forward = ops.token_focal_forward, backward = ops.token_focal_backward.  Gradient for logits only."""
+
+    @staticmethod
+    def forward(ctx, logits, onehot, text_mask, alpha):
+        keep = None if text_mask is None else text_mask > 0
+        ctx.save_for_backward(logits, onehot, keep)
+        ctx.alpha = float(alpha)
+        return ops.token_focal_forward(logits, onehot, keep, alpha)
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 4
+        logits, onehot, keep = ctx.saved_tensors
+        return (ops.token_focal_backward(logits, onehot, keep, g.float(), ctx.alpha),) + (None,) * 3
+
+
+def token_focal_sum(logits, onehot, text_mask=None, alpha=0.25):
+    """scalar: token_focal_loss(logits, onehot, text_mask, alpha) on hipie_token_focal_forward / _backward"""
+    return TokenFocalFunction.apply(logits, onehot, text_mask, alpha)

@@ -6,7 +6,8 @@ linears, LayerNorm / GroupNorm, the softmax attentions and the convolutions run 
 torch.autograd providing their backward (opt-in, HipBackendNorms: the LayerNorms of the ViT blocks and of the encoder layers on
 hipie_add_layernorm / hipie_layernorm_backward; opt-in, HipBackendMlp: their MLPs / FFNs as one node with the activation on
 hipie_act_forward / hipie_act_backward; opt-in, HipBackendWindows: the attention of the windowed ViT blocks on
-hipie_attn_train_win_forward / _backward).
+hipie_attn_train_win_forward / _backward; opt-in, HipBackendLosses: the point-sampled mask losses and the token focal loss of the two
+criteria on hipie_point_mask_loss_* / hipie_token_focal_*).
 
 Functional style over a dict ``sd`` of LIVE parameters (model.named_parameters() + buffers, reference key names), so gradients land in the
 model's own parameters.  Every function cites the reference code it follows.  Training-mode differences from the inference path:
@@ -128,6 +129,25 @@ class HipBackendWindows(HipBackend):
 
 class HipBackendAll(HipBackendNorms, HipBackendMlp, HipBackendWindows):
     """the three opt-in groups: the hand-written LayerNorm pair, the one-node MLP and the fused windowed attention"""
+
+
+class HipBackendLosses(HipBackend):
+    """HipBackend + the element-wise losses of both criteria on csrc/point_loss.hip: the point-sampled mask losses of a criterion call as one
+    node that indexes the un-gathered targets (functions.PointMaskLossFunction) and the token focal loss with the pad tokens dropped inside
+    the kernel (functions.TokenFocalFunction).  TrainStep hands the backend to DetCriterion / MaskCriterion as their `ops`.
+    Opt-in: TrainStep's default stays HipBackend; HipBackendAll does not include it."""
+
+    @staticmethod
+    def point_mask_loss(src, tgt_maps, tgt_index, pts, mode, alpha):
+        """src (N,H,W), tgt_maps (T,Ht,Wt), tgt_index (N,), pts (N,P,2); mode 0 = sigmoid CE, 1 = focal -> (lmask (N,), ldice (N,))"""
+        from .functions import point_mask_loss
+        return point_mask_loss(src, tgt_maps, tgt_index, pts, mode, alpha)
+
+    @staticmethod
+    def token_focal_sum(logits, onehot, text_mask, alpha):
+        """logits, onehot (B,Q,T), text_mask (B,T) or None -> the scalar criterion.token_focal_loss returns"""
+        from .functions import token_focal_sum
+        return token_focal_sum(logits, onehot, text_mask, alpha)
 
 
 # ------------------------------------------------------------------------------------------------ small helpers

@@ -317,6 +317,55 @@ int hipie_act_backward(const float* u, const float* g, float* du, float* a, floa
 int64_t hipie_act_backward_ws_bytes(int64_t rows, int N);
 
 /*
+ * The point-sampled mask losses of the training criteria (fp32), forward and backward.
+ * Replaces: DetCriterion.loss_masks (SetCriterion.loss_masks, models/deformable_detr/deformable_detr.py:452-524: point_sample of the
+ *           predictions and of the gathered targets, sigmoid_focal_loss + dice_loss, models/deformable_detr/segmentation.py:92-117,
+ *           jit_loss.py:28-48) and MaskCriterion.loss_masks (models/maskdino/criterion.py:286-336: sigmoid_ce_loss_jit + dice_loss_jit,
+ *           jit_loss.py:4-48), with point_sample = detectron2 point_rend/point_features.py:19-42 -- the gather of the matched target
+ *           masks, two grid_sample launches, the element-wise passes and their autograd mirrors (the grid-sampler backward among them).
+ *   src (N, H, W): matched mask logits, dense.   tgt (T, Ht, Wt): ALL target masks, not gathered; Ht, Wt independent of H, W.
+ *   tgt_index (N) int64: row of tgt per instance, in any order, repeats allowed; a value outside [0, T) reads as an all-zero target.
+ *   pts (N, P, 2): (x, y) in [0, 1]^2.  Sampling: bilinear, align_corners = false, pixel centres at (i + 0.5) / size, zero outside.
+ *   mode: 0 = sigmoid cross entropy, 1 = focal with exponent gamma = 2 (any other gamma is refused) and alpha (alpha < 0: no alpha term).
+ *   With lg, lab the two samples of a point and s = sigmoid(lg) -- lab is a bilinear sample, anything in [0, 1]:
+ *     lmask[n] = mean_p term(lg, lab)           CE in the softplus form max(lg, 0) - lg lab + log1p(exp(-|lg|)): finite for any logit
+ *     ldice[n] = 1 - (2 sum s lab + 1) / (sum s + sum lab + 1)
+ *     sums (N, 3) = (sum s lab, sum s, sum lab): what the backward needs of the forward.
+ * hipie_point_mask_loss_forward:  a workgroup per 1024 points of an instance, partial sums in `ws` (hipie_point_mask_loss_ws_bytes(N, P) =
+ *     N x ceil(P / 1024) x 16 bytes), added by a second kernel in a fixed order.  No atomics: bit-reproducible from call to call.
+ * hipie_point_mask_loss_backward: d_src (N, H, W) = d (sum_n g_mask[n] lmask[n] + g_dice[n] ldice[n]) / d src.  The samples are recomputed
+ *     (nothing of size N x P is kept); every point adds to the corners it read with fp32 hardware atomics into d_src, which is zeroed
+ *     here.  NOT bit-reproducible.  No gradient for tgt or pts.  d_src must not alias src; g_mask, g_dice are read only.
+ * Refused (-22): mode outside {0, 1}, gamma != 2, P <= 0 with N > 0, H*W or Ht*Wt >= 2^31 (offsets inside a map are 32-bit, the base of
+ *     an instance 64-bit), null pointers, a workspace that is too small.  N == 0: returns 0 without a launch, null pointers allowed.
+ */
+int hipie_point_mask_loss_forward(const float* src, const float* tgt, const int64_t* tgt_index, const float* pts, float* lmask, float* ldice,
+                                  float* sums, void* ws, int64_t ws_bytes, int64_t N, int H, int W, int64_t T, int Ht, int Wt, int P, int mode,
+                                  float alpha, float gamma, void* stream);
+int64_t hipie_point_mask_loss_ws_bytes(int64_t N, int P);
+int hipie_point_mask_loss_backward(const float* src, const float* tgt, const int64_t* tgt_index, const float* pts, const float* sums,
+                                   const float* g_mask, const float* g_dice, float* d_src, int64_t N, int H, int W, int64_t T, int Ht, int Wt,
+                                   int P, int mode, float alpha, float gamma, void* stream);
+
+/*
+ * The token-level focal loss of the vision-language class heads (fp32), forward and backward.
+ * Replaces: token_sigmoid_binary_focal_loss (models/deformable_detr/segmentation.py:120-166) as called by SetCriterion.loss_labelsVL
+ *           (deformable_detr.py:353-381) and MaskDINO's loss_labels_vl (maskdino/criterion.py:209-238): the boolean indexing with the
+ *           text mask (a nonzero, i.e. a host wait for everything queued), the element-wise passes and their autograd mirrors.
+ *   logits, onehot (B, Q, T);  keep (B, T) bytes or NULL: token t of image b counts when keep[b, t] != 0;  gamma must be 2.
+ * hipie_token_focal_forward:  out[0] = sum over kept (b, q, t) of alpha_t ce (1 - p_t)^2 (alpha < 0: no alpha_t).  A fixed grid of
+ *     min(ceil(n / 1024), 1024) workgroups, one partial each in `ws` (hipie_token_focal_ws_bytes(n = B Q T)), added by one workgroup in
+ *     a fixed order.  No atomics: bit-reproducible.
+ * hipie_token_focal_backward: dlogits = g[0] * d focal / d logits at kept tokens, exactly 0 at dropped ones; g is a DEVICE scalar.
+ * Neither waits on the host.  B*Q*T == 0: returns 0 without a launch and writes nothing, null pointers allowed.
+ */
+int hipie_token_focal_forward(const float* logits, const float* onehot, const uint8_t* keep, float* out, void* ws, int64_t ws_bytes, int B, int Q,
+                              int T, float alpha, float gamma, void* stream);
+int64_t hipie_token_focal_ws_bytes(int64_t n);
+int hipie_token_focal_backward(const float* logits, const float* onehot, const uint8_t* keep, const float* g, float* dlogits, int B, int Q, int T,
+                               float alpha, float gamma, void* stream);
+
+/*
  * hipie_vit_attn with the decomposed relative-position bias computed INSIDE the kernel from the (re-interpolated) tables
  * (get_rel_pos + add_decomposed_rel_pos, hipie/backbone/utils.py:63-125): bias_w[q, kx] = q . Rw[qx - kx + gw - 1] and
  * bias_h[q, ky] = q . Rh[qy - ky + gh - 1] are two MFMA products per wave in the prologue, so neither hipie_vit_relpos nor
