@@ -12,10 +12,11 @@
 // Lanes run along columns, 16 bytes each: a workgroup of 256 threads owns a tile of 1024 columns (blockIdx.x) and walks rows in chunks of
 // ACT_ROWS (blockIdx.y, grid stride): the ACT_ROWS loads of u and of g are issued before the first use.  No LDS on the element path.
 // dbias: every thread keeps the partial sums of its four columns in registers over all its rows and writes them into row blockIdx.y of
-// the workspace (nparts, N); a second kernel adds the partial rows in a fixed order.  No atomics: bit-reproducible from call to call.
+// the workspace (nparts, N); partial_rows_sum_kernel<8, 32> (row_norm.h) adds the partial rows in a fixed order.  No atomics: bit-reproducible from call to call.
 // The grid -- ceil(N / 1024) x min(ceil(rows / ACT_ROWS), max(1, ACT_MAX_WG / ceil(N / 1024))) -- is a function of (rows, N) alone.
 #include "common.h"
 #include "gelu.h"
+#include "row_norm.h"
 
 namespace hipie {
 
@@ -78,27 +79,6 @@ __global__ __launch_bounds__(256) void act_backward_kernel(const float* __restri
     }
   }
   if (WANT_B) *reinterpret_cast<float4*>(ws + (long)blockIdx.y * N + col) = make_float4(sum[0], sum[1], sum[2], sum[3]);
-}
-
-// ws (nparts, N) -> dbias (N).  A workgroup owns 32 columns; thread (group, col) adds the partial rows group, group + 8, ... in order, the 8
-// group sums are added in order by the threads of group 0.
-__global__ __launch_bounds__(256) void act_backward_finish_kernel(const float* __restrict__ ws, float* __restrict__ dbias, int nparts, int N) {
-  __shared__ float red[ACT_FIN_GROUPS][ACT_FIN_COLS];
-  const int cx = threadIdx.x % ACT_FIN_COLS, grp = threadIdx.x / ACT_FIN_COLS;
-  const int col = blockIdx.x * ACT_FIN_COLS + cx;
-  float acc = 0.f;
-  if (col < N) {
-#pragma unroll 8
-    for (int p = grp; p < nparts; p += ACT_FIN_GROUPS) acc += ws[(long)p * N + col];
-  }
-  red[grp][cx] = acc;
-  __syncthreads();
-  if (grp == 0 && col < N) {
-    float t = red[0][cx];
-#pragma unroll
-    for (int k = 1; k < ACT_FIN_GROUPS; ++k) t += red[k][cx];
-    dbias[col] = t;
-  }
 }
 
 static inline int act_col_tiles(int N) { return (N + ACT_COLS - 1) / ACT_COLS; }
@@ -165,7 +145,5 @@ extern "C" int hipie_act_backward(const float* u, const float* g, float* du, flo
   else launch_act_bwd<2>(a != nullptr, dbias != nullptr, grid, st, u, g, du, a, (float*)ws, (long)rows, N);
   const int rc = check_launch("act_backward");
   if (rc != HIPIE_OK || dbias == nullptr) return rc;
-  hipLaunchKernelGGL(act_backward_finish_kernel, dim3((unsigned)((N + ACT_FIN_COLS - 1) / ACT_FIN_COLS)), dim3(256), 0, st, (const float*)ws,
-                     dbias, parts, N);
-  return check_launch("act_backward (partial-row sum)");
+  return partial_rows_sum<ACT_FIN_GROUPS, ACT_FIN_COLS>("act_backward (partial-row sum)", (const float*)ws, dbias, nullptr, N, parts, N, st);
 }

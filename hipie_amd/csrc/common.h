@@ -85,6 +85,18 @@ __device__ __forceinline__ void hl_split(float x, f16_t& h, f16_t& l) {
   l = (f16_t)(x - (float)h);
 }
 
+// ---- dtype code -> type (host) ------------------------------------------------------------------------
+// f(T()) for the T of a HIPIE_F32 / HIPIE_F16 / HIPIE_BF16 code (a generic lambda reads it as decltype); another code is refused as "<what> <code>"
+template <typename F>
+static inline int with_dtype(int code, const char* what, F&& f) {
+  switch (code) {
+    case HIPIE_F32: return f(float());
+    case HIPIE_F16: return f(f16_t());
+    case HIPIE_BF16: return f(bf16_t());
+    default: return set_err(HIPIE_EINVAL, "%s %d", what, code);
+  }
+}
+
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 // A/B switches of the kernel studies (tile orders, wave counts, ablations: tools/bench_*.py).  The shipped library has ONE path per policy:

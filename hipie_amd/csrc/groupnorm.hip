@@ -10,6 +10,7 @@
 // var = E[(a-K)^2] - (E[a-K])^2 is then free of the cancellation that E[a^2] - mean^2 suffers when |mean| >> std (real
 // convolution biases folded in as pre-bias), at the cost of one extra scalar load per block.
 #include "common.h"
+#include "wave.h"
 
 namespace hipie {
 
@@ -62,6 +63,35 @@ __global__ __launch_bounds__(256) void gn_stats_nhwc_kernel(const T* __restrict_
   }
 }
 
+// sum and sum of squares of a group's SHIFTED values (shift K, n values) -> the group's mean and rstd
+__device__ __forceinline__ void gn_mean_rstd(float s, float ss, float n, float K, float eps, float& mean, float& rstd) {
+  const float ms = s / n;                                                // mean of the shifted values
+  mean = K + ms;
+  rstd = rsqrtf(fmaxf(ss / n - ms * ms, 0.f) + eps);
+}
+
+// channels-last, thread t < G: the partials of group t of image b, added in chunk order -> stat[0][t] = mean, stat[1][t] = rstd
+template <typename T>
+__device__ __forceinline__ void gn_group_stats_nhwc(const T* x, const float* prebias, const float* part, int b, int HW, int G, int nchunk,
+                                                    float eps, float (&stat)[2][64]) {
+  const int t = threadIdx.x;
+  float s = 0.f, ss = 0.f;
+  const float* pp = part + ((long)b * G + t) * nchunk * 2;
+  for (int k = 0; k < nchunk; ++k) { s += pp[2 * k]; ss += pp[2 * k + 1]; }
+  const float K = (float)x[(long)b * HW * (G * GN_CPG) + t * 8] + (prebias ? prebias[t * 8] : 0.f);
+  gn_mean_rstd(s, ss, (float)HW * GN_CPG, K, eps, stat[0][t], stat[1][t]);
+}
+
+// y = v * sc + sh for the 8 channels of group g: the normalisation, gamma / beta and the pre-bias in one fma per value
+__device__ __forceinline__ void gn_scale_shift(const float* gamma, const float* beta, const float* prebias, int g, float mean, float rstd,
+                                               float (&sc)[8], float (&sh)[8]) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    sc[i] = rstd * gamma[g * 8 + i];
+    sh[i] = beta[g * 8 + i] + ((prebias ? prebias[g * 8 + i] : 0.f) - mean) * sc[i];
+  }
+}
+
 template <typename T, typename OutT>
 __global__ __launch_bounds__(256) void gn_apply_nhwc_kernel(const T* __restrict__ x, const float* __restrict__ prebias,
                                                             const float* __restrict__ part, const float* __restrict__ gamma,
@@ -71,24 +101,10 @@ __global__ __launch_bounds__(256) void gn_apply_nhwc_kernel(const T* __restrict_
   const int b = blockIdx.y, chunk = blockIdx.x;
   const int g = threadIdx.x % G, pl = threadIdx.x / G, npl = 256 / G;
   const int C = G * GN_CPG;
-  if (threadIdx.x < G) {
-    float s = 0.f, ss = 0.f;
-    const float* pp = part + ((long)b * G + threadIdx.x) * nchunk * 2;
-    for (int k = 0; k < nchunk; ++k) { s += pp[2 * k]; ss += pp[2 * k + 1]; }
-    const float n = (float)HW * GN_CPG;
-    const float ms = s / n;                                              // mean of the shifted values
-    const float K = (float)x[(long)b * HW * C + threadIdx.x * 8] + (prebias ? prebias[threadIdx.x * 8] : 0.f);
-    stat[0][threadIdx.x] = K + ms;
-    stat[1][threadIdx.x] = rsqrtf(fmaxf(ss / n - ms * ms, 0.f) + eps);
-  }
+  if (threadIdx.x < G) gn_group_stats_nhwc(x, prebias, part, b, HW, G, nchunk, eps, stat);
   __syncthreads();
-  const float mean = stat[0][g], rstd = stat[1][g];
   float sc[8], sh[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    sc[i] = rstd * gamma[g * 8 + i];
-    sh[i] = beta[g * 8 + i] + ((prebias ? prebias[g * 8 + i] : 0.f) - mean) * sc[i];
-  }
+  gn_scale_shift(gamma, beta, prebias, g, stat[0][g], stat[1][g], sc, sh);
   const int p1 = min(HW, (chunk + 1) * per);
   for (int p = chunk * per + pl; p < p1; p += npl) {
     const long off = ((long)b * HW + p) * C + g * 8;
@@ -115,24 +131,10 @@ __global__ __launch_bounds__(256) void gn_apply_nhwc_to_nchw_kernel(const T* __r
   const int b = blockIdx.y, p0 = blockIdx.x * GN_TP;
   const int g = threadIdx.x % G, pl = threadIdx.x / G, npl = 256 / G;
   const int C = G * GN_CPG;
-  if (threadIdx.x < G) {
-    float s = 0.f, ss = 0.f;
-    const float* pp = part + ((long)b * G + threadIdx.x) * nchunk * 2;
-    for (int k = 0; k < nchunk; ++k) { s += pp[2 * k]; ss += pp[2 * k + 1]; }
-    const float n = (float)HW * GN_CPG;
-    const float ms = s / n;
-    const float K = (float)x[(long)b * HW * C + threadIdx.x * 8] + (prebias ? prebias[threadIdx.x * 8] : 0.f);
-    stat[0][threadIdx.x] = K + ms;
-    stat[1][threadIdx.x] = rsqrtf(fmaxf(ss / n - ms * ms, 0.f) + eps);
-  }
+  if (threadIdx.x < G) gn_group_stats_nhwc(x, prebias, part, b, HW, G, nchunk, eps, stat);
   __syncthreads();
-  const float mean = stat[0][g], rstd = stat[1][g];
   float sc[8], sh[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    sc[i] = rstd * gamma[g * 8 + i];
-    sh[i] = beta[g * 8 + i] + ((prebias ? prebias[g * 8 + i] : 0.f) - mean) * sc[i];
-  }
+  gn_scale_shift(gamma, beta, prebias, g, stat[0][g], stat[1][g], sc, sh);
   for (int p = pl; p < GN_TP; p += npl) {
     float v[8];
     V8<T>::ld(x + ((long)b * HW + p0 + p) * C + g * 8, v);
@@ -173,8 +175,8 @@ __global__ __launch_bounds__(256) void gn_stats_nchw_kernel(const T* __restrict_
 #pragma unroll
     for (int i = 0; i < 8; ++i) { const float a = v[i] + pb - K; s += a; ss = fmaf(a, a, ss); }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); ss += __shfl_xor(ss, o); }
+  s = wave_sum(s);
+  ss = wave_sum(ss);
   if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s; red[1][threadIdx.x >> 6] = ss; }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -198,15 +200,12 @@ __global__ __launch_bounds__(256) void gn_apply_nchw_kernel(const T* __restrict_
     const float* pp = part + ((long)b * G + g) * K * 2;
     float s = 0.f, ss = 0.f;
     for (int k = threadIdx.x; k < K; k += 64) { s += pp[2 * k]; ss += pp[2 * k + 1]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); ss += __shfl_xor(ss, o); }
+    s = wave_sum(s);
+    ss = wave_sum(ss);
     if (threadIdx.x == 0) {
-      const float n = (float)HW * GN_CPG;
-      const float ms = s / n;
       const int c0 = g * GN_CPG;
       const float K = (float)x[((long)b * C + c0) * HW] + (prebias ? prebias[c0] : 0.f);
-      stat[0] = K + ms;
-      stat[1] = rsqrtf(fmaxf(ss / n - ms * ms, 0.f) + eps);
+      gn_mean_rstd(s, ss, (float)HW * GN_CPG, K, eps, stat[0], stat[1]);
     }
   }
   __syncthreads();
@@ -257,17 +256,6 @@ static int launch_gn(const void* x, const float* prebias, const float* gamma, co
   return check_launch("group_norm");
 }
 
-template <typename T>
-static int gn_out(int od, const void* x, const float* prebias, const float* gamma, const float* beta, void* out, float* part, int B,
-                  int C, int HW, int nhwc, float eps, int relu, hipStream_t st) {
-  switch (od) {
-    case HIPIE_F32: return launch_gn<T, float>(x, prebias, gamma, beta, out, part, B, C, HW, nhwc, eps, relu, st);
-    case HIPIE_F16: return launch_gn<T, f16_t>(x, prebias, gamma, beta, out, part, B, C, HW, nhwc, eps, relu, st);
-    case HIPIE_BF16: return launch_gn<T, bf16_t>(x, prebias, gamma, beta, out, part, B, C, HW, nhwc, eps, relu, st);
-    default: return set_err(HIPIE_EINVAL, "group_norm: bad out dtype %d", od);
-  }
-}
-
 }  // namespace hipie
 
 extern "C" int hipie_group_norm(const void* x, const float* prebias, const float* gamma, const float* beta, void* out,
@@ -283,10 +271,9 @@ extern "C" int hipie_group_norm(const void* x, const float* prebias, const float
                 "group_norm: channels_last %d (0 NCHW, 1 channels-last, 2 channels-last in / NCHW out: H*W %% 64 == 0, got %d)", channels_last, HW);
   if (B == 0) return HIPIE_OK;
   hipStream_t st = (hipStream_t)stream;
-  switch (x_dtype) {
-    case HIPIE_F32: return gn_out<float>(out_dtype, x, prebias, gamma, beta, out, workspace, B, C, HW, channels_last, eps, relu, st);
-    case HIPIE_F16: return gn_out<f16_t>(out_dtype, x, prebias, gamma, beta, out, workspace, B, C, HW, channels_last, eps, relu, st);
-    case HIPIE_BF16: return gn_out<bf16_t>(out_dtype, x, prebias, gamma, beta, out, workspace, B, C, HW, channels_last, eps, relu, st);
-    default: return set_err(HIPIE_EINVAL, "group_norm: bad x dtype %d", x_dtype);
-  }
+  return with_dtype(x_dtype, "group_norm: bad x dtype", [&](auto tx) {
+    return with_dtype(out_dtype, "group_norm: bad out dtype", [&](auto to) {
+      return launch_gn<decltype(tx), decltype(to)>(x, prebias, gamma, beta, out, workspace, B, C, HW, channels_last, eps, relu, st);
+    });
+  });
 }

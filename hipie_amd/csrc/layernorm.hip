@@ -8,7 +8,7 @@
 // vector loads), statistics are fp32 wave reductions (two-pass: mean, then centred variance -- the same arithmetic as
 // torch's layer_norm), and both outputs are written once.  Bytes per row: C * (|x| + |delta| + |res| + |norm|).
 #include "common.h"
-#include "wave.h"
+#include "row_norm.h"
 
 namespace hipie {
 
@@ -42,8 +42,6 @@ template <> struct Vec4<hl8_t> {
   }
 };
 
-constexpr int LN_MAXV = 8;     // up to 8 x 4 elements per lane: C <= 2048
-
 template <typename Tx, typename Td, typename Tn>
 __global__ __launch_bounds__(256) void add_layernorm_kernel(const Tx* __restrict__ x, const Td* __restrict__ delta,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -56,14 +54,12 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const Tx* __restrict
   // layout the attention wrote) -- window partition / un-partition become index arithmetic of this pass
   const long orow = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (orow >= rows) return;
-  const int lane = threadIdx.x & 63;
-  const int nv = C / 256;                       // full 4-element vectors per lane (64 lanes x 4)
-  const int tail = (C - nv * 256) / 4;          // remaining vectors (< 64), one per lane for lane < tail
+  const LnRow r(C);
   const long row = out_src ? (long)out_src[orow] : orow;
   if (row < 0) {
     const float z[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int i = 0; i <= nv; ++i)
-      if ((i < nv) || (lane < tail)) Vec4<Tn>::store(norm_out + orow * C + i * 256 + lane * 4, z);
+    for (int i = 0; i <= r.nv; ++i)        // LnRow::on(i) for i <= nv, spelled out: with on(i) this cold loop is unrolled LN_MAXV times
+      if ((i < r.nv)|| (r.lane < r.tail)) Vec4<Tn>::store(norm_out + orow * C + r.col(i), z);
     return;
   }
   const long drow = delta_row ? (long)delta_row[row] : row;
@@ -72,9 +68,8 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const Tx* __restrict
   const Tx* xr = x + row * C;
 #pragma unroll
   for (int i = 0; i < LN_MAXV; ++i) {
-    const bool on = (i < nv) || (i == nv && lane < tail);
-    if (on) {
-      const int c = i * 256 + lane * 4;
+    if (r.on(i)) {
+      const int c = r.col(i);
       Vec4<Tx>::load(xr + c, v[i]);
       if (delta != nullptr) {
         float d[4];
@@ -90,33 +85,25 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const Tx* __restrict
       for (int e = 0; e < 4; ++e) v[i][e] = 0.f;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+  // ln_row_stats of row_norm.h, written out: through the helper this kernel measured 9 - 12 % slower at C = 256 (docs/measurements.md)
+  sum = wave_sum(sum);
   const float mean = sum / (float)C;
   float sq = 0.f;
 #pragma unroll
   for (int i = 0; i < LN_MAXV; ++i) {
-    const bool on = (i < nv) || (i == nv && lane < tail);
-    if (on) {
+    if (r.on(i)) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) { const float d = v[i][e] - mean; sq += d * d; }
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
+  sq = wave_sum(sq);
   const float rstd = rsqrtf(sq / (float)C + eps);
 #pragma unroll
   for (int i = 0; i < LN_MAXV; ++i) {
-    const bool on = (i < nv) || (i == nv && lane < tail);
-    if (on) {
-      const int c = i * 256 + lane * 4;
-      const float4 g = *reinterpret_cast<const float4*>(gamma + c);
-      const float4 b = *reinterpret_cast<const float4*>(beta + c);
+    if (r.on(i)) {
+      const int c = r.col(i);
       float o[4];
-      o[0] = (v[i][0] - mean) * rstd * g.x + b.x;
-      o[1] = (v[i][1] - mean) * rstd * g.y + b.y;
-      o[2] = (v[i][2] - mean) * rstd * g.z + b.z;
-      o[3] = (v[i][3] - mean) * rstd * g.w + b.w;
+      ln_affine(v[i], mean, rstd, gamma + c, beta + c, o);
       Vec4<Tn>::store(norm_out + orow * C + c, o);
       if (sum_out != nullptr) {               // the normalised row plus a second addend (e.g. the position embedding of the next query)
         float a[4];
@@ -147,39 +134,21 @@ static int launch_ln(const LnArgs& a) {
   return check_launch("add_layernorm");
 }
 
-template <typename Tx, typename Td>
-static int ln_out(const LnArgs& a) {
-  switch (a.norm_dtype) {
-    case HIPIE_F32: return launch_ln<Tx, Td, float>(a);
-    case HIPIE_F16: return launch_ln<Tx, Td, f16_t>(a);
-    case HIPIE_BF16: return launch_ln<Tx, Td, bf16_t>(a);
-    case HIPIE_HL8:
-      if (a.C % 8 != 0 || (reinterpret_cast<uintptr_t>(a.norm_out) & 31) != 0) return set_err(HIPIE_EINVAL, "add_layernorm: HL8 output needs C %% 8 == 0 and a 32-byte aligned buffer");
-      return launch_ln<Tx, Td, hl8_t>(a);
-    default: return set_err(HIPIE_EINVAL, "add_layernorm: bad norm dtype %d", a.norm_dtype);
-  }
-}
-
-template <typename Tx>
-static int ln_delta(const LnArgs& a) {
-  switch (a.delta_dtype) {
-    case HIPIE_F32: return ln_out<Tx, float>(a);
-    case HIPIE_F16: return ln_out<Tx, f16_t>(a);
-    case HIPIE_BF16: return ln_out<Tx, bf16_t>(a);
-    default: return set_err(HIPIE_EINVAL, "add_layernorm: bad delta dtype %d", a.delta_dtype);
-  }
-}
-
 static int add_layernorm(const LnArgs& a) {
   HIPIE_REQUIRE(a.x && a.gamma && a.beta && a.norm_out, "add_layernorm: null pointer");
   HIPIE_REQUIRE(a.rows >= 0 && a.C > 0 && a.C % 4 == 0 && a.C <= LN_MAXV * 256, "add_layernorm: C=%d must be a multiple of 4 and <= %d", a.C, LN_MAXV * 256);
   if (a.rows == 0) return HIPIE_OK;
-  switch (a.x_dtype) {
-    case HIPIE_F32: return ln_delta<float>(a);
-    case HIPIE_F16: return ln_delta<f16_t>(a);
-    case HIPIE_BF16: return ln_delta<bf16_t>(a);
-    default: return set_err(HIPIE_EINVAL, "add_layernorm: bad x dtype %d", a.x_dtype);
-  }
+  return with_dtype(a.x_dtype, "add_layernorm: bad x dtype", [&](auto tx) {
+    return with_dtype(a.delta_dtype, "add_layernorm: bad delta dtype", [&](auto td) {
+      using Tx = decltype(tx);
+      using Td = decltype(td);
+      if (a.norm_dtype == HIPIE_HL8) {
+        if (a.C % 8 != 0 || (reinterpret_cast<uintptr_t>(a.norm_out) & 31) != 0) return set_err(HIPIE_EINVAL, "add_layernorm: HL8 output needs C %% 8 == 0 and a 32-byte aligned buffer");
+        return launch_ln<Tx, Td, hl8_t>(a);
+      }
+      return with_dtype(a.norm_dtype, "add_layernorm: bad norm dtype", [&](auto tn) { return launch_ln<Tx, Td, decltype(tn)>(a); });
+    });
+  });
 }
 
 
@@ -195,15 +164,13 @@ __global__ __launch_bounds__(256) void add_layernorm_dec_kernel(const float* __r
                                                                 int C, float eps) {
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  const int lane = threadIdx.x & 63;
-  const int nv = C / 256, tail = (C - nv * 256) / 4;
+  const LnRow r(C);
   float v[LN_MAXV][4];
   float sum = 0.f;
 #pragma unroll
   for (int i = 0; i < LN_MAXV; ++i) {
-    const bool on = (i < nv) || (i == nv && lane < tail);
-    if (on) {
-      const long c = row * C + i * 256 + lane * 4;
+    if (r.on(i)) {
+      const long c = row * C + r.col(i);
       float d[4];
       Vec4<float>::load(x + c, v[i]);
       Vec4<Td>::load(delta + c, d);
@@ -214,34 +181,15 @@ __global__ __launch_bounds__(256) void add_layernorm_dec_kernel(const float* __r
       for (int e = 0; e < 4; ++e) v[i][e] = 0.f;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-  const float mean = sum / (float)C;
-  float sq = 0.f;
+  float mean, rstd;
+  ln_row_stats(r, v, sum, C, eps, mean, rstd);
 #pragma unroll
   for (int i = 0; i < LN_MAXV; ++i) {
-    const bool on = (i < nv) || (i == nv && lane < tail);
-    if (on) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { const float d = v[i][e] - mean; sq += d * d; }
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
-  const float rstd = rsqrtf(sq / (float)C + eps);
-#pragma unroll
-  for (int i = 0; i < LN_MAXV; ++i) {
-    const bool on = (i < nv) || (i == nv && lane < tail);
-    if (on) {
-      const int cc = i * 256 + lane * 4;
+    if (r.on(i)) {
+      const int cc = r.col(i);
       const long c = row * C + cc;
-      const float4 g = *reinterpret_cast<const float4*>(gamma + cc);
-      const float4 b = *reinterpret_cast<const float4*>(beta + cc);
       float o[4];
-      o[0] = (v[i][0] - mean) * rstd * g.x + b.x;
-      o[1] = (v[i][1] - mean) * rstd * g.y + b.y;
-      o[2] = (v[i][2] - mean) * rstd * g.z + b.z;
-      o[3] = (v[i][3] - mean) * rstd * g.w + b.w;
+      ln_affine(v[i], mean, rstd, gamma + cc, beta + cc, o);
       Vec4<float>::store(norm_out + c, o);
       if (norm16 != nullptr) Vec4<Ta>::store(norm16 + c, o);
       if (sum16 != nullptr) {
@@ -306,19 +254,12 @@ extern "C" int hipie_add_layernorm_dec(const float* x, const void* delta, const 
                 "add_layernorm_dec: HL8 outputs need C %% 8 == 0 and 32-byte aligned buffers");
   if (rows == 0) return HIPIE_OK;
   hipStream_t st = (hipStream_t)stream;
-#define HIPIE_LND(Td)                                                                                                          \
-  return aux_dtype == HIPIE_F16                                                                                                \
-             ? launch_ln_dec<Td, f16_t>(x, delta, gamma, beta, norm_out, norm16_out, addend, sum16_out, rows, C, eps, st)      \
-         : aux_dtype == HIPIE_HL8                                                                                              \
-             ? launch_ln_dec<Td, hl8_t>(x, delta, gamma, beta, norm_out, norm16_out, addend, sum16_out, rows, C, eps, st)      \
-             : launch_ln_dec<Td, bf16_t>(x, delta, gamma, beta, norm_out, norm16_out, addend, sum16_out, rows, C, eps, st);
-  switch (delta_dtype) {
-    case HIPIE_F32: HIPIE_LND(float)
-    case HIPIE_F16: HIPIE_LND(f16_t)
-    case HIPIE_BF16: HIPIE_LND(bf16_t)
-    default: return set_err(HIPIE_EINVAL, "add_layernorm_dec: bad delta dtype %d", delta_dtype);
-  }
-#undef HIPIE_LND
+  return with_dtype(delta_dtype, "add_layernorm_dec: bad delta dtype", [&](auto td) {
+    auto launch = [&](auto ta) {
+      return launch_ln_dec<decltype(td), decltype(ta)>(x, delta, gamma, beta, norm_out, norm16_out, addend, sum16_out, rows, C, eps, st);
+    };
+    return aux_dtype == HIPIE_F16 ? launch(f16_t()) : aux_dtype == HIPIE_HL8 ? launch(hl8_t()) : launch(bf16_t());
+  });
 }
 
 extern "C" int hipie_add_cast(const float* a, const void* b, void* out, int64_t n, int dtype, void* stream) {
@@ -331,12 +272,13 @@ extern "C" int hipie_add_cast(const float* a, const void* b, void* out, int64_t 
   hipStream_t st = (hipStream_t)stream;
   const long n4 = n / 4;
   const unsigned grid = (unsigned)((n4 + 255) / 256);
-  if (dtype == HIPIE_HL8)
-    hipLaunchKernelGGL((add_cast_kernel<hl8_t>), dim3(grid), dim3(256), 0, st, a, (const hl8_t*)b, (hl8_t*)out, n4);
-  else if (dtype == HIPIE_F16)
-    hipLaunchKernelGGL((add_cast_kernel<f16_t>), dim3(grid), dim3(256), 0, st, a, (const f16_t*)b, (f16_t*)out, n4);
-  else
-    hipLaunchKernelGGL((add_cast_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, a, (const bf16_t*)b, (bf16_t*)out, n4);
+  auto launch = [&](auto t) {
+    using Ta = decltype(t);
+    hipLaunchKernelGGL((add_cast_kernel<Ta>), dim3(grid), dim3(256), 0, st, a, (const Ta*)b, (Ta*)out, n4);
+  };
+  if (dtype == HIPIE_HL8) launch(hl8_t());
+  else if (dtype == HIPIE_F16) launch(f16_t());
+  else launch(bf16_t());
   return check_launch("add_cast");
 }
 

@@ -8,40 +8,39 @@
 // Replaces torch.autograd through nn.LayerNorm as Block.forward uses it (hipie/backbone/vit.py:212-230, eps 1e-6) and the post-norm
 // residuals of DeformableTransformerEncoderLayer.forward (deformable_transformer_dino.py:384-394): the library's layer-norm backward, its
 // separate parameter reduction and the accumulation of the residual gradient (three passes) become one.  mean and rstd are RECOMPUTED from
-// s with the forward kernel's arithmetic (two-pass: mean, then centred variance, the same lane order and wave reductions) -- the row is
-// read anyway, so no statistics tensors are saved.  One wave owns one row at a time (16-byte vector accesses, the forward's lane
+// s on LnRow and ln_row_stats of row_norm.h: the forward kernels' lane layout, and add_layernorm_dec_kernel's own code for the two wave
+// reductions and the variance pass (add_layernorm_kernel has the same statements written out) -- the row is read anyway, so no
+// statistics tensors are saved.  One wave owns one row at a time (16-byte vector accesses, the forward's lane
 // layout) and walks rows with a grid stride; the grid is min(ceil(rows / 4), LNB_MAX_WG) workgroups of four waves, a function of `rows`
 // alone.  Bytes per row: C * 4 * (|s| + |gy| + |gres| + |dx|) = 16 C.
 //
 // dgamma / dbeta: every wave keeps its partial sums in registers over all its rows; at the end the four waves of a workgroup are added
-// through LDS in wave order and the workgroup writes ONE partial row (2 C floats) into the workspace; a second kernel adds the partial
-// rows in a fixed order.  No atomics: the results are bit-reproducible from call to call.
+// through LDS in wave order and the workgroup writes ONE partial row (2 C floats) into the workspace; partial_rows_sum_kernel<16, 16> adds
+// the partial rows in a fixed order.  No atomics: the results are bit-reproducible from call to call.
 #include "common.h"
+#include "row_norm.h"
 
 namespace hipie {
 
-constexpr int LNB_MAXV = 8;          // up to 8 x 4 elements per lane: C <= 2048 (the forward's limit)
 constexpr int LNB_MAX_WG = 1024;     // workgroups of the row kernel = partial rows in the workspace: 16 waves per CU on 256 CUs
 constexpr int LNB_FIN_COLS = 16;     // the partial-row sum: a workgroup owns 16 columns, 16 groups of partial rows each
 constexpr int LNB_FIN_GROUPS = 16;
 
-// NV = vectors per lane = ceil(C / 256): the last one may be partial (lane < tail) -- the forward's `on` predicate with a static bound
+// NV = vectors per lane = ceil(C / 256): the last one may be partial (lane < tail)
 template <int NV, bool PARAMS>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restrict__ s, const float* __restrict__ gy, const float* gres,
                                                             const float* __restrict__ gamma, float* dx, float* __restrict__ ws, long rows,
                                                             int C, float eps) {
+  static_assert(NV <= LN_MAXV, "the forward's limit");
   __shared__ float part[PARAMS ? 3 * 2 * NV * 256 : 1];      // waves 1-3 park their partial sums here for wave 0
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int nv = C / 256;
-  const int tail = (C - nv * 256) / 4;
+  const int wave = threadIdx.x >> 6;
+  const LnRow r(C);
   float gm[NV][4], dg[NV][4], db[NV][4];
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
-    const bool on = (i < nv) || (i == nv && lane < tail);
-    const float4 w = on ? *reinterpret_cast<const float4*>(gamma + i * 256 + lane * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-    gm[i][0] = w.x; gm[i][1] = w.y; gm[i][2] = w.z; gm[i][3] = w.w;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) dg[i][e] = db[i][e] = 0.f;
+    for (int e = 0; e < 4; ++e) gm[i][e] = dg[i][e] = db[i][e] = 0.f;
+    if (r.on(i)) Vec4<float>::load(gamma + r.col(i), gm[i]);
   }
   const float inv_c = 1.f / (float)C;
   for (long row = (long)blockIdx.x * 4 + wave; row < rows; row += (long)gridDim.x * 4) {
@@ -50,13 +49,9 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
     float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      const bool on = (i < nv) || (i == nv && lane < tail);
-      if (on) {
-        const long c = base + i * 256 + lane * 4;
-        const float4 a = *reinterpret_cast<const float4*>(s + c);
-        const float4 b = *reinterpret_cast<const float4*>(gy + c);
-        v[i][0] = a.x; v[i][1] = a.y; v[i][2] = a.z; v[i][3] = a.w;
-        g[i][0] = b.x; g[i][1] = b.y; g[i][2] = b.z; g[i][3] = b.w;
+      if (r.on(i)) {
+        Vec4<float>::load(s + base + r.col(i), v[i]);
+        Vec4<float>::load(gy + base + r.col(i), g[i]);
 #pragma unroll
         for (int e = 0; e < 4; ++e) sum += v[i][e];
       } else {
@@ -64,26 +59,13 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
         for (int e = 0; e < 4; ++e) v[i][e] = g[i][e] = 0.f;
       }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-    const float mean = sum / (float)C;
-    float sq = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const bool on = (i < nv) || (i == nv && lane < tail);
-      if (on) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { const float d = v[i][e] - mean; sq += d * d; }
-      }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
-    const float rstd = rsqrtf(sq / (float)C + eps);
+    float mean, rstd;
+    ln_row_stats(r, v, sum, C, eps, mean, rstd);
     // v <- xhat, g <- gy * gamma (gy itself goes into the parameter sums first); the two row means of the input gradient
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      const bool on = (i < nv) || (i == nv && lane < tail);
+      const bool on = r.on(i);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float xh = on ? (v[i][e] - mean) * rstd : 0.f;
@@ -98,25 +80,21 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
         s2 += t * xh;
       }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      s1 += __shfl_xor(s1, o);
-      s2 += __shfl_xor(s2, o);
-    }
-    const float m1 = s1 * inv_c, m2 = s2 * inv_c;
+    const float m1 = wave_sum(s1) * inv_c, m2 = wave_sum(s2) * inv_c;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      const bool on = (i < nv) || (i == nv && lane < tail);
-      if (on) {
-        const long c = base + i * 256 + lane * 4;
+      if (r.on(i)) {
+        const long c = base + r.col(i);
         float o[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = rstd * (g[i][e] - m1 - v[i][e] * m2);
         if (gres != nullptr) {            // dx may BE gres: the lane reads its own four values before it writes them
-          const float4 r = *reinterpret_cast<const float4*>(gres + c);
-          o[0] += r.x; o[1] += r.y; o[2] += r.z; o[3] += r.w;
+          float q[4];
+          Vec4<float>::load(gres + c, q);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) o[e] += q[e];
         }
-        *reinterpret_cast<float4*>(dx + c) = make_float4(o[0], o[1], o[2], o[3]);
+        Vec4<float>::store(dx + c, o);
       }
     }
   }
@@ -126,8 +104,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
       float* p = part + (wave - 1) * 2 * NV * 256;
 #pragma unroll
       for (int i = 0; i < NV; ++i) {
-        *reinterpret_cast<float4*>(p + i * 256 + lane * 4) = make_float4(dg[i][0], dg[i][1], dg[i][2], dg[i][3]);
-        *reinterpret_cast<float4*>(p + (NV + i) * 256 + lane * 4) = make_float4(db[i][0], db[i][1], db[i][2], db[i][3]);
+        Vec4<float>::store(p + r.col(i), dg[i]);
+        Vec4<float>::store(p + NV * 256 + r.col(i), db[i]);
       }
     }
     __syncthreads();
@@ -138,42 +116,18 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
 #pragma unroll
         for (int w = 0; w < 3; ++w) {                 // ((w0 + w1) + w2) + w3
           const float* p = part + w * 2 * NV * 256;
-          const float4 a = *reinterpret_cast<const float4*>(p + i * 256 + lane * 4);
-          const float4 b = *reinterpret_cast<const float4*>(p + (NV + i) * 256 + lane * 4);
-          dg[i][0] += a.x; dg[i][1] += a.y; dg[i][2] += a.z; dg[i][3] += a.w;
-          db[i][0] += b.x; db[i][1] += b.y; db[i][2] += b.z; db[i][3] += b.w;
+          float a[4], b[4];
+          Vec4<float>::load(p + r.col(i), a);
+          Vec4<float>::load(p + NV * 256 + r.col(i), b);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { dg[i][e] += a[e]; db[i][e] += b[e]; }
         }
-        const bool on = (i < nv) || (i == nv && lane < tail);
-        if (on) {
-          const int c = i * 256 + lane * 4;
-          *reinterpret_cast<float4*>(out + c) = make_float4(dg[i][0], dg[i][1], dg[i][2], dg[i][3]);
-          *reinterpret_cast<float4*>(out + C + c) = make_float4(db[i][0], db[i][1], db[i][2], db[i][3]);
+        if (r.on(i)) {
+          Vec4<float>::store(out + r.col(i), dg[i]);
+          Vec4<float>::store(out + C + r.col(i), db[i]);
         }
       }
     }
-  }
-}
-
-// ws (nparts, 2 C) -> dgamma (C), dbeta (C).  A workgroup owns 16 of the 2 C columns; thread (group, col) adds the partial rows group,
-// group + 16, ... in order, the 16 group sums are added in order by the threads of group 0.
-__global__ __launch_bounds__(256) void layernorm_bwd_finish_kernel(const float* __restrict__ ws, float* __restrict__ dgamma,
-                                                                   float* __restrict__ dbeta, int nparts, int C) {
-  __shared__ float red[LNB_FIN_GROUPS][LNB_FIN_COLS];
-  const int cx = threadIdx.x % LNB_FIN_COLS, grp = threadIdx.x / LNB_FIN_COLS;
-  const int col = blockIdx.x * LNB_FIN_COLS + cx;                 // < 2 C: C % 4 == 0 makes 2 C a multiple of 8, not of 16
-  float acc = 0.f;
-  if (col < 2 * C) {
-#pragma unroll 8
-    for (int p = grp; p < nparts; p += LNB_FIN_GROUPS) acc += ws[(long)p * 2 * C + col];
-  }
-  red[grp][cx] = acc;
-  __syncthreads();
-  if (grp == 0 && col < 2 * C) {
-    float t = red[0][cx];
-#pragma unroll
-    for (int k = 1; k < LNB_FIN_GROUPS; ++k) t += red[k][cx];
-    if (col < C) dgamma[col] = t;
-    else dbeta[col - C] = t;
   }
 }
 
@@ -201,7 +155,7 @@ extern "C" int64_t hipie_layernorm_backward_ws_bytes(int64_t rows, int C) {
 extern "C" int hipie_layernorm_backward(const float* s, const float* gy, const float* gres, const float* gamma, float* dx, float* dgamma,
                                         float* dbeta, void* ws, int64_t ws_bytes, int64_t rows, int C, float eps, void* stream) {
   using namespace hipie;
-  HIPIE_REQUIRE(rows >= 0 && C > 0 && C % 4 == 0 && C <= LNB_MAXV * 256, "layernorm_backward: C=%d must be a multiple of 4 and <= %d", C, LNB_MAXV * 256);
+  HIPIE_REQUIRE(rows >= 0 && C > 0 && C % 4 == 0 && C <= LN_MAXV * 256, "layernorm_backward: C=%d must be a multiple of 4 and <= %d", C, LN_MAXV * 256);
   HIPIE_REQUIRE((dgamma == nullptr) == (dbeta == nullptr), "layernorm_backward: dgamma and dbeta go together (both or neither)");
   hipStream_t st = (hipStream_t)stream;
   const bool params = dgamma != nullptr;
@@ -232,7 +186,5 @@ extern "C" int hipie_layernorm_backward(const float* s, const float* gy, const f
   }
   const int rc = check_launch("layernorm_backward");
   if (rc != HIPIE_OK || !params) return rc;
-  hipLaunchKernelGGL(layernorm_bwd_finish_kernel, dim3((unsigned)((2 * C + LNB_FIN_COLS - 1) / LNB_FIN_COLS)), dim3(256), 0, st, w, dgamma,
-                     dbeta, grid, C);
-  return check_launch("layernorm_backward (partial-row sum)");
+  return partial_rows_sum<LNB_FIN_GROUPS, LNB_FIN_COLS>("layernorm_backward (partial-row sum)", w, dgamma, dbeta, C, grid, 2 * C, st);
 }

@@ -9,6 +9,7 @@
 // the nearest resize to the output resolution of segmentation_postprocess (models/ddetrs.py:1065-1070): the (n, H, W)
 // fp32 intermediate (420 MB per image at 1024^2) never exists; reads the stride-4 logits, writes the final bytes.
 #include "common.h"
+#include "wave.h"
 
 namespace hipie {
 
@@ -57,7 +58,7 @@ __global__ __launch_bounds__(NMS_THREADS) void batched_nms_kernel(
     cls = (int)classes[q];
   }
   // 2. max coordinate of the image (torchvision _batched_nms_coordinate_trick: offsets = idx * (max + 1))
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  mx = wave_max(mx);
   if ((t & 63) == 0) sred[t >> 6] = mx;
   __syncthreads();
   mx = sred[0];

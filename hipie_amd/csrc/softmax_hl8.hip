@@ -6,6 +6,7 @@
 // memory, which the six decoder layers amplify to 2e-3 on the mask logits at the headline configuration (tools/dec_err_full.py).
 // One wavefront per row; a lane owns whole groups of 8 columns (32 bytes in, 32 bytes out); masked and padding columns become 0.
 #include "common.h"
+#include "wave.h"
 
 namespace hipie {
 
@@ -40,8 +41,7 @@ __global__ __launch_bounds__(256) void softmax_hl8_kernel(const float* __restric
       for (int e = 0; e < 8; ++e) v[i][e] = -INFINITY;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  mx = wave_max(mx);
   float sum = 0.f;
   const float m2 = (mx == -INFINITY) ? 0.f : mx * 1.4426950408889634f;
 #pragma unroll
@@ -51,8 +51,7 @@ __global__ __launch_bounds__(256) void softmax_hl8_kernel(const float* __restric
       v[i][e] = __builtin_amdgcn_exp2f(v[i][e] * 1.4426950408889634f - m2);      // exp2(-inf) = 0 on masked / padding columns
       sum += v[i][e];
     }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+  sum = wave_sum(sum);
   const float inv = sum > 0.f ? 1.f / sum : 0.f;
   f16_t* pr = P + row * ldp;
 #pragma unroll

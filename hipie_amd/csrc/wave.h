@@ -1,5 +1,5 @@
-// wave.h -- the wave-level primitives the kernels share (gfx950, wave64), one definition each: LDS-DMA, s_waitcnt encodings, cross-half
-// and three-way maxima, the lane sum, the paired fp16 hi / lo split with its wait-state rules, 4-wide typed loads and stores.
+// wave.h -- the wave-level primitives the kernels share (gfx950, wave64), one definition each: LDS-DMA, s_waitcnt encodings, cross-half,
+// three-way and lane maxima, the lane sum, the paired fp16 hi / lo split with its wait-state rules, 4-wide typed loads and stores.
 // (mfma.h holds the MFMA / LDS-transpose lane layouts.)
 #pragma once
 #include "common.h"
@@ -58,6 +58,13 @@ __device__ __forceinline__ float xhalf_max(float x) {
   const unsigned int u = __builtin_bit_cast(unsigned int, x);
   const u32x2 r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
   return fmaxf(__builtin_bit_cast(float, (unsigned int)r[0]), __builtin_bit_cast(float, (unsigned int)r[1]));
+}
+
+// the maximum over the 64 lanes, in every lane: the xor butterfly
+__device__ __forceinline__ float wave_max(float x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
+  return x;
 }
 
 // ---- sums -----------------------------------------------------------------------------------------------------------------------------

@@ -105,6 +105,16 @@ def _chk(t, name, dtype=None):
     return t.data_ptr()
 
 
+def _dense_f32(t, name, align16=False):
+    """t as a dense fp32 device tensor, with align16 on a 16-byte boundary: a strided view, or one at an odd storage offset, is copied"""
+    if not t.is_cuda:
+        raise RuntimeError("Not implemented on the CPU (%s must be a CUDA/HIP tensor)" % name)
+    if t.dtype != torch.float32:
+        raise RuntimeError("%s must be torch.float32, got %s" % (name, t.dtype))
+    t = t.contiguous()
+    return t.clone() if align16 and t.data_ptr() % 16 else t
+
+
 def _check_im2col_step(B, im2col_step):
     """the reference op processes the batch in chunks of min(B, im2col_step) images and asserts that the chunk divides the batch
     (ms_deform_attn_cuda.cu:50-52, :112-114); this kernel has no chunking (one launch over B), but a call the reference would refuse
@@ -713,12 +723,8 @@ def layernorm_backward(s, gy, weight, eps, gres=None, want_param_grads=True):
     rows = s.numel() // C if C else 0
     if gy.shape != s.shape or (gres is not None and gres.shape != s.shape) or weight.numel() != C:
         raise RuntimeError("layernorm_backward: gy / gres must have the shape of s %s and weight its last dimension" % (tuple(s.shape),))
-
-    def rows16(t):                   # dense rows on a 16-byte boundary (a view at an odd storage offset is copied)
-        t = t.contiguous()
-        return t if t.data_ptr() % 16 == 0 else t.clone()
-    s, gy, weight = rows16(s), rows16(gy), rows16(weight)
-    gres = None if gres is None else rows16(gres)
+    s, gy, weight = _dense_f32(s, "s", True), _dense_f32(gy, "gy", True), _dense_f32(weight, "weight", True)
+    gres = None if gres is None else _dense_f32(gres, "gres", True)
     dx = torch.empty_like(s)
     dgamma = dbeta = ws = None
     ws_bytes = 0
@@ -735,14 +741,8 @@ def layernorm_backward(s, gy, weight, eps, gres=None, want_param_grads=True):
 
 
 def _act_rows16(t, name):
-    """(t as dense fp32 rows on a 16-byte boundary, rows, N): a strided view or one at an odd storage offset is copied"""
-    if not t.is_cuda:
-        raise RuntimeError("Not implemented on the CPU (%s must be a CUDA/HIP tensor)" % name)
-    if t.dtype != torch.float32:
-        raise RuntimeError("%s must be torch.float32, got %s" % (name, t.dtype))
-    t = t.contiguous()
-    if t.data_ptr() % 16:
-        t = t.clone()
+    """(t as dense fp32 rows on a 16-byte boundary, rows, N)"""
+    t = _dense_f32(t, name, True)
     N = t.shape[-1] if t.dim() else 1
     return t, (t.numel() // N if N else 0), N
 
@@ -788,17 +788,8 @@ def act_backward(u, g, act, want_a=False, want_bias_grad=False, out=None):
     return du, a, dbias
 
 
-def _loss_f32(t, name):
-    """t as a dense fp32 device tensor (a strided view is copied)"""
-    if not t.is_cuda:
-        raise RuntimeError("Not implemented on the CPU (%s must be a CUDA/HIP tensor)" % name)
-    if t.dtype != torch.float32:
-        raise RuntimeError("%s must be torch.float32, got %s" % (name, t.dtype))
-    return t if t.is_contiguous() else t.contiguous()
-
-
 def _point_loss_operands(src, tgt, tgt_index, pts):
-    src, tgt, pts = _loss_f32(src, "src"), _loss_f32(tgt, "tgt"), _loss_f32(pts, "pts")
+    src, tgt, pts = _dense_f32(src, "src"), _dense_f32(tgt, "tgt"), _dense_f32(pts, "pts")
     if not tgt_index.is_cuda:
         raise RuntimeError("Not implemented on the CPU (tgt_index must be a CUDA/HIP tensor)")
     if tgt_index.dtype != torch.int64:
@@ -832,7 +823,7 @@ def point_mask_loss_backward(src, tgt, tgt_index, pts, sums, g_mask, g_dice, mod
     """d_src (N,H,W) of point_mask_loss_forward for the gradients g_mask (N,), g_dice (N,) of its two outputs
     (hipie_point_mask_loss_backward): the samples are recomputed, the corners accumulated with fp32 atomics (not bit-reproducible)."""
     src, tgt, tgt_index, pts = _point_loss_operands(src, tgt, tgt_index, pts)
-    sums, g_mask, g_dice = _loss_f32(sums, "sums"), _loss_f32(g_mask, "g_mask"), _loss_f32(g_dice, "g_dice")
+    sums, g_mask, g_dice = _dense_f32(sums, "sums"), _dense_f32(g_mask, "g_mask"), _dense_f32(g_dice, "g_dice")
     N = src.shape[0]
     if sums.shape != (N, 3) or g_mask.shape != (N,) or g_dice.shape != (N,):
         raise RuntimeError("point_mask_loss_backward: sums (N,3), g_mask (N,), g_dice (N,) for N=%d" % N)
@@ -845,7 +836,7 @@ def point_mask_loss_backward(src, tgt, tgt_index, pts, sums, g_mask, g_dice, mod
 
 
 def _token_focal_operands(logits, onehot, keep):
-    logits, onehot = _loss_f32(logits, "logits"), _loss_f32(onehot, "onehot")
+    logits, onehot = _dense_f32(logits, "logits"), _dense_f32(onehot, "onehot")
     if logits.dim() != 3 or onehot.shape != logits.shape:
         raise RuntimeError("token_focal: logits and onehot (B,Q,T); got %s %s" % (tuple(logits.shape), tuple(onehot.shape)))
     if keep is not None:
@@ -878,7 +869,7 @@ def token_focal_backward(logits, onehot, keep, g, alpha=0.25):
     """dlogits (B,Q,T) = g * d focal / d logits at kept tokens, exactly 0 at dropped ones (hipie_token_focal_backward); g: 0-d DEVICE
     tensor, the gradient of token_focal_forward's output."""
     logits, onehot, keep = _token_focal_operands(logits, onehot, keep)
-    g = _loss_f32(g, "g")
+    g = _dense_f32(g, "g")
     if g.numel() != 1:
         raise RuntimeError("token_focal_backward: g must hold one value, got %s" % (tuple(g.shape),))
     B, Q, T = logits.shape

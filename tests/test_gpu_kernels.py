@@ -469,9 +469,10 @@ def test_flash_attn_generic(hd, nq, nk):
     assert rel_err(a.float().cpu(), ref) < 1e-3
 
 
-@pytest.mark.parametrize("C,rows", [(1280, 1000), (256, 4099), (160, 37), (2048, 5)])
+@pytest.mark.parametrize("C,rows", [(1280, 1000), (256, 4099), (160, 37), (2048, 5), (4, 1), (8, 3), (252, 5), (260, 7)])
 def test_add_layernorm(C, rows):
-    """hipie_add_layernorm vs torch fp32: fp32 in/out 2e-6; 16-bit storage within its rounding."""
+    """hipie_add_layernorm vs torch fp32: fp32 in/out 2e-6; 16-bit storage within its rounding.  The last four are the widths of the
+    backward's SHAPES: a tail vector only (4, 8), the longest tail (252), one full vector and a one-lane tail (260)."""
     import torch.nn.functional as F
     from hipie_amd import ops
     gen = torch.Generator().manual_seed(11)
@@ -696,16 +697,19 @@ def test_empty_inputs_are_handled():
 
 
 @pytest.mark.parametrize("dt,ddt", [(torch.float16, torch.float16), (torch.bfloat16, torch.float32)])
-def test_decoder_glue_layernorm_dec_and_add_cast(dt, ddt):
-    """hipie_add_layernorm_dec / hipie_add_cast against the eager chain they replace in the decoder layers."""
+@pytest.mark.parametrize("shape", [(3, 301, 256), (5, 8), (5, 260), (5, 2048)], ids=lambda s: "x".join(map(str, s)))
+def test_decoder_glue_layernorm_dec_and_add_cast(shape, dt, ddt):
+    """hipie_add_layernorm_dec / hipie_add_cast against the eager chain they replace in the decoder layers; 256 is the decoders' width,
+    8 is a tail vector only, 260 one full vector and a one-lane tail, 2048 the widest row."""
     import torch.nn.functional as F
     from hipie_amd import ops
     gen = torch.Generator().manual_seed(11)
-    x = torch.randn(3, 301, 256, generator=gen).to(DEV)
-    delta = torch.randn(3, 301, 256, generator=gen).to(DEV).to(ddt)
-    qp = torch.randn(3, 301, 256, generator=gen).to(DEV).to(dt)
-    w, b = torch.randn(256, generator=gen).to(DEV), torch.randn(256, generator=gen).to(DEV)
-    want = F.layer_norm(x + delta.float(), (256,), w, b, 1e-5)
+    C = shape[-1]
+    x = torch.randn(*shape, generator=gen).to(DEV)
+    delta = torch.randn(*shape, generator=gen).to(DEV).to(ddt)
+    qp = torch.randn(*shape, generator=gen).to(DEV).to(dt)
+    w, b = torch.randn(C, generator=gen).to(DEV), torch.randn(C, generator=gen).to(DEV)
+    want = F.layer_norm(x + delta.float(), (C,), w, b, 1e-5)
     n32, n16, s16 = ops.add_layernorm_dec(x, delta, w, b, 1e-5, dt, want16=True, addend=qp)
     assert rel_err(n32.cpu(), want.cpu()) < 2e-6
     assert torch.equal(n16, n32.to(dt))
@@ -713,6 +717,25 @@ def test_decoder_glue_layernorm_dec_and_add_cast(dt, ddt):
     n32b, none16, nones = ops.add_layernorm_dec(x, delta, w, b, 1e-5, dt)
     assert none16 is None and nones is None and torch.equal(n32b, n32)
     assert torch.equal(ops.add_cast(x, qp), (x + qp.float()).to(dt))
+
+
+@pytest.mark.parametrize("C", [8, 260, 1280])
+def test_layernorm_forward_kernels_agree(C):
+    """For fp32 x and delta the two forward kernels give the same fp32 bits, and the backward recomputes the forward's xhat: for ONE row
+    and gy = 1, dgamma = 0 + 1 * xhat is the backward's xhat, and with gamma = 1, beta = 0 the forward's output is its own.  (dx for
+    gy = 1 / gamma is a rounding residue, not exact zero: docs/measurements.md.)"""
+    from hipie_amd import ops
+    gen = torch.Generator().manual_seed(C)
+    x, d = (torch.randn(5, C, generator=gen) * 3).to(DEV), torch.randn(5, C, generator=gen).to(DEV)
+    w, b = (1 + 0.1 * torch.randn(C, generator=gen)).to(DEV), (0.1 * torch.randn(C, generator=gen)).to(DEV)
+    for eps in (1e-6, 1e-5):
+        s, n = ops.add_layernorm(x, d, w, b, eps, torch.float32)
+        assert torch.equal(ops.add_layernorm_dec(x, d, w, b, eps, torch.float16)[0], n)
+        one, zero = torch.ones(C, device=DEV), torch.zeros(C, device=DEV)
+        xhat = ops.add_layernorm(s, None, one, zero, eps, torch.float32)[1]
+        for r in range(s.shape[0]):
+            dgamma = ops.layernorm_backward(s[r:r + 1], one[None], w, eps)[1]
+            assert torch.equal(dgamma, xhat[r]), (eps, r)
 
 
 @pytest.mark.parametrize("nq", [910, 300])
