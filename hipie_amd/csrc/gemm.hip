@@ -82,6 +82,17 @@ int launch_gemm_k256(const void* X, long ldx_b, int x_f32, const void* W, long l
                      hipStream_t st);
 }
 
+// The MFMA shape of the wide split instances: true = the 16x16x32 form (gemm_tile.h, MS = 16).  ONE rule for wide && split: in the same-process
+// A/B on random operands (tools/bench_gemm_mfma.py, 7 rounds x 50 launches, 32768 rows; docs/measurements.md) the median of the 16x16x32
+// instance is below the MINIMUM of the 32x32x16 one on every shape -- ms, 32 -> 16: qkv 0.792 -> 0.715, fc1 + GELU 1.071 -> 0.987, proj 0.271 ->
+// 0.249, fc2 0.965 -> 0.877, proj / fc2 with fp32 output and residual 0.325 -> 0.279 / 1.007 -> 0.901, gathered qkv 0.787 -> 0.723 -- so no rule
+// on K is needed.  HIPIE_GEMM_MFMA=16|32 (study builds) is read at EVERY launch, unlike the switches of gemm_impl, so that the tool can
+// alternate the two instances inside one process.
+static inline bool gemm_mfma16() {
+  const char* e = study_env("HIPIE_GEMM_MFMA");
+  return e ? atoi(e) == 16 : true;
+}
+
 static int gemm_impl(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, const float* resid, int64_t ldr,
                      void* out, int64_t ldo, const int32_t* out_row, const int32_t* a_row, int64_t a_rows, int M, int N, int K, int in_fmt,
                      int out_fmt, int act, float alpha, float oscale, void* stream) {
@@ -144,6 +155,8 @@ static int gemm_impl(const void* A, int64_t lda, const void* W, int64_t ldw, con
   }
 #endif
   if (split && small_ok && a_row == nullptr) return a_f32 ? launch_gemm_small<2>(p, st) : launch_gemm_small<0>(p, st);
+  // wide split outputs (the four ViT linears, the gathered windowed qkv): the MFMA shape of the k loop, see gemm_mfma16
+  if (split && wide && gemm_mfma16()) return a_f32 ? launch_gemm<320, true, 2, 16>(p, st) : launch_gemm<320, true, 0, 16>(p, st);
   if (a_f32) return wide ? launch_gemm<320, true, 2>(p, st) : launch_gemm<256, true, 2>(p, st);
   if (split) return wide ? launch_gemm<320, true>(p, st) : launch_gemm<256, true>(p, st);
   return wide ? launch_gemm<320, false>(p, st) : launch_gemm<256, false>(p, st);

@@ -28,6 +28,11 @@
 //   * block -> tile map: the blocks of one XCD (blockIdx % 8) walk a contiguous range of tiles -- N index fastest for up to 4 column
 //     tiles, else in groups of 8 row panels with the row panel fastest (GemmParams::group_m) -- so the 32 workgroups resident on an
 //     XCD share 8 A row panels and 4 W panels through that XCD's L2.
+//   * MS = 16 (gemm_kernel's fourth parameter; BN = 320 split instances only): the same workgroup tile, waves, stages and DMA plan on
+//     v_mfma_f32_16x16x32_f16 -- a k32 stage is ONE k-step, a wave owns 4 token tiles x 10 feature tiles of 16 x 16 (the same 160 accumulator
+//     registers), lane (c = lane & 15, g = lane >> 4) reads k group g of row c.  The chip holds a higher clock on this shape in a power-
+//     limited loop (MI355X_MICROARCH.md, DVFS give-back).  Its LDS image has its own swizzle (gm_swz16): the one above is 2-way for the
+//     16 x 4 lane map.  gemm_impl chooses the shape (gemm.hip);
 // Epilogue (runtime switches, once per tile): * alpha, + bias, exact-erf GELU | ReLU, + fp32 residual, then the output as
 // fp32, fp16 or HL8 (optionally scaled) -- the HL8 form is directly the A operand of the next GEMM.
 #pragma once
@@ -204,8 +209,224 @@ __device__ __forceinline__ void gm_epi_quads(const f32x16& a, const float4* rq, 
   gm_epi_vals<NG>(x, G0, rq, sb, m, mok, nb, hi, p, has_res);
 }
 
-template <int BN, bool SPLIT, int VAR>
+// ---- the 16x16x32 instances (MS = 16) ----
+// LDS swizzle of their stage image: chunk k of row r sits at position k ^ gm_swz16(r).  A ds_read_b128 lane group is 4 + 4 + 8 lanes of three
+// k groups (MI355X_MICROARCH.md, LDS table: {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32), i.e. rows {0-3, 12-15} of one k
+// group and rows 4-11 of the next, or the complement: the 16 (row parity, position) pairs of a group are distinct when rows 4-11 take the
+// other half of the positions than rows 0-3 / 12-15 (bit 2) and the row pairs inside a half differ in bits 0-1.  Enumerated on the CPU for
+// both chunks of a k group (tools/lds_swizzle_check.py).
+__device__ __forceinline__ constexpr int gm_swz16(const int r) { return ((r >> 1) & 3) | (((((r & 15) + 4) >> 3) & 1) << 2); }
+
+// tile epilogue of a PAIR of 16-feature x 16-token MFMA tiles (features nb .. nb + 31 of one token tile): lane (c, g) holds token c and
+// features 16 i + 4 g .. + 3 of tile i.  The arithmetic of gm_epi_vals in the same order; rq = the residual values of the two quads
+// (zeros when there is no residual); sb = the pair's 32 bias values in LDS.  The lane-half exchange of gm_epi_vals becomes
+// v_permlane16_swap, which exchanges the ODD 16-lane rows of its first operand with the EVEN rows of its second (quarters 0 <-> 1, 2 <-> 3).
+__device__ __forceinline__ void gm_epi_vals16(const float (&x)[2][4], const float4* rq, const float* sb, const long m, const bool mok, const int nb,
+                                              const int g, const GemmParams& p, const bool has_res) {
+  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  const float alpha = p.alpha, osc = p.oscale;
+  const int act = p.act, ofmt = p.out_fmt;
+  float v[2][4];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const float4 b4 = *reinterpret_cast<const float4*>(sb + 16 * i + 4 * g);
+    v[i][0] = x[i][0] * alpha + b4.x;
+    v[i][1] = x[i][1] * alpha + b4.y;
+    v[i][2] = x[i][2] * alpha + b4.z;
+    v[i][3] = x[i][3] * alpha + b4.w;
+  }
+  if (act == 1) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[i][e] = gm_gelu(v[i][e]);
+  } else if (act == 2) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[i][e] = fmaxf(v[i][e], 0.f);
+  } else if (act == 3) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[i][e] = v[i][e] / (1.f + expf(-1.702f * v[i][e]));
+  }
+  if (has_res) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) { v[i][0] += rq[i].x; v[i][1] += rq[i].y; v[i][2] += rq[i].z; v[i][3] += rq[i].w; }
+  }
+  if (osc != 1.f) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[i][e] *= osc;
+  }
+  if (ofmt == HIPIE_F16) {
+    // the two tiles are exchanged between neighbouring quarters: quarter 0 ends up with features 0..7 of tile 0, quarter 1 with 0..7 of
+    // tile 1, quarters 2 / 3 with 8..15 of tile 0 / 1 -- ONE 16-byte piece each
+    const u32x2 s0 = __builtin_amdgcn_permlane16_swap(gm_pack2(v[0][0], v[0][1]), gm_pack2(v[1][0], v[1][1]), false, false);
+    const u32x2 s1 = __builtin_amdgcn_permlane16_swap(gm_pack2(v[0][2], v[0][3]), gm_pack2(v[1][2], v[1][3]), false, false);
+    const int n = nb + 16 * (g & 1) + 8 * (g >> 1);
+    if (mok && n < p.N) *reinterpret_cast<u32x4*>(reinterpret_cast<f16_t*>(p.out) + m * p.ldo + n) = (u32x4){s0[0], s1[0], s0[1], s1[1]};
+  } else {
+    // fp32 and HL8: a tile's 16 features are a 64-byte span of the output row, of which this lane holds the 16-byte piece at byte 16 g
+    // (fp32: features 4g ..+3; HL8: quarters 0 / 2 end up with the 8 hi values of a group, quarters 1 / 3 with its 8 lo values)
+    u32x4 piece[2];
+    if (ofmt == HIPIE_F32) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+        piece[i] = (u32x4){__builtin_bit_cast(unsigned int, v[i][0]), __builtin_bit_cast(unsigned int, v[i][1]),
+                           __builtin_bit_cast(unsigned int, v[i][2]), __builtin_bit_cast(unsigned int, v[i][3])};
+    } else {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        unsigned int H0, L0, H1, L1;
+        gm_split2(v[i][0], v[i][1], H0, L0);
+        gm_split2(v[i][2], v[i][3], H1, L1);
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(HIPIE_NO_FMA_MIX)
+        // inline-asm split in front of a lane swap: the wait states of settle() (wave.h), as in gm_epi_vals
+        asm volatile("s_nop 1" : "+v"(H0), "+v"(L0), "+v"(H1), "+v"(L1));
+#endif
+        const u32x2 s0 = __builtin_amdgcn_permlane16_swap(H0, L0, false, false);    // even quarter: (H0 own, H0 of the odd one); odd: (L0 of the even one, L0 own)
+        const u32x2 s1 = __builtin_amdgcn_permlane16_swap(H1, L1, false, false);
+        piece[i] = (u32x4){s0[0], s1[0], s0[1], s1[1]};
+      }
+    }
+    const long rowb = (m * p.ldo) * (ofmt == HIPIE_F32 ? 4 : 2) + (long)nb * 4 + 16 * g;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      if (mok && nb + 16 * i < p.N) *reinterpret_cast<u32x4*>(p.out + rowb + 64 * i) = piece[i];
+  }
+}
+
+// k loop and epilogue of gemm_kernel<BN, true, VAR, 16> behind the common front (tile map, DMA plan): `dma` is the kernel's own issue lambda
+template <int BN, bool AF32, typename Dma>
+__device__ __forceinline__ void gm_body16(const GemmParams& p, char* smem, const Dma& dma, const int m0, const int n0, const int wm, const int wn,
+                                          const int tid) {
+  constexpr int BM = 256, ROWS = BM + BN, STAGE = ROWS * 128, NI = ROWS / 64;
+  constexpr int NT = 4;                        // 16-token tiles per wave
+  constexpr int NF = BN / 32;                  // 16-feature tiles per wave
+  typedef Mfma16<f16_t>::frag frag;
+  const int lane = tid & 63, c = lane & 15, g = lane >> 4;
+
+  // ---- fragment addresses: row = tile base (multiple of 16) + c; chunk 2 g (hi | x0..x3) and 2 g + 1 (lo | x4..x7) of the lane's k group ----
+  const int swz = gm_swz16(c);
+  const char* xrow = smem + (wm * 64 + c) * 128;                     // + t * 16 * 128
+  const char* wrow = smem + (BM + wn * (BN / 2) + c) * 128;          // + j * 16 * 128
+  const int ch[2] = {16 * ((2 * g) ^ swz), 16 * ((2 * g + 1) ^ swz)};
+
+  f32x4 acc[NF][NT];
+#pragma unroll
+  for (int j = 0; j < NF; ++j)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[j][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  const int nkt = p.nkt;
+#pragma unroll
+  for (int i = 0; i < NI; ++i) dma(i, 0, 0);
+  __builtin_amdgcn_s_waitcnt(vmcnt(0));
+  __syncthreads();
+
+  for (int kt = 0; kt < nkt; ++kt) {
+    const int st = kt & 1;
+    const bool more = kt + 1 < nkt;
+    const char* xs = xrow + st * STAGE;
+    const char* ws = wrow + st * STAGE;
+    frag xa[2][NT];              // [hi | lo][token tile]: the stage's X fragments, read once
+    frag wa[3][2];               // [feature tile % 3][hi | lo]: two tiles ahead of the MFMAs
+    auto load_w = [&](const int j) {
+      wa[j % 3][0] = *reinterpret_cast<const frag*>(ws + j * 2048 + ch[0]);
+      wa[j % 3][1] = *reinterpret_cast<const frag*>(ws + j * 2048 + ch[1]);
+    };
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      xa[0][t] = *reinterpret_cast<const frag*>(xs + t * 2048 + ch[0]);
+      xa[1][t] = *reinterpret_cast<const frag*>(xs + t * 2048 + ch[1]);
+    }
+    load_w(0);
+    load_w(1);
+    if (AF32) {
+      // fp32 A rows: the two chunks hold x0..x3 / x4..x7 of the lane's k group (the bytes an HL8 group takes): split them here
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const f32x4 a = __builtin_bit_cast(f32x4, xa[0][t]), b = __builtin_bit_cast(f32x4, xa[1][t]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          f16_t hh, ll;
+          hl_split(a[e], hh, ll);
+          xa[0][t][e] = hh; xa[1][t][e] = ll;
+          hl_split(b[e], hh, ll);
+          xa[0][t][4 + e] = hh; xa[1][t][4 + e] = ll;
+        }
+      }
+    }
+    // the DMA plan of the 32x32x16 form: a feature tile's 12 MFMAs take the cycles of one of its sub-steps (6 of twice the length)
+    constexpr int DMA_BY = 4;
+    constexpr int PER = (NI + DMA_BY - 1) / DMA_BY;
+#pragma unroll
+    for (int j = 0; j < NF; ++j) {
+      if (j + 2 < NF) load_w(j + 2);
+      const frag wh = wa[j % 3][0], wl = wa[j % 3][1];
+#pragma unroll
+      for (int t = 0; t < NT; ++t) acc[j][t] = Mfma16<f16_t>::mma(wl, xa[0][t], acc[j][t]);
+#pragma unroll
+      for (int t = 0; t < NT; ++t) acc[j][t] = Mfma16<f16_t>::mma(wh, xa[1][t], acc[j][t]);
+#pragma unroll
+      for (int t = 0; t < NT; ++t) acc[j][t] = Mfma16<f16_t>::mma(wh, xa[0][t], acc[j][t]);
+      if (more) {
+#pragma unroll
+        for (int i = j * PER; i < (j + 1) * PER && i < NI; ++i) dma(i, kt + 1, st ^ 1);
+      }
+    }
+    __builtin_amdgcn_s_waitcnt(vmcnt(0));      // this wave's DMA writes of stage t+1 have landed
+    __syncthreads();                          // ... and everybody's; all reads of stage t are done
+  }
+
+  // ---- epilogue: lane = token c of a 16-token tile, registers = features 4 g .. 4 g + 3 of a 16-feature tile ----
+  const bool has_res = p.resid != nullptr;
+  float* sbias = reinterpret_cast<float*>(smem);     // the tile's bias values go through LDS once, as in the 32x32x16 form
+  if (tid < BN) sbias[tid] = (p.bias != nullptr && n0 + tid < p.N) ? p.bias[n0 + tid] : 0.f;
+  __syncthreads();
+  long orow[NT];                                     // output row of this lane's four tokens (identity, or the caller's row map: -1 drops the row)
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int m = m0 + wm * 64 + t * 16 + c;
+    orow[t] = (m < p.M) ? (p.out_row != nullptr ? (long)p.out_row[m] : (long)m) : -1;
+  }
+  // residual rows: the two quads of pair blk + 1 are requested before pair blk is processed
+  float4 rq[2][2];
+  auto load_res = [&](const int blk, float4 (&dst)[2]) {
+    const int t = blk / (NF / 2), jp = blk % (NF / 2);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int n = n0 + wn * (BN / 2) + jp * 32 + 16 * i + 4 * g;
+      dst[i] = (has_res && orow[t] >= 0 && n < p.N) ? *reinterpret_cast<const float4*>(p.resid + orow[t] * p.ldr + n) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  };
+  load_res(0, rq[0]);
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const long m = orow[t];
+#pragma unroll
+    for (int jp = 0; jp < NF / 2; ++jp) {
+      const int blk = t * (NF / 2) + jp;
+      if (blk + 1 < NT * (NF / 2)) load_res(blk + 1, rq[(blk + 1) & 1]);
+      const int nb = n0 + wn * (BN / 2) + jp * 32;              // first feature of the pair
+      float x[2][4];
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[i][e] = acc[2 * jp + i][t][e];
+      gm_epi_vals16(x, rq[blk & 1], sbias + (nb - n0), m, m >= 0, nb, g, p, has_res);
+    }
+  }
+}
+
+template <int BN, bool SPLIT, int VAR, int MS = 32>
 __global__ __launch_bounds__(512, 2) void gemm_kernel(const GemmParams pin) {
+  static_assert(MS == 32 || (MS == 16 && BN == 320 && SPLIT && (VAR == 0 || VAR == 2)),
+                "the 16x16x32 form exists for the wide split instances (HL8 and fp32 A rows) only");
   GemmParams p = pin;
   int vtile = -1;
   if (VAR == 8) {
@@ -277,7 +498,7 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel(const GemmParams pin) {
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const int r = 8 * (8 * i + wave) + rl;              // stage row
-      const int c = cp ^ ((r >> 1) & 7);                  // logical chunk stored at this position
+      const int c = cp ^ (MS == 16 ? gm_swz16(r) : ((r >> 1) & 7));      // logical chunk stored at this position
       if (r < BM) {
         const int mr = min(r, p.M - 1 - m0);
         // gather: the offset is taken from the START of A (all of A within 4 GB: checked on the host)
@@ -299,6 +520,11 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel(const GemmParams pin) {
     const char* sb = (isa ? abase : wbase) + ko;
     dma16(sb, dvoff[i], __builtin_amdgcn_readfirstlane(lds0 + (unsigned int)(stage * STAGE + 1024 * (8 * i + wave))));
   };
+
+  if constexpr (MS == 16) {
+    gm_body16<BN, VAR == 2>(p, smem, dma, m0, n0, wm, wn, tid);
+    return;
+  }
 
   // ---- fragment addresses: row = tile base (multiple of 32) + li, so the swizzle term is ((li >> 1) & 7) for every tile ----
   const int swz = (li >> 1) & 7;
@@ -750,7 +976,7 @@ static int launch_gemm_small(GemmParams& p, hipStream_t st) {
 #include "../../tools/ubench/gemm_overlap_study.h"     // round-4 timing study: not part of the product, lives with the micro-benchmarks
 #endif
 
-template <int BN, bool SPLIT, int VAR = 0>
+template <int BN, bool SPLIT, int VAR = 0, int MS = 32>
 static int launch_gemm(GemmParams& p, hipStream_t st, int batches = 1) {
   constexpr size_t lds = (size_t)2 * (256 + BN) * 128;
   p.tiles_m = (p.M + 255) / 256;
@@ -759,7 +985,7 @@ static int launch_gemm(GemmParams& p, hipStream_t st, int batches = 1) {
   // workgroups resident on an XCD hold 8 A panels x 4 W panels instead of 2 x 16 -- 40 % fewer operand rows through that XCD's L2.
   // Same-box A/B (profiles/r06_gemm_tile_order.txt): qkv 0.894 -> 0.874 ms, fc1 1.099 -> 1.076 ms; up to 4 column tiles the plain order already is 8 x 4.
   p.group_m = p.tiles_n > 4 ? 8 : 0;
-  auto kern = gemm_kernel<BN, SPLIT, VAR>;
+  auto kern = gemm_kernel<BN, SPLIT, VAR, MS>;
   static LdsLimit limit;
   limit.raise((const void*)kern, lds);
   if (VAR == 8)       // inner index fastest inside blockIdx.x (see the kernel): grid = tiles * n_inner x n_outer

@@ -8,6 +8,10 @@
 //    code that fills both operands with the same (half, j) -> k convention is correct whatever the hardware's k label)
 //   C/D: lane l, register r (0..15):  row = (r & 3) + 8 * (r >> 2) + 4 * (l >> 5),  col = l & 31
 //
+// v_mfma_f32_16x16x32_{bf16,f16}:  D(16x16) += A(16x32) . B(32x16), with c = l & 15 and g = l >> 4:
+//   A operand: lane l holds A[i = c][k-group g, j], j = 0..7;  B operand: B[k-group g, j][n = c] (the same slot convention on both sides)
+//   C/D: lane l, register r (0..3):  row = 4 g + r,  col = c
+//
 // v_mfma_f32_32x32x2_f32:  D(32x32) += A(32x2) . B(2x32);  A: lane l holds A[l & 31][l >> 5];  B: B[l >> 5][l & 31];
 //   C/D as above.
 //
@@ -42,6 +46,14 @@ template <> struct Mfma32<f16_t> {
   }
   static __device__ __forceinline__ half_frag tr_read(const f16_t* lds_ptr) {
     return __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4*)lds_ptr));
+  }
+};
+
+template <typename T> struct Mfma16;
+template <> struct Mfma16<f16_t> {
+  typedef f16x8 frag;
+  static __device__ __forceinline__ f32x4 mma(frag a, frag b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
   }
 };
 
