@@ -19,6 +19,7 @@
 // all hit one element adds its sum once: add_corner.)
 // Offsets inside one map are 32-bit (H * W < 2^31, checked); the base of instance n is 64-bit.
 #include "common.h"
+#include "point_sample.h"
 #include "wave.h"
 
 namespace hipie {
@@ -28,21 +29,7 @@ constexpr int PL_CHUNK = 1024;               // points per workgroup: 4 per thre
 constexpr int TF_MAX_WG = 1024;              // workgroups (= partial sums) of the token focal forward: 4 per thread of the second stage
 constexpr int TF_PER_WG = 1024;              // elements per workgroup before the grid stops growing
 
-// ---- the element-wise terms ------------------------------------------------------------------------------------------------------------
-struct Sigmoid {
-  float p, q, l1p;                           // sigmoid(x), 1 - sigmoid(x) (no cancellation: sigmoid(-x)), log(1 + exp(-|x|))
-};
-
-__device__ __forceinline__ Sigmoid sigmoid_parts(float x) {
-  const float e = expf(-fabsf(x));
-  const float r = 1.f / (1.f + e);
-  Sigmoid s;
-  s.p = x >= 0.f ? r : e * r;
-  s.q = x >= 0.f ? e * r : r;
-  s.l1p = log1pf(e);
-  return s;
-}
-
+// ---- the element-wise terms (Sigmoid, sigmoid_parts and the bilinear sample: point_sample.h) ---------------------------------------------
 // binary_cross_entropy_with_logits(x, t) in the stable softplus form, t in [0, 1]
 __device__ __forceinline__ float ce_value(float x, float t, const Sigmoid& s) { return fmaxf(x, 0.f) - x * t + s.l1p; }
 
@@ -65,41 +52,6 @@ __device__ __forceinline__ float term_grad(float x, float t, const Sigmoid& s, f
   const float u = s.p * (1.f - t) + s.q * t;
   const float at = alpha >= 0.f ? alpha * t + (1.f - alpha) * (1.f - t) : 1.f;
   return at * (dce * (u * u) + 2.f * ce * u * (s.p * s.q) * (1.f - 2.f * t));
-}
-
-// ---- bilinear sampling: grid_sample(align_corners=False, zero padding) at (x, y) in [0, 1]^2 ----------------------------------------
-struct Corners {
-  int off[4];                                // y * W + x of the nw, ne, sw, se corner; 0 for a corner outside the map
-  float w[4];                                // its weight; 0 outside
-};
-
-__device__ __forceinline__ Corners corners_of(float x, float y, int H, int W) {
-  // pixel coordinate x * W - 0.5 in one rounding.  The clamp keeps float -> int defined for any input and moves nothing that has a corner
-  // inside the map: below -1 and from W on every corner is outside anyway.  A NaN coordinate becomes -2: the sample is 0.
-  const float ix = fminf(fmaxf(fmaf(x, (float)W, -0.5f), -2.f), (float)W + 1.f);
-  const float iy = fminf(fmaxf(fmaf(y, (float)H, -0.5f), -2.f), (float)H + 1.f);
-  const float fx = floorf(ix), fy = floorf(iy);
-  const int x0 = (int)fx, y0 = (int)fy;
-  const float wx1 = ix - fx, wy1 = iy - fy;
-  const float wx0 = 1.f - wx1, wy0 = 1.f - wy1;
-  Corners c;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int xi = x0 + (k & 1), yi = y0 + (k >> 1);
-    const bool in = xi >= 0 && xi < W && yi >= 0 && yi < H;
-    c.off[k] = in ? yi * W + xi : 0;
-    c.w[k] = in ? ((k & 1) ? wx1 : wx0) * ((k >> 1) ? wy1 : wy0) : 0.f;
-  }
-  return c;
-}
-
-// a corner of weight 0 is not read (outside the map, or in it with the point on a pixel centre)
-__device__ __forceinline__ float sample(const float* __restrict__ map, const Corners& c) {
-  float v = 0.f;
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    if (c.w[k] != 0.f) v += c.w[k] * map[c.off[k]];
-  return v;
 }
 
 // ---- sums over a workgroup, in a fixed order ---------------------------------------------------------------------------------------------

@@ -10,17 +10,9 @@
 // by a bitonic network on (key, ~index) -- descending value, ascending index among equal values: a deterministic total order
 // (torch.topk leaves the order of ties open).  NaN sorts as the largest value, as in torch.
 #include "common.h"
+#include "topk_key.h"
 
 namespace hipie {
-
-// order-preserving key.  Canonical forms first: every NaN (either sign bit: 0 * -inf gives a negative one) is the largest key, as in
-// torch; -0.0 is folded into +0.0 so that equal values tie and the tie is broken by index.
-__device__ __forceinline__ unsigned int tk_key(float v) {
-  if (v != v) return 0xFFFFFFFFu;
-  v += 0.0f;
-  const unsigned int b = __builtin_bit_cast(unsigned int, v);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
 
 __global__ __launch_bounds__(1024) void topk_kernel(const float* __restrict__ x, long row_stride, int n, int k, long* __restrict__ idx_out,
                                                     float* __restrict__ val_out) {

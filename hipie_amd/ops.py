@@ -880,6 +880,95 @@ def token_focal_backward(logits, onehot, keep, g, alpha=0.25):
     return dlogits
 
 
+def _layout_f32(t, name, ndim):
+    """refuses t unless it is a contiguous fp32 tensor of `ndim` dimensions (nothing is copied; the device is checked by _on_device, last)"""
+    if t.dtype != torch.float32:
+        raise RuntimeError("%s must be torch.float32, got %s" % (name, t.dtype))
+    if t.dim() != ndim:
+        raise RuntimeError("%s must have %d dimensions, got %s" % (name, ndim, tuple(t.shape)))
+    if not t.is_contiguous():
+        raise RuntimeError("%s tensor has to be contiguous" % name)
+
+
+def _on_device(**tensors):
+    for name, t in tensors.items():
+        if t is not None and not t.is_cuda:
+            raise RuntimeError("Not implemented on the CPU (%s must be a CUDA/HIP tensor)" % name)
+
+
+def _workspace(ws, need, device, what):
+    """the caller's byte workspace when it is given (checked), else one that lives for the call"""
+    if ws is None:
+        return torch.empty(need, dtype=torch.uint8, device=device)
+    if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need:
+        raise RuntimeError("%s: workspace of %d contiguous uint8 elements needed, got %s %s" % (what, need, ws.dtype, tuple(ws.shape)))
+    return ws
+
+
+def uncertain_points_ws_bytes(N, C):
+    return int(_lib.load().hipie_uncertain_points_ws_bytes(int(N), int(C)))
+
+
+@_timed("uncertain_points")
+def uncertain_points(src, cand, rest, k, num_points=None, ws=None):
+    """the importance point selection of one criterion call (hipie_uncertain_points, fp32, no gradient): src (N,H,W) logits, cand (N,C,2)
+    the over-sampled candidates, rest (N,P-k,2) the fresh points (None: P = k) -> pts (N,P,2): pts[:, :k] = the k candidates whose sampled
+    |logit| is smallest, in ascending candidate index (ties at the threshold by index), pts[:, k:] = rest.  Bit-reproducible.
+    num_points: the P the caller expects; a rest that does not hold P - k points is refused.
+    ws: uint8 tensor of at least uncertain_points_ws_bytes(N, C) elements, or None: allocated for the call.
+    Nothing is copied: a strided or non-fp32 operand is refused; the layout is checked before the device."""
+    _layout_f32(src, "src", 3)
+    _layout_f32(cand, "cand", 3)
+    N, C, k = src.shape[0], cand.shape[1], int(k)
+    if cand.shape[0] != N or cand.shape[2] != 2:
+        raise RuntimeError("uncertain_points: cand must be (N=%d, C, 2), got %s" % (N, tuple(cand.shape)))
+    if not 0 <= k <= C:
+        raise RuntimeError("uncertain_points: k=%d must be in [0, C=%d]" % (k, C))
+    n_rest = 0
+    if rest is not None:
+        _layout_f32(rest, "rest", 3)
+        if rest.shape[0] != N or rest.shape[2] != 2:
+            raise RuntimeError("uncertain_points: rest must be (N=%d, P - k, 2), got %s" % (N, tuple(rest.shape)))
+        n_rest = rest.shape[1]
+    P = k + n_rest
+    if num_points is not None and P != int(num_points):
+        raise RuntimeError("uncertain_points: rest must hold P - k = %d points, got %d" % (int(num_points) - k, n_rest))
+    _on_device(src=src, cand=cand, rest=rest, ws=ws)
+    lib = _lib.load()
+    ws = _workspace(ws, int(lib.hipie_uncertain_points_ws_bytes(N, C)), src.device, "uncertain_points")
+    pts = src.new_empty(N, P, 2)
+    rc = lib.hipie_uncertain_points(src.data_ptr(), cand.data_ptr(), rest.data_ptr() if n_rest else None, pts.data_ptr(), ws.data_ptr(), ws.numel(),
+                                    N, src.shape[1], src.shape[2], C, P, k, _stream())
+    _lib.check(rc, "hipie_uncertain_points")
+    return pts
+
+
+def mask_match_cost_ws_bytes(Q, T, P):
+    return int(_lib.load().hipie_mask_match_cost_ws_bytes(int(Q), int(T), int(P)))
+
+
+@_timed("mask_match_cost")
+def mask_match_cost(pred, tgt, coords, ws=None):
+    """the point-sampled mask costs of one matcher call (hipie_mask_match_cost, fp32, no gradient): pred (Q,H,W) logits, tgt (T,Ht,Wt) in
+    [0,1] at its own resolution, coords (P,2) shared by all masks -> (ce (Q,T), dice (Q,T)) of matcher.mask_costs.  Bit-reproducible.
+    ws: uint8 tensor of at least mask_match_cost_ws_bytes(Q, T, P) elements on a 16-byte boundary, or None: allocated for the call.
+    Nothing is copied: a strided or non-fp32 operand is refused; the layout is checked before the device."""
+    _layout_f32(pred, "pred", 3)
+    _layout_f32(tgt, "tgt", 3)
+    _layout_f32(coords, "coords", 2)
+    Q, T, P = pred.shape[0], tgt.shape[0], coords.shape[0]
+    if coords.shape[1] != 2 or (P == 0 and Q * T > 0):
+        raise RuntimeError("mask_match_cost: coords must be (P > 0, 2), got %s" % (tuple(coords.shape),))
+    _on_device(pred=pred, tgt=tgt, coords=coords, ws=ws)
+    lib = _lib.load()
+    ws = _workspace(ws, int(lib.hipie_mask_match_cost_ws_bytes(Q, T, P)), pred.device, "mask_match_cost")
+    ce, dice = pred.new_empty(Q, T), pred.new_empty(Q, T)
+    rc = lib.hipie_mask_match_cost(pred.data_ptr(), tgt.data_ptr(), coords.data_ptr(), ce.data_ptr(), dice.data_ptr(), ws.data_ptr(), ws.numel(),
+                                   Q, pred.shape[1], pred.shape[2], T, tgt.shape[1], tgt.shape[2], P, _stream())
+    _lib.check(rc, "hipie_mask_match_cost")
+    return ce, dice
+
+
 @_timed("add_layernorm")
 def add_layernorm_sum(x, delta, weight, bias, eps, addend):
     """n = LayerNorm(x + delta) and n + addend, both in x's dtype, one launch (the encoder's post-norm + next `src + pos`)."""

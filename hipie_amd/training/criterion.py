@@ -17,7 +17,11 @@ in the reference.  Random point coordinates come from ``draw(shape, device)`` (d
     token_focal_sum(logits, onehot, text_mask, alpha) -> scalar
 (net.HipBackendLosses: functions.PointMaskLossFunction / TokenFocalFunction on csrc/point_loss.hip).  With it the point-sampled mask losses
 hand over ALL padded targets and the flat index of the matched ones -- the targets are not gathered -- and the token focal loss drops the pad
-tokens inside the kernel instead of by boolean indexing (a host wait).  The random draws and their order do not change."""
+tokens inside the kernel instead of by boolean indexing (a host wait).  The random draws and their order do not change.
+An `ops` that also has
+    uncertain_points(src (N,H,W), cand (N,C,2), rest (N,P-k,2) | None, k, num_points=None) -> pts (N,P,2)
+(net.HipBackendCriteria: functions.uncertain_points on csrc/point_select.hip) selects the importance points of those two calls: the same
+two draws, the chosen candidates in ascending candidate index instead of sorted by score."""
 import copy
 
 import torch
@@ -65,14 +69,19 @@ def sigmoid_ce_loss(logits, targets, count):
     return F.binary_cross_entropy_with_logits(logits, targets, reduction="none").mean(1).sum() / count
 
 
-def uncertain_points(logits, num_points, oversample, importance, draw):
+def uncertain_points(logits, num_points, oversample, importance, draw, select=None):
     """logits (N, 1, H, W) -> (N, num_points, 2): of `oversample * num_points` uniform candidates the `importance * num_points` whose
     sampled logit is closest to 0, then fresh uniform points for the rest (PointRend's get_uncertain_point_coords_with_randomness,
-    detectron2 point_rend/point_features.py:63-116, with the reference's uncertainty -|logit|)."""
+    detectron2 point_rend/point_features.py:63-116, with the reference's uncertainty -|logit|).
+    select (an `ops` object's uncertain_points, or None): the same two draws in the same order, then select(logits (N, H, W), cand, rest | None,
+    n_imp, num_points) -- the chosen candidates come back in ascending candidate index instead of sorted by score; the losses are sums over the points."""
     N = logits.shape[0]
     cand = draw((N, int(num_points * oversample), 2), logits.device)
-    score = -point_sample(logits, cand)[:, 0].abs()
     n_imp = int(importance * num_points)
+    if select is not None:
+        rest = draw((N, num_points - n_imp, 2), logits.device) if num_points - n_imp > 0 else None
+        return select(logits[:, 0], cand, rest, n_imp, num_points)
+    score = -point_sample(logits, cand)[:, 0].abs()
     top = score.topk(n_imp, dim=1)[1]
     pts = torch.gather(cand, 1, top[:, :, None].expand(N, n_imp, 2))
     if num_points - n_imp > 0:
@@ -202,7 +211,8 @@ class DetCriterion(nn.Module):
             return {"loss_mask": src.sum() * 0.0, "loss_dice": src.sum() * 0.0}
         if fused:                                           # the targets stay where they are: the kernel reads row `flat` of (B * max n, h, w)
             with torch.no_grad():
-                pts = uncertain_points(src, self.num_points, self.oversample_ratio, self.importance_sample_ratio, self.draw)
+                pts = uncertain_points(src, self.num_points, self.oversample_ratio, self.importance_sample_ratio, self.draw,
+                                       getattr(self.ops, "uncertain_points", None))
             flat = (matched[0] * tm.shape[1] + matched[1]).to(src.device)
             lmask, ldice = self.ops.point_mask_loss(src[:, 0], tm.flatten(0, 2), flat, pts, 1, 0.25)      # dense_focal_loss's default alpha
             return {"loss_mask": lmask.sum() / count, "loss_dice": ldice.sum() / count}
@@ -309,7 +319,8 @@ class MaskCriterion(nn.Module):
         if self.ops is not None and len(src):               # the targets stay where they are: the kernel reads row `flat` of (B * max n, H, W)
             tm = self._padded_targets(targets, src)
             with torch.no_grad():
-                pts = uncertain_points(src, self.num_points, self.oversample_ratio, self.importance_sample_ratio, self.draw)
+                pts = uncertain_points(src, self.num_points, self.oversample_ratio, self.importance_sample_ratio, self.draw,
+                                       getattr(self.ops, "uncertain_points", None))
             bi, ti = _perm(indices, 1)
             lmask, ldice = self.ops.point_mask_loss(src[:, 0], tm.flatten(0, 1), (bi * tm.shape[1] + ti).to(src.device), pts, 0, -1.0)
             return {"loss_mask": lmask.sum() / count, "loss_dice": ldice.sum() / count}

@@ -376,3 +376,23 @@ class TokenFocalFunction(torch.autograd.Function):
 def token_focal_sum(logits, onehot, text_mask=None, alpha=0.25):
     """scalar: token_focal_loss(logits, onehot, text_mask, alpha) on hipie_token_focal_forward / _backward"""
     return TokenFocalFunction.apply(logits, onehot, text_mask, alpha)
+
+
+@torch.no_grad()
+def uncertain_points(src, cand, rest, k, num_points=None):
+    """criterion.uncertain_points after its two draws, on hipie_uncertain_points: src (N,H,W) logits, cand (N,C,2), rest (N,P-k,2) or None ->
+    pts (N,P,2) in cand's dtype, the k candidates closest to logit 0 in ascending candidate index, then rest.  num_points: the caller's P; a
+    rest that does not hold P - k points is refused.  The operands are cast to fp32 and made dense, as mask_match_costs does (the torch
+    path takes any floating dtype).  No gradient; the key workspace lives for the call."""
+    ws = torch.empty(ops.uncertain_points_ws_bytes(src.shape[0], cand.shape[1]), dtype=torch.uint8, device=src.device)
+    pts = ops.uncertain_points(src.detach().float().contiguous(), cand.float().contiguous(), None if rest is None else rest.float().contiguous(), k,
+                               num_points=num_points, ws=ws)
+    return pts.to(cand.dtype)
+
+
+@torch.no_grad()
+def mask_match_costs(pred, tgt, coords):
+    """matcher.mask_costs on hipie_mask_match_cost: pred (Q,H,W) logits, tgt (T,Ht,Wt), coords (P,2) -> (ce (Q,T), dice (Q,T)).  No gradient; the
+    workspace (the sampled targets and the partial sums) lives for the call."""
+    ws = torch.empty(ops.mask_match_cost_ws_bytes(pred.shape[0], tgt.shape[0], coords.shape[0]), dtype=torch.uint8, device=pred.device)
+    return ops.mask_match_cost(pred.detach().float().contiguous(), tgt.float().contiguous(), coords.float().contiguous(), ws=ws)

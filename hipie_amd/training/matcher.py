@@ -65,8 +65,10 @@ def mask_costs(pred, tgt, coords):
     return ce, dice
 
 
-def cost_matrix(logits, boxes, target, w, masks=None, coords=None, stuff_takes_mean=True, with_boxes=True, class_mode="auto"):
-    """One image: logits (Q, L), boxes (Q, 4) cxcywh, target dict (boxes (T, 4), positive_map | labels, is_thing (T,), masks) -> (Q, T)."""
+def cost_matrix(logits, boxes, target, w, masks=None, coords=None, stuff_takes_mean=True, with_boxes=True, class_mode="auto", ops=None):
+    """One image: logits (Q, L), boxes (Q, 4) cxcywh, target dict (boxes (T, 4), positive_map | labels, is_thing (T,), masks) -> (Q, T).
+    ops (default None: mask_costs above): an object whose mask_match_costs(pred (Q,H,W), tgt (T,Ht,Wt), coords (P,2)) -> (ce, dice) computes
+    the two mask costs (net.HipBackendCriteria: functions.mask_match_costs on csrc/point_select.hip)."""
     prob = logits.sigmoid()
     C = w.cls * class_cost(prob, target, class_mode)
     if with_boxes:
@@ -82,7 +84,8 @@ def cost_matrix(logits, boxes, target, w, masks=None, coords=None, stuff_takes_m
             gi = torch.nan_to_num(gi, nan=0.0, posinf=float("inf"), neginf=float("-inf"))
         C = C + w.l1 * l1 + w.giou * gi
     if masks is not None:
-        ce, dice = mask_costs(masks, target["masks"].to(masks), coords)
+        costs = getattr(ops, "mask_match_costs", None) or mask_costs
+        ce, dice = costs(masks, target["masks"].to(masks), coords)
         C = C + w.mask * ce + w.dice * dice
     return C
 
@@ -147,10 +150,11 @@ def dynamic_k_assign(cost, iou):
 class HungarianMatcher(nn.Module):
     """weights: MatchWeights.  num_points: points of the mask costs (12544 = 112^2 in both heads).  stuff_takes_mean: the panoptic
     box handling (`panoptic_box_loss` / `panoptic_on`).  draw(shape, device) supplies uniform [0, 1) numbers (default torch.rand): the
-    reference draws ONE (1, num_points, 2) tensor per image, in batch order."""
+    reference draws ONE (1, num_points, 2) tensor per image, in batch order.  ops: see cost_matrix (the draws do not change)."""
 
-    def __init__(self, weights=None, num_points=112 * 112, stuff_takes_mean=True, draw=None, class_mode="auto"):
+    def __init__(self, weights=None, num_points=112 * 112, stuff_takes_mean=True, draw=None, class_mode="auto", ops=None):
         super().__init__()
+        self.ops = ops
         self.class_mode = class_mode                       # "map": positive maps (vl_loss), "ids": class ids, "auto": whichever the target has
         self.w = weights or MatchWeights()
         if not any((self.w.cls, self.w.l1, self.w.giou, self.w.mask)):
@@ -166,7 +170,7 @@ class HungarianMatcher(nn.Module):
         for b, tgt in enumerate(targets):
             m = masks[b] if (masks is not None and "mask" in costs) else None
             coords = self.draw((1, self.num_points, 2), logits.device)[0] if m is not None else None
-            C = cost_matrix(logits[b], boxes[b], tgt, self.w, m, coords, self.stuff_takes_mean, "box" in costs, self.class_mode)
+            C = cost_matrix(logits[b], boxes[b], tgt, self.w, m, coords, self.stuff_takes_mean, "box" in costs, self.class_mode, self.ops)
             out.append(assign(C.reshape(logits.shape[1], -1)))
         return out
 

@@ -7,7 +7,8 @@ torch.autograd providing their backward (opt-in, HipBackendNorms: the LayerNorms
 hipie_add_layernorm / hipie_layernorm_backward; opt-in, HipBackendMlp: their MLPs / FFNs as one node with the activation on
 hipie_act_forward / hipie_act_backward; opt-in, HipBackendWindows: the attention of the windowed ViT blocks on
 hipie_attn_train_win_forward / _backward; opt-in, HipBackendLosses: the point-sampled mask losses and the token focal loss of the two
-criteria on hipie_point_mask_loss_* / hipie_token_focal_*).
+criteria on hipie_point_mask_loss_* / hipie_token_focal_*; opt-in, HipBackendCriteria: on top of those the importance point selection of the
+criteria and the mask costs of the matchers on hipie_uncertain_points / hipie_mask_match_cost).
 
 Functional style over a dict ``sd`` of LIVE parameters (model.named_parameters() + buffers, reference key names), so gradients land in the
 model's own parameters.  Every function cites the reference code it follows.  Training-mode differences from the inference path:
@@ -148,6 +149,27 @@ class HipBackendLosses(HipBackend):
         """logits, onehot (B,Q,T), text_mask (B,T) or None -> the scalar criterion.token_focal_loss returns"""
         from .functions import token_focal_sum
         return token_focal_sum(logits, onehot, text_mask, alpha)
+
+
+class HipBackendCriteria(HipBackendLosses):
+    """HipBackendLosses + the two no_grad places that sample a mask at points, on csrc/point_select.hip: the importance point selection of both
+    criteria (functions.uncertain_points: the candidates' samples, the selection and the gather as two launches) and the mask costs of the
+    matchers (functions.mask_match_costs: the targets sampled once, the (Q, P) samples never written).  TrainStep hands the backend to the
+    criteria AND the matchers as their `ops`; with it nothing in them that samples a mask at points goes through grid_sample.
+    Opt-in: TrainStep's default stays HipBackend; HipBackendLosses and HipBackendAll do not include it."""
+
+    @staticmethod
+    def uncertain_points(src, cand, rest, k, num_points=None):
+        """src (N,H,W), cand (N,C,2), rest (N,P-k,2) or None -> pts (N,P,2): the k candidates with the smallest |sampled logit| in ascending
+        candidate index, then rest.  num_points: the caller's P (a rest of another length than P - k is refused)"""
+        from .functions import uncertain_points
+        return uncertain_points(src, cand, rest, k, num_points)
+
+    @staticmethod
+    def mask_match_costs(pred, tgt, coords):
+        """pred (Q,H,W), tgt (T,Ht,Wt), coords (P,2) -> (ce (Q,T), dice (Q,T)) of matcher.mask_costs"""
+        from .functions import mask_match_costs
+        return mask_match_costs(pred, tgt, coords)
 
 
 # ------------------------------------------------------------------------------------------------ small helpers

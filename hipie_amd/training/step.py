@@ -53,6 +53,8 @@ class TrainStep:
         self.draws = draws or _Draws()
         # the opt-in loss kernels (net.HipBackendLosses): both criteria get the backend as their `ops` when it has the two methods
         loss_ops = self.be if getattr(self.be, "point_mask_loss", None) and getattr(self.be, "token_focal_sum", None) else None
+        # the opt-in mask-cost kernel (net.HipBackendCriteria): the matchers get the backend the same way
+        match_ops = self.be if getattr(self.be, "mask_match_costs", None) else None
         d = self.draws
         draw = lambda shape, device: d.rand(tuple(shape), device)          # noqa: E731
         self.dn_number, self.label_noise_ratio, self.box_noise_scale = dn_number, label_noise_ratio, box_noise_scale
@@ -60,8 +62,10 @@ class TrainStep:
         self.mask_dino_weight, self.fusion_dropout, self.loss_weight = mask_dino_weight, fusion_dropout, loss_weight
         self.md_dn_number, self.md_noise_scale = md_dn_number, md_noise_scale
         # hipie_img.py:176-236: the matchers and the DINO criterion
-        self.matcher = HungarianMatcher(MatchWeights(2.0, 5.0, 2.0, 5.0, 5.0), num_points=num_points, stuff_takes_mean=True, draw=draw, class_mode="map")
-        self.matcher_bg = HungarianMatcher(MatchWeights(2.0, 0.0, 0.0, 5.0, 5.0), num_points=bg_matcher_points, stuff_takes_mean=False, draw=draw, class_mode="map")
+        self.matcher = HungarianMatcher(MatchWeights(2.0, 5.0, 2.0, 5.0, 5.0), num_points=num_points, stuff_takes_mean=True, draw=draw, class_mode="map",
+                                        ops=match_ops)
+        self.matcher_bg = HungarianMatcher(MatchWeights(2.0, 0.0, 0.0, 5.0, 5.0), num_points=bg_matcher_points, stuff_takes_mean=False, draw=draw,
+                                           class_mode="map", ops=match_ops)
         self.criterion = DetCriterion(self.matcher, ["labelsVL", "boxes", "masks"], focal_alpha=0.25, mask_out_stride=self.cfg["mask_stride"],
                                       point_sample_masks=True, panoptic_box_loss=True, still_cls_for_encoder=True, num_points=num_points, draw=draw, ota=True,
                                       ops=loss_ops)
@@ -77,7 +81,8 @@ class TrainStep:
         self.weight_dict = w
         # ddetrs_dn.py:176-196
         self.md_weights, md_dn_losses, md_matcher, md_losses = maskdino_loss_plan(
-            4.0, 5.0, 5.0, 5.0, 2.0, True, "seg", True, self.cfg["md_dec_layers"], True, 4.0, 5.0, 5.0, 5.0, 2.0, md_num_points, True, draw=draw)
+            4.0, 5.0, 5.0, 5.0, 2.0, True, "seg", True, self.cfg["md_dec_layers"], True, 4.0, 5.0, 5.0, 5.0, 2.0, md_num_points, True, draw=draw,
+            ops=match_ops)
         self.md_criterion = MaskCriterion(100, md_matcher, md_losses, vl_loss=True, num_points=md_num_points, oversample_ratio=3.0, importance_sample_ratio=0.75,
                                           dn="seg", dn_losses=md_dn_losses, panoptic_on=False, draw=draw, ops=loss_ops)
 

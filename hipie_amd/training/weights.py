@@ -3,10 +3,10 @@ from .matcher import HungarianMatcher, MatchWeights
 
 
 def maskdino_loss_plan(class_weight, mask_weight, dice_weight, box_weight, giou_weight, two_stage, dn, deep_supervision, dec_layers, box_loss,
-                       cost_class, cost_mask, cost_dice, cost_box, cost_giou, train_num_points, vl_loss, draw=None):
+                       cost_class, cost_mask, cost_dice, cost_box, cost_giou, train_num_points, vl_loss, draw=None, ops=None):
     """MODEL.MaskDINO.* -> (weight of every loss key the MaskDINO criterion can emit, the loss families of the de-noising part, the matcher,
-    the loss families).  Key growth as in the reference: base keys, their `_interm` copies (two-stage), `_dn` copies of all of those (dn ==
-    "seg") or of the non-mask ones ("standard"), then `_i` copies of everything for each of the `dec_layers` auxiliary layers."""
+    the loss families).  ops: handed to the matcher (HungarianMatcher).  Key growth as in the reference: base keys, their `_interm` copies
+    (two-stage), `_dn` copies of all of those (dn == "seg") or of the non-mask ones ("standard"), then `_i` copies of everything for each of the `dec_layers` auxiliary layers."""
     w = {"loss_ce": class_weight, "loss_mask": mask_weight, "loss_dice": dice_weight, "loss_bbox": box_weight, "loss_giou": giou_weight}
     if two_stage:
         w.update({k + "_interm": v for k, v in list(w.items())})
@@ -23,7 +23,7 @@ def maskdino_loss_plan(class_weight, mask_weight, dice_weight, box_weight, giou_
         for i in range(dec_layers):
             w.update({k + "_%d" % i: v for k, v in base})
     matcher = HungarianMatcher(MatchWeights(cost_class, cost_box, cost_giou, cost_mask, cost_dice), num_points=train_num_points, stuff_takes_mean=False,
-                               draw=draw, class_mode="map" if vl_loss else "ids")
+                               draw=draw, class_mode="map" if vl_loss else "ids", ops=ops)
     return w, dn_losses, matcher, (["labels", "masks", "boxes"] if box_loss else ["labels", "masks"])
 
 

@@ -366,6 +366,47 @@ int hipie_token_focal_backward(const float* logits, const float* onehot, const u
                                float alpha, float gamma, void* stream);
 
 /*
+ * The importance point selection of the training criteria (fp32, forward only).
+ * Replaces: get_uncertain_point_coords_with_randomness (detectron2 point_rend/point_features.py:63-116) as called by SetCriterion.loss_masks
+ *           (models/deformable_detr/deformable_detr.py:452-524) and models/maskdino/criterion.py:286-336 with the uncertainty -|logit|: the
+ *           (N, C) grid_sample of the candidates, abs / neg, torch.topk (12 launches), the gather of the chosen candidates and the cat.
+ *   src (N, H, W): mask logits, dense.   cand (N, C, 2): the over-sampled uniform candidates, (x, y) in [0, 1]^2.
+ *   rest (N, P - k, 2): the fresh uniform points.   pts (N, P, 2): the output.   Sampling as in hipie_point_mask_loss_forward.
+ *   Score of candidate c = -|sample(src[n], cand[n, c])|.  The k candidates with the LARGEST score (the smallest |logit|) are chosen; ties at
+ *   the threshold are taken in ascending candidate index, -0.0 ties with +0.0, a NaN sample counts as the largest score (torch.topk,
+ *   hipie_topk).  pts[n, 0:k] = the chosen candidates in ASCENDING CANDIDATE INDEX (torch.topk returns them sorted by score: the losses are
+ *   sums over the points, only their summation order differs);  pts[n, k:P] = rest[n].
+ *   Two launches: the keys of the candidates into `ws` (hipie_uncertain_points_ws_bytes(N, C) = N x C x 4 bytes), then a 4-pass radix
+ *   select and a ballot-ranked compaction per instance; no limit on k.  No floating-point atomics, grids that are functions of (N, C):
+ *   bit-reproducible from call to call.
+ * Refused (-22): k outside [0, min(C, P)], P or C >= 2^30, H*W outside [1, 2^31) with k > 0, null pointers (src, cand, ws may be null when
+ *     k == 0, rest when k == P), a workspace that is too small.  N == 0 or P == 0: returns 0 without a launch, null pointers allowed.
+ */
+int hipie_uncertain_points(const float* src, const float* cand, const float* rest, float* pts, void* ws, int64_t ws_bytes, int64_t N, int H,
+                           int W, int C, int P, int k, void* stream);
+int64_t hipie_uncertain_points_ws_bytes(int64_t N, int C);
+
+/*
+ * The point-sampled mask costs of the matchers (fp32, forward only).
+ * Replaces: batch_sigmoid_ce_loss + batch_dice_loss over point_sample (models/deformable_detr/matcher.py:22-69, 567-597;
+ *           models/maskdino/matcher.py:21-68): two grid_sample launches, the (Q, P) tensors softplus(-x), softplus(x) and sigmoid(x), the
+ *           (T, P) tensor 1 - t, three GEMMs and the broadcast arithmetic of the dice quotient.
+ *   pred (Q, H, W): mask logits.   tgt (T, Ht, Wt): target masks in [0, 1] at their own resolution.   coords (P, 2): (x, y) in [0, 1]^2,
+ *   the SAME points for every mask.   Sampling as in hipie_point_mask_loss_forward.   ce, dice (Q, T): the outputs.
+ *   With x = sample(pred[q]), t = sample(tgt[j]), s = sigmoid(x):
+ *     ce[q, j]   = (sum_p softplus(-x) t + softplus(x) (1 - t)) / P, computed as (sum_p softplus(x) - sum_p x t) / P
+ *     dice[q, j] = 1 - (2 sum_p s t + 1) / (sum_p s + sum_p t + 1)
+ *   Three launches: the targets are sampled once into `ws`; a workgroup per (4 queries, 2048 points) samples its queries into registers
+ *   (the Q x P samples are never written) and leaves its partial dot products in `ws`; a last kernel adds them in a fixed order.
+ *   ws: 16-byte aligned, at least hipie_mask_match_cost_ws_bytes(Q, T, P) bytes.  No atomics: bit-reproducible from call to call.
+ * Refused (-22): P outside [1, 2^30), H*W or Ht*Wt outside [1, 2^31), null pointers, a workspace that is too small or misaligned.
+ *     Q == 0 or T == 0: returns 0 without a launch, null pointers allowed.
+ */
+int hipie_mask_match_cost(const float* pred, const float* tgt, const float* coords, float* ce, float* dice, void* ws, int64_t ws_bytes, int64_t Q,
+                          int H, int W, int64_t T, int Ht, int Wt, int P, void* stream);
+int64_t hipie_mask_match_cost_ws_bytes(int64_t Q, int64_t T, int P);
+
+/*
  * hipie_vit_attn with the decomposed relative-position bias computed INSIDE the kernel from the (re-interpolated) tables
  * (get_rel_pos + add_decomposed_rel_pos, hipie/backbone/utils.py:63-125): bias_w[q, kx] = q . Rw[qx - kx + gw - 1] and
  * bias_h[q, ky] = q . Rh[qy - ky + gh - 1] are two MFMA products per wave in the prologue, so neither hipie_vit_relpos nor

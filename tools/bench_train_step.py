@@ -2,7 +2,7 @@
 """forward + backward time of ONE TRAINING STEP (hipie_amd/training/step.py) at the reference's training batch: ViT-H, 1024 x 1024, 2 images per
 GPU (configs/training/vit_huge_32g.yaml:1 -- 32 GPUs x 2), the 80-class caption, 8 synthetic targets per image (6 things, 2 stuff), DN_NUMBER 100,
 12544 mask points, random-init weights.  Prints ms for the forward (loss dictionary), the backward, and the peak memory.
-    python tools/bench_train_step.py [batch] [steps] [--hand-norms] [--fused-mlp] [--fused-windows] [--fused-losses]
+    python tools/bench_train_step.py [batch] [steps] [--hand-norms] [--fused-mlp] [--fused-windows] [--fused-losses] [--fused-criteria]
 --hand-norms: net.HipBackendNorms (the ViT / encoder LayerNorms on hipie_add_layernorm / hipie_layernorm_backward) instead of HipBackend
 --fused-mlp:  net.HipBackendMlp (the ViT MLPs / encoder FFNs as one autograd node, the activation recomputed by hipie_act_backward); with
               --hand-norms: net.HipBackendNormsMlp
@@ -10,6 +10,8 @@ GPU (configs/training/vit_huge_32g.yaml:1 -- 32 GPUs x 2), the 80-class caption,
               (all three: net.HipBackendAll)
 --fused-losses: net.HipBackendLosses (the point-sampled mask losses and the token focal loss of both criteria on hipie_point_mask_loss_* /
               hipie_token_focal_*); composes with the other three
+--fused-criteria: net.HipBackendCriteria (--fused-losses + the importance point selection of the criteria and the mask costs of the matchers on
+              hipie_uncertain_points / hipie_mask_match_cost); composes with the other three
 env: LIB_LINEAR=1 (library fp32 linears), PHASES=1 (synchronised forward phases), TORCH_PROF=1 (top kernels), HOSTPROF=1 (cProfile of a forward)"""
 import os
 import sys
@@ -47,8 +49,9 @@ def targets_for(batch, n_things, n_stuff, size, L, dev, seed=0):
 
 
 def main():
-    argv = [a for a in sys.argv[1:] if a not in ("--hand-norms", "--fused-mlp", "--fused-windows", "--fused-losses")]
-    fused_losses = "--fused-losses" in sys.argv[1:]
+    argv = [a for a in sys.argv[1:] if a not in ("--hand-norms", "--fused-mlp", "--fused-windows", "--fused-losses", "--fused-criteria")]
+    fused_criteria = "--fused-criteria" in sys.argv[1:]
+    fused_losses = "--fused-losses" in sys.argv[1:] and not fused_criteria
     hand_norms, fused_mlp, fused_windows = "--hand-norms" in sys.argv[1:], "--fused-mlp" in sys.argv[1:], "--fused-windows" in sys.argv[1:]
     B = int(argv[0]) if len(argv) > 0 else 2
     steps = int(argv[1]) if len(argv) > 1 else 3
@@ -77,6 +80,10 @@ def main():
     if fused_losses:                                         # the criteria were built with the default backend: hand them the new one
         step.be = net.HipBackendLosses if step.be is net.HipBackend else type(step.be.__name__ + "Losses", (step.be, net.HipBackendLosses), {})
         step.criterion.ops = step.md_criterion.ops = step.be
+    if fused_criteria:                                       # the criteria AND the matchers
+        step.be = net.HipBackendCriteria if step.be is net.HipBackend else type(step.be.__name__ + "Criteria", (step.be, net.HipBackendCriteria), {})
+        step.criterion.ops = step.md_criterion.ops = step.be
+        step.matcher.ops = step.matcher_bg.ops = step.md_criterion.matcher.ops = step.be
     if os.environ.get("LIB_LINEAR") == "1":                  # A/B: the big linears on the library instead of the split GEMM Function
 
         class LibBackend(step.be):
