@@ -969,6 +969,82 @@ def mask_match_cost(pred, tgt, coords, ws=None):
     return ce, dice
 
 
+OTA_MAX_Q, OTA_MAX_T, OTA_MAX_L = 4096, 256, 1024          # the limits of csrc/ota_match.hip (the match bitmap lives in LDS)
+
+
+def ota_match_ws_bytes(B, Q, Tmax):
+    return int(_lib.load().hipie_ota_match_ws_bytes(int(B), int(Q), int(Tmax)))
+
+
+def _layout_as(t, name, dtype, shape):
+    """refuses t unless it is a contiguous tensor of that dtype and shape (nothing is copied)"""
+    if t.dtype != dtype:
+        raise RuntimeError("%s must be %s, got %s" % (name, dtype, t.dtype))
+    if tuple(t.shape) != tuple(shape):
+        raise RuntimeError("%s must be %s, got %s" % (name, tuple(shape), tuple(t.shape)))
+    if not t.is_contiguous():
+        raise RuntimeError("%s tensor has to be contiguous" % name)
+
+
+def _ota_results(res, B, device):
+    """the (3, B) int32 block n_pairs | status | repair rounds of one matching call: the host reads it with one copy"""
+    if res is None:
+        return torch.zeros(3, B, dtype=torch.int32, device=device)
+    _layout_as(res, "res", torch.int32, (3, B))
+    return res
+
+
+@_timed("ota_cost")
+def ota_cost(logits, boxes, tgt_boxes, pos_map, n_tgt, center_radius=2.5, stride=32, ws=None, res=None):
+    """the SimOTA cost of a batch of images (hipie_ota_cost, fp32, no gradient): logits (B,Q,L) raw, boxes (B,Q,4) and tgt_boxes (B,Tmax,4)
+    cxcywh, pos_map (B,Tmax,L) uint8, n_tgt (B,) int32 -> (cost, iou, res): cost and iou (B,Tmax,Q), TARGET-major views of `ws`, as
+    matcher.ota_cost gives them transposed (+inf / 0 behind n_tgt[b]); res (3,B) int32 whose row 1 holds the status words (bit 0: a box with
+    x1 < x0 or y1 < y0, bit 1: a target without a positive token).  Bit-reproducible.
+    ws: uint8 tensor of at least ota_match_ws_bytes(B, Q, Tmax) elements, or None: allocated (it backs the two results).
+    Nothing is copied: a strided operand or one of another dtype is refused; the layout is checked before the device."""
+    _layout_f32(logits, "logits", 3)
+    _layout_f32(boxes, "boxes", 3)
+    _layout_f32(tgt_boxes, "tgt_boxes", 3)
+    B, Q, L = logits.shape
+    Tmax = tgt_boxes.shape[1]
+    _layout_as(boxes, "boxes", torch.float32, (B, Q, 4))
+    _layout_as(tgt_boxes, "tgt_boxes", torch.float32, (B, Tmax, 4))
+    _layout_as(pos_map, "pos_map", torch.uint8, (B, Tmax, L))
+    _layout_as(n_tgt, "n_tgt", torch.int32, (B,))
+    res = _ota_results(res, B, logits.device)
+    _on_device(logits=logits, boxes=boxes, tgt_boxes=tgt_boxes, pos_map=pos_map, n_tgt=n_tgt, ws=ws, res=res)
+    lib = _lib.load()
+    ws = _workspace(ws, int(lib.hipie_ota_match_ws_bytes(B, Q, Tmax)), logits.device, "ota_cost")
+    n = B * Tmax * Q * 4
+    cost, iou = ws[:n].view(torch.float32).view(B, Tmax, Q), ws[n:2 * n].view(torch.float32).view(B, Tmax, Q)
+    rc = lib.hipie_ota_cost(logits.data_ptr(), boxes.data_ptr(), tgt_boxes.data_ptr(), pos_map.data_ptr(), n_tgt.data_ptr(), cost.data_ptr(),
+                            iou.data_ptr(), res[1].data_ptr(), B, Q, Tmax, L, float(center_radius), float(stride), _stream())
+    _lib.check(rc, "hipie_ota_cost")
+    return cost, iou, res
+
+
+@_timed("ota_assign")
+def ota_assign(cost, iou, n_tgt, res=None):
+    """SimOTA's dynamic-k assignment (hipie_ota_assign, matcher.dynamic_k_assign with every tie at the lowest index) on the two (B,Tmax,Q)
+    buffers of ota_cost; `cost` is modified in place as the reference modifies it, up to its last +inf step -> (pair_q (B,Q), pair_t (B,Q),
+    best (B,Tmax), res): int32; image b's matched queries in ascending order are pair_q[b, :n] with the target of each in pair_t[b, :n],
+    n = res[0, b]; best[b, t] the matched query of target t with the smallest cost; res (3,B): n_pairs | status (bit 2: the repair loop was
+    stopped after Q rounds) | repair rounds.  One workgroup per image, bit-reproducible."""
+    _layout_f32(cost, "cost", 3)
+    B, Tmax, Q = cost.shape
+    _layout_as(iou, "iou", torch.float32, (B, Tmax, Q))
+    _layout_as(n_tgt, "n_tgt", torch.int32, (B,))
+    res = _ota_results(res, B, cost.device)
+    _on_device(cost=cost, iou=iou, n_tgt=n_tgt, res=res)
+    lib = _lib.load()
+    pairs = torch.empty(2, B, Q, dtype=torch.int32, device=cost.device)
+    best = torch.empty(B, Tmax, dtype=torch.int32, device=cost.device)
+    rc = lib.hipie_ota_assign(cost.data_ptr(), iou.data_ptr(), n_tgt.data_ptr(), pairs[0].data_ptr(), pairs[1].data_ptr(), best.data_ptr(),
+                              res[0].data_ptr(), res[1].data_ptr(), res[2].data_ptr(), B, Q, Tmax, _stream())
+    _lib.check(rc, "hipie_ota_assign")
+    return pairs[0], pairs[1], best, res
+
+
 @_timed("add_layernorm")
 def add_layernorm_sum(x, delta, weight, bias, eps, addend):
     """n = LayerNorm(x + delta) and n + addend, both in x's dtype, one launch (the encoder's post-norm + next `src + pos`)."""

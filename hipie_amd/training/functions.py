@@ -1,5 +1,7 @@
 """autograd Functions over the hand-written kernels that have a backward.  Forward and backward both run on
 libhipie_mi355.so; there is no CPU implementation (the ops raise on host tensors)."""
+import collections
+
 import torch
 
 from .. import ops
@@ -396,3 +398,55 @@ def mask_match_costs(pred, tgt, coords):
     workspace (the sampled targets and the partial sums) lives for the call."""
     ws = torch.empty(ops.mask_match_cost_ws_bytes(pred.shape[0], tgt.shape[0], coords.shape[0]), dtype=torch.uint8, device=pred.device)
     return ops.mask_match_cost(pred.detach().float().contiguous(), tgt.float().contiguous(), coords.float().contiguous(), ws=ws)
+
+
+OtaTargets = collections.namedtuple("OtaTargets", "tgt_boxes pos_map n_tgt counts")
+OTA_STATUS = ((1, "a box with x1 < x0 or y1 < y0"), (2, "a target without a positive token"), (4, "the repair loop did not end within Q rounds"))
+
+
+@torch.no_grad()
+def pack_ota_targets(targets, device):
+    """the targets of one step as hipie_ota_cost reads them, packed ONCE for all decoder levels: per-image dicts with "boxes" (T_i, 4) cxcywh
+    and "positive_map" (T_i, L) -> OtaTargets(tgt_boxes (B,Tmax,4) fp32 and pos_map (B,Tmax,L) uint8, zero behind T_i; n_tgt (B,) int32 on
+    the device; counts: the T_i as a host list).  Images without targets take no row; L is that of the maps (0 when no image has a map)."""
+    counts = [int(t["boxes"].shape[0]) for t in targets]
+    B, Tmax = len(targets), max(counts, default=0)
+    L = max((int(t["positive_map"].shape[1]) for t in targets if "positive_map" in t), default=0)
+    tgt_boxes = torch.zeros(B, Tmax, 4, dtype=torch.float32, device=device)
+    pos_map = torch.zeros(B, Tmax, L, dtype=torch.uint8, device=device)
+    for b, (t, n) in enumerate(zip(targets, counts)):
+        if n:
+            if t["positive_map"].shape != (n, L):
+                raise ValueError("pack_ota_targets: positive_map of image %d is %s, expected %s" % (b, tuple(t["positive_map"].shape), (n, L)))
+            tgt_boxes[b, :n] = t["boxes"].to(device)
+            pos_map[b, :n] = (t["positive_map"] != 0).to(device)
+    return OtaTargets(tgt_boxes, pos_map, torch.tensor(counts, dtype=torch.int32).to(device), counts)
+
+
+@torch.no_grad()
+def ota_match(logits, boxes, packed, center_radius=2.5, stride=32):
+    """HungarianMatcher.forward_ota on hipie_ota_cost + hipie_ota_assign: logits (B,Q,L), boxes (B,Q,4), packed = pack_ota_targets(...) ->
+    (pairs, best) in forward_ota's format: per image (query idx, target idx of each), int64 on the device, slices of the kernel's compacted
+    lists cut with the counts of ONE host copy; per image the best query of every target (images without targets: the empty pair and []).
+    Two launches for the batch.  A status bit raises ValueError (a degenerate box: the reference's assert; a target without a positive token;
+    a repair loop that does not end).  Shapes outside the kernels' limits (Q <= 4096, Tmax <= 256, L <= 1024): None, the torch path runs."""
+    B, Q, L = logits.shape
+    Tmax = packed.tgt_boxes.shape[1]
+    if len(packed.counts) != B or (Tmax and packed.pos_map.shape[2] != L):
+        raise ValueError("ota_match: targets packed for %d images and %d tokens, logits are %s" % (len(packed.counts), packed.pos_map.shape[2], tuple(logits.shape)))
+    dev = logits.device
+    if Q > ops.OTA_MAX_Q or Tmax > ops.OTA_MAX_T or L > ops.OTA_MAX_L:
+        return None
+    if Q == 0 or Tmax == 0:
+        e = torch.zeros(0, dtype=torch.int64, device=dev)
+        return [(e, e.clone()) for _ in range(B)], [[] if n == 0 else e.clone() for n in packed.counts]
+    cost, iou, res = ops.ota_cost(logits.detach().float().contiguous(), boxes.detach().float().contiguous(), packed.tgt_boxes, packed.pos_map, packed.n_tgt,
+                                  center_radius, stride)
+    pair_q, pair_t, best, res = ops.ota_assign(cost, iou, packed.n_tgt, res)
+    n_pairs, status, _ = res.cpu().tolist()                  # the one host read of the call
+    for b, s in enumerate(status):
+        if s:
+            raise ValueError("ota_match: image %d: %s" % (b, "; ".join(msg for bit, msg in OTA_STATUS if s & bit)))
+    pair_q, pair_t, best = pair_q.long(), pair_t.long(), best.long()
+    pairs = [(pair_q[b, :n], pair_t[b, :n]) for b, n in enumerate(n_pairs)]
+    return pairs, [best[b, :n] if n else [] for b, n in enumerate(packed.counts)]

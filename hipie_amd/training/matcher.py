@@ -150,7 +150,8 @@ def dynamic_k_assign(cost, iou):
 class HungarianMatcher(nn.Module):
     """weights: MatchWeights.  num_points: points of the mask costs (12544 = 112^2 in both heads).  stuff_takes_mean: the panoptic
     box handling (`panoptic_box_loss` / `panoptic_on`).  draw(shape, device) supplies uniform [0, 1) numbers (default torch.rand): the
-    reference draws ONE (1, num_points, 2) tensor per image, in batch order.  ops: see cost_matrix (the draws do not change)."""
+    reference draws ONE (1, num_points, 2) tensor per image, in batch order.  ops: see cost_matrix (the draws do not change) and
+    forward_ota."""
 
     def __init__(self, weights=None, num_points=112 * 112, stuff_takes_mean=True, draw=None, class_mode="auto", ops=None):
         super().__init__()
@@ -174,10 +175,24 @@ class HungarianMatcher(nn.Module):
             out.append(assign(C.reshape(logits.shape[1], -1)))
         return out
 
+    def pack_ota(self, targets, device):
+        """the targets as the `ota_match` op of `ops` reads them (one packing per step serves every decoder level), None without such an op"""
+        if getattr(self.ops, "ota_match", None) is None:
+            return None
+        return self.ops.pack_ota_targets(targets, device)
+
     @torch.no_grad()
-    def forward_ota(self, logits, boxes, targets):
+    def forward_ota(self, logits, boxes, targets, packed=None):
         """`forward_ota` (matcher.py:347-372; MODEL.DDETRS.OTA, on in the shipped configs): one-to-many SimOTA matching of the decoder
-        queries -> ([(query idx, target idx)] per image, [best query of every target] per image; images without targets: empty / [])."""
+        queries -> ([(query idx, target idx)] per image, [best query of every target] per image; images without targets: empty / []).
+        An `ops` object with ota_match(logits, boxes, packed) -> (pairs, best) | None (net.HipBackendMatching: functions.ota_match on
+        csrc/ota_match.hip) is asked first; packed: what pack_ota(targets, device) returned (None: packed here).  Without such an op, or
+        when it answers None (a shape outside its limits), the code below runs."""
+        op = getattr(self.ops, "ota_match", None)
+        if op is not None:
+            out = op(logits, boxes, packed if packed is not None else self.pack_ota(targets, logits.device))
+            if out is not None:
+                return out
         pairs, best = [], []
         prob = logits.sigmoid()
         for b, t in enumerate(targets):

@@ -8,7 +8,8 @@ hipie_add_layernorm / hipie_layernorm_backward; opt-in, HipBackendMlp: their MLP
 hipie_act_forward / hipie_act_backward; opt-in, HipBackendWindows: the attention of the windowed ViT blocks on
 hipie_attn_train_win_forward / _backward; opt-in, HipBackendLosses: the point-sampled mask losses and the token focal loss of the two
 criteria on hipie_point_mask_loss_* / hipie_token_focal_*; opt-in, HipBackendCriteria: on top of those the importance point selection of the
-criteria and the mask costs of the matchers on hipie_uncertain_points / hipie_mask_match_cost).
+criteria and the mask costs of the matchers on hipie_uncertain_points / hipie_mask_match_cost; opt-in, HipBackendMatching: on top of those
+the SimOTA matching of the foreground queries on hipie_ota_cost / hipie_ota_assign).
 
 Functional style over a dict ``sd`` of LIVE parameters (model.named_parameters() + buffers, reference key names), so gradients land in the
 model's own parameters.  Every function cites the reference code it follows.  Training-mode differences from the inference path:
@@ -170,6 +171,27 @@ class HipBackendCriteria(HipBackendLosses):
         """pred (Q,H,W), tgt (T,Ht,Wt), coords (P,2) -> (ce (Q,T), dice (Q,T)) of matcher.mask_costs"""
         from .functions import mask_match_costs
         return mask_match_costs(pred, tgt, coords)
+
+
+class HipBackendMatching(HipBackendCriteria):
+    """HipBackendCriteria + the one-to-many SimOTA matching of the foreground queries on csrc/ota_match.hip (functions.ota_match: the cost of
+    the whole batch from the raw logits and the dynamic-k assignment with its repair loop as two launches and one host read per decoder
+    level, instead of a Python loop over the images and the targets with a host wait each).  TrainStep packs the targets once per step
+    (functions.pack_ota_targets) and hands the backend to the matchers as their `ops`; HungarianMatcher.forward_ota asks it first and keeps
+    its torch path for shapes outside the kernels' limits.
+    Opt-in: TrainStep's default stays HipBackend; HipBackendCriteria and HipBackendAll do not include it."""
+
+    @staticmethod
+    def pack_ota_targets(targets, device):
+        """per-image target dicts -> functions.OtaTargets (padded boxes and positive maps, the counts on the device and on the host)"""
+        from .functions import pack_ota_targets
+        return pack_ota_targets(targets, device)
+
+    @staticmethod
+    def ota_match(logits, boxes, packed, center_radius=2.5, stride=32):
+        """logits (B,Q,L), boxes (B,Q,4), packed -> (pairs, best) of HungarianMatcher.forward_ota, or None outside the kernels' limits"""
+        from .functions import ota_match
+        return ota_match(logits, boxes, packed, center_radius, stride)
 
 
 # ------------------------------------------------------------------------------------------------ small helpers

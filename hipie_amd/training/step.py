@@ -53,8 +53,9 @@ class TrainStep:
         self.draws = draws or _Draws()
         # the opt-in loss kernels (net.HipBackendLosses): both criteria get the backend as their `ops` when it has the two methods
         loss_ops = self.be if getattr(self.be, "point_mask_loss", None) and getattr(self.be, "token_focal_sum", None) else None
-        # the opt-in mask-cost kernel (net.HipBackendCriteria): the matchers get the backend the same way
-        match_ops = self.be if getattr(self.be, "mask_match_costs", None) else None
+        # the opt-in mask-cost kernel (net.HipBackendCriteria) and SimOTA matching kernels (net.HipBackendMatching): the matchers get the
+        # backend the same way
+        match_ops = self.be if getattr(self.be, "mask_match_costs", None) or getattr(self.be, "ota_match", None) else None
         d = self.draws
         draw = lambda shape, device: d.rand(tuple(shape), device)          # noqa: E731
         self.dn_number, self.label_noise_ratio, self.box_noise_scale = dn_number, label_noise_ratio, box_noise_scale
@@ -166,6 +167,7 @@ class TrainStep:
         B = x.shape[0]
         groups = {k: dict(cls=[], box=[], msk=[], idx=[]) for k in ("fg", "bg", "gt")}
         ious = []
+        ota_targets = self.matcher.pack_ota(gt_fg, dev)                                 # once for all levels; None without the matching kernels
         for lvl in range(hs.shape[0]):
             reference = net.inverse_sigmoid(tr["init_ref"] if lvl == 0 else tr["inter_refs"][lvl - 1])
             cls = net.vl_align(hs[lvl], emb, sd, "detr.detr.class_embed.%d." % lvl)
@@ -192,7 +194,7 @@ class TrainStep:
             # foreground queries: one-to-many SimOTA matching, masks of the matched queries only (:553-590)
             g = groups["fg"]
             fcls, fbox = cls[:, start_fg:], box[:, start_fg:]
-            fidx, _ = self.matcher.forward_ota(fcls, fbox, gt_fg)
+            fidx, _ = self.matcher.forward_ota(fcls, fbox, gt_fg, packed=ota_targets)
             pts = torch.cat([(ref_fg[i].sigmoid()[:, :2] * scale[i][None])[pi.to(dev)] for i, (pi, _) in enumerate(fidx)], 0)
             prm = torch.cat([params[i, start_fg:][pi.to(dev)] for i, (pi, _) in enumerate(fidx)], 0)
             g["cls"].append(fcls)

@@ -407,6 +407,49 @@ int hipie_mask_match_cost(const float* pred, const float* tgt, const float* coor
 int64_t hipie_mask_match_cost_ws_bytes(int64_t Q, int64_t T, int P);
 
 /*
+ * The SimOTA cost of a batch of images (fp32, forward only).
+ * Replaces: the cost side of HungarianMatcherVL.forward_ota (hipie/models/deformable_detr/matcher.py:347-509: the sigmoid, the token
+ *           focal class cost against the positive map, generalized_box_iou with its host-side assert, the in-box / in-centre masks and the
+ *           two penalties), about forty launches and one host wait per image.
+ *   logits (B, Q, L): raw logits (the sigmoid is taken inside).   boxes (B, Q, 4), tgt_boxes (B, Tmax, 4): cxcywh.
+ *   pos_map (B, Tmax, L): uint8, non-zero = a positive token of the target.   n_tgt (B,): the targets of every image, the rest is padding.
+ *   cost, iou (B, Tmax, Q): the outputs, TARGET-major.  For t < n_tgt[b]:
+ *     cost = mean over the target's positive tokens (ascending) of the focal token cost - 3 x GIoU (the 1e-7 of box_ops.generalized_box_iou)
+ *            + 100 where the query centre is not both strictly inside the target box and within center_radius / stride of its centre
+ *            + 10000 on queries that are inside or near no target of their image;     iou = inter / union.
+ *     A target without a positive token gives NaN (the reference's mean over nothing).  For t >= n_tgt[b]: cost = +inf, iou = 0.
+ *   status (B,): written, not accumulated.  Bit 0: a query box or a target box of the image has x1 < x0 or y1 < y0 (the reference's assert);
+ *     bit 1: a target in front of n_tgt[b] has no positive token.
+ *   One launch; the token costs of a query row are computed once (LDS).  No atomics on memory: bit-reproducible from call to call.
+ * Refused (-22): Q > 4096, Tmax > 256, L outside [1, 1024], B > 65535, stride <= 0, null pointers.
+ *     B == 0, Q == 0 or Tmax == 0: returns 0 without a launch, null pointers allowed.
+ */
+int hipie_ota_cost(const float* logits, const float* boxes, const float* tgt_boxes, const unsigned char* pos_map, const int* n_tgt, float* cost,
+                   float* iou, int* status, int64_t B, int Q, int Tmax, int L, float center_radius, float stride, void* stream);
+
+/*
+ * SimOTA's dynamic-k assignment on the two buffers of hipie_ota_cost, one workgroup per image.
+ * Replaces: dynamic_k_matching (hipie/models/deformable_detr/matcher.py:347-509): per target a topk, an index-put and a host wait, the
+ *           host-side `while` of the repair loop and two nonzero.
+ *   cost (B, Tmax, Q): MODIFIED IN PLACE as the reference modifies it (+100000 on the rows that hold a match, once per repair round; the
+ *   reference's last step, +inf on everything unmatched, is not applied).   iou (B, Tmax, Q).   n_tgt (B,).
+ *   Target t takes its k_t cheapest queries, k_t = max(1, (int)(the sum of its min(Q, 10) largest IoUs, added in descending order)); a
+ *   query claimed by several targets keeps the cheapest; while a target is empty, every matched row gets +100000, every empty target takes
+ *   the arg-min of its column, and if a row then has several matches the rows that were contested BEFORE the loop (the reference re-uses
+ *   that mask) are reset to their current cheapest target.  Every tie goes to the lowest index.
+ *   pair_q, pair_t (B, Q): the matched queries of image b in ascending order and the first target of each, n_pairs[b] of them.
+ *   best (B, Tmax): per target the matched query of the smallest cost (0 behind n_tgt[b]).   rounds (B,): the repair rounds that ran.
+ *   status (B,): bit 2 is ORed in when the repair loop was stopped after Q rounds (the reference would not return).
+ *   n_tgt[b] == 0: n_pairs[b] = 0.  The only atomics are integer LDS atomics: bit-reproducible from call to call.
+ * Refused (-22): Q > 4096, Tmax > 256 (the match bitmap, Q x ceil(Tmax / 32) words, lives in LDS), null pointers.
+ *     B == 0, Q == 0 or Tmax == 0: returns 0 without a launch, null pointers allowed.
+ */
+int hipie_ota_assign(float* cost, const float* iou, const int* n_tgt, int* pair_q, int* pair_t, int* best, int* n_pairs, int* status, int* rounds,
+                     int64_t B, int Q, int Tmax, void* stream);
+/* bytes of the two (B, Tmax, Q) fp32 buffers, cost first (hipie/models/deformable_detr/matcher.py:347-509) */
+int64_t hipie_ota_match_ws_bytes(int64_t B, int64_t Q, int64_t Tmax);
+
+/*
  * hipie_vit_attn with the decomposed relative-position bias computed INSIDE the kernel from the (re-interpolated) tables
  * (get_rel_pos + add_decomposed_rel_pos, hipie/backbone/utils.py:63-125): bias_w[q, kx] = q . Rw[qx - kx + gw - 1] and
  * bias_h[q, ky] = q . Rh[qy - ky + gh - 1] are two MFMA products per wave in the prologue, so neither hipie_vit_relpos nor

@@ -2,7 +2,7 @@
 """forward + backward time of ONE TRAINING STEP (hipie_amd/training/step.py) at the reference's training batch: ViT-H, 1024 x 1024, 2 images per
 GPU (configs/training/vit_huge_32g.yaml:1 -- 32 GPUs x 2), the 80-class caption, 8 synthetic targets per image (6 things, 2 stuff), DN_NUMBER 100,
 12544 mask points, random-init weights.  Prints ms for the forward (loss dictionary), the backward, and the peak memory.
-    python tools/bench_train_step.py [batch] [steps] [--hand-norms] [--fused-mlp] [--fused-windows] [--fused-losses] [--fused-criteria]
+    python tools/bench_train_step.py [batch] [steps] [--hand-norms] [--fused-mlp] [--fused-windows] [--fused-losses] [--fused-criteria] [--fused-matching]
 --hand-norms: net.HipBackendNorms (the ViT / encoder LayerNorms on hipie_add_layernorm / hipie_layernorm_backward) instead of HipBackend
 --fused-mlp:  net.HipBackendMlp (the ViT MLPs / encoder FFNs as one autograd node, the activation recomputed by hipie_act_backward); with
               --hand-norms: net.HipBackendNormsMlp
@@ -12,7 +12,10 @@ GPU (configs/training/vit_huge_32g.yaml:1 -- 32 GPUs x 2), the 80-class caption,
               hipie_token_focal_*); composes with the other three
 --fused-criteria: net.HipBackendCriteria (--fused-losses + the importance point selection of the criteria and the mask costs of the matchers on
               hipie_uncertain_points / hipie_mask_match_cost); composes with the other three
-env: LIB_LINEAR=1 (library fp32 linears), PHASES=1 (synchronised forward phases), TORCH_PROF=1 (top kernels), HOSTPROF=1 (cProfile of a forward)"""
+--fused-matching: net.HipBackendMatching (--fused-criteria + the SimOTA matching of the foreground queries on hipie_ota_cost / hipie_ota_assign,
+              the targets packed once per step); composes with the other three
+env: LIB_LINEAR=1 (library fp32 linears), PHASES=1 (synchronised forward phases), TORCH_PROF=1 (top kernels), COUNTS=1 (device launches and host
+waits of one step), HOSTPROF=1 (cProfile of a forward)"""
 import os
 import sys
 import time
@@ -49,9 +52,10 @@ def targets_for(batch, n_things, n_stuff, size, L, dev, seed=0):
 
 
 def main():
-    argv = [a for a in sys.argv[1:] if a not in ("--hand-norms", "--fused-mlp", "--fused-windows", "--fused-losses", "--fused-criteria")]
-    fused_criteria = "--fused-criteria" in sys.argv[1:]
-    fused_losses = "--fused-losses" in sys.argv[1:] and not fused_criteria
+    argv = [a for a in sys.argv[1:] if a not in ("--hand-norms", "--fused-mlp", "--fused-windows", "--fused-losses", "--fused-criteria", "--fused-matching")]
+    fused_matching = "--fused-matching" in sys.argv[1:]
+    fused_criteria = "--fused-criteria" in sys.argv[1:] and not fused_matching
+    fused_losses = "--fused-losses" in sys.argv[1:] and not fused_criteria and not fused_matching
     hand_norms, fused_mlp, fused_windows = "--hand-norms" in sys.argv[1:], "--fused-mlp" in sys.argv[1:], "--fused-windows" in sys.argv[1:]
     B = int(argv[0]) if len(argv) > 0 else 2
     steps = int(argv[1]) if len(argv) > 1 else 3
@@ -82,6 +86,10 @@ def main():
         step.criterion.ops = step.md_criterion.ops = step.be
     if fused_criteria:                                       # the criteria AND the matchers
         step.be = net.HipBackendCriteria if step.be is net.HipBackend else type(step.be.__name__ + "Criteria", (step.be, net.HipBackendCriteria), {})
+        step.criterion.ops = step.md_criterion.ops = step.be
+        step.matcher.ops = step.matcher_bg.ops = step.md_criterion.matcher.ops = step.be
+    if fused_matching:                                       # the criteria, the matchers' mask costs and the SimOTA matching
+        step.be = net.HipBackendMatching if step.be is net.HipBackend else type(step.be.__name__ + "Matching", (step.be, net.HipBackendMatching), {})
         step.criterion.ops = step.md_criterion.ops = step.be
         step.matcher.ops = step.matcher_bg.ops = step.md_criterion.matcher.ops = step.be
     if os.environ.get("LIB_LINEAR") == "1":                  # A/B: the big linears on the library instead of the split GEMM Function
@@ -132,6 +140,26 @@ def main():
             total.backward()
             torch.cuda.synchronize()
         print(prof.key_averages().table(sort_by="cuda_time_total", row_limit=28, max_name_column_width=90))
+    if os.environ.get("COUNTS") == "1":                      # device launches (kernels, copies, fills) and host waits of one steady-state step
+        import warnings
+        from torch.autograd import DeviceType
+        from torch.profiler import ProfilerActivity, profile
+        model.zero_grad(set_to_none=True)
+        torch.cuda.synchronize()
+        torch.cuda.set_sync_debug_mode("warn")               # one warning per synchronising call
+        try:
+            with warnings.catch_warnings(record=True) as seen, profile(activities=[ProfilerActivity.CUDA]) as prof:
+                warnings.simplefilter("always")
+                with torch.enable_grad():
+                    total = sum(step.loss_dict(batch, targets).values())
+                n_fw = sum(1 for w in seen if "synchroniz" in str(w.message).lower())
+                total.backward()
+        finally:
+            torch.cuda.set_sync_debug_mode("default")
+        torch.cuda.synchronize()
+        n_all = sum(1 for w in seen if "synchroniz" in str(w.message).lower())
+        print("one step: %d device launches; host waits: %d in the forward, %d in the backward"
+              % (sum(1 for e in prof.events() if e.device_type == DeviceType.CUDA), n_fw, n_all - n_fw))
     if os.environ.get("HOSTPROF") == "1":                    # where the HOST time goes (the step is launch-bound on a slow host)
         import cProfile
         import io
