@@ -3,6 +3,9 @@
 //
 //     out[i,:] = softmax_j( clamp(scale * q_i.k_j) + bias_h[i, j / kw] + bias_w[i, j % kw] + mask_j ) . v_j
 //
+// A query with no attended key (every key of its batch item masked) gives zeros -- the contract of attn_f32.hip, attn_split.hip,
+// softmax_hl8.hip and the specialised kernels of bi_xattn.hip, so the answer does not depend on which kernel a length selects.
+//
 // Nothing of size Nq x Nk is ever written to HBM (the reference materialises the fp32 score tensor: 1.07 GB per image per
 // global block, backbone/vit.py:74-79; >= 4 tensors of (B*8, Nv, L) in fuse_helper.py:69-115).
 //
@@ -470,7 +473,7 @@ __global__ __launch_bounds__(WAVES * 64, ((WAVES == 8 || HD <= 80) && QB == 1) ?
 #pragma unroll
   for (int qb = 0; qb < QB; ++qb) {
     const float l_tot = LTRICK ? __shfl(O[qb][DB - 1][L_REG], li + 32 * L_HI) : l_run[qb] + __shfl_xor(l_run[qb], 32);
-    const float inv = 1.f / l_tot;
+    const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;      // no attended key: O = 0 and l = 0 -> zeros, not 0 * inf
     if (qi[qb] < p.Nq && p.out_f32) {
       float* orow = reinterpret_cast<float*>(p.out) + b * p.o_sb + h * p.o_sh + (long)qi[qb] * p.o_st;
 #pragma unroll

@@ -213,6 +213,7 @@ def msda_fused(value, spatial_shapes, level_start_index, ref, offsets, logits):
 def flash_attn(q, k, v, scale, bias_h=None, bias_w=None, key_mask=None, clamp=0.0, out_f32=False, k_hl8=False):
     """q (B,Nq,H,hd), k,v (B,Nk,H,hd) 16-bit (may be strided views with hd contiguous) -> (B,Nq,H*hd) in the operand dtype, or
     fp32 with out_f32.  bias_h (B*H,kh,Nq) / bias_w (B*H,Nq,kw) f32 decomposed rel-pos bias; key_mask (B,Nk) uint8/bool.
+    A query with no attended key (a batch item whose key_mask is all zero) gives zeros.
     k_hl8: k is a contiguous (B, Nk, 2*H*hd) fp16 HL8 buffer whose hi halves are the keys (read in place, HIPIE_K_HL8_HI)."""
     lib = _lib.load()
     B, Nq, H, hd = q.shape
@@ -495,7 +496,8 @@ _XA_WS = _Workspace()
 @_timed("bi_xattn")
 def bi_xattn(q, k, vv, vl, text_mask, clamp=50000.0, out_f32=False):
     """q, vv (B,Nv,H,hd); k, vl (B,L,H,hd) 16-bit contiguous; text_mask (B,L) -> out_v (B,Nv,H*hd), out_l (B,L,H*hd) (operand dtype,
-    or fp32 with out_f32: the generic flash kernel then runs both directions)."""
+    or fp32 with out_f32: the generic flash kernel then runs both directions).  A query with no attended key gives zeros: the out_v
+    rows of a batch item whose text_mask is all zero are zero at every L (whichever kernel the length selects); out_l has no mask."""
     lib = _lib.load()
     B, Nv, H, hd = q.shape
     L = k.shape[1]

@@ -132,6 +132,7 @@ int hipie_msda_fused_forward_strided(const void* value, int64_t value_row_stride
  *     out[b,i,h,:] = softmax_j( clamp(scale * q[b,i,h,:].k[b,j,h,:], +-clamp) + bias_h[bh,j / kw,i] + bias_w[bh,i,j % kw]
  *                               + (key_mask[b,j] ? 0 : -inf) ) . v[b,j,h,:]
  * with fp32 scores / softmax / accumulation, 16-bit MFMA operands, nothing of size Nq x Nk in HBM.
+ * A query with no attended key (key_mask all zero for its batch item) gives zeros, as in hipie_attn_f32 / hipie_attn_split.
  * q,k,v,out are addressed with explicit element strides (batch, token, head); head_dim contiguous.
  *   dtype      HIPIE_F16 or HIPIE_BF16 (q, k, v, out)
  *   head_dim   80 (ViT-H), 64 (ViT-B/L), 256 (VL fusion), 32

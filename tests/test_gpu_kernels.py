@@ -2,7 +2,11 @@
 against the reference-generated golden fixtures.  Tolerances are written next to each check:
   fp32 kernels (MSDA f32, dynamic mask, einsum precision 0/1): <= 2e-5 relative to the output scale;
   16-bit MFMA kernels: vs the oracle fed the SAME 16-bit-rounded inputs 1e-3 (fp16) / 8e-3 (bf16) -- the residual is the
-  rounding of P and of the output to 16 bit; vs the fp32 golden 2e-3 (fp16) / 2e-2 (bf16)."""
+  rounding of P and of the output to 16 bit; vs the fp32 golden 2e-3 (fp16) / 2e-2 (bf16).
+Per-branch float64 conformance files exist for csrc/msda.hip (tests/test_gpu_msda_forward.py) and for the 16-bit flash attention family,
+csrc/flash_attn.hip and csrc/bi_xattn.hip (tests/test_gpu_flash_attn.py: ops.flash_attn, vit_attn, vit_attn_fused, bi_xattn).  The other
+attention files -- attn_f32.hip, attn_split.hip, vit_attn.hip (vit_attn_rel), vit_attn_split.hip and the training kernels -- have no such
+file yet; the attention tests below are all they have."""
 import pytest
 import torch
 
