@@ -1,5 +1,5 @@
-// match_cost.h -- what the kernels of the matching costs share (ota_match.hip; the class and box costs of matcher.cost_matrix are the next
-// user), one definition each: the cxcywh -> xyxy corners, the pairwise box terms (intersection, union, GIoU with the 1e-7 of
+// match_cost.h -- what the kernels of the matching costs share (ota_match.hip: the SimOTA cost; hungarian_cost.hip: the class and box costs
+// of matcher.cost_matrix), one definition each: the cxcywh -> xyxy corners, the pairwise box terms (intersection, union, GIoU with the 1e-7 of
 // boxes.generalized_box_iou) and the focal token cost of matcher.focal_token_cost.  The operations and their order are those of the torch
 // formulation in fp32; floating-point contraction is off inside, so that no product is fused into the sum behind it.
 #pragma once

@@ -950,10 +950,12 @@ def mask_match_cost_ws_bytes(Q, T, P):
 
 
 @_timed("mask_match_cost")
-def mask_match_cost(pred, tgt, coords, ws=None):
+def mask_match_cost(pred, tgt, coords, ws=None, ce_out=None, dice_out=None):
     """the point-sampled mask costs of one matcher call (hipie_mask_match_cost, fp32, no gradient): pred (Q,H,W) logits, tgt (T,Ht,Wt) in
     [0,1] at its own resolution, coords (P,2) shared by all masks -> (ce (Q,T), dice (Q,T)) of matcher.mask_costs.  Bit-reproducible.
     ws: uint8 tensor of at least mask_match_cost_ws_bytes(Q, T, P) elements on a 16-byte boundary, or None: allocated for the call.
+    ce_out, dice_out: both None (the two results are allocated) or both contiguous fp32 (Q, T) tensors the results are written to and that
+    are returned -- views into a caller's buffer, e.g. an image's block of the packed costs of hungarian_cost.
     Nothing is copied: a strided or non-fp32 operand is refused; the layout is checked before the device."""
     _layout_f32(pred, "pred", 3)
     _layout_f32(tgt, "tgt", 3)
@@ -961,10 +963,15 @@ def mask_match_cost(pred, tgt, coords, ws=None):
     Q, T, P = pred.shape[0], tgt.shape[0], coords.shape[0]
     if coords.shape[1] != 2 or (P == 0 and Q * T > 0):
         raise RuntimeError("mask_match_cost: coords must be (P > 0, 2), got %s" % (tuple(coords.shape),))
-    _on_device(pred=pred, tgt=tgt, coords=coords, ws=ws)
+    if (ce_out is None) != (dice_out is None):
+        raise RuntimeError("mask_match_cost: ce_out and dice_out come together")
+    if ce_out is not None:
+        _layout_as(ce_out, "ce_out", torch.float32, (Q, T))
+        _layout_as(dice_out, "dice_out", torch.float32, (Q, T))
+    _on_device(pred=pred, tgt=tgt, coords=coords, ws=ws, ce_out=ce_out, dice_out=dice_out)
     lib = _lib.load()
     ws = _workspace(ws, int(lib.hipie_mask_match_cost_ws_bytes(Q, T, P)), pred.device, "mask_match_cost")
-    ce, dice = pred.new_empty(Q, T), pred.new_empty(Q, T)
+    ce, dice = (pred.new_empty(Q, T), pred.new_empty(Q, T)) if ce_out is None else (ce_out, dice_out)
     rc = lib.hipie_mask_match_cost(pred.data_ptr(), tgt.data_ptr(), coords.data_ptr(), ce.data_ptr(), dice.data_ptr(), ws.data_ptr(), ws.numel(),
                                    Q, pred.shape[1], pred.shape[2], T, tgt.shape[1], tgt.shape[2], P, _stream())
     _lib.check(rc, "hipie_mask_match_cost")
@@ -1045,6 +1052,101 @@ def ota_assign(cost, iou, n_tgt, res=None):
                               res[0].data_ptr(), res[1].data_ptr(), res[2].data_ptr(), B, Q, Tmax, _stream())
     _lib.check(rc, "hipie_ota_assign")
     return pairs[0], pairs[1], best, res
+
+
+HUNGARIAN_MAX_Q, HUNGARIAN_MAX_T, HUNGARIAN_MAX_L = 4096, 256, 1024          # the limits of csrc/hungarian_cost.hip (those of the SimOTA kernels)
+HUNGARIAN_STATUS = ((1, "a box with x1 < x0 or y1 < y0 (or a NaN)"), (8, "a label outside [0, L)"), (16, "the target offsets do not fit the packed output"))
+
+
+def hungarian_cost_ws_bytes(B, Q):
+    return int(_lib.load().hipie_hungarian_cost_ws_bytes(int(B), int(Q)))
+
+
+def _image_stride(t, name, row):
+    """the image stride of a fp32 (B, Q, row) tensor whose images are dense (a slice of the query dimension of a dense tensor is); nothing is copied"""
+    if t.dtype != torch.float32:
+        raise RuntimeError("%s must be torch.float32, got %s" % (name, t.dtype))
+    if t.dim() != 3 or t.shape[2] != row:
+        raise RuntimeError("%s must be (B, Q, %d), got %s" % (name, row, tuple(t.shape)))
+    B, Q = t.shape[:2]
+    if Q * row and (t.stride(2) != 1 or t.stride(1) != row or (B > 1 and t.stride(0) < Q * row)):
+        raise RuntimeError("%s tensor has to be dense within an image (strides %s)" % (name, tuple(t.stride())))
+    return t.stride(0) if B > 1 else Q * row
+
+
+@_timed("hungarian_cost")
+def hungarian_cost(logits, boxes, tgt_boxes, n_tgt, t_off, sum_t, weights, pos_map=None, labels=None, is_thing=None, ce=None, dice=None, with_boxes=True,
+                   stuff_takes_mean=True, out=None, ws=None):
+    """the cost matrices of a Hungarian matcher call for a batch of images (hipie_hungarian_cost, fp32, no gradient): logits (B,Q,L) raw, boxes
+    (B,Q,4) cxcywh (None with with_boxes=False; both may be slices of the query dimension of a dense tensor), tgt_boxes (B,Tmax,4), n_tgt and
+    t_off (B,) int32 (t_off: the exclusive prefix sum), sum_t: the host's total of n_tgt; weights: the five (cls, l1, giou, mask, dice);
+    exactly one of pos_map (B,Tmax,L) uint8 and labels (B,Tmax) int32; is_thing (B,Tmax) uint8 (needed with the stuff mean and the box costs);
+    ce, dice: None or the point-sampled mask costs, fp32 (Q * sum_t,), packed like the result
+    -> out, fp32 (Q * sum_t + B,): image b's costs are out[Q * t_off[b] : Q * (t_off[b] + n_tgt[b])].view(Q, n_tgt[b]) (QUERY-major, no
+    padding), and out[Q * sum_t:].view(torch.int32) holds the B status words (HUNGARIAN_STATUS) -- one copy carries both to the host.
+    out: such a tensor, or None: allocated.  ws: uint8 tensor of at least hungarian_cost_ws_bytes(B, Q) elements, or None: allocated when the
+    stuff mean needs it.  One launch, two with the stuff mean; bit-reproducible.
+    Nothing is copied: an operand of another dtype or layout, or a shape outside Q <= 4096, Tmax <= 256, 1 <= L <= 1024, B <= 65535, is
+    refused; the layout is checked before the device."""
+    ls = _image_stride(logits, "logits", logits.shape[2] if logits.dim() == 3 else 0)
+    B, Q, L = logits.shape
+    _layout_f32(tgt_boxes, "tgt_boxes", 3)
+    Tmax, sum_t = tgt_boxes.shape[1], int(sum_t)
+    _layout_as(tgt_boxes, "tgt_boxes", torch.float32, (B, Tmax, 4))
+    bs = 0
+    if with_boxes:
+        if boxes is None:
+            raise RuntimeError("hungarian_cost: boxes are needed with the box costs")
+        bs = _image_stride(boxes, "boxes", 4)
+        if tuple(boxes.shape) != (B, Q, 4):
+            raise RuntimeError("boxes must be %s, got %s" % ((B, Q, 4), tuple(boxes.shape)))
+    _layout_as(n_tgt, "n_tgt", torch.int32, (B,))
+    _layout_as(t_off, "t_off", torch.int32, (B,))
+    if (pos_map is None) == (labels is None):
+        raise RuntimeError("hungarian_cost: exactly one of pos_map and labels")
+    if pos_map is not None:
+        _layout_as(pos_map, "pos_map", torch.uint8, (B, Tmax, L))
+    else:
+        _layout_as(labels, "labels", torch.int32, (B, Tmax))
+    mean = bool(with_boxes and stuff_takes_mean)
+    if mean:
+        if is_thing is None:
+            raise RuntimeError("hungarian_cost: is_thing is needed with the stuff mean")
+        _layout_as(is_thing, "is_thing", torch.uint8, (B, Tmax))
+    if (ce is None) != (dice is None):
+        raise RuntimeError("hungarian_cost: ce and dice come together")
+    if not 0 <= sum_t <= B * Tmax:
+        raise RuntimeError("hungarian_cost: sum_t=%d outside [0, B x Tmax = %d]" % (sum_t, B * Tmax))
+    if ce is not None:
+        _layout_as(ce, "ce", torch.float32, (Q * sum_t,))
+        _layout_as(dice, "dice", torch.float32, (Q * sum_t,))
+    if Q > HUNGARIAN_MAX_Q or Tmax > HUNGARIAN_MAX_T or L > HUNGARIAN_MAX_L or (L < 1 and B * Q * Tmax > 0) or B > 65535:
+        raise RuntimeError("hungarian_cost: B=%d, Q=%d, Tmax=%d, L=%d outside B <= 65535, Q <= %d, Tmax <= %d, 1 <= L <= %d"
+                           % (B, Q, Tmax, L, HUNGARIAN_MAX_Q, HUNGARIAN_MAX_T, HUNGARIAN_MAX_L))
+    if out is not None:
+        _layout_as(out, "out", torch.float32, (Q * sum_t + B,))
+    _on_device(logits=logits, boxes=boxes if with_boxes else None, tgt_boxes=tgt_boxes, n_tgt=n_tgt, t_off=t_off, pos_map=pos_map, labels=labels,
+               is_thing=is_thing if mean else None, ce=ce, dice=dice, out=out, ws=ws)
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty(Q * sum_t + B, dtype=torch.float32, device=logits.device)
+    n = Q * sum_t
+    status = out[n:].view(torch.int32)
+    if B * Q * Tmax == 0:                                    # no launch: nothing to check either
+        status.zero_()
+        return out
+    if mean:
+        ws = _workspace(ws, int(lib.hipie_hungarian_cost_ws_bytes(B, Q)), logits.device, "hungarian_cost")
+    ptr = lambda t: None if t is None else t.data_ptr()          # noqa: E731
+    w = [float(x) for x in weights]
+    if len(w) != 5:
+        raise RuntimeError("hungarian_cost: five weights (cls, l1, giou, mask, dice), got %d" % len(w))
+    rc = lib.hipie_hungarian_cost(logits.data_ptr(), ls, ptr(boxes) if with_boxes else None, bs, tgt_boxes.data_ptr(), n_tgt.data_ptr(), t_off.data_ptr(),
+                                  ptr(pos_map), ptr(labels), ptr(is_thing) if mean else None, ptr(ce), ptr(dice), out.data_ptr() if n else None,
+                                  status.data_ptr(), ws.data_ptr() if mean else None, ws.numel() if mean else 0, B, Q, Tmax, L, sum_t, *w,
+                                  1 if with_boxes else 0, 1 if stuff_takes_mean else 0, _stream())
+    _lib.check(rc, "hipie_hungarian_cost")
+    return out
 
 
 @_timed("add_layernorm")

@@ -246,7 +246,12 @@ class DetCriterion(nn.Module):
                 if self.still_cls_for_encoder and "positive_map" in t:
                     t["positive_map"] = torch.ones(len(t["positive_map"]), 1, dtype=torch.bool, device=t["positive_map"].device)
                     enc["text_masks"] = None
-            idx = self.matcher.forward_boxes_only(enc["pred_logits"], enc["pred_boxes"], bin_targets)
+            pack = getattr(self.matcher, "pack", None)                                  # None without the Hungarian cost kernel (matcher `ops`)
+            packed = pack(bin_targets, enc["pred_logits"].device, masks=False) if pack else None
+            if packed is None:
+                idx = self.matcher.forward_boxes_only(enc["pred_logits"], enc["pred_boxes"], bin_targets)
+            else:
+                idx = self.matcher.forward_boxes_only(enc["pred_logits"], enc["pred_boxes"], bin_targets, packed=packed)
             for name in self.losses:
                 if name != "masks":
                     losses.update({k + "_enc": v for k, v in self._one(name, enc, bin_targets, idx, count).items()})
@@ -342,8 +347,10 @@ class MaskCriterion(nn.Module):
     def _one(self, name, out, targets, indices, count):
         return {"labels": self.loss_labels, "masks": self.loss_masks, "boxes": self.loss_boxes}[name](out, targets, indices, count)
 
-    def _match(self, out, targets):
-        return self.matcher(out["pred_logits"], out["pred_boxes"], targets, masks=out.get("pred_masks"))
+    def _match(self, out, targets, packed=None):
+        if packed is None:
+            return self.matcher(out["pred_logits"], out["pred_boxes"], targets, masks=out.get("pred_masks"))
+        return self.matcher(out["pred_logits"], out["pred_boxes"], targets, masks=out.get("pred_masks"), packed=packed)
 
     def forward(self, outputs, targets, mask_dict=None):
         """:370-463.  mask_dict (de-noising): {"output_known_lbs_bboxes": outputs of the de-noising part (+ "aux_outputs"), "scalar":
@@ -356,7 +363,9 @@ class MaskCriterion(nn.Module):
             if mask_dict["pad_size"] % groups:
                 raise ValueError("pad_size is not a multiple of the number of de-noising groups")
             dn_idx = dn_match_indices(targets, {"dn_num": groups, "single_padding": mask_dict["pad_size"] // groups}, dev)
-        idx = self._match(main, targets)
+        pack = getattr(self.matcher, "pack", None)                                      # the targets as the matcher's Hungarian cost kernel reads them,
+        packed = pack(targets, dev) if pack else None                                   # once for every output of this call; None without that kernel
+        idx = self._match(main, targets, packed)
         count = _target_count(targets, dev)
         losses = {}
         for name in self.losses:
@@ -374,13 +383,13 @@ class MaskCriterion(nn.Module):
         dn_part(known if use_dn else None, "")
         first = 0 if "interm_outputs" in outputs else 1
         for i, aux in enumerate(outputs.get("aux_outputs", ())):
-            aidx = self._match(aux, targets)
+            aidx = self._match(aux, targets, packed)
             for name in self.losses:
                 losses.update({k + "_%d" % i: v for k, v in self._one(name, aux, targets, aidx, count).items()})
             if i >= first:
                 dn_part(known["aux_outputs"][i] if use_dn else None, "_%d" % i)
         if "interm_outputs" in outputs:
-            iidx = self._match(outputs["interm_outputs"], targets)
+            iidx = self._match(outputs["interm_outputs"], targets, packed)
             for name in self.losses:
                 losses.update({k + "_interm": v for k, v in self._one(name, outputs["interm_outputs"], targets, iidx, count).items()})
         self._padded = None                                # the graph holds what it needs

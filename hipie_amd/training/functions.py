@@ -2,6 +2,7 @@
 libhipie_mi355.so; there is no CPU implementation (the ops raise on host tensors)."""
 import collections
 
+import numpy as np
 import torch
 
 from .. import ops
@@ -450,3 +451,103 @@ def ota_match(logits, boxes, packed, center_radius=2.5, stride=32):
     pair_q, pair_t, best = pair_q.long(), pair_t.long(), best.long()
     pairs = [(pair_q[b, :n], pair_t[b, :n]) for b, n in enumerate(n_pairs)]
     return pairs, [best[b, :n] if n else [] for b, n in enumerate(packed.counts)]
+
+
+MatchTargets = collections.namedtuple("MatchTargets", "tgt_boxes pos_map labels is_thing n_tgt t_off counts tgt_masks")
+
+
+@torch.no_grad()
+def pack_match_targets(targets, device, with_masks=True):
+    """the targets of a Hungarian matcher as hipie_hungarian_cost reads them, packed ONCE for many calls (every decoder level, every output of a
+    criterion call): per-image dicts with "boxes" (T_i, 4) cxcywh, "positive_map" (T_i, L) and / or "labels" (T_i,), optionally "is_thing"
+    (T_i,; absent: every target is a thing) and "masks" (T_i, H_i, W_i) -> MatchTargets(tgt_boxes (B,Tmax,4) fp32, pos_map (B,Tmax,L) uint8 or
+    None when no image has a map, labels (B,Tmax) int32 or None when an image with targets has none, is_thing (B,Tmax) uint8 -- all zero behind
+    T_i; n_tgt and t_off (B,) int32 on the device, t_off the exclusive prefix sum; counts: the T_i as a host list; tgt_masks: per image the
+    fp32 dense masks on the device, or None (with_masks=False, or an image with targets has none))."""
+    counts = [int(t["boxes"].shape[0]) for t in targets]
+    B, Tmax = len(targets), max(counts, default=0)
+    has_map = any("positive_map" in t for t in targets)
+    L = max((int(t["positive_map"].shape[1]) for t in targets if "positive_map" in t), default=0)
+    tgt_boxes = torch.zeros(B, Tmax, 4, dtype=torch.float32, device=device)
+    pos_map = torch.zeros(B, Tmax, L, dtype=torch.uint8, device=device) if has_map else None
+    has_labels = all("labels" in t for t, n in zip(targets, counts) if n)
+    labels = torch.zeros(B, Tmax, dtype=torch.int32, device=device) if has_labels else None
+    is_thing = torch.zeros(B, Tmax, dtype=torch.uint8, device=device)
+    for b, (t, n) in enumerate(zip(targets, counts)):
+        if n:
+            if has_map and (t.get("positive_map") is None or t["positive_map"].shape != (n, L)):
+                raise ValueError("pack_match_targets: positive_map of image %d is %s, expected %s"
+                                 % (b, None if t.get("positive_map") is None else tuple(t["positive_map"].shape), (n, L)))
+            tgt_boxes[b, :n] = t["boxes"].to(device)
+            if has_map:
+                pos_map[b, :n] = (t["positive_map"] != 0).to(device)
+            if has_labels:
+                labels[b, :n] = t["labels"].to(device)
+            is_thing[b, :n] = (t["is_thing"] != 0).to(device) if "is_thing" in t else 1
+    offs = [0]
+    for n in counts[:-1]:
+        offs.append(offs[-1] + n)
+    # one host -> device copy for the two count vectors
+    both = torch.tensor([counts, offs[:B]], dtype=torch.int32).to(device) if B else torch.zeros(2, 0, dtype=torch.int32, device=device)
+    tgt_masks = None
+    if with_masks and all("masks" in t for t, n in zip(targets, counts) if n):
+        tgt_masks = [t["masks"].to(device).float().contiguous() if n else None for t, n in zip(targets, counts)]
+    return MatchTargets(tgt_boxes, pos_map, labels, is_thing, both[0], both[1], counts, tgt_masks)
+
+
+@torch.no_grad()
+def hungarian_costs(logits, boxes, packed, w, masks=None, coords=None, stuff_takes_mean=True, with_boxes=True, class_mode="auto"):
+    """matcher.cost_matrix of every image of a batch on hipie_hungarian_cost (+ hipie_mask_match_cost per image with `masks`): logits (B,Q,L),
+    boxes (B,Q,4), packed = pack_match_targets(...), w: matcher.MatchWeights; masks: None or per image the (Q,H,W) mask logits, coords: then per
+    image the (P,2) points -> per image the (Q, T_i) cost matrix as a float32 numpy array on the HOST, views of ONE device -> host copy that
+    carries the costs of all images and their status words.  The mask costs of an image land directly in its block of the packed operands.
+    class_mode as matcher.class_cost: "map", "ids", or "auto" (the map when the targets have one).  A status bit raises ValueError and names the
+    image (a degenerate box: the ValueError of boxes.generalized_box_iou; a label outside [0, L)).  Shapes outside the kernel's limits
+    (Q <= 4096, Tmax <= 256, L <= 1024, B <= 65535): None, the torch path runs."""
+    B, Q, L = logits.shape
+    Tmax, sum_t = packed.tgt_boxes.shape[1], sum(packed.counts)
+    if len(packed.counts) != B:
+        raise ValueError("hungarian_costs: targets packed for %d images, logits are %s" % (len(packed.counts), tuple(logits.shape)))
+    use_map = packed.pos_map is not None if class_mode == "auto" else class_mode == "map"
+    if use_map and packed.pos_map is None:
+        raise KeyError("hungarian_costs: targets have no positive_map")
+    if not use_map and packed.labels is None:
+        raise KeyError("hungarian_costs: targets have no labels")
+    if use_map and Tmax and packed.pos_map.shape[2] != L:
+        raise ValueError("hungarian_costs: targets packed for %d tokens, logits are %s" % (packed.pos_map.shape[2], tuple(logits.shape)))
+    if masks is not None and packed.tgt_masks is None:
+        raise KeyError("hungarian_costs: targets were packed without masks")
+    if Q > ops.HUNGARIAN_MAX_Q or Tmax > ops.HUNGARIAN_MAX_T or L > ops.HUNGARIAN_MAX_L or L < 1 or B > 65535:
+        return None
+    if B == 0 or Q == 0 or sum_t == 0:
+        return [np.zeros((Q, n), dtype=np.float32) for n in packed.counts]
+    dev = logits.device
+
+    def images(t, row):                       # a slice of the query dimension keeps its images dense: no copy
+        t = t.detach()
+        if t.dtype != torch.float32:
+            t = t.float()
+        return t if t.stride(2) == 1 and t.stride(1) == row and (B == 1 or t.stride(0) >= Q * row) else t.contiguous()
+    offs = [0]
+    for n in packed.counts[:-1]:
+        offs.append(offs[-1] + n)
+    ce = dice = None
+    if masks is not None:
+        both = torch.empty(2, Q * sum_t, dtype=torch.float32, device=dev)
+        ce, dice = both[0], both[1]
+        for b, n in enumerate(packed.counts):
+            if n:
+                pred, pts = masks[b].detach().float().contiguous(), coords[b].float().contiguous()
+                ws = torch.empty(ops.mask_match_cost_ws_bytes(Q, n, pts.shape[0]), dtype=torch.uint8, device=dev)
+                lo, hi = Q * offs[b], Q * (offs[b] + n)
+                ops.mask_match_cost(pred, packed.tgt_masks[b], pts, ws=ws, ce_out=ce[lo:hi].view(Q, n), dice_out=dice[lo:hi].view(Q, n))
+    out = ops.hungarian_cost(images(logits, L), images(boxes, 4) if with_boxes else None, packed.tgt_boxes, packed.n_tgt, packed.t_off, sum_t,
+                             (w.cls, w.l1, w.giou, w.mask, w.dice), pos_map=packed.pos_map if use_map else None,
+                             labels=None if use_map else packed.labels, is_thing=packed.is_thing, ce=ce, dice=dice, with_boxes=with_boxes,
+                             stuff_takes_mean=stuff_takes_mean)
+    host = out.cpu().numpy()                                  # the one host read of the call: the costs and the status words
+    status = host[Q * sum_t:].view(np.int32)
+    for b, s in enumerate(status.tolist()):
+        if s:
+            raise ValueError("hungarian_costs: image %d: %s" % (b, "; ".join(msg for bit, msg in ops.HUNGARIAN_STATUS if s & bit)))
+    return [host[Q * o:Q * (o + n)].reshape(Q, n) for o, n in zip(offs, packed.counts)]

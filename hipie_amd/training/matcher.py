@@ -7,7 +7,9 @@
 * MaskDINO's ``HungarianMatcher`` (hipie/models/maskdino/matcher.py:76-259): the same costs with class ids or positive maps.
 
 One cost routine serves all of them.  The cost matrix is built on the tensors' device (one image at a time, like the reference); the
-linear sum assignment itself runs on the host in scipy, as in the reference (``C.cpu()`` -> ``linear_sum_assignment``)."""
+linear sum assignment itself runs on the host in scipy, as in the reference (``C.cpu()`` -> ``linear_sum_assignment``).  Opt-in, an `ops`
+object with ``hungarian_costs`` (net.HipBackendHungarian) builds the cost matrices of the whole batch in one kernel call and hands scipy
+slices of one host copy."""
 from dataclasses import dataclass
 
 import torch
@@ -97,6 +99,13 @@ def assign(C):
     return torch.as_tensor(i, dtype=torch.int64), torch.as_tensor(j, dtype=torch.int64)
 
 
+def assign_host(C):
+    """`assign` for a (Q, T) cost matrix that already is a host array (a slice of the one copy of functions.hungarian_costs)"""
+    from scipy.optimize import linear_sum_assignment
+    i, j = linear_sum_assignment(C)
+    return torch.as_tensor(i, dtype=torch.int64), torch.as_tensor(j, dtype=torch.int64)
+
+
 def ota_cost(prob, boxes, target, center_radius=2.5, stride=32):
     """SimOTA cost of one image for a DETR-style query set (matcher.py:374-403, 405-446): class cost + 3 x (-GIoU), +100 where the query
     centre is not BOTH inside the target box and within `center_radius / stride` (normalised units) of its centre, +10000 on queries
@@ -150,8 +159,8 @@ def dynamic_k_assign(cost, iou):
 class HungarianMatcher(nn.Module):
     """weights: MatchWeights.  num_points: points of the mask costs (12544 = 112^2 in both heads).  stuff_takes_mean: the panoptic
     box handling (`panoptic_box_loss` / `panoptic_on`).  draw(shape, device) supplies uniform [0, 1) numbers (default torch.rand): the
-    reference draws ONE (1, num_points, 2) tensor per image, in batch order.  ops: see cost_matrix (the draws do not change) and
-    forward_ota."""
+    reference draws ONE (1, num_points, 2) tensor per image, in batch order.  ops: see cost_matrix (the draws do not change),
+    forward (`hungarian_costs`) and forward_ota."""
 
     def __init__(self, weights=None, num_points=112 * 112, stuff_takes_mean=True, draw=None, class_mode="auto", ops=None):
         super().__init__()
@@ -164,14 +173,40 @@ class HungarianMatcher(nn.Module):
         self.stuff_takes_mean = stuff_takes_mean
         self.draw = draw or (lambda shape, device: torch.rand(shape, device=device))
 
+    def pack(self, targets, device, masks=True):
+        """the targets as the `hungarian_costs` op of `ops` reads them (one packing serves every decoder level / every output of a criterion
+        call; masks=False leaves the target masks out: a caller without mask costs), None without such an op"""
+        if getattr(self.ops, "hungarian_costs", None) is None:
+            return None
+        return self.ops.pack_match_targets(targets, device, masks)
+
+    def _batched(self, logits, boxes, targets, packed, masks, coords, stuff_takes_mean, with_boxes):
+        """[(query idx, target idx)] per image through the `hungarian_costs` op of `ops` (net.HipBackendHungarian: functions.hungarian_costs on
+        csrc/hungarian_cost.hip -- the costs of the whole batch, ONE device -> host copy, scipy on host slices), or None: no such op, mask
+        costs without a `mask_match_costs` op beside it, or the op declined (a shape outside its limits)"""
+        op = getattr(self.ops, "hungarian_costs", None)
+        if op is None or (masks is not None and getattr(self.ops, "mask_match_costs", None) is None):
+            return None
+        if packed is None:
+            packed = self.pack(targets, logits.device, masks is not None)
+        Cs = op(logits, boxes, packed, self.w, masks, coords, stuff_takes_mean, with_boxes, self.class_mode)
+        return None if Cs is None else [assign_host(C) for C in Cs]
+
     @torch.no_grad()
-    def forward(self, logits, boxes, targets, masks=None, costs=("cls", "box", "mask")):
-        """logits (B, Q, L), boxes (B, Q, 4), masks None | per-image sequence of (Q, H, W) -> [(query idx, target idx)] per image."""
+    def forward(self, logits, boxes, targets, masks=None, costs=("cls", "box", "mask"), packed=None):
+        """logits (B, Q, L), boxes (B, Q, 4), masks None | per-image sequence of (Q, H, W) -> [(query idx, target idx)] per image.
+        The draws come first, one (1, num_points, 2) per image in batch order, before any cost.  An `ops` object with hungarian_costs is asked
+        then (packed: what pack(targets, device) returned; None: packed here); without one, or when it answers None, the loop below runs."""
+        use_masks = masks is not None and "mask" in costs
+        coords = [self.draw((1, self.num_points, 2), logits.device)[0] for _ in targets] if use_masks else None
+        out = self._batched(logits, boxes, targets, packed, masks if use_masks else None, coords, self.stuff_takes_mean, "box" in costs)
+        if out is not None:
+            return out
         out = []
         for b, tgt in enumerate(targets):
-            m = masks[b] if (masks is not None and "mask" in costs) else None
-            coords = self.draw((1, self.num_points, 2), logits.device)[0] if m is not None else None
-            C = cost_matrix(logits[b], boxes[b], tgt, self.w, m, coords, self.stuff_takes_mean, "box" in costs, self.class_mode, self.ops)
+            m = masks[b] if use_masks else None
+            C = cost_matrix(logits[b], boxes[b], tgt, self.w, m, coords[b] if use_masks else None, self.stuff_takes_mean, "box" in costs, self.class_mode,
+                            self.ops)
             out.append(assign(C.reshape(logits.shape[1], -1)))
         return out
 
@@ -207,6 +242,9 @@ class HungarianMatcher(nn.Module):
         return pairs, best
 
     @torch.no_grad()
-    def forward_boxes_only(self, logits, boxes, targets):
-        """the `force_box_loss` entry (matcher.py:640-729): class + L1 + GIoU, stuff targets keep their own box costs."""
+    def forward_boxes_only(self, logits, boxes, targets, packed=None):
+        """the `force_box_loss` entry (matcher.py:640-729): class + L1 + GIoU, stuff targets keep their own box costs.  packed: see forward."""
+        out = self._batched(logits, boxes, targets, packed, None, None, False, True)
+        if out is not None:
+            return out
         return [assign(cost_matrix(logits[b], boxes[b], t, self.w, stuff_takes_mean=False, class_mode=self.class_mode)) for b, t in enumerate(targets)]

@@ -9,7 +9,8 @@ hipie_act_forward / hipie_act_backward; opt-in, HipBackendWindows: the attention
 hipie_attn_train_win_forward / _backward; opt-in, HipBackendLosses: the point-sampled mask losses and the token focal loss of the two
 criteria on hipie_point_mask_loss_* / hipie_token_focal_*; opt-in, HipBackendCriteria: on top of those the importance point selection of the
 criteria and the mask costs of the matchers on hipie_uncertain_points / hipie_mask_match_cost; opt-in, HipBackendMatching: on top of those
-the SimOTA matching of the foreground queries on hipie_ota_cost / hipie_ota_assign).
+the SimOTA matching of the foreground queries on hipie_ota_cost / hipie_ota_assign; opt-in, HipBackendHungarian: on top of those the cost
+matrices of the one-to-one Hungarian matchers on hipie_hungarian_cost).
 
 Functional style over a dict ``sd`` of LIVE parameters (model.named_parameters() + buffers, reference key names), so gradients land in the
 model's own parameters.  Every function cites the reference code it follows.  Training-mode differences from the inference path:
@@ -192,6 +193,27 @@ class HipBackendMatching(HipBackendCriteria):
         """logits (B,Q,L), boxes (B,Q,4), packed -> (pairs, best) of HungarianMatcher.forward_ota, or None outside the kernels' limits"""
         from .functions import ota_match
         return ota_match(logits, boxes, packed, center_radius, stride)
+
+
+class HipBackendHungarian(HipBackendMatching):
+    """HipBackendMatching + the cost matrices of the one-to-one Hungarian matchers on csrc/hungarian_cost.hip (functions.hungarian_costs: the
+    class, box and stuff-mean costs of the whole batch as one or two launches on top of the three mask-cost launches per image, ONE device ->
+    host copy per matcher call, scipy on host slices of it -- instead of about forty launches and two host waits per image).  TrainStep packs
+    the background targets once per step and the criteria pack theirs once per call (functions.pack_match_targets); HungarianMatcher.forward /
+    forward_boxes_only ask the backend first and keep their torch loop for shapes outside the kernel's limits.
+    Opt-in: TrainStep's default stays HipBackend; HipBackendMatching and HipBackendAll do not include it."""
+
+    @staticmethod
+    def pack_match_targets(targets, device, with_masks=True):
+        """per-image target dicts -> functions.MatchTargets (padded boxes, positive maps / labels, is_thing, counts and offsets, fp32 masks)"""
+        from .functions import pack_match_targets
+        return pack_match_targets(targets, device, with_masks)
+
+    @staticmethod
+    def hungarian_costs(logits, boxes, packed, w, masks=None, coords=None, stuff_takes_mean=True, with_boxes=True, class_mode="auto"):
+        """logits (B,Q,L), boxes (B,Q,4), packed -> per image the (Q, T_i) cost matrix on the host, or None outside the kernel's limits"""
+        from .functions import hungarian_costs
+        return hungarian_costs(logits, boxes, packed, w, masks, coords, stuff_takes_mean, with_boxes, class_mode)
 
 
 # ------------------------------------------------------------------------------------------------ small helpers

@@ -53,9 +53,10 @@ class TrainStep:
         self.draws = draws or _Draws()
         # the opt-in loss kernels (net.HipBackendLosses): both criteria get the backend as their `ops` when it has the two methods
         loss_ops = self.be if getattr(self.be, "point_mask_loss", None) and getattr(self.be, "token_focal_sum", None) else None
-        # the opt-in mask-cost kernel (net.HipBackendCriteria) and SimOTA matching kernels (net.HipBackendMatching): the matchers get the
-        # backend the same way
-        match_ops = self.be if getattr(self.be, "mask_match_costs", None) or getattr(self.be, "ota_match", None) else None
+        # the opt-in mask-cost kernel (net.HipBackendCriteria), SimOTA matching kernels (net.HipBackendMatching) and Hungarian cost kernel
+        # (net.HipBackendHungarian): the matchers get the backend the same way
+        match_ops = self.be if (getattr(self.be, "mask_match_costs", None) or getattr(self.be, "ota_match", None)
+                                or getattr(self.be, "hungarian_costs", None)) else None
         d = self.draws
         draw = lambda shape, device: d.rand(tuple(shape), device)          # noqa: E731
         self.dn_number, self.label_noise_ratio, self.box_noise_scale = dn_number, label_noise_ratio, box_noise_scale
@@ -168,6 +169,7 @@ class TrainStep:
         groups = {k: dict(cls=[], box=[], msk=[], idx=[]) for k in ("fg", "bg", "gt")}
         ious = []
         ota_targets = self.matcher.pack_ota(gt_fg, dev)                                 # once for all levels; None without the matching kernels
+        bg_targets = self.matcher_bg.pack(gt_bg, dev)                                   # the same for the background matcher; None without the Hungarian cost kernel
         for lvl in range(hs.shape[0]):
             reference = net.inverse_sigmoid(tr["init_ref"] if lvl == 0 else tr["inter_refs"][lvl - 1])
             cls = net.vl_align(hs[lvl], emb, sd, "detr.detr.class_embed.%d." % lvl)
@@ -186,7 +188,7 @@ class TrainStep:
             g = groups["bg"]
             bcls, bbox = cls[:, start_bg:start_fg], box[:, start_bg:start_fg]
             m = self.dyn_masks(mask_feats, ref_fg[:, start_bg:start_fg, :2].reshape(B * nbg, 2), params[:, start_bg:start_fg].reshape(B * nbg, -1), [nbg] * B)
-            bidx = self.matcher_bg(bcls, bbox, gt_bg, masks=[mm[0, :, 0] for mm in m], costs=("cls", "mask"))
+            bidx = self.matcher_bg(bcls, bbox, gt_bg, masks=[mm[0, :, 0] for mm in m], costs=("cls", "mask"), packed=bg_targets)
             g["cls"].append(bcls)
             g["box"].append(bbox)
             g["msk"].append([mm[:, ids.to(dev)] for (ids, _), mm in zip(bidx, m)])

@@ -451,6 +451,46 @@ int hipie_ota_assign(float* cost, const float* iou, const int* n_tgt, int* pair_
 int64_t hipie_ota_match_ws_bytes(int64_t B, int64_t Q, int64_t Tmax);
 
 /*
+ * The cost matrices of the one-to-one Hungarian matchers for a whole batch (fp32, forward only).
+ * Replaces: the cost side of HungarianMatcherVL.forward / forward with force_box_loss (models/deformable_detr/matcher.py:511-729) and of
+ *           MaskDINO's HungarianMatcher (models/maskdino/matcher.py:76-259), per image: the sigmoid, the element-wise passes of the focal
+ *           token cost, the matmul with the positive map (or the column gather by class id), cdist, generalized_box_iou with its host-side
+ *           assert, the index puts of the stuff mean, two nan_to_num and the weighted sums -- about forty launches and a host wait.
+ *   logits (B, Q, L): raw logits (the sigmoid is taken inside); image b starts at element b * logits_stride, its (Q, L) rows are dense.
+ *   boxes (B, Q, 4): cxcywh, image stride boxes_stride; tgt_boxes (B, Tmax, 4).  Both may be null when with_boxes == 0.
+ *   n_tgt (B,): the targets of every image, the rest is padding.   t_off (B,): the exclusive prefix sum of n_tgt.   sum_t: their total.
+ *   The class side is exactly one of   pos_map (B, Tmax, L): uint8, non-zero = a positive token of the target (map mode), and
+ *                                      labels (B, Tmax): int32, the class cost is the token cost of column labels[t] (ids mode).
+ *   is_thing (B, Tmax): uint8, read only with with_boxes && stuff_takes_mean.
+ *   ce, dice: both null, or both packed exactly like C and holding the point-sampled mask costs (hipie_mask_match_cost writes them there).
+ *   C: the output, PACKED and QUERY-major: image b is a dense row-major (Q, n_tgt[b]) block starting at element Q * t_off[b]; Q * sum_t
+ *   elements in all, no padding columns, an image without targets takes none.  In the order of matcher.cost_matrix:
+ *     cls = the sum over the target's positive tokens (ascending) of the focal token cost / their count (none: NaN, the reference's mean
+ *           over nothing; scipy refuses the matrix as it does today)            l1 = the sum of the four |differences|         gi = -GIoU
+ *     with stuff_takes_mean: every non-thing column of l1 takes the mean of l1 over all Q x thing entries of its image, the same for gi;
+ *           then every NaN of l1 and gi becomes 0 and infinities stay (an image without things gets 0).  Without it nothing is zeroed.
+ *     C = (((w_cls cls + w_l1 l1) + w_giou gi) + w_mask ce) + w_dice dice, the box terms and the mask terms left out when absent.
+ *   status (B,): written, not accumulated.  Bit 0: with_boxes and a query or target box of the image has a corner pair out of order or a
+ *     NaN (the ValueError of boxes.generalized_box_iou); bit 3: ids mode and a label outside [0, L) (its column is NaN); bit 4: t_off[b] +
+ *     n_tgt[b] does not fit sum_t (nothing of the image is written).
+ *   One launch; with the stuff mean a pre-pass leaves float64 partial sums per 64 queries in `ws` (8-byte aligned, at least
+ *   hipie_hungarian_cost_ws_bytes(B, Q) bytes; may be null otherwise) and every workgroup adds them in the same order.  No floating-point
+ *   atomics, grids are functions of (B, Q): bit-reproducible from call to call.
+ * Refused (-22): Q > 4096, Tmax > 256, L outside [1, 1024], B > 65535, sum_t > B x Tmax, both or neither of pos_map / labels, one of ce /
+ *     dice alone, an image stride below a dense image, null pointers, a workspace that is too small or misaligned.
+ *     B == 0, Q == 0 or Tmax == 0: returns 0 without a launch, null pointers allowed.
+ */
+int hipie_hungarian_cost(const float* logits, int64_t logits_stride, const float* boxes, int64_t boxes_stride, const float* tgt_boxes,
+                         const int* n_tgt, const int* t_off, const unsigned char* pos_map, const int* labels, const unsigned char* is_thing,
+                         const float* ce, const float* dice, float* C, int* status, void* ws, int64_t ws_bytes, int64_t B, int Q, int Tmax,
+                         int L, int64_t sum_t, float w_cls, float w_l1, float w_giou, float w_mask, float w_dice, int with_boxes,
+                         int stuff_takes_mean, void* stream);
+/* bytes of the packed output, Q * sum_t fp32 elements */
+int64_t hipie_hungarian_cost_bytes(int64_t Q, int64_t sum_t);
+/* bytes of the stuff mean's partial sums */
+int64_t hipie_hungarian_cost_ws_bytes(int64_t B, int64_t Q);
+
+/*
  * hipie_vit_attn with the decomposed relative-position bias computed INSIDE the kernel from the (re-interpolated) tables
  * (get_rel_pos + add_decomposed_rel_pos, hipie/backbone/utils.py:63-125): bias_w[q, kx] = q . Rw[qx - kx + gw - 1] and
  * bias_h[q, ky] = q . Rh[qy - ky + gh - 1] are two MFMA products per wave in the prologue, so neither hipie_vit_relpos nor
