@@ -60,6 +60,8 @@ SIGNATURES = {
     "hipie_hungarian_cost": [c_p, c_l, c_p, c_l] + [c_p] * 11 + [c_l, c_l, c_i, c_i, c_i, c_l] + [c_f] * 5 + [c_i, c_i, c_p],
     "hipie_hungarian_cost_bytes": [c_l, c_l],
     "hipie_hungarian_cost_ws_bytes": [c_l, c_l],
+    "hipie_hungarian_assign": [c_p] * 8 + [c_l, c_l, c_i, c_i, c_l, c_p],
+    "hipie_hungarian_assign_ws_bytes": [c_l, c_l],
     "hipie_add_layernorm_sum": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_f, c_i, c_i, c_i, c_p],
     "hipie_add_layernorm_rows": [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_f, c_i, c_i, c_i, c_p, c_p, c_p],
     "hipie_batched_nms": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_i, c_p],
@@ -138,7 +140,7 @@ def load():
                                                       "hipie_layernorm_backward_ws_bytes", "hipie_act_backward_ws_bytes", "hipie_point_mask_loss_ws_bytes",
                                                       "hipie_token_focal_ws_bytes", "hipie_uncertain_points_ws_bytes",
                                                       "hipie_mask_match_cost_ws_bytes", "hipie_ota_match_ws_bytes", "hipie_hungarian_cost_bytes",
-                                                      "hipie_hungarian_cost_ws_bytes") else ctypes.c_int)
+                                                      "hipie_hungarian_cost_ws_bytes", "hipie_hungarian_assign_ws_bytes") else ctypes.c_int)
     _lib = lib
     return lib
 

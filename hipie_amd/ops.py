@@ -1149,6 +1149,51 @@ def hungarian_cost(logits, boxes, tgt_boxes, n_tgt, t_off, sum_t, weights, pos_m
     return out
 
 
+# the status words of hungarian_assign: the cost kernel's bits carried over, and the solver's own (the first two are scipy's messages)
+HUNGARIAN_STATUS = HUNGARIAN_STATUS + ((32, "matrix contains invalid numeric entries"), (64, "cost matrix is infeasible"),
+                                       (128, "the search of a row did not end within min(Q, T) columns"))
+
+
+def hungarian_assign_ws_bytes(Q, sum_t):
+    return int(_lib.load().hipie_hungarian_assign_ws_bytes(int(Q), int(sum_t)))
+
+
+@_timed("hungarian_assign")
+def hungarian_assign(costs, n_tgt, t_off, sum_t, Q, Tmax, ws=None):
+    """the one-to-one assignment of every image of a batch on the device (hipie_hungarian_assign: scipy.optimize.linear_sum_assignment's
+    pairs, tie for tie): costs fp32 (Q * sum_t + B,), what hungarian_cost returns -- image b's (Q, n_tgt[b]) block query-major at element
+    Q * t_off[b], the B status words of the cost kernel behind the blocks; n_tgt, t_off (B,) int32; sum_t, Q, Tmax: host integers
+    -> (pair_q, pair_t, status): pair_q, pair_t (B, K) int64 with K = min(Q, Tmax), image b's pairs in its first min(Q, n_tgt[b]) entries in
+    ascending query order and 0 behind them; status (B,) int32 (HUNGARIAN_STATUS): the cost kernel's bits carried over, 32: a NaN or -inf in the
+    block, 64: infeasible, 128: the iteration cap.  An image with a non-zero status has all-zero pairs.  Nothing is read by the host.
+    ws: uint8 tensor of at least hungarian_assign_ws_bytes(Q, sum_t) elements, or None: allocated.  One launch, a workgroup per image.
+    Nothing is copied: an operand of another dtype or layout, or a shape outside Q <= 4096, Tmax <= 256, B <= 65535, is refused; the layout
+    is checked before the device."""
+    if n_tgt.dim() != 1:
+        raise RuntimeError("n_tgt must be (B,), got %s" % (tuple(n_tgt.shape),))
+    B, Q, Tmax, sum_t = int(n_tgt.shape[0]), int(Q), int(Tmax), int(sum_t)
+    _layout_as(n_tgt, "n_tgt", torch.int32, (B,))
+    _layout_as(t_off, "t_off", torch.int32, (B,))
+    if Q < 0 or Tmax < 0 or not 0 <= sum_t <= B * Tmax:
+        raise RuntimeError("hungarian_assign: Q=%d, Tmax=%d, sum_t=%d outside Q >= 0, Tmax >= 0, 0 <= sum_t <= B x Tmax = %d" % (Q, Tmax, sum_t, B * Tmax))
+    _layout_as(costs, "costs", torch.float32, (Q * sum_t + B,))
+    if Q > HUNGARIAN_MAX_Q or Tmax > HUNGARIAN_MAX_T or B > 65535:
+        raise RuntimeError("hungarian_assign: B=%d, Q=%d, Tmax=%d outside B <= 65535, Q <= %d, Tmax <= %d" % (B, Q, Tmax, HUNGARIAN_MAX_Q, HUNGARIAN_MAX_T))
+    _on_device(costs=costs, n_tgt=n_tgt, t_off=t_off, ws=ws)
+    lib = _lib.load()
+    K, n = min(Q, Tmax), Q * sum_t
+    pairs = torch.empty(2, B, K, dtype=torch.int64, device=costs.device)
+    status = torch.empty(B, dtype=torch.int32, device=costs.device)
+    if B * Q * Tmax == 0:                                    # no launch: nothing to solve (K == 0 or B == 0: the pairs are empty)
+        status.copy_(costs[n:].view(torch.int32))
+        return pairs[0], pairs[1], status
+    ws = _workspace(ws, int(lib.hipie_hungarian_assign_ws_bytes(Q, sum_t)), costs.device, "hungarian_assign")
+    rc = lib.hipie_hungarian_assign(costs.data_ptr() if n else None, costs[n:].data_ptr(), n_tgt.data_ptr(), t_off.data_ptr(), pairs[0].data_ptr(),
+                                    pairs[1].data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), B, Q, Tmax, sum_t, _stream())
+    _lib.check(rc, "hipie_hungarian_assign")
+    return pairs[0], pairs[1], status
+
+
 @_timed("add_layernorm")
 def add_layernorm_sum(x, delta, weight, bias, eps, addend):
     """n = LayerNorm(x + delta) and n + addend, both in x's dtype, one launch (the encoder's post-norm + next `src + pos`)."""

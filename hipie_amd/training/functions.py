@@ -495,32 +495,30 @@ def pack_match_targets(targets, device, with_masks=True):
     return MatchTargets(tgt_boxes, pos_map, labels, is_thing, both[0], both[1], counts, tgt_masks)
 
 
-@torch.no_grad()
-def hungarian_costs(logits, boxes, packed, w, masks=None, coords=None, stuff_takes_mean=True, with_boxes=True, class_mode="auto"):
-    """matcher.cost_matrix of every image of a batch on hipie_hungarian_cost (+ hipie_mask_match_cost per image with `masks`): logits (B,Q,L),
-    boxes (B,Q,4), packed = pack_match_targets(...), w: matcher.MatchWeights; masks: None or per image the (Q,H,W) mask logits, coords: then per
-    image the (P,2) points -> per image the (Q, T_i) cost matrix as a float32 numpy array on the HOST, views of ONE device -> host copy that
-    carries the costs of all images and their status words.  The mask costs of an image land directly in its block of the packed operands.
-    class_mode as matcher.class_cost: "map", "ids", or "auto" (the map when the targets have one).  A status bit raises ValueError and names the
-    image (a degenerate box: the ValueError of boxes.generalized_box_iou; a label outside [0, L)).  Shapes outside the kernel's limits
-    (Q <= 4096, Tmax <= 256, L <= 1024, B <= 65535): None, the torch path runs."""
+def _hungarian_device_costs(what, logits, boxes, packed, w, masks, coords, stuff_takes_mean, with_boxes, class_mode):
+    """everything of hungarian_costs / hungarian_match in front of the first use of the costs: the checks, the mask costs of every image and
+    hipie_hungarian_cost -> None (a shape outside the kernel's limits: the torch path runs), or (out, offs): the packed device buffer of
+    ops.hungarian_cost (None when there is nothing to compute: no image, no query or no target) and the host list of the images' offsets"""
     B, Q, L = logits.shape
     Tmax, sum_t = packed.tgt_boxes.shape[1], sum(packed.counts)
     if len(packed.counts) != B:
-        raise ValueError("hungarian_costs: targets packed for %d images, logits are %s" % (len(packed.counts), tuple(logits.shape)))
+        raise ValueError("%s: targets packed for %d images, logits are %s" % (what, len(packed.counts), tuple(logits.shape)))
     use_map = packed.pos_map is not None if class_mode == "auto" else class_mode == "map"
     if use_map and packed.pos_map is None:
-        raise KeyError("hungarian_costs: targets have no positive_map")
+        raise KeyError("%s: targets have no positive_map" % what)
     if not use_map and packed.labels is None:
-        raise KeyError("hungarian_costs: targets have no labels")
+        raise KeyError("%s: targets have no labels" % what)
     if use_map and Tmax and packed.pos_map.shape[2] != L:
-        raise ValueError("hungarian_costs: targets packed for %d tokens, logits are %s" % (packed.pos_map.shape[2], tuple(logits.shape)))
+        raise ValueError("%s: targets packed for %d tokens, logits are %s" % (what, packed.pos_map.shape[2], tuple(logits.shape)))
     if masks is not None and packed.tgt_masks is None:
-        raise KeyError("hungarian_costs: targets were packed without masks")
+        raise KeyError("%s: targets were packed without masks" % what)
     if Q > ops.HUNGARIAN_MAX_Q or Tmax > ops.HUNGARIAN_MAX_T or L > ops.HUNGARIAN_MAX_L or L < 1 or B > 65535:
         return None
+    offs = [0]
+    for n in packed.counts[:-1]:
+        offs.append(offs[-1] + n)
     if B == 0 or Q == 0 or sum_t == 0:
-        return [np.zeros((Q, n), dtype=np.float32) for n in packed.counts]
+        return None, offs[:B]
     dev = logits.device
 
     def images(t, row):                       # a slice of the query dimension keeps its images dense: no copy
@@ -528,9 +526,6 @@ def hungarian_costs(logits, boxes, packed, w, masks=None, coords=None, stuff_tak
         if t.dtype != torch.float32:
             t = t.float()
         return t if t.stride(2) == 1 and t.stride(1) == row and (B == 1 or t.stride(0) >= Q * row) else t.contiguous()
-    offs = [0]
-    for n in packed.counts[:-1]:
-        offs.append(offs[-1] + n)
     ce = dice = None
     if masks is not None:
         both = torch.empty(2, Q * sum_t, dtype=torch.float32, device=dev)
@@ -545,9 +540,49 @@ def hungarian_costs(logits, boxes, packed, w, masks=None, coords=None, stuff_tak
                              (w.cls, w.l1, w.giou, w.mask, w.dice), pos_map=packed.pos_map if use_map else None,
                              labels=None if use_map else packed.labels, is_thing=packed.is_thing, ce=ce, dice=dice, with_boxes=with_boxes,
                              stuff_takes_mean=stuff_takes_mean)
+    return out, offs
+
+
+@torch.no_grad()
+def hungarian_costs(logits, boxes, packed, w, masks=None, coords=None, stuff_takes_mean=True, with_boxes=True, class_mode="auto"):
+    """matcher.cost_matrix of every image of a batch on hipie_hungarian_cost (+ hipie_mask_match_cost per image with `masks`): logits (B,Q,L),
+    boxes (B,Q,4), packed = pack_match_targets(...), w: matcher.MatchWeights; masks: None or per image the (Q,H,W) mask logits, coords: then per
+    image the (P,2) points -> per image the (Q, T_i) cost matrix as a float32 numpy array on the HOST, views of ONE device -> host copy that
+    carries the costs of all images and their status words.  The mask costs of an image land directly in its block of the packed operands.
+    class_mode as matcher.class_cost: "map", "ids", or "auto" (the map when the targets have one).  A status bit raises ValueError and names the
+    image (a degenerate box: the ValueError of boxes.generalized_box_iou; a label outside [0, L)).  Shapes outside the kernel's limits
+    (Q <= 4096, Tmax <= 256, L <= 1024, B <= 65535): None, the torch path runs."""
+    got = _hungarian_device_costs("hungarian_costs", logits, boxes, packed, w, masks, coords, stuff_takes_mean, with_boxes, class_mode)
+    if got is None:
+        return None
+    out, offs = got
+    Q, sum_t = logits.shape[1], sum(packed.counts)
+    if out is None:
+        return [np.zeros((Q, n), dtype=np.float32) for n in packed.counts]
     host = out.cpu().numpy()                                  # the one host read of the call: the costs and the status words
     status = host[Q * sum_t:].view(np.int32)
     for b, s in enumerate(status.tolist()):
         if s:
             raise ValueError("hungarian_costs: image %d: %s" % (b, "; ".join(msg for bit, msg in ops.HUNGARIAN_STATUS if s & bit)))
     return [host[Q * o:Q * (o + n)].reshape(Q, n) for o, n in zip(offs, packed.counts)]
+
+
+@torch.no_grad()
+def hungarian_match(logits, boxes, packed, w, masks=None, coords=None, stuff_takes_mean=True, with_boxes=True, class_mode="auto"):
+    """HungarianMatcher.forward / forward_boxes_only without a host wait: the costs of hungarian_costs stay on the device and
+    hipie_hungarian_assign solves every image's assignment there (scipy's pairs, tie for tie) -> (pairs, status): per image (query idx, target
+    idx) int64 on the DEVICE, views of the kernel's (B, K) outputs whose lengths min(Q, T_i) the host knows from the packed counts; status (B,)
+    int32 on the device (ops.HUNGARIAN_STATUS): the caller decides when to read it (HungarianMatcher: at once, or at check()).  An image with a non-zero
+    status has all-zero pairs, which index nothing out of range.  The same arguments as hungarian_costs, and None under the same conditions."""
+    got = _hungarian_device_costs("hungarian_match", logits, boxes, packed, w, masks, coords, stuff_takes_mean, with_boxes, class_mode)
+    if got is None:
+        return None
+    out, offs = got
+    B, Q = logits.shape[:2]
+    dev = logits.device
+    if out is None:
+        e = torch.zeros(0, dtype=torch.int64, device=dev)
+        return [(e, e.clone()) for _ in range(B)], torch.zeros(B, dtype=torch.int32, device=dev)
+    pair_q, pair_t, status = ops.hungarian_assign(out, packed.n_tgt, packed.t_off, sum(packed.counts), Q, packed.tgt_boxes.shape[1])
+    return [(pair_q[b, :min(Q, n)], pair_t[b, :min(Q, n)]) for b, n in enumerate(packed.counts)], status
+

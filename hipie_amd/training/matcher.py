@@ -9,7 +9,8 @@
 One cost routine serves all of them.  The cost matrix is built on the tensors' device (one image at a time, like the reference); the
 linear sum assignment itself runs on the host in scipy, as in the reference (``C.cpu()`` -> ``linear_sum_assignment``).  Opt-in, an `ops`
 object with ``hungarian_costs`` (net.HipBackendHungarian) builds the cost matrices of the whole batch in one kernel call and hands scipy
-slices of one host copy."""
+slices of one host copy; one with ``hungarian_match`` (net.HipBackendAssign) solves the assignment on the device too, and the pairs come
+back as device tensors without a host wait."""
 from dataclasses import dataclass
 
 import torch
@@ -160,11 +161,16 @@ class HungarianMatcher(nn.Module):
     """weights: MatchWeights.  num_points: points of the mask costs (12544 = 112^2 in both heads).  stuff_takes_mean: the panoptic
     box handling (`panoptic_box_loss` / `panoptic_on`).  draw(shape, device) supplies uniform [0, 1) numbers (default torch.rand): the
     reference draws ONE (1, num_points, 2) tensor per image, in batch order.  ops: see cost_matrix (the draws do not change),
-    forward (`hungarian_costs`) and forward_ota."""
+    forward (`hungarian_costs`, `hungarian_match`) and forward_ota.  defer_status: with a `hungarian_match` op, False reads the status words of
+    a call at its end (one small host read; a non-zero word raises ValueError and names the image); True appends them to `pending` and
+    check() reads all of them in one copy -- a call then makes no host wait at all."""
 
-    def __init__(self, weights=None, num_points=112 * 112, stuff_takes_mean=True, draw=None, class_mode="auto", ops=None):
+    def __init__(self, weights=None, num_points=112 * 112, stuff_takes_mean=True, draw=None, class_mode="auto", ops=None, defer_status=False):
         super().__init__()
         self.ops = ops
+        self.defer_status = bool(defer_status)
+        self.pending = []                                  # (status (B,) int32 on the device, label) of every call not yet checked
+        self.calls = 0
         self.class_mode = class_mode                       # "map": positive maps (vl_loss), "ids": class ids, "auto": whichever the target has
         self.w = weights or MatchWeights()
         if not any((self.w.cls, self.w.l1, self.w.giou, self.w.mask)):
@@ -176,19 +182,65 @@ class HungarianMatcher(nn.Module):
     def pack(self, targets, device, masks=True):
         """the targets as the `hungarian_costs` op of `ops` reads them (one packing serves every decoder level / every output of a criterion
         call; masks=False leaves the target masks out: a caller without mask costs), None without such an op"""
-        if getattr(self.ops, "hungarian_costs", None) is None:
+        if getattr(self.ops, "hungarian_costs", None) is None and getattr(self.ops, "hungarian_match", None) is None:
             return None
         return self.ops.pack_match_targets(targets, device, masks)
 
+    @staticmethod
+    def _status_error(words, label):
+        """the ValueError of the first non-zero status word of a call (ops.HUNGARIAN_STATUS), naming the image; None: all zero"""
+        from ..ops import HUNGARIAN_STATUS
+        for b, s in enumerate(words):
+            if s:
+                return ValueError("hungarian_match: %s: image %d: %s" % (label, b, "; ".join(msg for bit, msg in HUNGARIAN_STATUS if s & bit)))
+        return None
+
+    def check(self):
+        """reads the status words of every deferred call in ONE copy, clears the list and raises for the first non-zero word"""
+        HungarianMatcher.check_all((self,))
+
+    @staticmethod
+    def check_all(matchers):
+        """check() for several matchers with ONE copy for all of them (TrainStep: its three matchers, one host read per step)"""
+        pending = [p for m in matchers for p in m.pending]
+        for m in matchers:
+            m.pending = []
+        if not pending:
+            return
+        words = torch.cat([s for s, _ in pending]).cpu().tolist()
+        at = 0
+        for s, label in pending:
+            err = HungarianMatcher._status_error(words[at:at + s.numel()], label)
+            if err is not None:
+                raise err
+            at += s.numel()
+
     def _batched(self, logits, boxes, targets, packed, masks, coords, stuff_takes_mean, with_boxes):
         """[(query idx, target idx)] per image through the `hungarian_costs` op of `ops` (net.HipBackendHungarian: functions.hungarian_costs on
-        csrc/hungarian_cost.hip -- the costs of the whole batch, ONE device -> host copy, scipy on host slices), or None: no such op, mask
-        costs without a `mask_match_costs` op beside it, or the op declined (a shape outside its limits)"""
+        csrc/hungarian_cost.hip -- the costs of the whole batch, ONE device -> host copy, scipy on host slices) or, when it has one, its
+        `hungarian_match` op (net.HipBackendAssign: functions.hungarian_match, the assignment on csrc/hungarian_assign.hip too -- device pairs, no
+        host wait but the status read, see defer_status); None: no such op, mask costs without a `mask_match_costs` op beside it, or the op
+        declined (a shape outside its limits)"""
+        match = getattr(self.ops, "hungarian_match", None)
         op = getattr(self.ops, "hungarian_costs", None)
-        if op is None or (masks is not None and getattr(self.ops, "mask_match_costs", None) is None):
+        if (op is None and match is None) or (masks is not None and getattr(self.ops, "mask_match_costs", None) is None):
             return None
         if packed is None:
             packed = self.pack(targets, logits.device, masks is not None)
+        if match is not None:
+            got = match(logits, boxes, packed, self.w, masks, coords, stuff_takes_mean, with_boxes, self.class_mode)
+            if got is None:
+                return None
+            pairs, status = got
+            self.calls += 1
+            label = "call %d (Q=%d, %s)" % (self.calls, logits.shape[1], "class + box" if masks is None else "with masks")
+            if self.defer_status:
+                self.pending.append((status, label))
+            else:
+                err = self._status_error(status.cpu().tolist(), label)          # the one (small) host read of the call
+                if err is not None:
+                    raise err
+            return pairs
         Cs = op(logits, boxes, packed, self.w, masks, coords, stuff_takes_mean, with_boxes, self.class_mode)
         return None if Cs is None else [assign_host(C) for C in Cs]
 

@@ -10,7 +10,8 @@ hipie_attn_train_win_forward / _backward; opt-in, HipBackendLosses: the point-sa
 criteria on hipie_point_mask_loss_* / hipie_token_focal_*; opt-in, HipBackendCriteria: on top of those the importance point selection of the
 criteria and the mask costs of the matchers on hipie_uncertain_points / hipie_mask_match_cost; opt-in, HipBackendMatching: on top of those
 the SimOTA matching of the foreground queries on hipie_ota_cost / hipie_ota_assign; opt-in, HipBackendHungarian: on top of those the cost
-matrices of the one-to-one Hungarian matchers on hipie_hungarian_cost).
+matrices of the one-to-one Hungarian matchers on hipie_hungarian_cost; opt-in, HipBackendAssign: on top of those the assignment itself on
+hipie_hungarian_assign, the pairs staying on the device).
 
 Functional style over a dict ``sd`` of LIVE parameters (model.named_parameters() + buffers, reference key names), so gradients land in the
 model's own parameters.  Every function cites the reference code it follows.  Training-mode differences from the inference path:
@@ -214,6 +215,22 @@ class HipBackendHungarian(HipBackendMatching):
         """logits (B,Q,L), boxes (B,Q,4), packed -> per image the (Q, T_i) cost matrix on the host, or None outside the kernel's limits"""
         from .functions import hungarian_costs
         return hungarian_costs(logits, boxes, packed, w, masks, coords, stuff_takes_mean, with_boxes, class_mode)
+
+
+class HipBackendAssign(HipBackendHungarian):
+    """HipBackendHungarian + the one-to-one assignment itself on csrc/hungarian_assign.hip (functions.hungarian_match: the packed costs stay
+    on the device and one more launch solves every image's assignment there, with scipy's pairs tie for tie -- no device -> host copy of the
+    costs, no scipy, no host -> device copy of the pairs).  A matcher call is two or three kinds of launches and no host wait; the pairs are
+    device int64 tensors whose lengths the host knows from the packed counts.  TrainStep builds its matchers with defer_status=True and reads
+    the status words of all their calls once, at the end of loss_dict (HungarianMatcher.check).
+    Opt-in: TrainStep's default stays HipBackend; HipBackendHungarian and HipBackendAll do not include it."""
+
+    @staticmethod
+    def hungarian_match(logits, boxes, packed, w, masks=None, coords=None, stuff_takes_mean=True, with_boxes=True, class_mode="auto"):
+        """logits (B,Q,L), boxes (B,Q,4), packed -> (per image (query idx, target idx) int64 on the device, status (B,) int32 on the device),
+        or None outside the kernels' limits"""
+        from .functions import hungarian_match
+        return hungarian_match(logits, boxes, packed, w, masks, coords, stuff_takes_mean, with_boxes, class_mode)
 
 
 # ------------------------------------------------------------------------------------------------ small helpers

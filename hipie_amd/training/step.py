@@ -57,6 +57,9 @@ class TrainStep:
         # (net.HipBackendHungarian): the matchers get the backend the same way
         match_ops = self.be if (getattr(self.be, "mask_match_costs", None) or getattr(self.be, "ota_match", None)
                                 or getattr(self.be, "hungarian_costs", None)) else None
+        # the opt-in assignment kernel (net.HipBackendAssign): the matchers' pairs stay on the device and the status words of their calls are
+        # read once, at the end of loss_dict
+        defer = getattr(self.be, "hungarian_match", None) is not None
         d = self.draws
         draw = lambda shape, device: d.rand(tuple(shape), device)          # noqa: E731
         self.dn_number, self.label_noise_ratio, self.box_noise_scale = dn_number, label_noise_ratio, box_noise_scale
@@ -65,9 +68,9 @@ class TrainStep:
         self.md_dn_number, self.md_noise_scale = md_dn_number, md_noise_scale
         # hipie_img.py:176-236: the matchers and the DINO criterion
         self.matcher = HungarianMatcher(MatchWeights(2.0, 5.0, 2.0, 5.0, 5.0), num_points=num_points, stuff_takes_mean=True, draw=draw, class_mode="map",
-                                        ops=match_ops)
+                                        ops=match_ops, defer_status=defer)
         self.matcher_bg = HungarianMatcher(MatchWeights(2.0, 0.0, 0.0, 5.0, 5.0), num_points=bg_matcher_points, stuff_takes_mean=False, draw=draw,
-                                           class_mode="map", ops=match_ops)
+                                           class_mode="map", ops=match_ops, defer_status=defer)
         self.criterion = DetCriterion(self.matcher, ["labelsVL", "boxes", "masks"], focal_alpha=0.25, mask_out_stride=self.cfg["mask_stride"],
                                       point_sample_masks=True, panoptic_box_loss=True, still_cls_for_encoder=True, num_points=num_points, draw=draw, ota=True,
                                       ops=loss_ops)
@@ -84,7 +87,8 @@ class TrainStep:
         # ddetrs_dn.py:176-196
         self.md_weights, md_dn_losses, md_matcher, md_losses = maskdino_loss_plan(
             4.0, 5.0, 5.0, 5.0, 2.0, True, "seg", True, self.cfg["md_dec_layers"], True, 4.0, 5.0, 5.0, 5.0, 2.0, md_num_points, True, draw=draw,
-            ops=match_ops)
+            ops=match_ops, defer_status=defer)
+        self.matchers = (self.matcher, self.matcher_bg, md_matcher)
         self.md_criterion = MaskCriterion(100, md_matcher, md_losses, vl_loss=True, num_points=md_num_points, oversample_ratio=3.0, importance_sample_ratio=0.75,
                                           dn="seg", dn_losses=md_dn_losses, panoptic_on=False, draw=draw, ops=loss_ops)
 
@@ -282,6 +286,8 @@ class TrainStep:
         lang = {"hidden": lang["hidden"].float(), "masks": lang["masks"]}
         targets = [{k: (v.to(x.device) if torch.is_tensor(v) else v) for k, v in t.items()} for t in targets]
         raw, _ = self.coco_forward(x, pad, sizes, targets, lang, task)
+        HungarianMatcher.check_all(self.matchers)                                       # check() of the three matchers as one read: the deferred status
+                                                                                        # words of the assignment kernel; nothing pending without it
         out = {}
         for k, v in raw.items():
             if "_maskdino" in k:

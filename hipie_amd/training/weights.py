@@ -3,9 +3,9 @@ from .matcher import HungarianMatcher, MatchWeights
 
 
 def maskdino_loss_plan(class_weight, mask_weight, dice_weight, box_weight, giou_weight, two_stage, dn, deep_supervision, dec_layers, box_loss,
-                       cost_class, cost_mask, cost_dice, cost_box, cost_giou, train_num_points, vl_loss, draw=None, ops=None):
+                       cost_class, cost_mask, cost_dice, cost_box, cost_giou, train_num_points, vl_loss, draw=None, ops=None, defer_status=False):
     """MODEL.MaskDINO.* -> (weight of every loss key the MaskDINO criterion can emit, the loss families of the de-noising part, the matcher,
-    the loss families).  ops: handed to the matcher (HungarianMatcher).  Key growth as in the reference: base keys, their `_interm` copies
+    the loss families).  ops, defer_status: handed to the matcher (HungarianMatcher).  Key growth as in the reference: base keys, their `_interm` copies
     (two-stage), `_dn` copies of all of those (dn == "seg") or of the non-mask ones ("standard"), then `_i` copies of everything for each of the `dec_layers` auxiliary layers."""
     w = {"loss_ce": class_weight, "loss_mask": mask_weight, "loss_dice": dice_weight, "loss_bbox": box_weight, "loss_giou": giou_weight}
     if two_stage:
@@ -23,7 +23,7 @@ def maskdino_loss_plan(class_weight, mask_weight, dice_weight, box_weight, giou_
         for i in range(dec_layers):
             w.update({k + "_%d" % i: v for k, v in base})
     matcher = HungarianMatcher(MatchWeights(cost_class, cost_box, cost_giou, cost_mask, cost_dice), num_points=train_num_points, stuff_takes_mean=False,
-                               draw=draw, class_mode="map" if vl_loss else "ids", ops=ops)
+                               draw=draw, class_mode="map" if vl_loss else "ids", ops=ops, defer_status=defer_status)
     return w, dn_losses, matcher, (["labels", "masks", "boxes"] if box_loss else ["labels", "masks"])
 
 

@@ -491,6 +491,33 @@ int64_t hipie_hungarian_cost_bytes(int64_t Q, int64_t sum_t);
 int64_t hipie_hungarian_cost_ws_bytes(int64_t B, int64_t Q);
 
 /*
+ * The one-to-one assignment of the Hungarian matchers for a batch of images, on the packed costs of hipie_hungarian_cost: per image the pairs
+ * of scipy.optimize.linear_sum_assignment on its (Q, n_tgt[b]) block, tie for tie, as int64 on the device.  One launch, one workgroup of 256
+ * threads per image; nothing is read by the host.
+ * Replaces: `C.cpu()` and linear_sum_assignment per image (models/deformable_detr/matcher.py:599-606, models/maskdino/matcher.py:171-178) and
+ *           the host -> device copies of the index tensors wherever the criteria index with them.
+ *   C: hipie_hungarian_cost's output, unchanged: image b is a dense row-major (Q, n_tgt[b]) block at element Q * t_off[b], Q * sum_t elements.
+ *   cost_status (B,): the status words the cost kernel wrote (they sit behind the blocks of its output).
+ *   n_tgt, t_off (B,), sum_t: as for hipie_hungarian_cost.
+ *   pair_q, pair_t (B, K) int64, K = min(Q, Tmax): image b's min(Q, n_tgt[b]) pairs (query, target) in ascending query order, 0 behind them.
+ *   status (B,): written, not accumulated.  cost_status[b], bit 4 when t_off[b] + n_tgt[b] does not fit sum_t, and the solver's own bits:
+ *     bit 5 (32): the block holds a NaN or -inf ("matrix contains invalid numeric entries"; +inf entries are legal), bit 6 (64): "cost matrix is
+ *     infeasible", bit 7 (128): the search of a row did not end within min(Q, n) columns (valid input cannot get there; the bound of the loop).
+ *     An image with a non-zero status is not solved and all its pairs are 0: valid indices, whatever is indexed with them before the status is read.
+ *   The solver is scipy's (Crouse 2016, shortest augmenting paths) operation for operation: float64 adds, subtracts and compares on the widened
+ *     costs, reduced cost ((minVal + C[i][j]) - u[i]) - v[j], the unscanned columns listed in reverse with a removed entry replaced by the last,
+ *     the lowest candidate chosen as the sequential scan chooses it (an unassigned column at the largest list position, else the smallest position).
+ *     With Q > n_tgt[b] the rows are the targets (scipy's transposition); the block is first written target-major into `ws`.
+ *   ws: 4-byte aligned, at least hipie_hungarian_assign_ws_bytes(Q, sum_t) bytes.  Bit-reproducible; every loop is bounded by min(Q, Tmax) <= 256.
+ * Refused (-22): Q > 4096, Tmax > 256, B > 65535, sum_t > B x Tmax, null pointers, a workspace that is too small or misaligned.
+ *     B == 0, Q == 0 or Tmax == 0: returns 0 without a launch, null pointers allowed.
+ */
+int hipie_hungarian_assign(const float* C, const int* cost_status, const int* n_tgt, const int* t_off, int64_t* pair_q, int64_t* pair_t, int* status,
+                           void* ws, int64_t ws_bytes, int64_t B, int Q, int Tmax, int64_t sum_t, void* stream);
+/* bytes of the target-major copy of the costs, Q * sum_t fp32 elements (never 0) */
+int64_t hipie_hungarian_assign_ws_bytes(int64_t Q, int64_t sum_t);
+
+/*
  * hipie_vit_attn with the decomposed relative-position bias computed INSIDE the kernel from the (re-interpolated) tables
  * (get_rel_pos + add_decomposed_rel_pos, hipie/backbone/utils.py:63-125): bias_w[q, kx] = q . Rw[qx - kx + gw - 1] and
  * bias_h[q, ky] = q . Rh[qy - ky + gh - 1] are two MFMA products per wave in the prologue, so neither hipie_vit_relpos nor

@@ -1,0 +1,336 @@
+"""GPU: hipie_hungarian_assign (csrc/hungarian_assign.hip) through ops.hungarian_assign, functions.hungarian_match and the opt-in
+net.HipBackendAssign wiring of HungarianMatcher.forward / forward_boxes_only and TrainStep.
+
+The pairs are held to the installed scipy.optimize.linear_sum_assignment EXACTLY: on hand-made packed buffers with real ties (zeros, 0/1 and
+0..2 costs, duplicated rows and columns, +inf entries, the adversarial matrix of the longest search), and on the cost kernel's own blocks
+with the three conditions of _hungarian_cases (exact, optimal in float64, equal to the torch path where the optimum is separated).  A
+deferred matcher call makes no host wait (torch's sync debug mode), and the step computes the same pairs and the same losses as with
+net.HipBackendHungarian with one host read instead of one per matcher call."""
+import functools
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+from _assign_cases import FILLS, RAW_SHAPES, ST_INFEASIBLE, ST_INVALID, adversarial, filled, pack_blocks, scipy_pairs
+from _hungarian_cases import (IDS, SEEDS, SHAPES, SMALL, W_BOX, Golden, assignment_gap, bound_of, case_coords, golden_cases, hungarian_case, optimum,
+                              reference_cost, same_pairs, slack, total_cost)
+from hipie_amd.training.matcher import HungarianMatcher, MatchWeights
+from test_training import Replay
+
+
+@pytest.fixture(autouse=True)
+def _grad_enabled():
+    """other test modules of the suite switch autograd off for the whole process"""
+    with torch.enable_grad():
+        yield
+
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+W_ALL = MatchWeights(2.0, 5.0, 2.0, 5.0, 5.0)
+
+
+def _on(dev, targets):
+    return [{k: v.to(dev) for k, v in t.items()} for t in targets]
+
+
+@functools.lru_cache(maxsize=None)
+def _device_case(key):
+    logits, boxes, targets, pred = hungarian_case(*key)
+    return logits.to(DEV), boxes.to(DEV), _on(DEV, targets), pred.to(DEV)
+
+
+def _solve(blocks, cost_status=None):
+    """ops.hungarian_assign on hand-made blocks of one Q -> (pair_q, pair_t, status) on the host"""
+    from hipie_amd import ops
+    costs, n_tgt, t_off, sum_t, Tmax = pack_blocks(blocks, DEV, cost_status)
+    Q = blocks[0].shape[0]
+    pq, pt, st = ops.hungarian_assign(costs, n_tgt, t_off, sum_t, Q, Tmax)
+    assert pq.shape == pt.shape == (len(blocks), min(Q, Tmax)) and pq.dtype == pt.dtype == torch.int64 and st.dtype == torch.int32
+    return pq.cpu().numpy(), pt.cpu().numpy(), st.cpu().tolist()
+
+
+def _is_scipys(tag, blocks, pq, pt, skip=()):
+    for b, C in enumerate(blocks):
+        if b in skip:
+            assert not pq[b].any() and not pt[b].any(), (tag, b, "a refused image keeps all-zero pairs")
+            continue
+        i, j = scipy_pairs(C)
+        k = len(i)
+        assert k == min(C.shape)
+        assert np.array_equal(pq[b, :k], i) and np.array_equal(pt[b, :k], j), (tag, b, "the pairs are not scipy's")
+        assert not pq[b, k:].any() and not pt[b, k:].any(), (tag, b, "behind the pairs: zeros")
+
+
+# ------------------------------------------------------------------------------------------------ 1. the raw op
+@pytest.mark.parametrize("shape", RAW_SHAPES, ids=lambda s: "%dx%d" % s)
+def test_pairs_are_scipys_on_matrices_with_ties(shape):
+    """the five fills of a shape as ONE batch of five images"""
+    blocks = [filled(*shape, fill) for fill in FILLS]
+    pq, pt, st = _solve(blocks)
+    assert st == [0] * len(blocks)
+    _is_scipys("%dx%d" % shape, blocks, pq, pt)
+
+
+def test_a_ragged_batch_with_an_empty_last_image():
+    for Q, counts, fill in ((70, (9, 6, 0), "012"), (20, (37, 20, 0), "dup"), (5, (9, 3, 0), "01")):
+        blocks = [filled(Q, n, fill) if n else np.zeros((Q, 0), dtype=np.float32) for n in counts]
+        pq, pt, st = _solve(blocks)
+        assert st == [0, 0, 0] and not pq[2].any() and not pt[2].any()
+        _is_scipys("ragged %d" % Q, blocks[:2], pq, pt)
+
+
+@pytest.mark.parametrize("shape", [(900, 100), (4096, 256)], ids=lambda s: "%dx%d" % s)
+def test_the_longest_search_terminates_and_matches(shape):
+    """C[q, t] = -(q + t) t: close to nr (nr + 1) / 2 inner iterations (4951 at 900 x 100: test_hungarian_assign_cpu.py counts them; 32641 at
+    4096 x 256)"""
+    blocks = [adversarial(*shape)]
+    pq, pt, st = _solve(blocks)
+    assert st == [0]
+    _is_scipys("adversarial %dx%d" % shape, blocks, pq, pt)
+
+
+# ------------------------------------------------------------------------------------------------ 2. status
+def test_status_bits_name_their_image_and_leave_zero_pairs():
+    from hipie_amd import ops
+    msgs = dict(ops.HUNGARIAN_STATUS)
+    for Q, T in ((20, 5), (6, 9)):                             # solved transposed, and as it stands
+        good = filled(Q, T, "dup")
+        nan, neg, inf = good.copy(), good.copy(), good.copy()
+        nan[Q - 1, T - 2] = np.nan
+        neg[0, 1] = -np.inf
+        if Q > T:
+            inf[:, 1] = np.inf                                 # a target no query can take
+        else:
+            inf[2, :] = np.inf                                 # a query that can take no target
+        for f, msg in ((nan, "invalid numeric"), (neg, "invalid numeric"), (inf, "infeasible")):
+            with pytest.raises(ValueError, match=msg):
+                scipy_pairs(f)
+        blocks = [good, nan, good[::-1].copy(), neg, inf, filled(Q, T, "012")]
+        pq, pt, st = _solve(blocks)
+        assert st == [0, ST_INVALID, 0, ST_INVALID, ST_INFEASIBLE, 0], (Q, T, st)
+        _is_scipys("status %dx%d" % (Q, T), blocks, pq, pt, skip=(1, 3, 4))
+        err = HungarianMatcher._status_error(st, "a call")
+        assert "image 1: " + msgs[32] in str(err)
+        assert "image 4: " + msgs[64] in str(HungarianMatcher._status_error([0] * 4 + st[4:], "a call"))
+        # a status word of the cost kernel is carried over and refuses its image
+        pq, pt, st = _solve([good, good, good], cost_status=[0, 1, 8])
+        assert st == [0, 1, 8]
+        _is_scipys("carried %dx%d" % (Q, T), [good] * 3, pq, pt, skip=(1, 2))
+    # offsets that do not fit the packed block: bit 16, nothing of the image is read
+    costs, n_tgt, t_off, sum_t, Tmax = pack_blocks([filled(20, 5, "dup")] * 2, DEV)
+    t_off = torch.tensor([0, 6], dtype=torch.int32).to(DEV)
+    pq, pt, st = ops.hungarian_assign(costs, n_tgt, t_off, sum_t, 20, Tmax)
+    assert st.tolist() == [0, 16] and not pq[1].any() and not pt[1].any()
+
+
+def test_a_cost_kernel_status_reaches_the_matcher():
+    from hipie_amd.training import functions, net
+    key = SHAPES[3] + (0, "mixed")
+    logits, boxes, targets, _ = _device_case(key)
+    bad_t = [dict(t) for t in hungarian_case(*key)[2]]
+    bad_t[1]["boxes"] = bad_t[1]["boxes"].clone()
+    bad_t[1]["boxes"][3, 2] = -0.1                                # a target box with negative width
+    packed = functions.pack_match_targets(_on(DEV, bad_t), DEV)
+    pairs, status = functions.hungarian_match(logits, boxes, packed, W_BOX)
+    assert status.tolist() == [0, 1, 0] and not pairs[1][0].any() and not pairs[1][1].any() and len(pairs[1][0]) == 6
+    with pytest.raises(ValueError, match="image 1: a box with x1 < x0"):
+        HungarianMatcher(W_BOX, class_mode="map", ops=net.HipBackendAssign)(logits, boxes, _on(DEV, bad_t))
+
+
+# ------------------------------------------------------------------------------------------------ 3. through the backend
+def _check_assignment(tag, pairs, blocks, refs, torch_pairs=None, must_be_separated=False):
+    """_check_assignment of test_gpu_hungarian_cost.py for device pairs: (a) exact on the kernel's own block, (b) optimality in float64,
+    (c) equality with the torch path under its precondition"""
+    for b, ((q, t), C, (c64, c32)) in enumerate(zip(pairs, blocks, refs)):
+        assert q.dtype == t.dtype == torch.int64 and q.is_cuda and t.is_cuda
+        q, t = q.cpu(), t.cpu()
+        if C.shape[1] == 0:
+            assert q.numel() == 0 and t.numel() == 0
+            continue
+        i, j = scipy_pairs(np.array(C))
+        assert np.array_equal(q.numpy(), i) and np.array_equal(t.numpy(), j), (tag, b, "the pairs are not scipy's on the kernel's block")
+        bound = bound_of(c32, c64)
+        room, over = slack(c64, bound), total_cost(c64, (q.numpy(), t.numpy())) - optimum(c64)[0]
+        gap = assignment_gap(c64)
+        print("ASSIGN %-40s image %d over the optimum %.3e  room %.3e  gap %.3e" % (tag, b, over, room, gap))
+        assert over <= room, (tag, b, over, room)
+        if must_be_separated:
+            assert gap > room, (tag, b, gap, room)
+        if torch_pairs is not None and gap > room:
+            assert same_pairs([(q, t)], [torch_pairs[b]]), (tag, b)
+
+
+@pytest.mark.parametrize("stuff", [True, False], ids=["stuff-mean", "own-boxes"])
+@pytest.mark.parametrize("key", [pytest.param(s + (seed, "mixed"), id="%s-%d" % (IDS(s), seed)) for s in SHAPES for seed in SEEDS])
+def test_assignment_on_the_kernel_costs(key, stuff):
+    """class + box costs with the weights (2, 5, 2); the kernel's blocks come from functions.hungarian_costs on the same operands (the cost kernel
+    is bit-reproducible)"""
+    from hipie_amd.training import functions, net
+    logits, boxes, targets, _ = _device_case(key)
+    cpu = hungarian_case(*key)
+    m = HungarianMatcher(W_BOX, stuff_takes_mean=stuff, class_mode="map", ops=net.HipBackendAssign)
+    packed = m.pack(targets, DEV)
+    pairs = m(logits, boxes, targets, packed=packed)
+    blocks = functions.hungarian_costs(logits, boxes, packed, W_BOX, stuff_takes_mean=stuff, class_mode="map")
+    torch_pairs = HungarianMatcher(W_BOX, stuff_takes_mean=stuff, class_mode="map")(cpu[0], cpu[1], cpu[2])
+    refs = [(reference_cost(cpu[0][b], cpu[1][b], t, W_BOX, torch.float64, stuff_takes_mean=stuff),
+             reference_cost(cpu[0][b], cpu[1][b], t, W_BOX, torch.float32, stuff_takes_mean=stuff)) for b, t in enumerate(cpu[2])]
+    _check_assignment("%s-%d stuff=%d" % (IDS(key), key[5], stuff), pairs, blocks, refs, torch_pairs, must_be_separated=key[:5] in SMALL)
+
+
+def _spy(monkeypatch):
+    from hipie_amd.training import functions
+    answers = []
+
+    def spied(*a, _f=functions.hungarian_match, **k):
+        answers.append(_f(*a, **k))
+        return answers[-1]
+    monkeypatch.setattr(functions, "hungarian_match", spied)
+    return answers
+
+
+def test_the_backend_gives_the_reference_fixtures(monkeypatch):
+    from hipie_amd.training import net
+    answers = _spy(monkeypatch)
+    for name, (got, want) in Golden(DEV).run(net.HipBackendAssign, Replay).items():
+        assert all(q.is_cuda and t.is_cuda for q, t in got), name
+        assert same_pairs(got, want), (name, got, want)
+    assert len(answers) == 5 and all(a is not None for a in answers)
+
+
+def test_the_tie_instance_is_scipys_and_optimal():
+    from hipie_amd.training import functions, net
+    logits, boxes, targets, _, _ = golden_cases()["tie"]
+    targets = [dict(targets[0], is_thing=torch.ones(3, dtype=torch.bool))]
+    for stuff in (True, False):
+        m = HungarianMatcher(W_BOX, stuff_takes_mean=stuff, class_mode="map", ops=net.HipBackendAssign)
+        packed = m.pack(_on(DEV, targets), DEV)
+        pairs = m(logits.to(DEV), boxes.to(DEV), _on(DEV, targets), packed=packed)
+        blocks = functions.hungarian_costs(logits.to(DEV), boxes.to(DEV), packed, W_BOX, stuff_takes_mean=stuff, class_mode="map")
+        refs = [(reference_cost(logits[0], boxes[0], targets[0], W_BOX, torch.float64, stuff_takes_mean=stuff),
+                 reference_cost(logits[0], boxes[0], targets[0], W_BOX, torch.float32, stuff_takes_mean=stuff))]
+        _check_assignment("tie stuff=%d" % stuff, pairs, blocks, refs)
+
+
+def test_a_target_without_positive_tokens_raises_invalid_numeric():
+    from hipie_amd.training import net
+    key = SHAPES[3] + (1, "mixed")
+    logits, boxes, _, _ = _device_case(key)
+    targets = [dict(t) for t in hungarian_case(*key)[2]]
+    targets[1]["positive_map"] = targets[1]["positive_map"].clone()
+    targets[1]["positive_map"][4] = False
+    with pytest.raises(ValueError, match="image 1: matrix contains invalid numeric"):
+        HungarianMatcher(W_BOX, stuff_takes_mean=False, class_mode="map", ops=net.HipBackendAssign)(logits, boxes, _on(DEV, targets))
+    later = HungarianMatcher(W_BOX, stuff_takes_mean=False, class_mode="map", ops=net.HipBackendAssign, defer_status=True)
+    pairs = later(logits, boxes, _on(DEV, targets))
+    assert not pairs[1][0].any() and not pairs[1][1].any() and len(later.pending) == 1
+    with pytest.raises(ValueError, match="image 1: matrix contains invalid numeric"):
+        later.check()
+    assert later.pending == []
+
+
+def test_a_shape_outside_the_limits_runs_the_torch_path(monkeypatch):
+    from hipie_amd.training import net
+    lg, bx, tg, _ = hungarian_case(1, 300, 257, 16, False, 0)
+    answers = _spy(monkeypatch)
+    with_ops = HungarianMatcher(W_BOX, class_mode="map", ops=net.HipBackendAssign)(lg.to(DEV), bx.to(DEV), _on(DEV, tg))
+    assert answers == [None]
+    assert same_pairs(with_ops, HungarianMatcher(W_BOX, class_mode="map")(lg.to(DEV), bx.to(DEV), _on(DEV, tg)))
+
+
+def test_two_calls_give_identical_bytes():
+    from hipie_amd.training import functions
+    for key, kw in ((SHAPES[5] + (0, "mixed"), dict(stuff_takes_mean=True)), (SHAPES[3] + (1, "mixed"), dict(class_mode="ids")),
+                    (SHAPES[2] + (0, "mixed"), dict(stuff_takes_mean=False))):
+        logits, boxes, targets, _ = _device_case(key)
+        packed = functions.pack_match_targets(targets, DEV)
+        first, st1 = functions.hungarian_match(logits, boxes, packed, W_BOX, **kw)
+        first = [(q.clone(), t.clone()) for q, t in first]
+        torch.randn(1 << 20, device=DEV).sum()                    # other work in between
+        second, st2 = functions.hungarian_match(logits, boxes, packed, W_BOX, **kw)
+        assert same_pairs(first, second) and st1.tolist() == st2.tolist() == [0] * len(first), key
+
+
+# ------------------------------------------------------------------------------------------------ 4. no host wait
+def _host_waits(fn):
+    """the synchronising calls of fn() as torch's sync debug mode reports them (one warning each) -> (count, fn's result)"""
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("warn")
+    try:
+        with warnings.catch_warnings(record=True) as seen:
+            warnings.simplefilter("always")
+            out = fn()
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    torch.cuda.synchronize()
+    return sum(1 for w in seen if "synchroniz" in str(w.message).lower()), out
+
+
+@pytest.mark.parametrize("with_masks", [False, True], ids=["boxes", "masks"])
+def test_a_deferred_matcher_call_makes_no_host_wait(with_masks):
+    """the 2 x 900 x 100 x 256 case; the same call through net.HipBackendHungarian reads the costs on the host"""
+    from hipie_amd.training import net
+    key = SHAPES[5] + (0, "mixed")
+    logits, boxes, targets, pred = _device_case(key)
+    coords = case_coords(logits.shape[0], 300, 0).to(DEV)
+    masks = list(pred) if with_masks else None
+    waits, pairs = {}, {}
+    for be in (net.HipBackendAssign, net.HipBackendHungarian):
+        points = iter(list(coords) * 2)
+        m = HungarianMatcher(W_ALL, num_points=300, draw=lambda shape, device: next(points)[None], class_mode="map", ops=be,  # noqa: B023
+                             defer_status=be is net.HipBackendAssign)
+        packed = m.pack(targets, DEV)
+        m(logits, boxes, targets, masks=masks, packed=packed)          # the first call loads the kernels
+        waits[be], pairs[be] = _host_waits(lambda: m(logits, boxes, targets, masks=masks, packed=packed))          # noqa: B023
+        m.check()
+    print("ASSIGN host waits of a matcher call (masks=%d): %d with the assignment kernel, %d with scipy on the host"
+          % (with_masks, waits[net.HipBackendAssign], waits[net.HipBackendHungarian]))
+    assert waits[net.HipBackendAssign] == 0
+    assert waits[net.HipBackendHungarian] >= 1
+    assert same_pairs(pairs[net.HipBackendAssign], pairs[net.HipBackendHungarian])
+
+
+# ------------------------------------------------------------------------------------------------ 5. the step
+def test_train_step_with_the_assignment_kernel_matches_the_hungarian_backend(monkeypatch):
+    """one TrainStep forward on the small fixture model with net.HipBackendAssign against net.HipBackendHungarian: identical pairs in every
+    Hungarian matcher call, the same number of draws, every loss entry EQUAL (the same arithmetic on the same pairs), and the host waits of
+    loss_dict: each matcher call loses its one read and one deferred status read is added.
+    Both runs ask the library for deterministic convolutions: without that the step is not reproducible from run to run with ONE backend --
+    the convolutions of the mask branch (net.mask_head_small_conv, in front of every matcher) return other bits in about one run of three,
+    which moves `loss_mask` by one ulp (72.2514572 / 72.2514648) whichever backend runs; with it ten alternated runs agree in every stage
+    and every entry (docs/measurements.md)."""
+    from hipie_amd.training import net
+    from test_gpu_point_loss import _train_step_case
+    seen = []
+    for name in ("forward", "forward_boxes_only"):
+        def recorded(self, *a, _f=getattr(HungarianMatcher, name), **k):
+            out = _f(self, *a, **k)
+            seen.append(out)
+            return out
+        monkeypatch.setattr(HungarianMatcher, name, recorded)
+    runs = {}
+    monkeypatch.setattr(torch.backends.cudnn, "deterministic", True)
+    for be in (net.HipBackendAssign, net.HipBackendHungarian):
+        z, meta, model, step, batch, targets = _train_step_case("cuda", be)
+        assert step.matcher_bg.ops is be and step.md_criterion.matcher.ops is be
+        assert all(m.defer_status is (be is net.HipBackendAssign) for m in step.matchers)
+        del seen[:]
+        with torch.enable_grad():
+            waits, losses = _host_waits(lambda: step.loss_dict(batch, targets))          # noqa: B023
+        assert step.draws.calls == int(z["n_rand"])                               # the same random draws, in the same order
+        assert all(m.pending == [] for m in step.matchers)
+        runs[be] = ({k: float(v.detach()) for k, v in losses.items()}, [[(q.cpu(), t.cpu()) for q, t in out] for out in seen], waits)
+    (got, got_pairs, got_waits), (want, want_pairs, want_waits) = runs[net.HipBackendAssign], runs[net.HipBackendHungarian]
+    n_calls = len(want_pairs)
+    assert len(got_pairs) == n_calls >= step.cfg["dec_layers"] + 2
+    for i, (g, w) in enumerate(zip(got_pairs, want_pairs)):
+        assert same_pairs(g, w), ("matcher call", i, g, w)
+    print("ASSIGN step: %d Hungarian matcher calls; host waits of loss_dict %d with the assignment kernel, %d with scipy on the host"
+          % (n_calls, got_waits, want_waits))
+    assert sorted(got) == sorted(want)
+    differ = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
+    assert not differ, differ
+    assert got_waits <= want_waits - n_calls + 1, (got_waits, want_waits, n_calls)

@@ -3,7 +3,7 @@
 GPU (configs/training/vit_huge_32g.yaml:1 -- 32 GPUs x 2), the 80-class caption, 8 synthetic targets per image (6 things, 2 stuff), DN_NUMBER 100,
 12544 mask points, random-init weights.  Prints ms for the forward (loss dictionary), the backward, and the peak memory.
     python tools/bench_train_step.py [batch] [steps] [--hand-norms] [--fused-mlp] [--fused-windows] [--fused-losses] [--fused-criteria] [--fused-matching]
-                                                            [--fused-hungarian]
+                                                            [--fused-hungarian] [--fused-assign]
 --hand-norms: net.HipBackendNorms (the ViT / encoder LayerNorms on hipie_add_layernorm / hipie_layernorm_backward) instead of HipBackend
 --fused-mlp:  net.HipBackendMlp (the ViT MLPs / encoder FFNs as one autograd node, the activation recomputed by hipie_act_backward); with
               --hand-norms: net.HipBackendNormsMlp
@@ -17,6 +17,8 @@ GPU (configs/training/vit_huge_32g.yaml:1 -- 32 GPUs x 2), the 80-class caption,
               the targets packed once per step); composes with the other three
 --fused-hungarian: net.HipBackendHungarian (--fused-matching + the cost matrices of the one-to-one Hungarian matchers on hipie_hungarian_cost, one
               device -> host copy per matcher call, the targets packed once per step / criterion call); composes with the other three
+--fused-assign: net.HipBackendAssign (--fused-hungarian + the one-to-one assignment itself on hipie_hungarian_assign: the pairs stay on the device,
+              no host wait per matcher call, the status words of all calls read once per step); composes with the other three
 env: LIB_LINEAR=1 (library fp32 linears), PHASES=1 (synchronised forward phases), TORCH_PROF=1 (top kernels), COUNTS=1 (device launches and host
 waits of one step), HOSTPROF=1 (cProfile of a forward)"""
 import os
@@ -56,8 +58,9 @@ def targets_for(batch, n_things, n_stuff, size, L, dev, seed=0):
 
 def main():
     argv = [a for a in sys.argv[1:] if a not in ("--hand-norms", "--fused-mlp", "--fused-windows", "--fused-losses", "--fused-criteria", "--fused-matching",
-                                                   "--fused-hungarian")]
-    fused_hungarian = "--fused-hungarian" in sys.argv[1:]
+                                                   "--fused-hungarian", "--fused-assign")]
+    fused_assign = "--fused-assign" in sys.argv[1:]
+    fused_hungarian = "--fused-hungarian" in sys.argv[1:] or fused_assign
     fused_matching = "--fused-matching" in sys.argv[1:] or fused_hungarian
     fused_criteria = "--fused-criteria" in sys.argv[1:] and not fused_matching
     fused_losses = "--fused-losses" in sys.argv[1:] and not fused_criteria and not fused_matching
@@ -94,10 +97,13 @@ def main():
         step.criterion.ops = step.md_criterion.ops = step.be
         step.matcher.ops = step.matcher_bg.ops = step.md_criterion.matcher.ops = step.be
     if fused_matching:                                       # the criteria, the matchers' mask costs and the SimOTA matching
-        top = net.HipBackendHungarian if fused_hungarian else net.HipBackendMatching          # the second: + the Hungarian matchers' cost matrices
+        # the second: + the Hungarian matchers' cost matrices; the third: + their assignment
+        top = net.HipBackendAssign if fused_assign else net.HipBackendHungarian if fused_hungarian else net.HipBackendMatching
         step.be = top if step.be is net.HipBackend else type(step.be.__name__ + top.__name__[10:], (step.be, top), {})
         step.criterion.ops = step.md_criterion.ops = step.be
         step.matcher.ops = step.matcher_bg.ops = step.md_criterion.matcher.ops = step.be
+        for m in step.matchers:                              # as TrainStep builds them with such a backend: one status read per step
+            m.defer_status = fused_assign
     if os.environ.get("LIB_LINEAR") == "1":                  # A/B: the big linears on the library instead of the split GEMM Function
 
         class LibBackend(step.be):
