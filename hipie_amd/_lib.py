@@ -103,6 +103,11 @@ SIGNATURES = {
     "hipie_attn_train_backward": [c_p] * 13 + [c_i, c_i, c_p],
     "hipie_attn_train_win_forward": [c_p] * 8 + [c_i, c_i, c_p],
     "hipie_attn_train_win_backward": [c_p] * 13 + [c_i, c_i, c_p],
+    "hipie_attn_pack_kv": [c_p] * 6 + [c_i] * 6 + [c_p],
+    "hipie_attn_pack_q": [c_p, c_p, c_l, c_l, c_l, c_l, c_p, c_l, c_l, c_l, c_l, c_p, c_p] + [c_i] * 6 + [c_f, c_p],
+    "hipie_attn_grad_amax": [c_p, c_l, c_p, c_p],
+    "hipie_attn_pack_grad": [c_p] * 10 + [c_i] * 5 + [c_p],
+    "hipie_attn_unpack_grad": [c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_p, c_l, c_l, c_l, c_p, c_p] + [c_i] * 6 + [c_f, c_p],
     "hipie_selftest": [c_i, c_p, c_p, c_p, c_p],
 }
 

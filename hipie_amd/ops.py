@@ -1631,6 +1631,159 @@ def attn_train_win_backward(q_pair, k_pair, v96_pair, do96_pair, lse, delta):
     return _attn_train_backward(_ATTN_TRAIN_WIN, q_pair, k_pair, v96_pair, do96_pair, lse, delta)
 
 
+# ---- the pack / unpack passes around them (csrc/attn_pack.hip): the attention of a ViT block as one node, functions.VitAttentionFunction
+ATTN_PACK_HD = 80
+
+
+def _attn_pack_dev(who, tensors, dtype=torch.float32):
+    for name, t in tensors:
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise RuntimeError("Not implemented on the CPU (%s: %s must be a CUDA/HIP tensor)" % (who, name))
+        if t.dtype != dtype:
+            raise RuntimeError("%s: %s must be %s, got %s" % (who, name, dtype, t.dtype))
+
+
+def _attn_pack_dense(who, name, t, shape):
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise RuntimeError("%s: %s must be a contiguous %s tensor, got %s" % (who, name, tuple(shape), tuple(t.shape)))
+    return t.data_ptr()
+
+
+def _attn_pack_pair(who, name, pair, shape):
+    _attn_pack_dev(who, ((name + " hi", pair[0]), (name + " lo", pair[1])), torch.float16)
+    return [_attn_pack_dense(who, name, t, shape) for t in pair]
+
+
+def attn_pack_rows(N, padded):
+    """rows per (image, head) item in the planes: N, or N rounded up to 128 (the padded form of functions.fused_attention)"""
+    return -(-N // 128) * 128 if padded else N
+
+
+@_timed("attn_pack_kv")
+def attn_pack_kv(qkv, heads, H, W, cols, padded=False):
+    """hipie_attn_pack_kv: qkv (B', H W, 3 heads 80) fp32 rows of the qkv linear -> (rq (B' heads, N, 80) fp32: the head-major q,
+    the k' pair (B' heads, Np, cols): [k | onehot(n // W) | onehot(n % W) | 0..], the v pair (B' heads, Np, 80)); cols 224 | 128;
+    padded: Np = N rounded up to 128, the padding rows zero but for k' column 80 + H + W = -30000 (else Np = N)"""
+    who = "attn_pack_kv"
+    _attn_pack_dev(who, (("qkv", qkv),))
+    N = H * W
+    if qkv.dim() != 3 or qkv.shape[1] != N or qkv.shape[2] != 3 * heads * ATTN_PACK_HD:
+        raise RuntimeError("%s: qkv (B', %d, %d), got %s" % (who, N, 3 * heads * ATTN_PACK_HD, tuple(qkv.shape)))
+    B = qkv.shape[0]
+    _attn_pack_dense(who, "qkv", qkv, qkv.shape)
+    Np, dev = attn_pack_rows(N, padded), qkv.device
+    rq = torch.empty(B * heads, N, ATTN_PACK_HD, dtype=torch.float32, device=dev)
+    k = (torch.empty(B * heads, Np, cols, dtype=torch.float16, device=dev), torch.empty(B * heads, Np, cols, dtype=torch.float16, device=dev))
+    v = (torch.empty(B * heads, Np, ATTN_PACK_HD, dtype=torch.float16, device=dev), torch.empty(B * heads, Np, ATTN_PACK_HD, dtype=torch.float16, device=dev))
+    rc = _lib.load().hipie_attn_pack_kv(qkv.data_ptr(), rq.data_ptr(), k[0].data_ptr(), k[1].data_ptr(), v[0].data_ptr(), v[1].data_ptr(), B, heads,
+                                        H, W, Np, cols, _stream())
+    _lib.check(rc, "hipie_attn_pack_kv")
+    return rq, k, v
+
+
+def _attn_pack_strides(who, name, t, shape):
+    """element strides of a (BH, H, W, K) view, or of a (BH, N, K) one whose rows n = h W + w have one stride"""
+    if t.dim() == 3 and tuple(t.shape) == (shape[0], shape[1] * shape[2], shape[3]):
+        return (t.stride(0), t.stride(1) * shape[2], t.stride(1), t.stride(2))
+    if tuple(t.shape) != tuple(shape):
+        raise RuntimeError("%s: %s must be %s or (BH, N, K), got %s" % (who, name, tuple(shape), tuple(t.shape)))
+    return tuple(t.stride())
+
+
+@_timed("attn_pack_q")
+def attn_pack_q(rq, rel_h, rel_w, heads, H, W, cols, padded=False):
+    """hipie_attn_pack_q: rq (BH, H W, 80) of attn_pack_kv, rel_h (BH, H, W, H) and rel_w (BH, H, W, W) fp32 -- ANY strided views (also
+    (BH, N, K)): the element strides go to the kernel, nothing is copied -> the q' pair (BH, Np, cols): [rq * 80^-0.5 | rel_h | rel_w | 0..],
+    in the padded form column 80 + H + W = 1 on the real rows and the padding rows zero"""
+    who = "attn_pack_q"
+    _attn_pack_dev(who, (("rq", rq), ("rel_h", rel_h), ("rel_w", rel_w)))
+    N = H * W
+    BH = rq.shape[0]
+    _attn_pack_dense(who, "rq", rq, (BH, N, ATTN_PACK_HD))
+    if BH % heads:
+        raise RuntimeError("%s: %d items are no multiple of %d heads" % (who, BH, heads))
+    sh, sw = _attn_pack_strides(who, "rel_h", rel_h, (BH, H, W, H)), _attn_pack_strides(who, "rel_w", rel_w, (BH, H, W, W))
+    Np = attn_pack_rows(N, padded)
+    q = (torch.empty(BH, Np, cols, dtype=torch.float16, device=rq.device), torch.empty(BH, Np, cols, dtype=torch.float16, device=rq.device))
+    rc = _lib.load().hipie_attn_pack_q(rq.data_ptr(), rel_h.data_ptr(), *sh, rel_w.data_ptr(), *sw, q[0].data_ptr(), q[1].data_ptr(), BH // heads, heads,
+                                       H, W, Np, cols, ATTN_PACK_HD ** -0.5, _stream())
+    _lib.check(rc, "hipie_attn_pack_q")
+    return q
+
+
+@_timed("attn_grad_amax")
+def attn_grad_amax(go):
+    """hipie_attn_grad_amax: max |go| of a dense fp32 device tensor (a multiple of 4 elements) as a one-element device tensor -- the bits of
+    go.abs().amax(), no host wait"""
+    _attn_pack_dev("attn_grad_amax", (("go", go),))
+    _attn_pack_dense("attn_grad_amax", "go", go, go.shape)
+    amax = torch.empty(1, dtype=torch.float32, device=go.device)
+    rc = _lib.load().hipie_attn_grad_amax(go.data_ptr(), go.numel(), amax.data_ptr(), _stream())
+    _lib.check(rc, "hipie_attn_grad_amax")
+    return amax
+
+
+@_timed("attn_pack_grad")
+def attn_pack_grad(go, out, v_pair, scale, heads, H, W):
+    """hipie_attn_pack_grad: go (B', H W, heads 80) fp32 token-major, out (BH, Np, 80) fp32 and the 80-wide v pair (BH, Np, 80) of the forward,
+    scale a one-element device tensor -> (the dO pair (BH, Np, 96) of scale * go, the v pair (BH, Np, 96), delta (BH, Np) fp32 =
+    scale * sum_c go * out); rows >= N zero"""
+    who = "attn_pack_grad"
+    _attn_pack_dev(who, (("go", go), ("out", out), ("scale", scale)))
+    N = H * W
+    if go.dim() != 3 or go.shape[1] != N or go.shape[2] != heads * ATTN_PACK_HD:
+        raise RuntimeError("%s: go (B', %d, %d), got %s" % (who, N, heads * ATTN_PACK_HD, tuple(go.shape)))
+    B = go.shape[0]
+    BH, Np = B * heads, out.shape[1] if out.dim() == 3 else -1
+    _attn_pack_dense(who, "go", go, go.shape)
+    _attn_pack_dense(who, "out", out, (BH, Np, ATTN_PACK_HD))
+    vp = _attn_pack_pair(who, "v", v_pair, (BH, Np, ATTN_PACK_HD))
+    if scale.numel() != 1:
+        raise RuntimeError("%s: scale must have one element" % who)
+    dev = go.device
+    do = (torch.empty(BH, Np, 96, dtype=torch.float16, device=dev), torch.empty(BH, Np, 96, dtype=torch.float16, device=dev))
+    v96 = (torch.empty(BH, Np, 96, dtype=torch.float16, device=dev), torch.empty(BH, Np, 96, dtype=torch.float16, device=dev))
+    delta = torch.empty(BH, Np, dtype=torch.float32, device=dev)
+    rc = _lib.load().hipie_attn_pack_grad(go.data_ptr(), out.data_ptr(), vp[0], vp[1], scale.data_ptr(), do[0].data_ptr(), do[1].data_ptr(),
+                                          v96[0].data_ptr(), v96[1].data_ptr(), delta.data_ptr(), B, heads, H, W, Np, _stream())
+    _lib.check(rc, "hipie_attn_pack_grad")
+    return do, v96, delta
+
+
+@_timed("attn_unpack_grad")
+def attn_unpack_grad(dq, dk, dv, dq_h, dq_w, inv, heads, H, W):
+    """hipie_attn_unpack_grad: dq' (BH, Np, cols), dk, dv (BH, Np, 80) fp32 of the backward op; dq_h, dq_w (dq_w may be None): the rel-pos
+    terms of dq as (BH, H, W, 80) fp32 views with ANY strides that are multiples of 4 in front of the 80 contiguous columns; inv a one-element
+    device tensor -> dqkv (B', H W, 3 heads 80) fp32: q = (dq'[..., :80] * 80^-0.5 + dq_h + dq_w) * inv, k = dk * inv, v = dv * inv"""
+    who = "attn_unpack_grad"
+    _attn_pack_dev(who, (("dq", dq), ("dk", dk), ("dv", dv), ("dq_h", dq_h), ("dq_w", dq_w), ("inv", inv)))
+    N = H * W
+    if dq.dim() != 3 or dq.shape[0] % heads:
+        raise RuntimeError("%s: dq' (BH, Np, cols), got %s" % (who, tuple(dq.shape)))
+    BH, Np, cols = dq.shape
+    _attn_pack_dense(who, "dq", dq, dq.shape)
+    _attn_pack_dense(who, "dk", dk, (BH, Np, ATTN_PACK_HD))
+    _attn_pack_dense(who, "dv", dv, (BH, Np, ATTN_PACK_HD))
+    strides = []
+    for name, t in (("dq_h", dq_h), ("dq_w", dq_w)):
+        if t is None:
+            strides.append((0, 0, 0))
+            continue
+        if tuple(t.shape) != (BH, H, W, ATTN_PACK_HD) or t.stride(3) != 1:
+            raise RuntimeError("%s: %s must be (%d, %d, %d, 80) with contiguous columns, got %s" % (who, name, BH, H, W, tuple(t.shape)))
+        strides.append(tuple(t.stride()[:3]))
+    if inv.numel() != 1:
+        raise RuntimeError("%s: inv must have one element" % who)
+    dqkv = torch.empty(BH // heads, N, 3 * heads * ATTN_PACK_HD, dtype=torch.float32, device=dq.device)
+    rc = _lib.load().hipie_attn_unpack_grad(dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), dq_h.data_ptr(), *strides[0],
+                                            None if dq_w is None else dq_w.data_ptr(), *strides[1], inv.data_ptr(), dqkv.data_ptr(), BH // heads, heads,
+                                            H, W, Np, cols, ATTN_PACK_HD ** -0.5, _stream())
+    _lib.check(rc, "hipie_attn_unpack_grad")
+    return dqkv
+
+
 @_timed("fill_rows")
 def fill_rows(dst, rows, src_row):
     """dst[rows[i]] = src_row for every i (hipie_fill_rows): dst (R, W) contiguous device tensor, rows int32 (n,), src_row (W,) of dst's

@@ -289,6 +289,109 @@ def window_attention(qa, ka, v):
     return WindowAttentionFunction.apply(qa, ka, v) if window_attention_ok(qa, ka, v) else None
 
 
+def _rows_of_grid_row(t):
+    """(BH, H, W, C) -> (H, BH W, C), the operand of a rel-pos product batched over the grid rows h.  The rows (item, w) of one grid row do
+    not merge into one stride: a copy"""
+    BH, H, W, C = t.shape
+    return t.permute(1, 0, 2, 3).reshape(H, BH * W, C)
+
+
+def _rows_of_grid_column(t):
+    """(BH, H, W, C) -> (W, BH H, C), the operand of a rel-pos product batched over the grid columns w.  The rows (item, h) of one grid column
+    merge into ONE stride whenever an item's rows are dense (stride(0) == H * stride(1)): a view, which the library product takes as it is"""
+    BH, H, W, C = t.shape
+    return t.permute(2, 0, 1, 3).reshape(W, BH * H, C)
+
+
+class VitAttentionFunction(torch.autograd.Function):
+    """The attention of a ViT block between its two linears as ONE node: qkv (B', N, 3 heads 80), the rows of the qkv linear, and the
+    gathered rel-pos tables Rh (H, H, 80), Rw (W, W, 80) of net.get_rel_pos -> (B', N, heads 80), the rows of the proj linear.  What
+    net.vit_attention composes from reshape / permute / unbind, the scale, two einsums, two cats and FusedAttentionFunction /
+    WindowAttentionFunction (three f16_pair passes forward; amax, delta, two f16_pair passes, three rescales and a pad backward, and
+    autograd's undoing of the views at full qkv size) is here
+        forward   ops.attn_pack_kv -> two library batched products on rq -> ops.attn_pack_q -> the forward op -> one copy to token-major
+        backward  ops.attn_grad_amax -> ops.attn_pack_grad -> the backward op -> four (six with table gradients) batched products on strided
+                  views of dq' -> ops.attn_unpack_grad, which writes d(qkv) once
+    with the operand planes, the bits and the attention kernels of the composition.  fp32 q' / k' are never built.  Saved: the q' / k' pairs,
+    the 80-wide v pair, out, lse, Rh, Rw, and rq only when a table needs its gradient -- nothing is a view of qkv.
+    cols 224: hipie_attn_train_* (N a multiple of 128, or `padded` to one as functions.fused_attention pads); cols 128: hipie_attn_train_win_*."""
+
+    @staticmethod
+    def forward(ctx, qkv, Rh, Rw, heads, H, W, cols, padded):
+        B, N, BH = qkv.shape[0], H * W, qkv.shape[0] * heads
+        rq, kp, vp = ops.attn_pack_kv(qkv.contiguous(), heads, H, W, cols, padded)
+        a_h, a_w = _rows_of_grid_row(rq.view(BH, H, W, 80)), _rows_of_grid_column(rq.view(BH, H, W, 80))
+        # rel_h[b, h, w, k] = rq[b, h, w, :] . Rh[h, k, :] and rel_w[b, h, w, k] = rq[b, h, w, :] . Rw[w, k, :], left in the layouts of the
+        # products: pack_q reads them through their strides
+        rel_h = torch.bmm(a_h, Rh.transpose(1, 2)).view(H, BH, W, H).permute(1, 0, 2, 3)
+        rel_w = torch.bmm(a_w, Rw.transpose(1, 2)).view(W, BH, H, W).permute(1, 2, 0, 3)
+        qp = ops.attn_pack_q(rq, rel_h, rel_w, heads, H, W, cols, padded)
+        out, lse = (ops.attn_train_forward if cols == 224 else ops.attn_train_win_forward)(qp, kp, vp)
+        tables = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        ctx.save_for_backward(qp[0], qp[1], kp[0], kp[1], vp[0], vp[1], out, lse, Rh, Rw, rq if tables else None)
+        ctx.geom = (heads, H, W, cols)
+        return out.view(B, heads, -1, 80)[:, :, :N].permute(0, 2, 1, 3).reshape(B, N, heads * 80)
+
+    @staticmethod
+    def backward(ctx, go):
+        qh, ql, kh, kl, vh, vl, out, lse, Rh, Rw, rq = ctx.saved_tensors
+        heads, H, W, cols = ctx.geom
+        BH, Np = out.shape[:2]
+        N = H * W
+        go = go.reshape(BH // heads, N, heads * 80).float().contiguous()
+        # dO enters the kernels as fp16 pairs scaled by a power of two (_attention_backward); the maximum comes from one kernel, the scalar
+        # expression stays on its one element: no host wait
+        scale = torch.exp2(torch.floor(torch.log2(16.0 / ops.attn_grad_amax(go).clamp_min(1e-30))))
+        inv = 1.0 / scale
+        dop, v96, delta = ops.attn_pack_grad(go, out, (vh, vl), scale, heads, H, W)
+        dq, dk, dv = (ops.attn_train_backward if cols == 224 else ops.attn_train_win_backward)((qh, ql), (kh, kl), v96, dop, lse, delta)
+        d4 = dq[:, :N].view(BH, H, W, cols)
+        g_h, g_w = _rows_of_grid_row(d4[..., 80:80 + H]), _rows_of_grid_column(d4[..., 80 + H:80 + H + W])
+        # the rel-pos terms of dq, each in the layout of its product; unpack_grad adds them through their strides
+        dq_h = torch.bmm(g_h, Rh).view(H, BH, W, 80).permute(1, 0, 2, 3)
+        dq_w = torch.bmm(g_w, Rw).view(W, BH, H, 80).permute(1, 2, 0, 3)
+        dqkv = ops.attn_unpack_grad(dq, dk, dv, dq_h, dq_w, inv, heads, H, W)
+        dRh = dRw = None
+        if rq is not None:
+            if ctx.needs_input_grad[1]:
+                dRh = torch.bmm(g_h.transpose(1, 2), _rows_of_grid_row(rq.view(BH, H, W, 80))) * inv
+            if ctx.needs_input_grad[2]:
+                dRw = torch.bmm(g_w.transpose(1, 2), _rows_of_grid_column(rq.view(BH, H, W, 80))) * inv
+        return dqkv, dRh, dRw, None, None, None, None, None
+
+
+def packed_attention_instance(H, W, windows=False):
+    """(operand columns, padded) of the kernel instance VitAttentionFunction runs an H x W grid on, or None when none covers it"""
+    N = H * W
+    if N >= 128 and N % 128 == 0 and 80 + H + W <= 224:
+        return 224, False
+    if N % 128 and N >= 1024 and 80 + H + W + 1 <= 224:
+        return 224, True
+    if windows and 2 <= N <= 256 and 80 + H + W <= 128:
+        return 128, False
+    return None
+
+
+def vit_attention_packed(qkv, Rh, Rw, heads, H, W, windows=False):
+    """the attention of a ViT block from the rows of its qkv linear, qkv (B', H W, 3 heads 80), and the gathered rel-pos tables Rh (H, H, 80),
+    Rw (W, W, 80) as one node (VitAttentionFunction) -> (B', H W, heads 80), or None when not covered (the caller's composition runs).
+    Covered: device fp32, head width 80, net.FOLD_REL_POS on, and
+        the global instance      H W a multiple of 128 and 80 + H + W <= 224
+        its padded form          H W >= 1024 and 80 + H + W + 1 <= 224 (the padding of functions.fused_attention)
+        the window instance      only with `windows`: 2 <= H W <= 256 and 80 + H + W <= 128"""
+    from . import net
+    N = H * W
+    tensors = (qkv, Rh, Rw)
+    if not (net.FOLD_REL_POS and all(t.is_cuda and t.dtype == torch.float32 for t in tensors) and qkv.dim() == 3 and heads >= 1
+            and tuple(qkv.shape[1:]) == (N, 3 * heads * 80) and qkv.shape[0] >= 1 and tuple(Rh.shape) == (H, H, 80) and tuple(Rw.shape) == (W, W, 80)):
+        return None
+    inst = packed_attention_instance(H, W, windows)
+    if inst is None:
+        return None
+    cols, padded = inst
+    return VitAttentionFunction.apply(qkv, Rh, Rw, heads, H, W, cols, padded)
+
+
 class AddLayerNormFunction(torch.autograd.Function):
     """s = x + delta;  y = LayerNorm(s) * weight + bias  -> (s, y): a residual add and the LayerNorm that follows it (Block.forward,
     backbone/vit.py:212-230; the post-norms of DeformableTransformerEncoderLayer.forward, deformable_transformer_dino.py:384-394) as one

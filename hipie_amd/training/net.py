@@ -6,9 +6,10 @@ linears, LayerNorm / GroupNorm, the softmax attentions and the convolutions run 
 torch.autograd providing their backward (opt-in, HipBackendNorms: the LayerNorms of the ViT blocks and of the encoder layers on
 hipie_add_layernorm / hipie_layernorm_backward; opt-in, HipBackendMlp: their MLPs / FFNs as one node with the activation on
 hipie_act_forward / hipie_act_backward; opt-in, HipBackendWindows: the attention of the windowed ViT blocks on
-hipie_attn_train_win_forward / _backward; opt-in, HipBackendLosses: the point-sampled mask losses and the token focal loss of the two
-criteria on hipie_point_mask_loss_* / hipie_token_focal_*; opt-in, HipBackendCriteria: on top of those the importance point selection of the
-criteria and the mask costs of the matchers on hipie_uncertain_points / hipie_mask_match_cost; opt-in, HipBackendMatching: on top of those
+hipie_attn_train_win_forward / _backward; opt-in, HipBackendPackedAttention / HipBackendPackedWindows: the attention of a ViT block between its
+two linears as one node, its operands packed and unpacked by hipie_attn_pack_*; opt-in, HipBackendLosses: the point-sampled mask losses and
+the token focal loss of the two criteria on hipie_point_mask_loss_* / hipie_token_focal_*; opt-in, HipBackendCriteria: on top of those the
+importance point selection of the criteria and the mask costs of the matchers on hipie_uncertain_points / hipie_mask_match_cost; opt-in, HipBackendMatching: on top of those
 the SimOTA matching of the foreground queries on hipie_ota_cost / hipie_ota_assign; opt-in, HipBackendHungarian: on top of those the cost
 matrices of the one-to-one Hungarian matchers on hipie_hungarian_cost; opt-in, HipBackendAssign: on top of those the assignment itself on
 hipie_hungarian_assign, the pairs staying on the device).
@@ -129,6 +130,30 @@ class HipBackendWindows(HipBackend):
         formulation runs.  Asked only where fused_attention declined."""
         from .functions import window_attention
         return window_attention(qa, ka, v)
+
+
+class HipBackendPackedAttention(HipBackend):
+    """HipBackend + the attention of the GLOBAL ViT blocks as ONE autograd node from the rows of the qkv linear to the rows of the proj linear
+    (functions.VitAttentionFunction): the operands of the fused kernels are packed from / unpacked into the token-major rows by
+    hipie_attn_pack_* (csrc/attn_pack.hip) instead of a chain of torch passes, the attention kernels and their operand bits being the same.
+    The windowed blocks keep the materialised formulation.  Opt-in: TrainStep's default stays HipBackend."""
+
+    @staticmethod
+    def packed_attention(qkv, Rh, Rw, heads, H, W):
+        """qkv (B', H W, 3 heads hd), Rh (H, H, hd), Rw (W, W, hd) of get_rel_pos -> (B', H W, heads hd), or None: vit_attention's own
+        composition runs (functions.vit_attention_packed names what is covered)"""
+        from .functions import vit_attention_packed
+        return vit_attention_packed(qkv, Rh, Rw, heads, H, W, windows=False)
+
+
+class HipBackendPackedWindows(HipBackendPackedAttention, HipBackendWindows):
+    """HipBackendPackedAttention + the same node over the short-sequence kernels of HipBackendWindows for the WINDOWED blocks (a block the
+    node does not cover falls to HipBackendWindows' composition)"""
+
+    @staticmethod
+    def packed_attention(qkv, Rh, Rw, heads, H, W):
+        from .functions import vit_attention_packed
+        return vit_attention_packed(qkv, Rh, Rw, heads, H, W, windows=True)
 
 
 class HipBackendAll(HipBackendNorms, HipBackendMlp, HipBackendWindows):
@@ -367,9 +392,16 @@ def vit_attention(x, sd, p, heads, be=None):
     passes over 2 GB per block)."""
     B, H, W, C = x.shape
     hd = C // heads
-    qkv = _blin(x, sd, p + "qkv.", be).reshape(B, H * W, 3, heads, -1).permute(2, 0, 3, 1, 4)
-    q, k, v = qkv.reshape(3, B * heads, H * W, -1).unbind(0)
+    qkv = _blin(x, sd, p + "qkv.", be)
     Rh, Rw = get_rel_pos(H, H, sd[p + "rel_pos_h"]), get_rel_pos(W, W, sd[p + "rel_pos_w"])
+    packed = getattr(be, "packed_attention", None)
+    if packed is not None:
+        # HipBackendPackedAttention: everything between the two linears as one node (functions.VitAttentionFunction, csrc/attn_pack.hip)
+        o = packed(qkv.reshape(B, H * W, -1), Rh, Rw, heads, H, W)
+        if o is not None:
+            return _blin(o.view(B, H, W, -1), sd, p + "proj.", be)
+    qkv = qkv.reshape(B, H * W, 3, heads, -1).permute(2, 0, 3, 1, 4)
+    q, k, v = qkv.reshape(3, B * heads, H * W, -1).unbind(0)
     rq = q.reshape(B * heads, H, W, hd)
     rel_h = torch.einsum("bhwc,hkc->bhwk", rq, Rh).reshape(B * heads, H * W, H)
     rel_w = torch.einsum("bhwc,wkc->bhwk", rq, Rw).reshape(B * heads, H * W, W)

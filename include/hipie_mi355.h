@@ -790,6 +790,40 @@ int hipie_attn_train_win_backward(const void* q_hi, const void* q_lo, const void
                                   const void* do_hi, const void* do_lo, const void* lse, const void* delta, void* dq, void* dk, void* dv,
                                   int BH, int N, void* stream);
 
+/*
+ * The operand pack / unpack passes around the four entries above (csrc/attn_pack.hip), which make the attention of a ViT block of the training
+ * step ONE node from the qkv rows to the token-major output: what Attention.forward (hipie/backbone/vit.py:67-83) and add_decomposed_rel_pos
+ * (hipie/backbone/utils.py:96-125) do between the qkv Linear and the attention product -- the reshape / permute / unbind of qkv, the scale,
+ * the two concatenations -- and what autograd does to undo them.  Shared geometry: B images or windows, heads, an H x W grid, N = H W rows per
+ * (image, head) item, head width 80; the planes hold Np rows per item: Np = N, or N rounded up to 128 (the padded form: padding keys are
+ * masked through operand column cq = 80 + H + W, which is 1 in q' on real rows and -30000 in k' on padding rows; padding rows are zero
+ * otherwise); cols = 224 (csrc/attn_train.hip) | 128 (csrc/attn_train_win.hip) operand columns.  Planes are the fp16 pairs of hipie_to_f16_pair,
+ * bit for bit.  Every pointer 16-byte aligned.  HIPIE_EINVAL without a launch for a null pointer, a non-positive size, another cols, an Np that
+ * is neither of the two, 80 + H + W (+ 1 when padded) > cols, or a misaligned operand.
+ *   pack_kv:     qkv (B, N, 3, heads, 80) f32 -> rq (B heads, N, 80) f32, the head-major q; the k' pair (B heads, Np, cols): [k | onehot(n / W) |
+ *                onehot(n % W) | 0..]; the v pair (B heads, Np, 80)
+ *   pack_q:      rq, rel_h (B heads, H, W, H) and rel_w (B heads, H, W, W) f32 given with their four ELEMENT strides (whatever layout the
+ *                library product left) -> the q' pair (B heads, Np, cols): [rq * qscale | rel_h | rel_w | 0..]
+ *   grad_amax:   max |go| over n f32 values (n a multiple of 4) -> one device float; the bits of a max reduction in any order
+ *   pack_grad:   go (B, N, heads, 80) f32 token-major, out (B heads, Np, 80) f32, the 80-wide v pair, scale (device float) -> the dO pair
+ *                (B heads, Np, 96) of scale * go, the v pair (B heads, Np, 96), columns 80.. zero; delta (B heads, Np) f32 = scale * sum_c go * out
+ *                in a fixed order; padding rows zero
+ *   unpack_grad: dq' (B heads, Np, cols), dk, dv (B heads, Np, 80) f32; dq_h and dq_w (dq_w may be NULL), the rel-pos terms of dq as
+ *                (B heads, H, W, 80) f32 with three element strides each (multiples of 4; the 80 columns contiguous); inv (device float)
+ *                -> dqkv (B, N, 3, heads, 80) f32: q = (dq'[:80] * qscale + dq_h + dq_w) * inv, k = dk * inv, v = dv * inv; rows >= N are dropped
+ */
+int hipie_attn_pack_kv(const void* qkv, void* rq, void* k_hi, void* k_lo, void* v_hi, void* v_lo, int B, int heads, int H, int W, int Np, int cols,
+                       void* stream);
+int hipie_attn_pack_q(const void* rq, const void* rel_h, int64_t hs_b, int64_t hs_h, int64_t hs_w, int64_t hs_k, const void* rel_w, int64_t ws_b,
+                      int64_t ws_h, int64_t ws_w, int64_t ws_k, void* q_hi, void* q_lo, int B, int heads, int H, int W, int Np, int cols, float qscale,
+                      void* stream);
+int hipie_attn_grad_amax(const void* go, int64_t n, void* amax, void* stream);
+int hipie_attn_pack_grad(const void* go, const void* out, const void* v_hi, const void* v_lo, const void* scale, void* do_hi, void* do_lo,
+                         void* v96_hi, void* v96_lo, void* delta, int B, int heads, int H, int W, int Np, void* stream);
+int hipie_attn_unpack_grad(const void* dq, const void* dk, const void* dv, const void* dq_h, int64_t hs_b, int64_t hs_h, int64_t hs_w,
+                           const void* dq_w, int64_t ws_b, int64_t ws_h, int64_t ws_w, const void* inv, void* dqkv, int B, int heads, int H, int W,
+                           int Np, int cols, float qscale, void* stream);
+
 /* dst + rows[i] * ld_bytes <- the row_bytes bytes at src_row, for i < n_rows (negative entries are skipped): one constant row into a
  * listed set of rows.  Used to write the HL8 qkv BIAS row into the padding rows of a window-layout qkv buffer -- the qkv of a padding token
  * of window_partition is the bias, its LayerNorm output being zero (hipie/backbone/utils.py:29-37, vit.py:67-71).  16-byte units. */
