@@ -15,6 +15,7 @@ c_p = ctypes.c_void_p
 c_i = ctypes.c_int
 c_l = ctypes.c_int64
 c_f = ctypes.c_float
+c_d = ctypes.c_double
 
 # name -> argtypes, in the order of include/hipie_mi355.h
 SIGNATURES = {
@@ -62,6 +63,10 @@ SIGNATURES = {
     "hipie_hungarian_cost_ws_bytes": [c_l, c_l],
     "hipie_hungarian_assign": [c_p] * 8 + [c_l, c_l, c_i, c_i, c_l, c_p],
     "hipie_hungarian_assign_ws_bytes": [c_l, c_l],
+    "hipie_optim_chunk": [],
+    "hipie_optim_norm_ws_bytes": [c_l],
+    "hipie_optim_grad_norm": [c_p, c_l, c_p, c_l, c_p, c_l, c_f, c_p, c_p],
+    "hipie_optim_adamw_step": [c_p, c_l, c_p, c_l, c_p, c_p, c_p, c_p, c_i, c_d, c_d, c_d, c_p, c_d, c_f, c_i, c_p],
     "hipie_add_layernorm_sum": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_f, c_i, c_i, c_i, c_p],
     "hipie_add_layernorm_rows": [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_f, c_i, c_i, c_i, c_p, c_p, c_p],
     "hipie_batched_nms": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_i, c_p],
@@ -145,7 +150,7 @@ def load():
                                                       "hipie_layernorm_backward_ws_bytes", "hipie_act_backward_ws_bytes", "hipie_point_mask_loss_ws_bytes",
                                                       "hipie_token_focal_ws_bytes", "hipie_uncertain_points_ws_bytes",
                                                       "hipie_mask_match_cost_ws_bytes", "hipie_ota_match_ws_bytes", "hipie_hungarian_cost_bytes",
-                                                      "hipie_hungarian_cost_ws_bytes", "hipie_hungarian_assign_ws_bytes") else ctypes.c_int)
+                                                      "hipie_hungarian_cost_ws_bytes", "hipie_hungarian_assign_ws_bytes", "hipie_optim_norm_ws_bytes") else ctypes.c_int)
     _lib = lib
     return lib
 

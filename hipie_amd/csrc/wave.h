@@ -74,6 +74,11 @@ __device__ __forceinline__ float wave_sum(float x) {
   for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
   return x;
 }
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+  return x;
+}
 
 // ---- paired fp16 hi / lo split ------------------------------------------------------------------------------------------------------
 // two values -> one VGPR of fp16 hi halves and one of lo halves: hi = fp16(x) for the pair in one v_cvt_pk_f16_f32, lo = fp16(x - hi)

@@ -4,6 +4,8 @@ Mirrors the reference's operator boundary: ``ms_deform_attn_forward
 behaviour of the pybind module ``MultiScaleDeformableAttention`` (contiguity / device checks raise RuntimeError, CPU
 tensors raise "Not implemented on the CPU", ops/src/ms_deform_attn.h:28-39).  All functions are inference-only.
 """
+import ctypes
+
 import torch
 
 from . import _lib
@@ -1192,6 +1194,74 @@ def hungarian_assign(costs, n_tgt, t_off, sum_t, Q, Tmax, ws=None):
                                     pairs[1].data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), B, Q, Tmax, sum_t, _stream())
     _lib.check(rc, "hipie_hungarian_assign")
     return pairs[0], pairs[1], status
+
+
+OPTIM_MAX_GROUPS = 8
+OPTIM_SEGMENT_WORDS = 6          # int64 words of a segment record: p, g, m, v, numel, group
+
+
+def optim_chunk():
+    """elements per chunk-map entry of the optimizer kernels (hipie_optim_chunk)"""
+    return int(_lib.load().hipie_optim_chunk())
+
+
+def optim_norm_ws_bytes(n_chunks):
+    return int(_lib.load().hipie_optim_norm_ws_bytes(int(n_chunks)))
+
+
+def _optim_tables(who, table, cmap):
+    """the segment table (n_seg, 6) int64 and the chunk map (n_chunks, 2) int64 of the optimizer kernels: layout, then device"""
+    for t, name, words in ((table, "table", OPTIM_SEGMENT_WORDS), (cmap, "cmap", 2)):
+        if t.dim() != 2:
+            raise RuntimeError("%s must be (n, %d), got %s" % (name, words, tuple(t.shape)))
+        _layout_as(t, name, torch.int64, (int(t.shape[0]), words))
+    _on_device(table=table, cmap=cmap)
+    if cmap.device != table.device:
+        raise RuntimeError("%s: table and cmap on different devices" % who)
+    return int(table.shape[0]), int(cmap.shape[0])
+
+
+@_timed("optim_grad_norm")
+def optim_grad_norm(table, cmap, grad_scale=1.0, ws=None):
+    """the 2-norm of grad_scale x (every gradient of the segment table) as a 0-dim fp32 device tensor (hipie_optim_grad_norm: float64 sums in a
+    fixed order, bit-reproducible, nothing read by the host).  table (n_seg, 6) int64: the records { p, g, m, v addresses, numel, group } (g == 0: no
+    gradient); cmap (n_chunks, 2) int64: (segment, element offset) per optim_chunk() elements.  The ADDRESSES in the table are the caller's
+    promise: the tensors behind them stay alive until this returns (the launches are then ordered on the stream).  ws: uint8 tensor of at least
+    optim_norm_ws_bytes(n_chunks) elements, or None: allocated.  Two launches."""
+    n_seg, n_chunks = _optim_tables("optim_grad_norm", table, cmap)
+    out = torch.empty((), dtype=torch.float32, device=table.device)
+    if n_seg == 0 or n_chunks == 0:
+        return out.zero_()
+    lib = _lib.load()
+    ws = _workspace(ws, int(lib.hipie_optim_norm_ws_bytes(n_chunks)), table.device, "optim_grad_norm")
+    _on_device(ws=ws)
+    rc = lib.hipie_optim_grad_norm(table.data_ptr(), n_seg, cmap.data_ptr(), n_chunks, ws.data_ptr(), ws.numel(), float(grad_scale), out.data_ptr(), _stream())
+    _lib.check(rc, "hipie_optim_grad_norm")
+    return out
+
+
+@_timed("optim_adamw_step")
+def optim_adamw_step(table, cmap, steps, bc, group_lr, group_wd, betas, eps, norm=None, max_norm=0.0, grad_scale=1.0, write_grads=False):
+    """one AdamW step of every tensor of the segment table that has a gradient, in place (hipie_optim_adamw_step; table, cmap as for
+    optim_grad_norm): steps (n_seg,) int32 the per-parameter step counts and bc (n_seg, 2) fp32 their bias corrections, both on the device and
+    advanced by the call; group_lr, group_wd: host sequences of at most 8 floats, indexed by a record's group; betas (b1, b2), eps: host floats.
+    norm: the 0-dim device tensor of optim_grad_norm -- the gradients enter as g x grad_scale x min(max_norm / (norm + 1e-6), 1) -- or None: no
+    clipping.  write_grads: the clipped gradients are also written back.  Nothing is read by the host.  Two launches."""
+    n_seg, n_chunks = _optim_tables("optim_adamw_step", table, cmap)
+    _layout_as(steps, "steps", torch.int32, (n_seg,))
+    _layout_as(bc, "bc", torch.float32, (n_seg, 2))
+    if norm is not None:
+        _layout_as(norm, "norm", torch.float32, ())
+    _on_device(steps=steps, bc=bc, norm=norm)
+    n_groups = len(group_lr)
+    if len(group_wd) != n_groups or not 1 <= n_groups <= OPTIM_MAX_GROUPS:
+        raise RuntimeError("optim_adamw_step: %d learning rates, %d weight decays: one each for 1 to %d groups" % (n_groups, len(group_wd), OPTIM_MAX_GROUPS))
+    arr = ctypes.c_double * n_groups
+    lr, wd = arr(*[float(x) for x in group_lr]), arr(*[float(x) for x in group_wd])
+    rc = _lib.load().hipie_optim_adamw_step(table.data_ptr(), n_seg, cmap.data_ptr(), n_chunks, steps.data_ptr(), bc.data_ptr(), lr, wd, n_groups,
+                                            float(betas[0]), float(betas[1]), float(eps), None if norm is None else norm.data_ptr(),
+                                            float(max_norm), float(grad_scale), int(bool(write_grads)), _stream())
+    _lib.check(rc, "hipie_optim_adamw_step")
 
 
 @_timed("add_layernorm")

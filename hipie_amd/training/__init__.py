@@ -11,7 +11,8 @@
   matcher.py, criterion.py, dn.py, targets.py, weights.py, boxes.py
                the host logic: matching costs + assignment (Hungarian, SimOTA), the set-prediction losses of both heads, contrastive
                de-noising queries, target preparation, loss weighting -- each pinned against the reference's classes;
-  ddp.py       bucketed gradient all-reduce over RCCL (what create_ddp_model does for the reference).
+  ddp.py       bucketed gradient all-reduce over RCCL (what create_ddp_model does for the reference);
+  optim.py     gradient clipping + AdamW as two passes over memory (csrc/optim_step.hip), opt-in: build_optimizer(model, hand=True).
 Every function that draws random numbers in the reference takes them as an argument (or from a ``draw`` callable), so results compare
 with the reference entry for entry."""
 from .boxes import box_cxcywh_to_xyxy, generalized_box_iou, paired_giou_loss, paired_iou      # noqa: F401
@@ -22,3 +23,4 @@ from .weights import maskdino_loss_plan, weighted_merge                         
 from .targets import prepare_targets, split_things_stuff                                       # noqa: F401
 from .ddp import GradientBuckets                                                               # noqa: F401
 from .step import TrainStep, build_optimizer, train_iteration                                  # noqa: F401
+from .optim import HipAdamW                                                                    # noqa: F401

@@ -297,14 +297,18 @@ class TrainStep:
         return out
 
 
-def build_optimizer(model, base_lr=1e-4, backbone_multiplier=0.1, weight_decay=0.01):
+def build_optimizer(model, base_lr=1e-4, backbone_multiplier=0.1, weight_decay=0.01, hand=False):
     """SOLVER of configs/training/*.yaml: AdamW, BASE_LR 1e-4, BACKBONE_MULTIPLIER 0.1, WEIGHT_DECAY 0.01 (the text encoder is frozen:
-    MODEL.FREEZE_TEXT_ENCODER)."""
+    MODEL.FREEZE_TEXT_ENCODER).  hand=True (opt-in): the same two groups on training/optim.py's HipAdamW, whose clip_and_step train_iteration
+    calls in place of clip_grad_norm_ + step()."""
     bb, rest = [], []
     for n, p in model.named_parameters():
         if not p.requires_grad or n.startswith("text_encoder."):
             continue
         (bb if ".backbone.0." in n else rest).append(p)
+    if hand:
+        from .optim import HipAdamW
+        return HipAdamW([{"params": rest, "lr": base_lr}, {"params": bb, "lr": base_lr * backbone_multiplier}], lr=base_lr, weight_decay=weight_decay)
     # the multi-tensor (`fused`) implementation on the device: the same update in a handful of launches instead of several per parameter
     # (1241 tensors: 64 -> 13 ms per iteration at ViT-H)
     fused = bool(rest or bb) and all(p.is_cuda for p in rest + bb)
@@ -325,7 +329,10 @@ def train_iteration(step, optimizer, batched_inputs, targets, buckets=None, clip
         total.backward()
     if buckets is not None:
         buckets.finish()
-    params = [p for g in optimizer.param_groups for p in g["params"] if p.grad is not None]
-    norm = torch.nn.utils.clip_grad_norm_(params, clip_norm) if clip_norm else None
-    optimizer.step()
+    if hasattr(optimizer, "clip_and_step"):                                              # training/optim.py: norm, clip and update as two passes
+        norm = optimizer.clip_and_step(clip_norm if clip_norm else None)
+    else:
+        params = [p for g in optimizer.param_groups for p in g["params"] if p.grad is not None]
+        norm = torch.nn.utils.clip_grad_norm_(params, clip_norm) if clip_norm else None
+        optimizer.step()
     return {k: v.detach() for k, v in losses.items()}, norm

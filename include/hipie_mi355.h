@@ -518,6 +518,46 @@ int hipie_hungarian_assign(const float* C, const int* cost_status, const int* n_
 int64_t hipie_hungarian_assign_ws_bytes(int64_t Q, int64_t sum_t);
 
 /*
+ * The tail of a training iteration behind backward() as two passes over memory (csrc/optim_step.hip): the total gradient norm, and the clip
+ * and the AdamW update of EVERY parameter tensor in one launch; fp32, nothing is read by the host, bit-reproducible from call to call.
+ * Replaces: torch.nn.utils.clip_grad_norm_ inside FullModelGradientClippingOptimizer.step (projects/HIPIE/train_net.py:199-228, with
+ *           scale_norm's multiply of every gradient by 1 / ACC_ITER in front of it): the per-tensor norms, their stack and norm, the
+ *           coefficient and the multiply that reads and writes every gradient -- here the coefficient is a scalar of the update;
+ *           torch.optim.AdamW as used by projects/HIPIE/train_net.py:189-239: the multi-tensor step over 1241 tensors, with the
+ *           per-parameter learning-rate groups of :167-187 as a group index per tensor.
+ *   table: n_seg records of 48 bytes on the device, one per parameter tensor: { float* p, g, m, v; int64 numel; int32 group; int32 0 }.
+ *     g == NULL: the tensor has no gradient this step -- it adds nothing to the norm and the update skips it whole (no weight decay, m, v
+ *     and its step count untouched, as torch does).  Any 4-byte aligned addresses: a tensor whose address is 16-byte aligned is accessed
+ *     16 bytes at a time, another one 4 bytes at a time (gradients that are views into a flat bucket), per tensor.
+ *   map: n_chunks pairs { int64 segment; int64 offset } on the device: the elements [offset, min(offset + hipie_optim_chunk(), numel)) of the
+ *     segment, every element of every segment exactly once, offsets multiples of hipie_optim_chunk().  A function of the sizes alone.  An
+ *     entry outside its segment or the table is skipped.
+ *   hipie_optim_grad_norm: *norm = (float)(sqrt(sum of g^2) x |grad_scale|): squares and sums in float64, one partial sum per chunk in its
+ *     own slot of `ws` (8-byte aligned, hipie_optim_norm_ws_bytes(n_chunks) bytes), every sum in a fixed order that depends on neither the
+ *     grid nor the alignment of a gradient; no atomics.  Two launches.
+ *   hipie_optim_adamw_step: steps (n_seg) int32, the per-parameter step counts, and bc (n_seg, 2) f32 live on the device: every segment with
+ *     a gradient gets t = ++steps[s] and bc[s] = (1 - beta1^t, sqrt(1 - beta2^t)), computed in float64.  Then per element, in fp32 without
+ *     contraction and in the order of torch's single-tensor AdamW:
+ *       c = norm ? min(max_norm / (*norm + 1e-6), 1) : 1 (a NaN stays a NaN, as torch.clamp keeps it);  g' = (g x grad_scale) x c;
+ *       p = p x (1 - lr wd);  m = lerp(m, g', 1 - beta1);  v = v x beta2 + ((1 - beta2) g') g';  p = p - (lr / bc1) (m / (sqrt(v) / sqrt(bc2) + eps))
+ *     group_lr, group_wd: n_groups <= 8 doubles each on the HOST, read during the call and passed to the kernel by value (a scheduler that
+ *     changes lr every iteration uploads nothing).  norm: the device float of hipie_optim_grad_norm, or NULL for no clipping (max_norm is
+ *     then ignored).  write_grads != 0: g' is also written back into g.  Two launches.
+ * Refused (-22): a negative count, more than 8 groups, a beta outside [0, 1), eps <= 0, max_norm < 0 with a norm, a null table, map,
+ *     workspace, norm output, steps, bc or group array, a misaligned table, map or workspace, a workspace that is too small.
+ *     n_seg == 0 or n_chunks == 0: returns 0 without a launch, null pointers allowed.
+ */
+#define HIPIE_OPTIM_CHUNK 16384
+int hipie_optim_chunk(void);
+/* bytes of the float64 partial sums, one per chunk (never 0) */
+int64_t hipie_optim_norm_ws_bytes(int64_t n_chunks);
+int hipie_optim_grad_norm(const void* table, int64_t n_seg, const void* map, int64_t n_chunks, void* ws, int64_t ws_bytes, float grad_scale,
+                          float* norm, void* stream);
+int hipie_optim_adamw_step(const void* table, int64_t n_seg, const void* map, int64_t n_chunks, int32_t* steps, float* bc,
+                           const double* group_lr, const double* group_wd, int n_groups, double beta1, double beta2, double eps,
+                           const float* norm, double max_norm, float grad_scale, int write_grads, void* stream);
+
+/*
  * hipie_vit_attn with the decomposed relative-position bias computed INSIDE the kernel from the (re-interpolated) tables
  * (get_rel_pos + add_decomposed_rel_pos, hipie/backbone/utils.py:63-125): bias_w[q, kx] = q . Rw[qx - kx + gw - 1] and
  * bias_h[q, ky] = q . Rh[qy - ky + gh - 1] are two MFMA products per wave in the prologue, so neither hipie_vit_relpos nor
