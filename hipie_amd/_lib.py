@@ -3,13 +3,17 @@
 The library is built in-tree (``make -C hipie_amd/csrc`` or ``__graft_entry__.build()``).  There is NO fallback: if the
 shared object is missing or does not export a symbol, importing the op layer raises -- the product never silently runs a
 PyTorch/CPU substitute for a hand-written kernel.
+
+The prototypes and the integer ``#define``s are READ from the header at import: the header is the only description of an entry point.
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # HIPIE_LIB_PATH: another build of the SAME ABI, for same-box A/B timing of a kernel change (tools/); the default is the in-tree library
 LIB_PATH = os.environ.get("HIPIE_LIB_PATH") or os.path.join(_HERE, "csrc", "libhipie_mi355.so")
+HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "hipie_mi355.h")          # where csrc/Makefile finds it
 
 c_p = ctypes.c_void_p
 c_i = ctypes.c_int
@@ -17,114 +21,55 @@ c_l = ctypes.c_int64
 c_f = ctypes.c_float
 c_d = ctypes.c_double
 
-# name -> argtypes, in the order of include/hipie_mi355.h
-SIGNATURES = {
-    "hipie_version": [],
-    "hipie_last_error": [],
-    "hipie_msda_forward": [c_p, c_p, c_p, c_p, c_p, c_p] + [c_i] * 8 + [c_p],
-    "hipie_msda_fused_forward": [c_p, c_p, c_p, c_p, c_p, c_p, c_p] + [c_i] * 10 + [c_l, c_l, c_p],
-    "hipie_msda_fused_forward_strided": [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p] + [c_i] * 10 + [c_l, c_l, c_p],
-    "hipie_flash_attn": [c_p, c_p, c_p, c_p] + [c_i] * 5 + [c_l] * 12 + [c_p, c_p, c_i, c_i, c_p, c_f, c_f, c_i, c_p],
-    "hipie_vit_attn": [c_p, c_p, c_p, c_p] + [c_i] * 5 + [c_f, c_i, c_p],
-    "hipie_vit_attn_fused": [c_p, c_p, c_p, c_p] + [c_i] * 5 + [c_f, c_i, c_p],
-    "hipie_vit_attn_rel": [c_p, c_p, c_p, c_p] + [c_i] * 7 + [c_p],
-    "hipie_bi_xattn": [c_p, c_p, c_p, c_p, c_p, c_p, c_p] + [c_i] * 5 + [c_f, c_i, c_p],
-    "hipie_bi_xattn_ws": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l] + [c_i] * 5 + [c_f, c_i, c_p],
-    "hipie_bi_xattn_workspace": [c_i] * 5,
-    "hipie_mask_einsum": [c_p, c_p, c_p] + [c_i] * 6 + [c_p],
-    "hipie_mask_einsum_workspace": [c_i, c_i, c_i],
-    "hipie_mask_einsum_ws": [c_p, c_p, c_p, c_p, c_p, c_l] + [c_i] * 6 + [c_p],
-    "hipie_mask_einsum16": [c_p, c_p, c_p, c_p, c_p] + [c_i] * 6 + [c_p],
-    "hipie_dynamic_mask": [c_p, c_p, c_p, c_p] + [c_i] * 7 + [c_p],
-    "hipie_dynamic_mask16": [c_p, c_p, c_p, c_p] + [c_i] * 7 + [c_p],
-    "hipie_dynamic_mask_backward": [c_p] * 7 + [c_i] * 6 + [c_p],
-    "hipie_vit_relpos": [c_p, c_p, c_p, c_p, c_p] + [c_i] * 6 + [c_p],
-    "hipie_add_layernorm": [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_f, c_i, c_i, c_i, c_p],
-    "hipie_layernorm_backward": [c_p] * 8 + [c_l, c_l, c_i, c_f, c_p],
-    "hipie_layernorm_backward_ws_bytes": [c_l, c_i],
-    "hipie_act_forward": [c_p, c_p, c_l, c_i, c_i, c_p],
-    "hipie_act_backward": [c_p] * 6 + [c_l, c_i, c_i, c_p],
-    "hipie_act_backward_ws_bytes": [c_l, c_i],
-    "hipie_point_mask_loss_forward": [c_p] * 8 + [c_l, c_l, c_i, c_i, c_l, c_i, c_i, c_i, c_i, c_f, c_f, c_p],
-    "hipie_point_mask_loss_ws_bytes": [c_l, c_i],
-    "hipie_point_mask_loss_backward": [c_p] * 8 + [c_l, c_i, c_i, c_l, c_i, c_i, c_i, c_i, c_f, c_f, c_p],
-    "hipie_token_focal_forward": [c_p] * 5 + [c_l, c_i, c_i, c_i, c_f, c_f, c_p],
-    "hipie_token_focal_ws_bytes": [c_l],
-    "hipie_token_focal_backward": [c_p] * 5 + [c_i, c_i, c_i, c_f, c_f, c_p],
-    "hipie_uncertain_points": [c_p] * 5 + [c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_p],
-    "hipie_uncertain_points_ws_bytes": [c_l, c_i],
-    "hipie_mask_match_cost": [c_p] * 6 + [c_l, c_l, c_i, c_i, c_l, c_i, c_i, c_i, c_p],
-    "hipie_mask_match_cost_ws_bytes": [c_l, c_l, c_i],
-    "hipie_ota_cost": [c_p] * 8 + [c_l, c_i, c_i, c_i, c_f, c_f, c_p],
-    "hipie_ota_assign": [c_p] * 9 + [c_l, c_i, c_i, c_p],
-    "hipie_ota_match_ws_bytes": [c_l, c_l, c_l],
-    "hipie_hungarian_cost": [c_p, c_l, c_p, c_l] + [c_p] * 11 + [c_l, c_l, c_i, c_i, c_i, c_l] + [c_f] * 5 + [c_i, c_i, c_p],
-    "hipie_hungarian_cost_bytes": [c_l, c_l],
-    "hipie_hungarian_cost_ws_bytes": [c_l, c_l],
-    "hipie_hungarian_assign": [c_p] * 8 + [c_l, c_l, c_i, c_i, c_l, c_p],
-    "hipie_hungarian_assign_ws_bytes": [c_l, c_l],
-    "hipie_optim_chunk": [],
-    "hipie_optim_norm_ws_bytes": [c_l],
-    "hipie_optim_grad_norm": [c_p, c_l, c_p, c_l, c_p, c_l, c_f, c_p, c_p],
-    "hipie_optim_adamw_step": [c_p, c_l, c_p, c_l, c_p, c_p, c_p, c_p, c_i, c_d, c_d, c_d, c_p, c_d, c_f, c_i, c_p],
-    "hipie_add_layernorm_sum": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_f, c_i, c_i, c_i, c_p],
-    "hipie_add_layernorm_rows": [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_f, c_i, c_i, c_i, c_p, c_p, c_p],
-    "hipie_batched_nms": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_i, c_p],
-    "hipie_mask_finalize": [c_p, c_i, c_p] + [c_i] * 8 + [c_f, c_p, c_p],
-    "hipie_sem_pan": [c_p] * 8 + [c_i] * 11 + [c_p],
-    "hipie_sine_embed": [c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_f, c_i, c_p],
-    "hipie_box_refine": [c_p, c_p, c_p, c_l, c_f, c_i, c_p],
-    "hipie_ref_point_mlp": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_f, c_i, c_p],
-    "hipie_box_head": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_f, c_p],
-    "hipie_add_layernorm_dec": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_f, c_i, c_i, c_p],
-    "hipie_add_cast": [c_p, c_p, c_p, c_l, c_i, c_p],
-    "hipie_group_norm": [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_p],
-    "hipie_gemm": [c_p, c_l, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_p] + [c_i] * 6 + [c_f, c_f, c_p],
-    "hipie_gemm_f8x": [c_p, c_l, c_p, c_l, c_p, c_p, c_p, c_l, c_p, c_l, c_p] + [c_i] * 6 + [c_f, c_f, c_p],
-    "hipie_to_f8x": [c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_p],
-    "hipie_gemm_ln": [c_p, c_l, c_p, c_l, c_p, c_p, c_l, c_p, c_p, c_f, c_p, c_l, c_p, c_l, c_i, c_i, c_i, c_f, c_p],
-    "hipie_gemm_gather": [c_p, c_l, c_l, c_p, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_p] + [c_i] * 6 + [c_f, c_f, c_p],
-    "hipie_vit_attn_split": [c_p, c_p, c_p, c_p] + [c_i] * 5 + [c_p],
-    "hipie_msda_backward": [c_p] * 9 + [c_i] * 8 + [c_p],
-    "hipie_msda_backward_ws": [c_p] * 9 + [c_i] * 8 + [c_p, c_l, c_p],
-    "hipie_msda_backward_workspace": [c_i] * 6,
-    "hipie_gemm_batched": [c_p, c_l, c_l, c_l, c_p, c_l, c_l, c_l, c_p, c_l, c_l, c_l] + [c_i] * 6 + [c_f, c_p],
-    "hipie_gemm_batched_softmax_bias": [c_p, c_l, c_l, c_l, c_p, c_l, c_l, c_l, c_p, c_l, c_l, c_l] + [c_i] * 5 + [c_p, c_i, c_p, c_f, c_f, c_p],
-    "hipie_gemm_batched_resid": [c_p, c_l, c_l, c_l, c_p, c_l, c_l, c_l, c_p, c_p, c_l, c_l, c_l, c_p, c_l, c_l, c_l] + [c_i] * 5 + [c_f, c_p],
-    "hipie_gemm_batched_softmax": [c_p, c_l, c_l, c_l, c_p, c_l, c_l, c_l, c_p, c_l, c_l, c_l] + [c_i] * 5 + [c_p, c_i, c_f, c_f, c_p],
-    "hipie_softmax_hl8": [c_p, c_l, c_p, c_l, c_l, c_i, c_i, c_p, c_l, c_f, c_p],
-    "hipie_attn_f32": [c_p] * 5 + [c_i] * 5 + [c_l] * 6 + [c_f, c_p],
-    "hipie_attn_split": [c_p] * 5 + [c_i] * 5 + [c_l] * 6 + [c_f, c_p],
-    "hipie_attn_f32_rows": [c_p] * 5 + [c_i] * 5 + [c_l] * 6 + [c_f, c_p],
-    "hipie_attn_split_rows": [c_p] * 5 + [c_i] * 5 + [c_l] * 6 + [c_f, c_p],
-    "hipie_conv3x3_split": [c_p, c_l, c_p, c_p, c_p, c_l, c_l] + [c_i] * 6 + [c_p],
-    "hipie_ffn_fused": [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_p],
-    "hipie_topk": [c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_p],
-    "hipie_fill_rows": [c_p, c_l, c_p, c_l, c_p, c_l, c_p],
-    "hipie_to_hl8": [c_p, c_l, c_p, c_l, c_l, c_i, c_i, c_f, c_p],
-    "hipie_to_hl8_t": [c_p, c_l, c_p, c_l, c_l, c_i, c_l, c_f, c_p],
-    "hipie_attn_train_forward": [c_p] * 8 + [c_i, c_i, c_p],
-    "hipie_to_f16_pair": [c_p, c_l, c_p, c_p, c_l, c_i, c_i, c_p, c_p],
-    "hipie_attn_train_backward": [c_p] * 13 + [c_i, c_i, c_p],
-    "hipie_attn_train_win_forward": [c_p] * 8 + [c_i, c_i, c_p],
-    "hipie_attn_train_win_backward": [c_p] * 13 + [c_i, c_i, c_p],
-    "hipie_attn_pack_kv": [c_p] * 6 + [c_i] * 6 + [c_p],
-    "hipie_attn_pack_q": [c_p, c_p, c_l, c_l, c_l, c_l, c_p, c_l, c_l, c_l, c_l, c_p, c_p] + [c_i] * 6 + [c_f, c_p],
-    "hipie_attn_grad_amax": [c_p, c_l, c_p, c_p],
-    "hipie_attn_pack_grad": [c_p] * 10 + [c_i] * 5 + [c_p],
-    "hipie_attn_unpack_grad": [c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_p, c_l, c_l, c_l, c_p, c_p] + [c_i] * 6 + [c_f, c_p],
-    "hipie_selftest": [c_i, c_p, c_p, c_p, c_p],
-}
-
-_lib = None
+_VALUE_TYPES = {"int": c_i, "int64_t": c_l, "float": c_f, "double": c_d}          # every pointer is a c_void_p
+_RETURN_TYPES = {"int": c_i, "int64_t": c_l, "const char*": ctypes.c_char_p}
 
 
 class HipieLibraryError(RuntimeError):
     pass
 
 
+def parse_header(text):
+    """(name -> argtypes, name -> restype, macro -> int) of a header in the style of include/hipie_mi355.h, in its order.  Every statement
+    must be a prototype ``ret hipie_name(args);`` over the types above: anything else is refused, nothing is guessed."""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    constants = {m.group(1): int(m.group(2), 0) for m in re.finditer(
+        r"^[ \t]*#[ \t]*define[ \t]+(HIPIE_\w+)[ \t]+\(?(-?(?:0[xX][0-9a-fA-F]+|\d+))\)?[ \t]*$", text, flags=re.M)}
+    text = re.sub(r'^[ \t]*#.*$|extern\s+"C"\s*\{', "", text, flags=re.M).strip()
+    if text.endswith("}"):                                   # the brace that closes extern "C"
+        text = text[:-1]
+    signatures, restypes = {}, {}
+    for stmt in text.split(";"):
+        stmt = " ".join(stmt.split())
+        if not stmt:
+            continue
+        m = re.fullmatch(r"(.+?)\s*\b(hipie_\w+)\s*\((.*)\)", stmt)
+        if m is None:
+            raise HipieLibraryError("hipie_mi355.h: not a prototype: `%s`" % stmt)
+        ret, name, params = re.sub(r"\s*\*", "*", m.group(1)), m.group(2), m.group(3).strip()
+        if ret not in _RETURN_TYPES or name in signatures:
+            raise HipieLibraryError("hipie_mi355.h: unknown return type or repeated name in `%s`" % stmt)
+        argtypes = []
+        for param in ([] if params in ("", "void") else params.split(",")):
+            words = [w for w in param.split() if w != "const"]
+            if "*" in param:
+                argtypes.append(c_p)
+            elif len(words) == 2 and words[0] in _VALUE_TYPES:
+                argtypes.append(_VALUE_TYPES[words[0]])
+            else:
+                raise HipieLibraryError("hipie_mi355.h: unknown parameter type `%s` in `%s`" % (param.strip(), stmt))
+        signatures[name], restypes[name] = argtypes, _RETURN_TYPES[ret]
+    return signatures, restypes, constants
+
+
+with open(HEADER_PATH) as _f:
+    SIGNATURES, RESTYPES, CONSTANTS = parse_header(_f.read())
+
+_lib = None
+
+
 def load():
-    """dlopen the library once and set the prototypes; raises HipieLibraryError when it is absent or incomplete."""
+    """dlopen the library once and set the prototypes; raises HipieLibraryError when it is absent, incomplete or of another ABI version."""
     global _lib
     if _lib is not None:
         return _lib
@@ -145,12 +90,10 @@ def load():
         except AttributeError:
             raise HipieLibraryError("%s does not export %s (stale build?)" % (LIB_PATH, name))
         fn.argtypes = argtypes
-        fn.restype = (ctypes.c_char_p if name == "hipie_last_error" else
-                      ctypes.c_int64 if name in ("hipie_bi_xattn_workspace", "hipie_mask_einsum_workspace", "hipie_msda_backward_workspace",
-                                                      "hipie_layernorm_backward_ws_bytes", "hipie_act_backward_ws_bytes", "hipie_point_mask_loss_ws_bytes",
-                                                      "hipie_token_focal_ws_bytes", "hipie_uncertain_points_ws_bytes",
-                                                      "hipie_mask_match_cost_ws_bytes", "hipie_ota_match_ws_bytes", "hipie_hungarian_cost_bytes",
-                                                      "hipie_hungarian_cost_ws_bytes", "hipie_hungarian_assign_ws_bytes", "hipie_optim_norm_ws_bytes") else ctypes.c_int)
+        fn.restype = RESTYPES[name]
+    if lib.hipie_version() != CONSTANTS["HIPIE_ABI_VERSION"]:
+        raise HipieLibraryError("%s has ABI version %d, include/hipie_mi355.h has %d (stale build?)"
+                                % (LIB_PATH, lib.hipie_version(), CONSTANTS["HIPIE_ABI_VERSION"]))
     _lib = lib
     return lib
 

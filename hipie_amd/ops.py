@@ -11,10 +11,10 @@ import torch
 from . import _lib
 from .derived import derived
 
-_DT = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
-F32, F16, BF16, HL8 = 0, 1, 2, 4          # include/hipie_mi355.h: HIPIE_F32 / F16 / BF16 / HL8
-OUT_F32 = 0x100                           # HIPIE_OUT_F32
-K_HL8_HI = 0x200       # hipie_flash_attn: keys are the hi halves of an HL8 buffer (HIPIE_K_HL8_HI)
+# the HIPIE_* codes and flags of include/hipie_mi355.h, read from it (K_HL8_HI: hipie_flash_attn's keys are the hi halves of an HL8 buffer)
+F32, F16, BF16, F64, HL8, OUT_F32, K_HL8_HI, ATTN_FAST = (
+    _lib.CONSTANTS["HIPIE_" + n] for n in ("F32", "F16", "BF16", "F64", "HL8", "OUT_F32", "K_HL8_HI", "ATTN_FAST"))
+_DT = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
 
 
 class _Profile(object):
@@ -85,6 +85,25 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+_BOUND = {}          # entry point -> its ctypes function, bound on the first call (the training forward makes thousands of calls per step)
+
+
+def _call(name, *args):
+    """the one checked call into the library: entry point `name` on the current stream (every entry point that returns a status takes the
+    stream last); a non-zero status raises with the library's message and the symbol that was called"""
+    fn = _BOUND.get(name)
+    if fn is None:
+        fn = _BOUND[name] = getattr(_lib.load(), name)
+    rc = fn(*args, _stream())
+    if rc:
+        _lib.check(rc, name)
+
+
+def _size(name, *args):
+    """a size query of the library (*_ws_bytes, *_workspace, hipie_optim_chunk): it returns the number, takes no stream and has no status"""
+    return int(getattr(_lib.load(), name)(*args))
+
+
 def _code(dtype):
     """C-ABI element code of an output type: a torch dtype, or the string "hl8" (split fp16, HIPIE_HL8)."""
     return HL8 if dtype == "hl8" else _DT[dtype]
@@ -129,7 +148,6 @@ def _check_im2col_step(B, im2col_step):
 def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step=64):
     """MSDA.ms_deform_attn_forward (ops/src/vision.cpp:13-16): value (B,S,M,D), shapes (L,2) i64, level_start (L,) i64,
     sampling_loc (B,Lq,M,L,P,2), attn_weight (B,Lq,M,L,P) -> (B,Lq,M*D).  value may be f32/f16/bf16 with f32 loc/attn, or all f64."""
-    lib = _lib.load()
     B, S, M, D = value.shape
     _check_im2col_step(B, im2col_step)
     _, Lq, _, L, P, _ = sampling_loc.shape
@@ -138,12 +156,9 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
         raise RuntimeError("ms_deform_attn_forward: unsupported dtype %s" % value.dtype)
     aux = torch.float64 if f64 else torch.float32
     out = torch.empty(B, Lq, M * D, dtype=value.dtype, device=value.device)
-    rc = lib.hipie_msda_forward(_chk(value, "value"), _chk(spatial_shapes, "spatial_shapes", torch.int64),
-                                _chk(level_start_index, "level_start_index", torch.int64),
-                                _chk(sampling_loc, "sampling_loc", aux),
-                                _chk(attn_weight, "attn_weight", aux), out.data_ptr(),
-                                B, S, M, D, L, Lq, P, 3 if f64 else _DT[value.dtype], _stream())
-    _lib.check(rc, "hipie_msda_forward")
+    _call("hipie_msda_forward", _chk(value, "value"), _chk(spatial_shapes, "spatial_shapes", torch.int64),
+          _chk(level_start_index, "level_start_index", torch.int64), _chk(sampling_loc, "sampling_loc", aux),
+          _chk(attn_weight, "attn_weight", aux), out.data_ptr(), B, S, M, D, L, Lq, P, F64 if f64 else _DT[value.dtype])
     return out
 
 
@@ -151,7 +166,6 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
     """MSDA.ms_deform_attn_backward (ops/src/vision.cpp:13-16; ms_deform_attn_cuda.cu:83-153): the gradients of the op above with
     respect to value, sampling_loc and attn_weight, all f32 or all f64 -> (grad_value, grad_sampling_loc, grad_attn_weight).
     Runs hipie_msda_backward_ws: the gather form for fp32 and D = 32, the atomic kernel of hipie_msda_backward otherwise."""
-    lib = _lib.load()
     B, S, M, D = value.shape
     _check_im2col_step(B, im2col_step)
     _, Lq, _, L, P, _ = sampling_loc.shape
@@ -163,14 +177,12 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
     gv = torch.empty_like(value, memory_format=torch.contiguous_format)
     gl = torch.empty(sampling_loc.shape, dtype=dt, device=value.device)
     ga = torch.empty(attn_weight.shape, dtype=dt, device=value.device)
-    need = int(lib.hipie_msda_backward_workspace(B, S, M, L, Lq, P)) if dt == torch.float32 and D == 32 and B * Lq > 0 else 0
+    need = _size("hipie_msda_backward_workspace", B, S, M, L, Lq, P) if dt == torch.float32 and D == 32 and B * Lq > 0 else 0
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=value.device)      # the gather form's bins and corner records (fp32, D = 32)
-    rc = lib.hipie_msda_backward_ws(_chk(value, "value", dt), _chk(spatial_shapes, "spatial_shapes", torch.int64),
-                                    _chk(level_start_index, "level_start_index", torch.int64), _chk(sampling_loc, "sampling_loc", dt),
-                                    _chk(attn_weight, "attn_weight", dt), _chk(grad_output.contiguous(), "grad_output", dt),
-                                    gv.data_ptr(), gl.data_ptr(), ga.data_ptr(), B, S, M, D, L, Lq, P, 3 if dt == torch.float64 else F32,
-                                    ws.data_ptr(), need, _stream())
-    _lib.check(rc, "hipie_msda_backward")
+    _call("hipie_msda_backward_ws", _chk(value, "value", dt), _chk(spatial_shapes, "spatial_shapes", torch.int64),
+          _chk(level_start_index, "level_start_index", torch.int64), _chk(sampling_loc, "sampling_loc", dt),
+          _chk(attn_weight, "attn_weight", dt), _chk(grad_output.contiguous(), "grad_output", dt),
+          gv.data_ptr(), gl.data_ptr(), ga.data_ptr(), B, S, M, D, L, Lq, P, F64 if dt == torch.float64 else F32, ws.data_ptr(), need)
     return gv, gl, ga
 
 
@@ -178,7 +190,6 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
 def msda_fused(value, spatial_shapes, level_start_index, ref, offsets, logits):
     """value (B,S,M,D); ref (B,Lq,L,2|4) f32; offsets (B,Lq,M,L,P,2); logits (B,Lq,M,L*P) (f32/f16/bf16, same dtype; they
     may be column slices of ONE projection output: only the last dim block must be contiguous) -> (B,Lq,M*D)."""
-    lib = _lib.load()
     B, S, M, D = value.shape
     vrow = M * D
     if not value.is_contiguous():             # a column block of a wider (B, S, n * M * D) projection output: sampled in place
@@ -201,13 +212,10 @@ def msda_fused(value, spatial_shapes, level_start_index, ref, offsets, logits):
     if not value.is_cuda or value.dtype not in _DT:
         raise RuntimeError("Not implemented on the CPU (value)" if not value.is_cuda else "msda_fused: bad value dtype")
     # dense values go in with row stride 0 (= M * D inside the library): the % 8 requirement applies to strided column blocks only
-    rc = lib.hipie_msda_fused_forward_strided(value.data_ptr(), 0 if value.is_contiguous() else vrow,
-                                              _chk(spatial_shapes, "spatial_shapes", torch.int64),
-                                              _chk(level_start_index, "level_start_index", torch.int64),
-                                              _chk(ref, "ref", torch.float32), offsets.data_ptr(), logits.data_ptr(), out.data_ptr(),
-                                              B, S, M, D, L, Lq, P, ref.shape[-1], _DT[value.dtype], _DT[offsets.dtype],
-                                              off_stride, lg_stride, _stream())
-    _lib.check(rc, "hipie_msda_fused_forward")
+    _call("hipie_msda_fused_forward_strided", value.data_ptr(), 0 if value.is_contiguous() else vrow,
+          _chk(spatial_shapes, "spatial_shapes", torch.int64), _chk(level_start_index, "level_start_index", torch.int64),
+          _chk(ref, "ref", torch.float32), offsets.data_ptr(), logits.data_ptr(), out.data_ptr(),
+          B, S, M, D, L, Lq, P, ref.shape[-1], _DT[value.dtype], _DT[offsets.dtype], off_stride, lg_stride)
     return out
 
 
@@ -217,7 +225,6 @@ def flash_attn(q, k, v, scale, bias_h=None, bias_w=None, key_mask=None, clamp=0.
     fp32 with out_f32.  bias_h (B*H,kh,Nq) / bias_w (B*H,Nq,kw) f32 decomposed rel-pos bias; key_mask (B,Nk) uint8/bool.
     A query with no attended key (a batch item whose key_mask is all zero) gives zeros.
     k_hl8: k is a contiguous (B, Nk, 2*H*hd) fp16 HL8 buffer whose hi halves are the keys (read in place, HIPIE_K_HL8_HI)."""
-    lib = _lib.load()
     B, Nq, H, hd = q.shape
     Nk = k.shape[1]
     if k_hl8:
@@ -238,12 +245,10 @@ def flash_attn(q, k, v, scale, bias_h=None, bias_w=None, key_mask=None, clamp=0.
     if key_mask is not None:
         key_mask = key_mask.to(torch.uint8).contiguous()
         mp = _chk(key_mask, "key_mask")
-    rc = lib.hipie_flash_attn(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, H, Nq, Nk, hd,
-                              q.stride(0), q.stride(1), q.stride(2), *(ks if k_hl8 else (k.stride(0), k.stride(1), k.stride(2))),
-                              v.stride(0), v.stride(1), v.stride(2), Nq * H * hd, H * hd, hd,
-                              bhp, bwp, kh, kw, mp, float(scale), float(clamp),
-                              _DT[q.dtype] | (OUT_F32 if out_f32 else 0) | (K_HL8_HI if k_hl8 else 0), _stream())
-    _lib.check(rc, "hipie_flash_attn")
+    _call("hipie_flash_attn", q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, H, Nq, Nk, hd,
+          q.stride(0), q.stride(1), q.stride(2), *(ks if k_hl8 else (k.stride(0), k.stride(1), k.stride(2))),
+          v.stride(0), v.stride(1), v.stride(2), Nq * H * hd, H * hd, hd, bhp, bwp, kh, kw, mp, float(scale), float(clamp),
+          _DT[q.dtype] | (OUT_F32 if out_f32 else 0) | (K_HL8_HI if k_hl8 else 0))
     return out
 
 
@@ -257,7 +262,6 @@ def bi_i2t_split(q_hl8, k, vl, text_mask, heads, clamp=50000.0, n_keys=None):
     multiple of 32 tokens and split on the way.  n_keys (host int, optional): every attended token sits in the first n_keys columns --
     the masked keys behind them have probability exactly 0 (-9e15 before the softmax) and are left out, so a PAD_MAX prompt (4096
     columns, 194 of them attended) costs what its real tokens cost and nothing of size Nv x L is allocated."""
-    lib = _lib.load()
     B, Nv, E2 = q_hl8.shape
     E = E2 // 2
     hd = E // heads
@@ -278,21 +282,16 @@ def bi_i2t_split(q_hl8, k, vl, text_mask, heads, clamp=50000.0, n_keys=None):
     mk = text_mask.to(torch.uint8).contiguous()
     if Lp <= 256:
         # a text of up to 256 tokens is ONE column tile: the masked softmax runs in the logits GEMM's epilogue, S never exists
-        rc = lib.hipie_gemm_batched_softmax(q_hl8.data_ptr(), 2 * E, Nv * 2 * E, 2 * hd, k_hl8.data_ptr(), 2 * E, Lp * 2 * E, 2 * hd,
-                                            P.data_ptr(), 2 * Lp, heads * Nv * 2 * Lp, Nv * 2 * Lp, B, heads, Nv, Lp, hd, mk.data_ptr(), L,
-                                            float(clamp), 1.0, _stream())
-        _lib.check(rc, "hipie_gemm_batched_softmax")
+        _call("hipie_gemm_batched_softmax", q_hl8.data_ptr(), 2 * E, Nv * 2 * E, 2 * hd, k_hl8.data_ptr(), 2 * E, Lp * 2 * E, 2 * hd,
+              P.data_ptr(), 2 * Lp, heads * Nv * 2 * Lp, Nv * 2 * Lp, B, heads, Nv, Lp, hd, mk.data_ptr(), L, float(clamp), 1.0)
     else:
         S = torch.empty(B, heads, Nv, Lp, dtype=torch.float32, device=dev)
-        rc = lib.hipie_gemm_batched(q_hl8.data_ptr(), 2 * E, Nv * 2 * E, 2 * hd, k_hl8.data_ptr(), 2 * E, Lp * 2 * E, 2 * hd,
-                                    S.data_ptr(), Lp, heads * Nv * Lp, Nv * Lp, B, heads, Nv, Lp, hd, F32, 1.0, _stream())
-        _lib.check(rc, "hipie_gemm_batched")
-        rc = lib.hipie_softmax_hl8(S.data_ptr(), Lp, P.data_ptr(), 2 * Lp, B * heads * Nv, L, Lp, mk.data_ptr(), heads * Nv, float(clamp), _stream())
-        _lib.check(rc, "hipie_softmax_hl8")
+        _call("hipie_gemm_batched", q_hl8.data_ptr(), 2 * E, Nv * 2 * E, 2 * hd, k_hl8.data_ptr(), 2 * E, Lp * 2 * E, 2 * hd,
+              S.data_ptr(), Lp, heads * Nv * Lp, Nv * Lp, B, heads, Nv, Lp, hd, F32, 1.0)
+        _call("hipie_softmax_hl8", S.data_ptr(), Lp, P.data_ptr(), 2 * Lp, B * heads * Nv, L, Lp, mk.data_ptr(), heads * Nv, float(clamp))
     out = torch.empty(B, Nv, E, dtype=torch.float32, device=dev)
-    rc = lib.hipie_gemm_batched(P.data_ptr(), 2 * Lp, heads * Nv * 2 * Lp, Nv * 2 * Lp, vt_hl8.data_ptr(), 2 * Lp, heads * hd * 2 * Lp, hd * 2 * Lp,
-                                out.data_ptr(), E, Nv * E, hd, B, heads, Nv, hd, Lp, F32, 1.0, _stream())
-    _lib.check(rc, "hipie_gemm_batched")
+    _call("hipie_gemm_batched", P.data_ptr(), 2 * Lp, heads * Nv * 2 * Lp, Nv * 2 * Lp, vt_hl8.data_ptr(), 2 * Lp, heads * hd * 2 * Lp, hd * 2 * Lp,
+          out.data_ptr(), E, Nv * E, hd, B, heads, Nv, hd, Lp, F32, 1.0)
     return out
 
 
@@ -313,7 +312,6 @@ def bi_i2t_folded(v_hl8, M, cb, vl, text_mask, heads, wo, bo, resid=None, clamp=
     already cut to the attended columns); vl (B, L, E) fp32 text values; wo (C_out, E), bo (C_out) the output projection; resid (B, Nv, C_out)
     fp32 or None -> (B, Nv, C_out) fp32.  TWO launches over the visual tokens (hipie_gemm_batched_softmax_bias: P as HL8, the logits never
     exist; hipie_gemm_batched_resid: K = heads * Lp).  L <= 256.  The reassociation moves the rounding of the logits at the 1e-7 level."""
-    lib = _lib.load()
     B, Nv, C2 = v_hl8.shape
     C = C2 // 2
     L = M.shape[2]
@@ -335,10 +333,8 @@ def bi_i2t_folded(v_hl8, M, cb, vl, text_mask, heads, wo, bo, resid=None, clamp=
     u_hl8 = to_hl8(U.view(B, Co, heads * Lp))                                          # (B, C_out, 2 H Lp): K = (head, text token)
     P = torch.empty(B, Nv, heads * 2 * Lp, dtype=torch.float16, device=dev)
     mk = text_mask.to(torch.uint8).contiguous()
-    rc = lib.hipie_gemm_batched_softmax_bias(v_hl8.data_ptr(), 2 * C, Nv * 2 * C, 0, m_hl8.data_ptr(), 2 * C, heads * Lp * 2 * C, Lp * 2 * C,
-                                             P.data_ptr(), heads * 2 * Lp, Nv * heads * 2 * Lp, 2 * Lp, B, heads, Nv, Lp, C, mk.data_ptr(), L,
-                                             cbp.data_ptr(), float(clamp), 1.0, _stream())
-    _lib.check(rc, "hipie_gemm_batched_softmax_bias")
+    _call("hipie_gemm_batched_softmax_bias", v_hl8.data_ptr(), 2 * C, Nv * 2 * C, 0, m_hl8.data_ptr(), 2 * C, heads * Lp * 2 * C, Lp * 2 * C,
+          P.data_ptr(), heads * 2 * Lp, Nv * heads * 2 * Lp, 2 * Lp, B, heads, Nv, Lp, C, mk.data_ptr(), L, cbp.data_ptr(), float(clamp), 1.0)
     out = torch.empty(B, Nv, Co, dtype=torch.float32, device=dev)
     r = None
     if resid is not None:
@@ -347,15 +343,13 @@ def bi_i2t_folded(v_hl8, M, cb, vl, text_mask, heads, wo, bo, resid=None, clamp=
             raise RuntimeError("bi_i2t_folded: resid must be contiguous fp32 (B, Nv, C_out)")
     bo32 = None if bo is None else bo.float().contiguous()
     KK = heads * Lp
-    rc = lib.hipie_gemm_batched_resid(P.data_ptr(), 2 * KK, Nv * 2 * KK, 0, u_hl8.data_ptr(), 2 * KK, Co * 2 * KK, 0,
-                                      None if bo32 is None else bo32.data_ptr(), None if r is None else r.data_ptr(),
-                                      Co, Nv * Co, 0, out.data_ptr(), Co, Nv * Co, 0, B, 1, Nv, Co, KK, 1.0, _stream())
-    _lib.check(rc, "hipie_gemm_batched_resid")
+    _call("hipie_gemm_batched_resid", P.data_ptr(), 2 * KK, Nv * 2 * KK, 0, u_hl8.data_ptr(), 2 * KK, Co * 2 * KK, 0,
+          None if bo32 is None else bo32.data_ptr(), None if r is None else r.data_ptr(),
+          Co, Nv * Co, 0, out.data_ptr(), Co, Nv * Co, 0, B, 1, Nv, Co, KK, 1.0)
     return out
 
 
 def _small_attn(fn_name, q, k, v, scale, key_mask):
-    lib = _lib.load()
     B, Nq, H, hd = q.shape
     Nk = k.shape[1]
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
@@ -368,9 +362,8 @@ def _small_attn(fn_name, q, k, v, scale, key_mask):
     if key_mask is not None:
         key_mask = key_mask.to(torch.uint8).contiguous()
         mp = key_mask.data_ptr()
-    rc = getattr(lib, fn_name)(q.data_ptr(), k.data_ptr(), v.data_ptr(), mp, out.data_ptr(), B, H, Nq, Nk, hd, q.stride(0), q.stride(1),
-                               k.stride(0), k.stride(1), v.stride(0), v.stride(1), float(scale), _stream())
-    _lib.check(rc, fn_name)
+    _call(fn_name, q.data_ptr(), k.data_ptr(), v.data_ptr(), mp, out.data_ptr(), B, H, Nq, Nk, hd, q.stride(0), q.stride(1),
+          k.stride(0), k.stride(1), v.stride(0), v.stride(1), float(scale))
     return out
 
 
@@ -385,7 +378,6 @@ def attn_f32(q, k, v, scale, key_mask=None):
 def attn_f32_rows(q, k, v, scale, query_mask, split=False):
     """hipie_attn_f32_rows (exact fp32 FMA) / hipie_attn_split_rows (split=True: matrix pipe, fp32-class): attention with a mask per query row --
     query_mask (B, Nq, Nk) bool / uint8, True = may attend"""
-    lib = _lib.load()
     B, Nq, H, hd = q.shape
     Nk = k.shape[1]
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
@@ -395,10 +387,8 @@ def attn_f32_rows(q, k, v, scale, query_mask, split=False):
         raise RuntimeError("attn_f32_rows: query_mask (B, Nq, Nk), got %s" % (tuple(query_mask.shape),))
     qm = query_mask.to(torch.uint8).contiguous()
     out = torch.empty(B, Nq, H * hd, dtype=torch.float32, device=q.device)
-    fn = lib.hipie_attn_split_rows if split else lib.hipie_attn_f32_rows
-    rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), qm.data_ptr(), out.data_ptr(), B, H, Nq, Nk, hd, q.stride(0), q.stride(1),
-            k.stride(0), k.stride(1), v.stride(0), v.stride(1), float(scale), _stream())
-    _lib.check(rc, "hipie_attn_split_rows" if split else "hipie_attn_f32_rows")
+    _call("hipie_attn_split_rows" if split else "hipie_attn_f32_rows", q.data_ptr(), k.data_ptr(), v.data_ptr(), qm.data_ptr(), out.data_ptr(),
+          B, H, Nq, Nk, hd, q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1), float(scale))
     return out
 
 
@@ -417,14 +407,12 @@ def attn_f32_ok(hd):
 def vit_attn(qkv, rel_h, rel_w, grid_hw, heads, scale):
     """qkv (B, gh*gw, 3*heads*hd) 16-bit packed as (3, heads, hd); rel_h (B*heads, gh, N) f32 (key-row major),
     rel_w (B*heads, N, gw) f32 -> (B, N, heads*hd)."""
-    lib = _lib.load()
     gh, gw = grid_hw
     B, N, C3 = qkv.shape
     hd = C3 // (3 * heads)
     out = torch.empty(B, N, heads * hd, dtype=qkv.dtype, device=qkv.device)
-    rc = lib.hipie_vit_attn(_chk(qkv, "qkv"), _chk(rel_h, "rel_h", torch.float32), _chk(rel_w, "rel_w", torch.float32),
-                            out.data_ptr(), B, gh, gw, heads, hd, float(scale), _DT[qkv.dtype], _stream())
-    _lib.check(rc, "hipie_vit_attn")
+    _call("hipie_vit_attn", _chk(qkv, "qkv"), _chk(rel_h, "rel_h", torch.float32), _chk(rel_w, "rel_w", torch.float32),
+          out.data_ptr(), B, gh, gw, heads, hd, float(scale), _DT[qkv.dtype])
     return out
 
 
@@ -437,19 +425,16 @@ def vit_attn_fused_ok(grid_hw, hd):
 def vit_attn_fused(qkv, tab_h, tab_w, grid_hw, heads, scale):
     """global ViT attention with the decomposed rel-pos bias computed in the kernel prologue from the tables:
     qkv (B, gh*gw, 3*heads*hd) 16-bit, tab_h (2*gh-1, hd), tab_w (2*gw-1, hd) same dtype -> (B, N, heads*hd)."""
-    lib = _lib.load()
     gh, gw = grid_hw
     B, N, C3 = qkv.shape
     hd = C3 // (3 * heads)
     out = torch.empty(B, N, heads * hd, dtype=qkv.dtype, device=qkv.device)
-    rc = lib.hipie_vit_attn_fused(_chk(qkv, "qkv"), _chk(tab_h, "tab_h", qkv.dtype), _chk(tab_w, "tab_w", qkv.dtype),
-                                  out.data_ptr(), B, gh, gw, heads, hd, float(scale), _DT[qkv.dtype], _stream())
-    _lib.check(rc, "hipie_vit_attn_fused")
+    _call("hipie_vit_attn_fused", _chk(qkv, "qkv"), _chk(tab_h, "tab_h", qkv.dtype), _chk(tab_w, "tab_w", qkv.dtype),
+          out.data_ptr(), B, gh, gw, heads, hd, float(scale), _DT[qkv.dtype])
     return out
 
 
 LOG2E = 1.4426950408889634
-ATTN_FAST = 1            # include/hipie_mi355.h: HIPIE_ATTN_FAST
 
 
 def vit_attn_rel_ok(grid_hw, hd):
@@ -463,14 +448,12 @@ def vit_attn_rel(qkv, tab_h, tab_w, grid_hw, heads, fast=False):
     """ViT attention (global or windowed) with the decomposed rel-pos bias computed in the kernel.  Operand contract of
     hipie_vit_attn_rel: qkv (B, gh*gw, 3*heads*hd) 16-bit whose q rows are PRE-SCALED by scale*log2(e); tab_h (2*gh-1, hd),
     tab_w (2*gw-1, hd) = the (re-interpolated) rel-pos tables DIVIDED by scale, same dtype -> (B, N, heads*hd)."""
-    lib = _lib.load()
     gh, gw = grid_hw
     B, N, C3 = qkv.shape
     hd = C3 // (3 * heads)
     out = torch.empty(B, N, heads * hd, dtype=qkv.dtype, device=qkv.device)
-    rc = lib.hipie_vit_attn_rel(_chk(qkv, "qkv"), _chk(tab_h, "tab_h", qkv.dtype), _chk(tab_w, "tab_w", qkv.dtype),
-                                out.data_ptr(), B, gh, gw, heads, hd, _DT[qkv.dtype], ATTN_FAST if fast else 0, _stream())
-    _lib.check(rc, "hipie_vit_attn_rel")
+    _call("hipie_vit_attn_rel", _chk(qkv, "qkv"), _chk(tab_h, "tab_h", qkv.dtype), _chk(tab_w, "tab_w", qkv.dtype),
+          out.data_ptr(), B, gh, gw, heads, hd, _DT[qkv.dtype], ATTN_FAST if fast else 0)
     return out
 
 
@@ -500,19 +483,17 @@ def bi_xattn(q, k, vv, vl, text_mask, clamp=50000.0, out_f32=False):
     """q, vv (B,Nv,H,hd); k, vl (B,L,H,hd) 16-bit contiguous; text_mask (B,L) -> out_v (B,Nv,H*hd), out_l (B,L,H*hd) (operand dtype,
     or fp32 with out_f32: the generic flash kernel then runs both directions).  A query with no attended key gives zeros: the out_v
     rows of a batch item whose text_mask is all zero are zero at every L (whichever kernel the length selects); out_l has no mask."""
-    lib = _lib.load()
     B, Nv, H, hd = q.shape
     L = k.shape[1]
     text_mask = text_mask.to(torch.uint8).contiguous()
     odt = torch.float32 if out_f32 else q.dtype
     out_v = torch.empty(B, Nv, H * hd, dtype=odt, device=q.device)
     out_l = torch.empty(B, L, H * hd, dtype=odt, device=q.device)
-    need = 0 if out_f32 else int(lib.hipie_bi_xattn_workspace(B, H, Nv, L, hd))          # split partials of the text -> image direction (0: none)
+    need = 0 if out_f32 else _size("hipie_bi_xattn_workspace", B, H, Nv, L, hd)          # split partials of the text -> image direction (0: none)
     ws = _XA_WS.get(need, q.device) if need > 0 else None
-    rc = lib.hipie_bi_xattn_ws(_chk(q, "q"), _chk(k, "k"), _chk(vv, "vv"), _chk(vl, "vl"), _chk(text_mask, "text_mask"),
-                               out_v.data_ptr(), out_l.data_ptr(), None if ws is None else ws.data_ptr(), need, B, H, Nv, L, hd,
-                               float(clamp), _DT[q.dtype] | (OUT_F32 if out_f32 else 0), _stream())
-    _lib.check(rc, "hipie_bi_xattn")
+    _call("hipie_bi_xattn_ws", _chk(q, "q"), _chk(k, "k"), _chk(vv, "vv"), _chk(vl, "vl"), _chk(text_mask, "text_mask"),
+          out_v.data_ptr(), out_l.data_ptr(), None if ws is None else ws.data_ptr(), need, B, H, Nv, L, hd,
+          float(clamp), _DT[q.dtype] | (OUT_F32 if out_f32 else 0))
     return out_v, out_l
 
 
@@ -525,7 +506,6 @@ def mask_einsum(mask_embed, mask_features, precision=1, out_dtype=torch.float32,
     precision 0 = exact fp32 MFMA, 1 = bf16x3 split (default; ~2^-16), 2 = plain bf16.  Precisions 1 | 2 run hipie_mask_einsum_ws (the
     embedding split once into a cached scratch buffer and staged by LDS-DMA) and take row_bias (B,Q) f32, added to every pixel of
     its query row; workspace=False: the workspace-free entry point hipie_mask_einsum (every workgroup splits the embedding)."""
-    lib = _lib.load()
     B, Q, C = mask_embed.shape
     _, _, Hh, Ww = mask_features.shape
     out = torch.empty(B, Q, Hh, Ww, dtype=out_dtype, device=mask_embed.device)
@@ -533,7 +513,7 @@ def mask_einsum(mask_embed, mask_features, precision=1, out_dtype=torch.float32,
     if int(precision) == 0 or not workspace:
         if row_bias is not None:
             raise RuntimeError("mask_einsum: row_bias needs precision 1 | 2 and the workspace form")
-        rc = lib.hipie_mask_einsum(e, f, out.data_ptr(), B, Q, C, Hh * Ww, int(precision), _DT[out_dtype], _stream())
+        _call("hipie_mask_einsum", e, f, out.data_ptr(), B, Q, C, Hh * Ww, int(precision), _DT[out_dtype])
     else:
         rb = None
         if row_bias is not None:
@@ -541,10 +521,9 @@ def mask_einsum(mask_embed, mask_features, precision=1, out_dtype=torch.float32,
             if tuple(rbt.shape) != (B, Q):
                 raise ValueError("mask_einsum: row_bias must be (B, Q) = (%d, %d), got %s" % (B, Q, tuple(rbt.shape)))
             rb = _chk(rbt, "row_bias", torch.float32)
-        need = int(lib.hipie_mask_einsum_workspace(B, Q, C))
+        need = _size("hipie_mask_einsum_workspace", B, Q, C)
         ws = _ME_WS.get(need, mask_embed.device)
-        rc = lib.hipie_mask_einsum_ws(e, f, rb, out.data_ptr(), ws.data_ptr(), need, B, Q, C, Hh * Ww, int(precision), _DT[out_dtype], _stream())
-    _lib.check(rc, "hipie_mask_einsum")
+        _call("hipie_mask_einsum_ws", e, f, rb, out.data_ptr(), ws.data_ptr(), need, B, Q, C, Hh * Ww, int(precision), _DT[out_dtype])
     return out
 
 
@@ -564,7 +543,6 @@ def mask_einsum_backward(mask_embed, mask_features, grad_out):
                          per image, far fewer than the CUs), the partial products summed afterwards;
       grad_features[b] = E[b]^T (C x Q) . G[b] (Q x HW)    -- as A . W^T with A = E^T and W = G^T (both K = Q contiguous, Q padded to 32).
     The row-bias gradient of the forward's `row_bias` is grad_out.sum((2, 3)) (the caller's)."""
-    lib = _lib.load()
     B, Q, C = mask_embed.shape
     _, _, Hh, Ww = mask_features.shape
     HW = Hh * Ww
@@ -581,9 +559,8 @@ def mask_einsum_backward(mask_embed, mask_features, grad_out):
     Kc = HWp // nk
     gh, fh = to_hl8(_pad_last(G, HWp)), to_hl8(_pad_last(F_, HWp))              # (B, Q | C, 2 HWp)
     part = torch.empty(B, nk, Q, C, dtype=torch.float32, device=dev)
-    rc = lib.hipie_gemm_batched(gh.data_ptr(), 2 * HWp, Q * 2 * HWp, 2 * Kc, fh.data_ptr(), 2 * HWp, C * 2 * HWp, 2 * Kc,
-                                part.data_ptr(), C, nk * Q * C, Q * C, B, nk, Q, C, Kc, F32, 1.0, _stream())
-    _lib.check(rc, "hipie_gemm_batched")
+    _call("hipie_gemm_batched", gh.data_ptr(), 2 * HWp, Q * 2 * HWp, 2 * Kc, fh.data_ptr(), 2 * HWp, C * 2 * HWp, 2 * Kc,
+          part.data_ptr(), C, nk * Q * C, Q * C, B, nk, Q, C, Kc, F32, 1.0)
     grad_e = part.sum(1) if nk > 1 else part[:, 0]
     # ---- grad_features: K = Q ----
     Qp = (Q + 31) // 32 * 32
@@ -593,9 +570,8 @@ def mask_einsum_backward(mask_embed, mask_features, grad_out):
     gT[:, :HW, :Q] = G.transpose(1, 2)
     gTh = to_hl8(gT)                                                             # (B, N8, 2 Qp)
     gf = torch.empty(B, C, N8, dtype=torch.float32, device=dev)
-    rc = lib.hipie_gemm_batched(eT.data_ptr(), 2 * Qp, C * 2 * Qp, 0, gTh.data_ptr(), 2 * Qp, N8 * 2 * Qp, 0, gf.data_ptr(), N8, C * N8, 0,
-                                B, 1, C, N8, Qp, F32, 1.0, _stream())
-    _lib.check(rc, "hipie_gemm_batched")
+    _call("hipie_gemm_batched", eT.data_ptr(), 2 * Qp, C * 2 * Qp, 0, gTh.data_ptr(), 2 * Qp, N8 * 2 * Qp, 0, gf.data_ptr(), N8, C * N8, 0,
+          B, 1, C, N8, Qp, F32, 1.0)
     if N8 != HW:
         gf = gf[..., :HW].contiguous()
     return grad_e, gf.view(B, C, Hh, Ww)
@@ -606,7 +582,6 @@ def mask_einsum16(mask_embed, mask_features, split=True, out_dtype=None, row_bia
     """einsum("bqc,bchw->bqhw") on 16-bit features: mask_embed (B,Q,C) f32 (split here into 16-bit hi + lo parts: two MFMAs per
     product; split=False: hi only), mask_features (B,C,H,W) f16 | bf16 contiguous -> (B,Q,H,W) out_dtype (default: the feature
     dtype); row_bias (B,Q) is added to every pixel of its query row.  Q <= 320."""
-    lib = _lib.load()
     B, Q, C = mask_embed.shape
     _, _, Hh, Ww = mask_features.shape
     dt = mask_features.dtype
@@ -615,9 +590,8 @@ def mask_einsum16(mask_embed, mask_features, split=True, out_dtype=None, row_bia
     lo = (mask_embed.float() - hi.float()).to(dt).contiguous() if split else None
     out = torch.empty(B, Q, Hh, Ww, dtype=out_dtype, device=mask_embed.device)
     rb = None if row_bias is None else _chk(row_bias.float().contiguous(), "row_bias", torch.float32)
-    rc = lib.hipie_mask_einsum16(_chk(hi, "embed_hi"), None if lo is None else _chk(lo, "embed_lo"), _chk(mask_features, "mask_features"),
-                                 rb, out.data_ptr(), B, Q, C, Hh * Ww, _DT[dt], _DT[out_dtype], _stream())
-    _lib.check(rc, "hipie_mask_einsum16")
+    _call("hipie_mask_einsum16", _chk(hi, "embed_hi"), None if lo is None else _chk(lo, "embed_lo"), _chk(mask_features, "mask_features"),
+          rb, out.data_ptr(), B, Q, C, Hh * Ww, _DT[dt], _DT[out_dtype])
     return out
 
 
@@ -627,7 +601,6 @@ def dynamic_mask(mask_feats, ref_points, params, num_queries, stride=8, up=2, ou
     mlp_dtype fp16 / bf16: the three layers on the matrix pipe with operands of that type (hipie_dynamic_mask16; up = 2,
     W % 4 == 0, stride % 4 == 0); "split": the same kernel on fp16 PAIRS (weights and activations hi + lo, three products each: fp32-class,
     the split policy); None / fp32: the fp32 VALU kernel."""
-    lib = _lib.load()
     B, C, H, W = mask_feats.shape
     if C != 8 or params.shape[-1] != 169:
         raise RuntimeError("dynamic_mask: expects 8 feature channels and 169 parameters per instance")
@@ -635,15 +608,12 @@ def dynamic_mask(mask_feats, ref_points, params, num_queries, stride=8, up=2, ou
     out = torch.empty(n, up * H, up * W, dtype=out_dtype, device=mask_feats.device)
     split = mlp_dtype == "split" and out_dtype in (torch.float32, torch.float16)
     if (split or mlp_dtype in (torch.float16, torch.bfloat16)) and up == 2 and W % 4 == 0 and stride % 4 == 0 and stride * max(H, W) <= 8192:
-        rc = lib.hipie_dynamic_mask16(_chk(mask_feats, "mask_feats", torch.float32), _chk(ref_points, "ref_points", torch.float32),
-                                      _chk(params, "params", torch.float32), out.data_ptr(), B, num_queries, H, W,
-                                      int(stride), HL8 if split else _DT[mlp_dtype], _DT[out_dtype], _stream())
-        _lib.check(rc, "hipie_dynamic_mask16")
+        _call("hipie_dynamic_mask16", _chk(mask_feats, "mask_feats", torch.float32), _chk(ref_points, "ref_points", torch.float32),
+              _chk(params, "params", torch.float32), out.data_ptr(), B, num_queries, H, W,
+              int(stride), HL8 if split else _DT[mlp_dtype], _DT[out_dtype])
         return out
-    rc = lib.hipie_dynamic_mask(_chk(mask_feats, "mask_feats", torch.float32), _chk(ref_points, "ref_points", torch.float32),
-                                _chk(params, "params", torch.float32), out.data_ptr(), B, num_queries, H, W,
-                                int(stride), int(up), _DT[out_dtype], _stream())
-    _lib.check(rc, "hipie_dynamic_mask")
+    _call("hipie_dynamic_mask", _chk(mask_feats, "mask_feats", torch.float32), _chk(ref_points, "ref_points", torch.float32),
+          _chk(params, "params", torch.float32), out.data_ptr(), B, num_queries, H, W, int(stride), int(up), _DT[out_dtype])
     return out
 
 
@@ -651,7 +621,6 @@ def dynamic_mask(mask_feats, ref_points, params, num_queries, stride=8, up=2, ou
 def dynamic_mask_backward(mask_feats, ref_points, params, grad_out, num_queries, stride=8, up=2):
     """gradients of dynamic_mask (row f-4; hipie_dynamic_mask_backward): mask_feats (B,8,H,W), ref_points (B*Q,2), params (B*Q,169),
     grad_out (B*Q, up*H, up*W) fp32 -> (grad_feats (B,8,H,W), grad_refs (B*Q,2), grad_params (B*Q,169)) fp32."""
-    lib = _lib.load()
     B, C, H, W = mask_feats.shape
     n = B * num_queries
     if C != 8 or params.shape[-1] != 169 or params.numel() != n * 169 or ref_points.numel() != n * 2:
@@ -662,10 +631,9 @@ def dynamic_mask_backward(mask_feats, ref_points, params, grad_out, num_queries,
     gf = torch.empty(B, 8, H, W, dtype=torch.float32, device=dev)
     gr = torch.empty(n, 2, dtype=torch.float32, device=dev)
     gp = torch.empty(n, 169, dtype=torch.float32, device=dev)
-    rc = lib.hipie_dynamic_mask_backward(_chk(mask_feats, "mask_feats", torch.float32), _chk(ref_points, "ref_points", torch.float32),
-                                         _chk(params, "params", torch.float32), _chk(grad_out, "grad_out", torch.float32),
-                                         gf.data_ptr(), gr.data_ptr(), gp.data_ptr(), B, num_queries, H, W, int(stride), int(up), _stream())
-    _lib.check(rc, "hipie_dynamic_mask_backward")
+    _call("hipie_dynamic_mask_backward", _chk(mask_feats, "mask_feats", torch.float32), _chk(ref_points, "ref_points", torch.float32),
+          _chk(params, "params", torch.float32), _chk(grad_out, "grad_out", torch.float32),
+          gf.data_ptr(), gr.data_ptr(), gp.data_ptr(), B, num_queries, H, W, int(stride), int(up))
     return gf, gr, gp
 
 
@@ -673,15 +641,13 @@ def dynamic_mask_backward(mask_feats, ref_points, params, grad_out, num_queries,
 def vit_relpos(qkv, tab_h, tab_w, grid_hw, heads):
     """qkv (B, N, 3*heads*hd) 16-bit; tab_h (2gh-1, hd), tab_w (2gw-1, hd) same dtype -> rel_h (B*heads, gh, N), rel_w
     (B*heads, N, gw) f32, the bias tables of hipie_vit_attn."""
-    lib = _lib.load()
     gh, gw = grid_hw
     B, N, C3 = qkv.shape
     hd = C3 // (3 * heads)
     rel_h = torch.empty(B * heads, gh, N, dtype=torch.float32, device=qkv.device)
     rel_w = torch.empty(B * heads, N, gw, dtype=torch.float32, device=qkv.device)
-    rc = lib.hipie_vit_relpos(_chk(qkv, "qkv"), _chk(tab_h, "tab_h", qkv.dtype), _chk(tab_w, "tab_w", qkv.dtype),
-                              rel_h.data_ptr(), rel_w.data_ptr(), B, gh, gw, heads, hd, _DT[qkv.dtype], _stream())
-    _lib.check(rc, "hipie_vit_relpos")
+    _call("hipie_vit_relpos", _chk(qkv, "qkv"), _chk(tab_h, "tab_h", qkv.dtype), _chk(tab_w, "tab_w", qkv.dtype),
+          rel_h.data_ptr(), rel_w.data_ptr(), B, gh, gw, heads, hd, _DT[qkv.dtype])
     return rel_h, rel_w
 
 
@@ -690,7 +656,6 @@ def add_layernorm(x, delta, weight, bias, eps, norm_dtype, want_res=True, delta_
     """s = x + delta (delta may be None); returns (s in x.dtype or None, LayerNorm(s) in norm_dtype).  x (..., C).
     Row maps (int32, optional): ``out_src`` (out_rows,) = x row feeding each output row (-1: zeros) -- the normalised output
     then has out_rows rows; ``delta_row`` (rows of x,) = row of ``delta`` that belongs to x row r."""
-    lib = _lib.load()
     C = x.shape[-1]
     rows = x.numel() // C
     res = torch.empty_like(x) if (want_res and delta is not None) else None
@@ -705,11 +670,10 @@ def add_layernorm(x, delta, weight, bias, eps, norm_dtype, want_res=True, delta_
             None if res is None else res.data_ptr(), out.data_ptr(), out_rows, C, float(eps),
             _DT[x.dtype], _DT[x.dtype if delta is None else delta.dtype], _code(norm_dtype))
     if delta_row is None and out_src is None:
-        rc = lib.hipie_add_layernorm(*args, _stream())
+        _call("hipie_add_layernorm", *args)
     else:
-        rc = lib.hipie_add_layernorm_rows(*args, None if delta_row is None else _chk(delta_row, "delta_row", torch.int32),
-                                          None if out_src is None else _chk(out_src, "out_src", torch.int32), _stream())
-    _lib.check(rc, "hipie_add_layernorm")
+        _call("hipie_add_layernorm_rows", *args, None if delta_row is None else _chk(delta_row, "delta_row", torch.int32),
+              None if out_src is None else _chk(out_src, "out_src", torch.int32))
     return (x if delta is None else res), out
 
 
@@ -722,7 +686,6 @@ def layernorm_backward(s, gy, weight, eps, gres=None, want_param_grads=True):
     for n, t in (("s", s), ("gy", gy), ("weight", weight), ("gres", gres)):
         if t is not None and not t.is_cuda:
             raise RuntimeError("Not implemented on the CPU (%s must be a CUDA/HIP tensor)" % n)
-    lib = _lib.load()
     C = s.shape[-1]
     rows = s.numel() // C if C else 0
     if gy.shape != s.shape or (gres is not None and gres.shape != s.shape) or weight.numel() != C:
@@ -734,13 +697,12 @@ def layernorm_backward(s, gy, weight, eps, gres=None, want_param_grads=True):
     ws_bytes = 0
     if want_param_grads:
         dgamma, dbeta = torch.empty_like(weight), torch.empty_like(weight)
-        ws_bytes = int(lib.hipie_layernorm_backward_ws_bytes(rows, C))
+        ws_bytes = _size("hipie_layernorm_backward_ws_bytes", rows, C)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=s.device)
-    rc = lib.hipie_layernorm_backward(_chk(s, "s", torch.float32), _chk(gy, "gy", torch.float32),
-                                      None if gres is None else _chk(gres, "gres", torch.float32), _chk(weight, "weight", torch.float32),
-                                      dx.data_ptr(), None if dgamma is None else dgamma.data_ptr(), None if dbeta is None else dbeta.data_ptr(),
-                                      None if ws is None else ws.data_ptr(), ws_bytes, rows, C, float(eps), _stream())
-    _lib.check(rc, "hipie_layernorm_backward")
+    _call("hipie_layernorm_backward", _chk(s, "s", torch.float32), _chk(gy, "gy", torch.float32),
+          None if gres is None else _chk(gres, "gres", torch.float32), _chk(weight, "weight", torch.float32),
+          dx.data_ptr(), None if dgamma is None else dgamma.data_ptr(), None if dbeta is None else dbeta.data_ptr(),
+          None if ws is None else ws.data_ptr(), ws_bytes, rows, C, float(eps))
     return dx, dgamma, dbeta
 
 
@@ -757,8 +719,7 @@ def act_forward(u, act):
     for bit) | ACT_RELU.  The forward half of the training step's MLP node (functions.MlpFunction)."""
     u, rows, N = _act_rows16(u, "u")
     a = torch.empty_like(u)
-    rc = _lib.load().hipie_act_forward(u.data_ptr(), a.data_ptr(), rows, N, int(act), _stream())
-    _lib.check(rc, "hipie_act_forward")
+    _call("hipie_act_forward", u.data_ptr(), a.data_ptr(), rows, N, int(act))
     return a
 
 
@@ -782,13 +743,11 @@ def act_backward(u, g, act, want_a=False, want_bias_grad=False, out=None):
     du = out if usable else torch.empty_like(u)
     a = torch.empty_like(u) if want_a else None
     dbias = ws = None
-    lib = _lib.load()
     if want_bias_grad:
         dbias = torch.empty(N, dtype=torch.float32, device=u.device)
-        ws = torch.empty(int(lib.hipie_act_backward_ws_bytes(rows, N)), dtype=torch.uint8, device=u.device)
-    rc = lib.hipie_act_backward(u.data_ptr(), g.data_ptr(), du.data_ptr(), None if a is None else a.data_ptr(),
-                                None if dbias is None else dbias.data_ptr(), None if ws is None else ws.data_ptr(), rows, N, int(act), _stream())
-    _lib.check(rc, "hipie_act_backward")
+        ws = torch.empty(_size("hipie_act_backward_ws_bytes", rows, N), dtype=torch.uint8, device=u.device)
+    _call("hipie_act_backward", u.data_ptr(), g.data_ptr(), du.data_ptr(), None if a is None else a.data_ptr(),
+          None if dbias is None else dbias.data_ptr(), None if ws is None else ws.data_ptr(), rows, N, int(act))
     return du, a, dbias
 
 
@@ -810,15 +769,13 @@ def point_mask_loss_forward(src, tgt, tgt_index, pts, mode, alpha=-1.0):
     target masks, tgt_index (N,) int64 rows of tgt, pts (N,P,2) (x, y) in [0,1]^2; mode 0 = sigmoid CE, 1 = focal (gamma 2, alpha) ->
     (lmask (N,), ldice (N,), sums (N,3) for point_mask_loss_backward).  Bit-reproducible; the workspace lives for the call."""
     src, tgt, tgt_index, pts = _point_loss_operands(src, tgt, tgt_index, pts)
-    lib = _lib.load()
     N, P = src.shape[0], pts.shape[1]
     lmask, ldice, sums = src.new_empty(N), src.new_empty(N), src.new_empty(N, 3)
-    ws_bytes = int(lib.hipie_point_mask_loss_ws_bytes(N, P))
+    ws_bytes = _size("hipie_point_mask_loss_ws_bytes", N, P)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=src.device)
-    rc = lib.hipie_point_mask_loss_forward(src.data_ptr(), tgt.data_ptr(), tgt_index.data_ptr(), pts.data_ptr(), lmask.data_ptr(), ldice.data_ptr(),
-                                           sums.data_ptr(), ws.data_ptr(), ws_bytes, N, src.shape[1], src.shape[2], tgt.shape[0], tgt.shape[1],
-                                           tgt.shape[2], P, int(mode), float(alpha), 2.0, _stream())
-    _lib.check(rc, "hipie_point_mask_loss_forward")
+    _call("hipie_point_mask_loss_forward", src.data_ptr(), tgt.data_ptr(), tgt_index.data_ptr(), pts.data_ptr(), lmask.data_ptr(), ldice.data_ptr(),
+          sums.data_ptr(), ws.data_ptr(), ws_bytes, N, src.shape[1], src.shape[2], tgt.shape[0], tgt.shape[1], tgt.shape[2], P, int(mode),
+          float(alpha), 2.0)
     return lmask, ldice, sums
 
 
@@ -832,10 +789,9 @@ def point_mask_loss_backward(src, tgt, tgt_index, pts, sums, g_mask, g_dice, mod
     if sums.shape != (N, 3) or g_mask.shape != (N,) or g_dice.shape != (N,):
         raise RuntimeError("point_mask_loss_backward: sums (N,3), g_mask (N,), g_dice (N,) for N=%d" % N)
     d_src = torch.empty_like(src)
-    rc = _lib.load().hipie_point_mask_loss_backward(src.data_ptr(), tgt.data_ptr(), tgt_index.data_ptr(), pts.data_ptr(), sums.data_ptr(),
-                                                    g_mask.data_ptr(), g_dice.data_ptr(), d_src.data_ptr(), N, src.shape[1], src.shape[2],
-                                                    tgt.shape[0], tgt.shape[1], tgt.shape[2], pts.shape[1], int(mode), float(alpha), 2.0, _stream())
-    _lib.check(rc, "hipie_point_mask_loss_backward")
+    _call("hipie_point_mask_loss_backward", src.data_ptr(), tgt.data_ptr(), tgt_index.data_ptr(), pts.data_ptr(), sums.data_ptr(),
+          g_mask.data_ptr(), g_dice.data_ptr(), d_src.data_ptr(), N, src.shape[1], src.shape[2],
+          tgt.shape[0], tgt.shape[1], tgt.shape[2], pts.shape[1], int(mode), float(alpha), 2.0)
     return d_src
 
 
@@ -857,14 +813,12 @@ def token_focal_forward(logits, onehot, keep=None, alpha=0.25):
     """sum over (b, q, t) with keep[b, t] != 0 of the binary focal loss (gamma 2) of logits (B,Q,T) against onehot (B,Q,T)
     (hipie_token_focal_forward, fp32) -> 0-d tensor.  keep (B,T) or None.  Bit-reproducible, no host wait."""
     logits, onehot, keep = _token_focal_operands(logits, onehot, keep)
-    lib = _lib.load()
     B, Q, T = logits.shape
     out = logits.new_zeros(())
-    ws_bytes = int(lib.hipie_token_focal_ws_bytes(logits.numel()))
+    ws_bytes = _size("hipie_token_focal_ws_bytes", logits.numel())
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=logits.device)
-    rc = lib.hipie_token_focal_forward(logits.data_ptr(), onehot.data_ptr(), None if keep is None else keep.data_ptr(), out.data_ptr(),
-                                       ws.data_ptr(), ws_bytes, B, Q, T, float(alpha), 2.0, _stream())
-    _lib.check(rc, "hipie_token_focal_forward")
+    _call("hipie_token_focal_forward", logits.data_ptr(), onehot.data_ptr(), None if keep is None else keep.data_ptr(), out.data_ptr(),
+          ws.data_ptr(), ws_bytes, B, Q, T, float(alpha), 2.0)
     return out
 
 
@@ -878,9 +832,8 @@ def token_focal_backward(logits, onehot, keep, g, alpha=0.25):
         raise RuntimeError("token_focal_backward: g must hold one value, got %s" % (tuple(g.shape),))
     B, Q, T = logits.shape
     dlogits = torch.empty_like(logits)
-    rc = _lib.load().hipie_token_focal_backward(logits.data_ptr(), onehot.data_ptr(), None if keep is None else keep.data_ptr(), g.data_ptr(),
-                                                dlogits.data_ptr(), B, Q, T, float(alpha), 2.0, _stream())
-    _lib.check(rc, "hipie_token_focal_backward")
+    _call("hipie_token_focal_backward", logits.data_ptr(), onehot.data_ptr(), None if keep is None else keep.data_ptr(), g.data_ptr(),
+          dlogits.data_ptr(), B, Q, T, float(alpha), 2.0)
     return dlogits
 
 
@@ -910,7 +863,7 @@ def _workspace(ws, need, device, what):
 
 
 def uncertain_points_ws_bytes(N, C):
-    return int(_lib.load().hipie_uncertain_points_ws_bytes(int(N), int(C)))
+    return _size("hipie_uncertain_points_ws_bytes", int(N), int(C))
 
 
 @_timed("uncertain_points")
@@ -938,17 +891,15 @@ def uncertain_points(src, cand, rest, k, num_points=None, ws=None):
     if num_points is not None and P != int(num_points):
         raise RuntimeError("uncertain_points: rest must hold P - k = %d points, got %d" % (int(num_points) - k, n_rest))
     _on_device(src=src, cand=cand, rest=rest, ws=ws)
-    lib = _lib.load()
-    ws = _workspace(ws, int(lib.hipie_uncertain_points_ws_bytes(N, C)), src.device, "uncertain_points")
+    ws = _workspace(ws, _size("hipie_uncertain_points_ws_bytes", N, C), src.device, "uncertain_points")
     pts = src.new_empty(N, P, 2)
-    rc = lib.hipie_uncertain_points(src.data_ptr(), cand.data_ptr(), rest.data_ptr() if n_rest else None, pts.data_ptr(), ws.data_ptr(), ws.numel(),
-                                    N, src.shape[1], src.shape[2], C, P, k, _stream())
-    _lib.check(rc, "hipie_uncertain_points")
+    _call("hipie_uncertain_points", src.data_ptr(), cand.data_ptr(), rest.data_ptr() if n_rest else None, pts.data_ptr(), ws.data_ptr(), ws.numel(),
+          N, src.shape[1], src.shape[2], C, P, k)
     return pts
 
 
 def mask_match_cost_ws_bytes(Q, T, P):
-    return int(_lib.load().hipie_mask_match_cost_ws_bytes(int(Q), int(T), int(P)))
+    return _size("hipie_mask_match_cost_ws_bytes", int(Q), int(T), int(P))
 
 
 @_timed("mask_match_cost")
@@ -971,12 +922,10 @@ def mask_match_cost(pred, tgt, coords, ws=None, ce_out=None, dice_out=None):
         _layout_as(ce_out, "ce_out", torch.float32, (Q, T))
         _layout_as(dice_out, "dice_out", torch.float32, (Q, T))
     _on_device(pred=pred, tgt=tgt, coords=coords, ws=ws, ce_out=ce_out, dice_out=dice_out)
-    lib = _lib.load()
-    ws = _workspace(ws, int(lib.hipie_mask_match_cost_ws_bytes(Q, T, P)), pred.device, "mask_match_cost")
+    ws = _workspace(ws, _size("hipie_mask_match_cost_ws_bytes", Q, T, P), pred.device, "mask_match_cost")
     ce, dice = (pred.new_empty(Q, T), pred.new_empty(Q, T)) if ce_out is None else (ce_out, dice_out)
-    rc = lib.hipie_mask_match_cost(pred.data_ptr(), tgt.data_ptr(), coords.data_ptr(), ce.data_ptr(), dice.data_ptr(), ws.data_ptr(), ws.numel(),
-                                   Q, pred.shape[1], pred.shape[2], T, tgt.shape[1], tgt.shape[2], P, _stream())
-    _lib.check(rc, "hipie_mask_match_cost")
+    _call("hipie_mask_match_cost", pred.data_ptr(), tgt.data_ptr(), coords.data_ptr(), ce.data_ptr(), dice.data_ptr(), ws.data_ptr(), ws.numel(),
+          Q, pred.shape[1], pred.shape[2], T, tgt.shape[1], tgt.shape[2], P)
     return ce, dice
 
 
@@ -984,7 +933,7 @@ OTA_MAX_Q, OTA_MAX_T, OTA_MAX_L = 4096, 256, 1024          # the limits of csrc/
 
 
 def ota_match_ws_bytes(B, Q, Tmax):
-    return int(_lib.load().hipie_ota_match_ws_bytes(int(B), int(Q), int(Tmax)))
+    return _size("hipie_ota_match_ws_bytes", int(B), int(Q), int(Tmax))
 
 
 def _layout_as(t, name, dtype, shape):
@@ -1024,13 +973,11 @@ def ota_cost(logits, boxes, tgt_boxes, pos_map, n_tgt, center_radius=2.5, stride
     _layout_as(n_tgt, "n_tgt", torch.int32, (B,))
     res = _ota_results(res, B, logits.device)
     _on_device(logits=logits, boxes=boxes, tgt_boxes=tgt_boxes, pos_map=pos_map, n_tgt=n_tgt, ws=ws, res=res)
-    lib = _lib.load()
-    ws = _workspace(ws, int(lib.hipie_ota_match_ws_bytes(B, Q, Tmax)), logits.device, "ota_cost")
+    ws = _workspace(ws, _size("hipie_ota_match_ws_bytes", B, Q, Tmax), logits.device, "ota_cost")
     n = B * Tmax * Q * 4
     cost, iou = ws[:n].view(torch.float32).view(B, Tmax, Q), ws[n:2 * n].view(torch.float32).view(B, Tmax, Q)
-    rc = lib.hipie_ota_cost(logits.data_ptr(), boxes.data_ptr(), tgt_boxes.data_ptr(), pos_map.data_ptr(), n_tgt.data_ptr(), cost.data_ptr(),
-                            iou.data_ptr(), res[1].data_ptr(), B, Q, Tmax, L, float(center_radius), float(stride), _stream())
-    _lib.check(rc, "hipie_ota_cost")
+    _call("hipie_ota_cost", logits.data_ptr(), boxes.data_ptr(), tgt_boxes.data_ptr(), pos_map.data_ptr(), n_tgt.data_ptr(), cost.data_ptr(),
+          iou.data_ptr(), res[1].data_ptr(), B, Q, Tmax, L, float(center_radius), float(stride))
     return cost, iou, res
 
 
@@ -1047,12 +994,10 @@ def ota_assign(cost, iou, n_tgt, res=None):
     _layout_as(n_tgt, "n_tgt", torch.int32, (B,))
     res = _ota_results(res, B, cost.device)
     _on_device(cost=cost, iou=iou, n_tgt=n_tgt, res=res)
-    lib = _lib.load()
     pairs = torch.empty(2, B, Q, dtype=torch.int32, device=cost.device)
     best = torch.empty(B, Tmax, dtype=torch.int32, device=cost.device)
-    rc = lib.hipie_ota_assign(cost.data_ptr(), iou.data_ptr(), n_tgt.data_ptr(), pairs[0].data_ptr(), pairs[1].data_ptr(), best.data_ptr(),
-                              res[0].data_ptr(), res[1].data_ptr(), res[2].data_ptr(), B, Q, Tmax, _stream())
-    _lib.check(rc, "hipie_ota_assign")
+    _call("hipie_ota_assign", cost.data_ptr(), iou.data_ptr(), n_tgt.data_ptr(), pairs[0].data_ptr(), pairs[1].data_ptr(), best.data_ptr(),
+          res[0].data_ptr(), res[1].data_ptr(), res[2].data_ptr(), B, Q, Tmax)
     return pairs[0], pairs[1], best, res
 
 
@@ -1061,7 +1006,7 @@ HUNGARIAN_STATUS = ((1, "a box with x1 < x0 or y1 < y0 (or a NaN)"), (8, "a labe
 
 
 def hungarian_cost_ws_bytes(B, Q):
-    return int(_lib.load().hipie_hungarian_cost_ws_bytes(int(B), int(Q)))
+    return _size("hipie_hungarian_cost_ws_bytes", int(B), int(Q))
 
 
 def _image_stride(t, name, row):
@@ -1129,7 +1074,6 @@ def hungarian_cost(logits, boxes, tgt_boxes, n_tgt, t_off, sum_t, weights, pos_m
         _layout_as(out, "out", torch.float32, (Q * sum_t + B,))
     _on_device(logits=logits, boxes=boxes if with_boxes else None, tgt_boxes=tgt_boxes, n_tgt=n_tgt, t_off=t_off, pos_map=pos_map, labels=labels,
                is_thing=is_thing if mean else None, ce=ce, dice=dice, out=out, ws=ws)
-    lib = _lib.load()
     if out is None:
         out = torch.empty(Q * sum_t + B, dtype=torch.float32, device=logits.device)
     n = Q * sum_t
@@ -1138,16 +1082,15 @@ def hungarian_cost(logits, boxes, tgt_boxes, n_tgt, t_off, sum_t, weights, pos_m
         status.zero_()
         return out
     if mean:
-        ws = _workspace(ws, int(lib.hipie_hungarian_cost_ws_bytes(B, Q)), logits.device, "hungarian_cost")
+        ws = _workspace(ws, _size("hipie_hungarian_cost_ws_bytes", B, Q), logits.device, "hungarian_cost")
     ptr = lambda t: None if t is None else t.data_ptr()          # noqa: E731
     w = [float(x) for x in weights]
     if len(w) != 5:
         raise RuntimeError("hungarian_cost: five weights (cls, l1, giou, mask, dice), got %d" % len(w))
-    rc = lib.hipie_hungarian_cost(logits.data_ptr(), ls, ptr(boxes) if with_boxes else None, bs, tgt_boxes.data_ptr(), n_tgt.data_ptr(), t_off.data_ptr(),
-                                  ptr(pos_map), ptr(labels), ptr(is_thing) if mean else None, ptr(ce), ptr(dice), out.data_ptr() if n else None,
-                                  status.data_ptr(), ws.data_ptr() if mean else None, ws.numel() if mean else 0, B, Q, Tmax, L, sum_t, *w,
-                                  1 if with_boxes else 0, 1 if stuff_takes_mean else 0, _stream())
-    _lib.check(rc, "hipie_hungarian_cost")
+    _call("hipie_hungarian_cost", logits.data_ptr(), ls, ptr(boxes) if with_boxes else None, bs, tgt_boxes.data_ptr(), n_tgt.data_ptr(), t_off.data_ptr(),
+          ptr(pos_map), ptr(labels), ptr(is_thing) if mean else None, ptr(ce), ptr(dice), out.data_ptr() if n else None,
+          status.data_ptr(), ws.data_ptr() if mean else None, ws.numel() if mean else 0, B, Q, Tmax, L, sum_t, *w,
+          1 if with_boxes else 0, 1 if stuff_takes_mean else 0)
     return out
 
 
@@ -1157,7 +1100,7 @@ HUNGARIAN_STATUS = HUNGARIAN_STATUS + ((32, "matrix contains invalid numeric ent
 
 
 def hungarian_assign_ws_bytes(Q, sum_t):
-    return int(_lib.load().hipie_hungarian_assign_ws_bytes(int(Q), int(sum_t)))
+    return _size("hipie_hungarian_assign_ws_bytes", int(Q), int(sum_t))
 
 
 @_timed("hungarian_assign")
@@ -1182,17 +1125,15 @@ def hungarian_assign(costs, n_tgt, t_off, sum_t, Q, Tmax, ws=None):
     if Q > HUNGARIAN_MAX_Q or Tmax > HUNGARIAN_MAX_T or B > 65535:
         raise RuntimeError("hungarian_assign: B=%d, Q=%d, Tmax=%d outside B <= 65535, Q <= %d, Tmax <= %d" % (B, Q, Tmax, HUNGARIAN_MAX_Q, HUNGARIAN_MAX_T))
     _on_device(costs=costs, n_tgt=n_tgt, t_off=t_off, ws=ws)
-    lib = _lib.load()
     K, n = min(Q, Tmax), Q * sum_t
     pairs = torch.empty(2, B, K, dtype=torch.int64, device=costs.device)
     status = torch.empty(B, dtype=torch.int32, device=costs.device)
     if B * Q * Tmax == 0:                                    # no launch: nothing to solve (K == 0 or B == 0: the pairs are empty)
         status.copy_(costs[n:].view(torch.int32))
         return pairs[0], pairs[1], status
-    ws = _workspace(ws, int(lib.hipie_hungarian_assign_ws_bytes(Q, sum_t)), costs.device, "hungarian_assign")
-    rc = lib.hipie_hungarian_assign(costs.data_ptr() if n else None, costs[n:].data_ptr(), n_tgt.data_ptr(), t_off.data_ptr(), pairs[0].data_ptr(),
-                                    pairs[1].data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), B, Q, Tmax, sum_t, _stream())
-    _lib.check(rc, "hipie_hungarian_assign")
+    ws = _workspace(ws, _size("hipie_hungarian_assign_ws_bytes", Q, sum_t), costs.device, "hungarian_assign")
+    _call("hipie_hungarian_assign", costs.data_ptr() if n else None, costs[n:].data_ptr(), n_tgt.data_ptr(), t_off.data_ptr(), pairs[0].data_ptr(),
+          pairs[1].data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), B, Q, Tmax, sum_t)
     return pairs[0], pairs[1], status
 
 
@@ -1202,11 +1143,11 @@ OPTIM_SEGMENT_WORDS = 6          # int64 words of a segment record: p, g, m, v, 
 
 def optim_chunk():
     """elements per chunk-map entry of the optimizer kernels (hipie_optim_chunk)"""
-    return int(_lib.load().hipie_optim_chunk())
+    return _size("hipie_optim_chunk")
 
 
 def optim_norm_ws_bytes(n_chunks):
-    return int(_lib.load().hipie_optim_norm_ws_bytes(int(n_chunks)))
+    return _size("hipie_optim_norm_ws_bytes", int(n_chunks))
 
 
 def _optim_tables(who, table, cmap):
@@ -1232,11 +1173,9 @@ def optim_grad_norm(table, cmap, grad_scale=1.0, ws=None):
     out = torch.empty((), dtype=torch.float32, device=table.device)
     if n_seg == 0 or n_chunks == 0:
         return out.zero_()
-    lib = _lib.load()
-    ws = _workspace(ws, int(lib.hipie_optim_norm_ws_bytes(n_chunks)), table.device, "optim_grad_norm")
+    ws = _workspace(ws, _size("hipie_optim_norm_ws_bytes", n_chunks), table.device, "optim_grad_norm")
     _on_device(ws=ws)
-    rc = lib.hipie_optim_grad_norm(table.data_ptr(), n_seg, cmap.data_ptr(), n_chunks, ws.data_ptr(), ws.numel(), float(grad_scale), out.data_ptr(), _stream())
-    _lib.check(rc, "hipie_optim_grad_norm")
+    _call("hipie_optim_grad_norm", table.data_ptr(), n_seg, cmap.data_ptr(), n_chunks, ws.data_ptr(), ws.numel(), float(grad_scale), out.data_ptr())
     return out
 
 
@@ -1258,25 +1197,22 @@ def optim_adamw_step(table, cmap, steps, bc, group_lr, group_wd, betas, eps, nor
         raise RuntimeError("optim_adamw_step: %d learning rates, %d weight decays: one each for 1 to %d groups" % (n_groups, len(group_wd), OPTIM_MAX_GROUPS))
     arr = ctypes.c_double * n_groups
     lr, wd = arr(*[float(x) for x in group_lr]), arr(*[float(x) for x in group_wd])
-    rc = _lib.load().hipie_optim_adamw_step(table.data_ptr(), n_seg, cmap.data_ptr(), n_chunks, steps.data_ptr(), bc.data_ptr(), lr, wd, n_groups,
-                                            float(betas[0]), float(betas[1]), float(eps), None if norm is None else norm.data_ptr(),
-                                            float(max_norm), float(grad_scale), int(bool(write_grads)), _stream())
-    _lib.check(rc, "hipie_optim_adamw_step")
+    _call("hipie_optim_adamw_step", table.data_ptr(), n_seg, cmap.data_ptr(), n_chunks, steps.data_ptr(), bc.data_ptr(), lr, wd, n_groups,
+          float(betas[0]), float(betas[1]), float(eps), None if norm is None else norm.data_ptr(),
+          float(max_norm), float(grad_scale), int(bool(write_grads)))
 
 
 @_timed("add_layernorm")
 def add_layernorm_sum(x, delta, weight, bias, eps, addend):
     """n = LayerNorm(x + delta) and n + addend, both in x's dtype, one launch (the encoder's post-norm + next `src + pos`)."""
-    lib = _lib.load()
     C = x.shape[-1]
     rows = x.numel() // C
     if addend.dtype != x.dtype or addend.shape != x.shape:
         raise RuntimeError("add_layernorm_sum: addend must match x")
     out, s = torch.empty_like(x), torch.empty_like(x)
-    rc = lib.hipie_add_layernorm_sum(_chk(x, "x"), _chk(delta, "delta"), _chk(weight, "weight", torch.float32),
-                                     _chk(bias, "bias", torch.float32), None, out.data_ptr(), _chk(addend, "addend"), s.data_ptr(),
-                                     rows, C, float(eps), _DT[x.dtype], _DT[delta.dtype], _DT[x.dtype], _stream())
-    _lib.check(rc, "hipie_add_layernorm_sum")
+    _call("hipie_add_layernorm_sum", _chk(x, "x"), _chk(delta, "delta"), _chk(weight, "weight", torch.float32),
+          _chk(bias, "bias", torch.float32), None, out.data_ptr(), _chk(addend, "addend"), s.data_ptr(),
+          rows, C, float(eps), _DT[x.dtype], _DT[delta.dtype], _DT[x.dtype])
     return out, s
 
 
@@ -1284,7 +1220,6 @@ def add_layernorm_sum(x, delta, weight, bias, eps, addend):
 def add_layernorm_dec(x, delta, weight, bias, eps, aux_dtype, want16=False, addend=None):
     """n = LayerNorm(x + delta) for the fp32 query stream of the decoders: returns (n f32, n in aux_dtype or None,
     (n + addend) in aux_dtype or None) from one launch.  x (..., C) f32; delta any of f32/f16/bf16; addend aux_dtype."""
-    lib = _lib.load()
     C = x.shape[-1]
     rows = x.numel() // C
     out = torch.empty_like(x)
@@ -1293,11 +1228,10 @@ def add_layernorm_dec(x, delta, weight, bias, eps, aux_dtype, want16=False, adde
     if addend is not None and ((addend.dtype != aux_dtype or addend.shape != x.shape) if aux_dtype != "hl8" else
                                (addend.dtype != torch.float16 or addend.numel() != 2 * x.numel())):
         raise RuntimeError("add_layernorm_dec: addend must match x's shape in aux_dtype")
-    rc = lib.hipie_add_layernorm_dec(_chk(x, "x", torch.float32), _chk(delta, "delta"), _chk(weight, "weight", torch.float32),
-                                     _chk(bias, "bias", torch.float32), out.data_ptr(), None if n16 is None else n16.data_ptr(),
-                                     None if addend is None else _chk(addend, "addend"), None if s16 is None else s16.data_ptr(),
-                                     rows, C, float(eps), _DT[delta.dtype], _code(aux_dtype), _stream())
-    _lib.check(rc, "hipie_add_layernorm_dec")
+    _call("hipie_add_layernorm_dec", _chk(x, "x", torch.float32), _chk(delta, "delta"), _chk(weight, "weight", torch.float32),
+          _chk(bias, "bias", torch.float32), out.data_ptr(), None if n16 is None else n16.data_ptr(),
+          None if addend is None else _chk(addend, "addend"), None if s16 is None else s16.data_ptr(),
+          rows, C, float(eps), _DT[delta.dtype], _code(aux_dtype))
     return out, n16, s16
 
 
@@ -1315,7 +1249,6 @@ def group_norm(x, groups, weight, bias, eps, relu=False, prebias=None, out_dtype
     """GroupNorm(groups, C = 8 * groups)(x + prebias[c]) (+ ReLU) on a (B,C,H,W) tensor in the memory format it arrives in
     (channels-last stays channels-last: no NHWC -> NCHW copy); fp32 statistics.  out_nchw: a channels-last input leaves as a dense
     NCHW tensor (transposed inside the kernel; H*W % 64 == 0) -- what `.contiguous()` would make of the result, without that pass."""
-    lib = _lib.load()
     B, C, H, W = x.shape
     nhwc = x.is_contiguous(memory_format=torch.channels_last) and not (x.is_contiguous() and C > 1 and H * W > 1)
     if not nhwc and not x.is_contiguous():
@@ -1330,35 +1263,29 @@ def group_norm(x, groups, weight, bias, eps, relu=False, prebias=None, out_dtype
     ws = _GN_WS.get(key)
     if ws is None:
         ws = _GN_WS[key] = torch.empty(2 * B * groups * 512, dtype=torch.float32, device=x.device)
-    rc = lib.hipie_group_norm(x.data_ptr(), None if prebias is None else _chk(prebias, "prebias", torch.float32),
-                              _chk(weight, "weight", torch.float32), _chk(bias, "bias", torch.float32), out.data_ptr(),
-                              ws.data_ptr(), B, C, H * W, groups, int(nhwc), float(eps), 1 if relu else 0,
-                              _DT[x.dtype], _DT[out_dtype], _stream())
-    _lib.check(rc, "hipie_group_norm")
+    _call("hipie_group_norm", x.data_ptr(), None if prebias is None else _chk(prebias, "prebias", torch.float32),
+          _chk(weight, "weight", torch.float32), _chk(bias, "bias", torch.float32), out.data_ptr(),
+          ws.data_ptr(), B, C, H * W, groups, int(nhwc), float(eps), 1 if relu else 0, _DT[x.dtype], _DT[out_dtype])
     return out
 
 
 @_timed("add_cast")
 def add_cast(a, b):
     """(a f32 + b 16-bit) rounded once to b's dtype; same shapes, numel % 4 == 0."""
-    lib = _lib.load()
     if a.shape != b.shape:
         raise RuntimeError("add_cast: shapes differ")
     out = torch.empty_like(b)
-    rc = lib.hipie_add_cast(_chk(a, "a", torch.float32), _chk(b, "b"), out.data_ptr(), a.numel(), _DT[b.dtype], _stream())
-    _lib.check(rc, "hipie_add_cast")
+    _call("hipie_add_cast", _chk(a, "a", torch.float32), _chk(b, "b"), out.data_ptr(), a.numel(), _DT[b.dtype])
     return out
 
 
 @_timed("add_cast")
 def add_to_hl8(a, b_hl8):
     """HL8 of (a + b): a (..., C) fp32, b_hl8 (..., 2C) fp16 HL8 of the same rows -> (..., 2C) HL8, one pass (hipie_add_cast, HL8 form)."""
-    lib = _lib.load()
     if b_hl8.dtype != torch.float16 or b_hl8.numel() != 2 * a.numel() or a.shape[-1] % 8 or not a.is_cuda:
         raise RuntimeError("add_to_hl8: a (.., C) fp32 and b (.., 2C) HL8 device tensors, C %% 8 == 0")
     out = torch.empty_like(b_hl8)
-    rc = lib.hipie_add_cast(_chk(a, "a", torch.float32), _chk(b_hl8, "b"), out.data_ptr(), a.numel(), HL8, _stream())
-    _lib.check(rc, "hipie_add_cast")
+    _call("hipie_add_cast", _chk(a, "a", torch.float32), _chk(b_hl8, "b"), out.data_ptr(), a.numel(), HL8)
     return out
 
 
@@ -1366,16 +1293,14 @@ def add_to_hl8(a, b_hl8):
 def batched_nms(boxes, scores, classes, iou_threshold, coordinate_trick=None):
     """boxes (B,Q,4) normalised cxcywh, scores (B,Q), classes (B,Q) int64 -> keep (B,Q) int32 (query indices in
     decreasing-score order, -1 padded), count (B) int32.  torchvision.ops.batched_nms semantics per image."""
-    lib = _lib.load()
     B, Q = scores.shape
     if coordinate_trick is None:
         coordinate_trick = Q * 4 <= 4000                  # torchvision/ops/boxes.py batched_nms switch
     order = scores.sort(dim=1, descending=True, stable=True)[1].to(torch.int32)
     keep = torch.empty(B, Q, dtype=torch.int32, device=boxes.device)
     count = torch.empty(B, dtype=torch.int32, device=boxes.device)
-    rc = lib.hipie_batched_nms(_chk(boxes, "boxes", torch.float32), _chk(classes, "classes", torch.int64), order.data_ptr(),
-                               keep.data_ptr(), count.data_ptr(), B, Q, float(iou_threshold), int(coordinate_trick), _stream())
-    _lib.check(rc, "hipie_batched_nms")
+    _call("hipie_batched_nms", _chk(boxes, "boxes", torch.float32), _chk(classes, "classes", torch.int64), order.data_ptr(),
+          keep.data_ptr(), count.data_ptr(), B, Q, float(iou_threshold), int(coordinate_trick))
     return keep, count
 
 
@@ -1383,14 +1308,11 @@ def batched_nms(boxes, scores, classes, iou_threshold, coordinate_trick=None):
 def mask_finalize(masks, qidx, up, crop_hw, out_hw, threshold):
     """masks (Q,hm,wm) stride-`up` logits, qidx (n) int32 rows (or None) -> (n,out_h,out_w) uint8:
     bilinear x`up` -> sigmoid > threshold -> crop -> nearest resize to out_hw."""
-    lib = _lib.load()
     Q, hm, wm = masks.shape
     n = Q if qidx is None else int(qidx.shape[0])
     out = torch.empty(n, out_hw[0], out_hw[1], dtype=torch.uint8, device=masks.device)
-    rc = lib.hipie_mask_finalize(_chk(masks, "masks"), _DT[masks.dtype], None if qidx is None else _chk(qidx, "qidx", torch.int32),
-                                 n, hm, wm, int(up), int(crop_hw[0]), int(crop_hw[1]), int(out_hw[0]), int(out_hw[1]),
-                                 float(threshold), out.data_ptr(), _stream())
-    _lib.check(rc, "hipie_mask_finalize")
+    _call("hipie_mask_finalize", _chk(masks, "masks"), _DT[masks.dtype], None if qidx is None else _chk(qidx, "qidx", torch.int32),
+          n, hm, wm, int(up), int(crop_hw[0]), int(crop_hw[1]), int(out_hw[0]), int(out_hw[1]), float(threshold), out.data_ptr())
     return out
 
 
@@ -1408,7 +1330,6 @@ def sem_pan(masks_lo, cls_all, pscore, up, crop_hw, out_hw, precision=0):
     sem (C,oh,ow) f32, pan_idx (oh,ow) int32 (-1: no kept query), pan_own (oh,ow) bool, area (N) int32.
     More than SEM_PAN_CLASSES classes (ADE-847, LVIS-1203: BASELINE configs[3]/[4]) run as class tiles of one launch each;
     the panoptic outputs do not depend on the classes and are taken from the first tile."""
-    lib = _lib.load()
     N, C = cls_all.shape
     _, hm, wm = masks_lo.shape
     dev = masks_lo.device
@@ -1435,10 +1356,9 @@ def sem_pan(masks_lo, cls_all, pscore, up, crop_hw, out_hw, precision=0):
             if spare is None:
                 spare = (torch.empty_like(pan_idx), torch.empty_like(pan_own), torch.zeros_like(area))
             outs = spare
-        rc = lib.hipie_sem_pan(masks_ptr, hi.data_ptr(), None if lo is None else lo.data_ptr(),
-                               ps.data_ptr(), sem[c0:c0 + cn].data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(),
-                               N, npad, cn, hm, wm, int(up), int(crop_hw[0]), int(crop_hw[1]), oh, ow, int(precision), _stream())
-        _lib.check(rc, "hipie_sem_pan")
+        _call("hipie_sem_pan", masks_ptr, hi.data_ptr(), None if lo is None else lo.data_ptr(),
+              ps.data_ptr(), sem[c0:c0 + cn].data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(),
+              N, npad, cn, hm, wm, int(up), int(crop_hw[0]), int(crop_hw[1]), oh, ow, int(precision))
     return sem, pan_idx, pan_own.bool(), area[:N]
 
 
@@ -1449,7 +1369,6 @@ _DIM_T = {}
 def sine_embed(ref, num_pos_feats=128, temperature=10000, out_dtype=torch.float32):
     """get_sine_pos_embed(ref, exchange_xy=True): ref (..., 2|4) f32 (last-dim stride 1) -> (..., ncoord * num_pos_feats)."""
     import math
-    lib = _lib.load()
     nc = ref.shape[-1]
     ref = ref.float()
     rs = nc
@@ -1467,9 +1386,7 @@ def sine_embed(ref, num_pos_feats=128, temperature=10000, out_dtype=torch.float3
     out = torch.empty(ref.shape[:-1] + (nc * num_pos_feats,), dtype=out_dtype, device=ref.device)
     if not ref.is_cuda:
         raise RuntimeError("Not implemented on the CPU (ref must be a CUDA/HIP tensor)")
-    rc = lib.hipie_sine_embed(ref.data_ptr(), dim_t.data_ptr(), out.data_ptr(), n, nc, num_pos_feats, rs,
-                              2 * math.pi, _DT[out_dtype], _stream())
-    _lib.check(rc, "hipie_sine_embed")
+    _call("hipie_sine_embed", ref.data_ptr(), dim_t.data_ptr(), out.data_ptr(), n, nc, num_pos_feats, rs, 2 * math.pi, _DT[out_dtype])
     return out
 
 
@@ -1490,7 +1407,6 @@ def ref_point_mlp(ref, head, num_pos_feats=128, temperature=10000):
     """query_pos = head(get_sine_pos_embed(ref)) in one launch: ref (B, Q, 4) f32 (row-strided view allowed), head = the
     2-layer ref_point_head (512 -> 256 -> 256) -> (B, Q, 256) in the head's weight dtype."""
     import math
-    lib = _lib.load()
     ref = ref.float()
     rs = 4
     if ref.dim() == 3 and ref.stride(-1) == 1 and ref.stride(0) == ref.shape[1] * ref.stride(1) and ref.stride(1) >= 4:
@@ -1507,9 +1423,8 @@ def ref_point_mlp(ref, head, num_pos_feats=128, temperature=10000):
     dt = w1t.dtype
     n = ref.numel() // 4
     out = torch.empty(ref.shape[:-1] + (256,), dtype=dt, device=ref.device)
-    rc = lib.hipie_ref_point_mlp(ref.data_ptr(), dim_t.data_ptr(), w1t.data_ptr(), b1.data_ptr(), w2t.data_ptr(), b2.data_ptr(),
-                                 out.data_ptr(), n, rs, 2 * math.pi, _DT[dt], _stream())
-    _lib.check(rc, "hipie_ref_point_mlp")
+    _call("hipie_ref_point_mlp", ref.data_ptr(), dim_t.data_ptr(), w1t.data_ptr(), b1.data_ptr(), w2t.data_ptr(), b2.data_ptr(),
+          out.data_ptr(), n, rs, 2 * math.pi, _DT[dt])
     return out
 
 
@@ -1523,33 +1438,26 @@ def box_head_ok(x, mlp):
 @_timed("box_head")
 def box_head(x, ref, mlp, eps=1e-5):
     """sigmoid(mlp(x) + inverse_sigmoid(ref)) in one launch: x (..., 256) f32, ref (..., 4) f32, mlp = MLP(256, 256, 4, 3) f32."""
-    lib = _lib.load()
     x, ref = x.contiguous(), ref.float().contiguous()
     (w1t, b1), (w2t, b2), (w3t, b3) = _transposed(list(mlp.layers))
     out = torch.empty_like(ref)
-    rc = lib.hipie_box_head(_chk(x, "x", torch.float32), _chk(ref, "ref", torch.float32), w1t.data_ptr(), b1.data_ptr(), w2t.data_ptr(),
-                            b2.data_ptr(), w3t.data_ptr(), b3.data_ptr(), out.data_ptr(), ref.numel() // 4, float(eps), _stream())
-    _lib.check(rc, "hipie_box_head")
+    _call("hipie_box_head", _chk(x, "x", torch.float32), _chk(ref, "ref", torch.float32), w1t.data_ptr(), b1.data_ptr(), w2t.data_ptr(),
+          b2.data_ptr(), w3t.data_ptr(), b3.data_ptr(), out.data_ptr(), ref.numel() // 4, float(eps))
     return out
 
 
 @_timed("box_refine")
 def box_refine(delta, ref, eps=1e-5):
     """sigmoid(delta + inverse_sigmoid(ref)): delta (..., 4) f32|f16|bf16, ref (..., 4) f32 -> (..., 4) f32."""
-    lib = _lib.load()
     delta, ref = delta.contiguous(), ref.float().contiguous()
     out = torch.empty_like(ref)
-    rc = lib.hipie_box_refine(_chk(delta, "delta"), _chk(ref, "ref", torch.float32), out.data_ptr(), ref.numel(), float(eps),
-                              _DT[delta.dtype], _stream())
-    _lib.check(rc, "hipie_box_refine")
+    _call("hipie_box_refine", _chk(delta, "delta"), _chk(ref, "ref", torch.float32), out.data_ptr(), ref.numel(), float(eps), _DT[delta.dtype])
     return out
 
 
 def selftest(which, a, b=None):
-    lib = _lib.load()
     out = torch.empty(32 * 32 if which == 0 else 256, dtype=torch.float32, device=a.device)
-    rc = lib.hipie_selftest(which, a.data_ptr(), None if b is None else b.data_ptr(), out.data_ptr(), _stream())
-    _lib.check(rc, "hipie_selftest")
+    _call("hipie_selftest", which, a.data_ptr(), None if b is None else b.data_ptr(), out.data_ptr())
     return out
 
 
@@ -1576,7 +1484,6 @@ def hl8_unpack(x):
 @_timed("to_hl8")
 def to_hl8(x, scale=1.0):
     """(rows..., K) fp32 | fp16 device tensor (last dim contiguous, uniform row stride) -> (rows..., 2K) fp16 HL8 (hipie_to_hl8)."""
-    lib = _lib.load()
     K = x.shape[-1]
     x2 = x.reshape(-1, K)
     if x2.stride(-1) != 1:
@@ -1584,8 +1491,7 @@ def to_hl8(x, scale=1.0):
     out = torch.empty(*x.shape[:-1], 2 * K, dtype=torch.float16, device=x.device)
     if not x.is_cuda:
         raise RuntimeError("Not implemented on the CPU (to_hl8)")
-    rc = lib.hipie_to_hl8(x2.data_ptr(), x2.stride(0), out.data_ptr(), 2 * K, x2.shape[0], K, _DT[x.dtype], float(scale), _stream())
-    _lib.check(rc, "hipie_to_hl8")
+    _call("hipie_to_hl8", x2.data_ptr(), x2.stride(0), out.data_ptr(), 2 * K, x2.shape[0], K, _DT[x.dtype], float(scale))
     return out
 
 
@@ -1593,7 +1499,6 @@ def to_hl8(x, scale=1.0):
 def to_hl8_t(x, pad_to=32, scale=1.0):
     """(M, C) fp32 device tensor (last dim contiguous, any row stride) -> (C, 2 Mp) fp16 HL8 of x^T, Mp = M rounded up to `pad_to`, the padding
     columns zero (hipie_to_hl8_t): a split operand whose K runs over the rows of x."""
-    lib = _lib.load()
     if x.dim() != 2 or x.dtype != torch.float32 or not x.is_cuda:
         raise RuntimeError("to_hl8_t: a 2-D fp32 device tensor")
     if x.stride(1) != 1:
@@ -1601,8 +1506,7 @@ def to_hl8_t(x, pad_to=32, scale=1.0):
     M, C = x.shape
     Mp = -(-M // pad_to) * pad_to
     out = torch.empty(C, 2 * Mp, dtype=torch.float16, device=x.device)
-    rc = lib.hipie_to_hl8_t(x.data_ptr(), x.stride(0), out.data_ptr(), 2 * Mp, M, C, Mp, float(scale), _stream())
-    _lib.check(rc, "hipie_to_hl8_t")
+    _call("hipie_to_hl8_t", x.data_ptr(), x.stride(0), out.data_ptr(), 2 * Mp, M, C, Mp, float(scale))
     return out
 
 
@@ -1613,15 +1517,13 @@ def f16_pair(x, cols=None, scale=None):
     C = x.shape[-1]
     Cp = C if cols is None else max(cols, C)
     if x.is_cuda and x.dtype == torch.float32 and Cp % 8 == 0:
-        lib = _lib.load()
         x2 = x.reshape(-1, C)
         if x2.stride(1) != 1 or (x2.shape[0] > 1 and x2.stride(0) < C):
             x2 = x2.contiguous()
         hi = torch.empty(*x.shape[:-1], Cp, dtype=torch.float16, device=x.device)
         lo = torch.empty_like(hi)
         sc = 0 if scale is None else scale.float().reshape(1).data_ptr()
-        rc = lib.hipie_to_f16_pair(x2.data_ptr(), x2.stride(0) if x2.shape[0] > 1 else C, hi.data_ptr(), lo.data_ptr(), x2.shape[0], C, Cp, sc, _stream())
-        _lib.check(rc, "hipie_to_f16_pair")
+        _call("hipie_to_f16_pair", x2.data_ptr(), x2.stride(0) if x2.shape[0] > 1 else C, hi.data_ptr(), lo.data_ptr(), x2.shape[0], C, Cp, sc)
         return hi, lo
     raise RuntimeError("f16_pair: an fp32 device tensor and a column count that is a multiple of 8 (got %s %s on %s, %d columns)"
                        % (x.dtype, tuple(x.shape), x.device, Cp))
@@ -1654,8 +1556,7 @@ def _attn_train_forward(inst, q_pair, k_pair, v_pair):
     planes, BH, N = _attn_train_operands(who, inst, (q_pair, k_pair, v_pair), (80,))
     out = torch.empty(BH, N, 80, dtype=torch.float32, device=planes[0].device)
     lse = torch.empty(BH, N, dtype=torch.float32, device=planes[0].device)
-    rc = getattr(_lib.load(), "hipie_" + who)(*[t.data_ptr() for t in planes], out.data_ptr(), lse.data_ptr(), BH, N, _stream())
-    _lib.check(rc, "hipie_" + who)
+    _call("hipie_" + who, *[t.data_ptr() for t in planes], out.data_ptr(), lse.data_ptr(), BH, N)
     return out, lse
 
 
@@ -1668,9 +1569,7 @@ def _attn_train_backward(inst, q_pair, k_pair, v96_pair, do96_pair, lse, delta):
     dq = torch.empty(BH, N, inst[1], dtype=torch.float32, device=planes[0].device)
     dk = torch.empty(BH, N, 80, dtype=torch.float32, device=planes[0].device)
     dv = torch.empty(BH, N, 80, dtype=torch.float32, device=planes[0].device)
-    rc = getattr(_lib.load(), "hipie_" + who)(*[t.data_ptr() for t in planes], lse.data_ptr(), delta.data_ptr(), dq.data_ptr(), dk.data_ptr(),
-                                              dv.data_ptr(), BH, N, _stream())
-    _lib.check(rc, "hipie_" + who)
+    _call("hipie_" + who, *[t.data_ptr() for t in planes], lse.data_ptr(), delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), BH, N)
     return dq, dk, dv
 
 
@@ -1747,9 +1646,8 @@ def attn_pack_kv(qkv, heads, H, W, cols, padded=False):
     rq = torch.empty(B * heads, N, ATTN_PACK_HD, dtype=torch.float32, device=dev)
     k = (torch.empty(B * heads, Np, cols, dtype=torch.float16, device=dev), torch.empty(B * heads, Np, cols, dtype=torch.float16, device=dev))
     v = (torch.empty(B * heads, Np, ATTN_PACK_HD, dtype=torch.float16, device=dev), torch.empty(B * heads, Np, ATTN_PACK_HD, dtype=torch.float16, device=dev))
-    rc = _lib.load().hipie_attn_pack_kv(qkv.data_ptr(), rq.data_ptr(), k[0].data_ptr(), k[1].data_ptr(), v[0].data_ptr(), v[1].data_ptr(), B, heads,
-                                        H, W, Np, cols, _stream())
-    _lib.check(rc, "hipie_attn_pack_kv")
+    _call("hipie_attn_pack_kv", qkv.data_ptr(), rq.data_ptr(), k[0].data_ptr(), k[1].data_ptr(), v[0].data_ptr(), v[1].data_ptr(), B, heads,
+          H, W, Np, cols)
     return rq, k, v
 
 
@@ -1777,9 +1675,8 @@ def attn_pack_q(rq, rel_h, rel_w, heads, H, W, cols, padded=False):
     sh, sw = _attn_pack_strides(who, "rel_h", rel_h, (BH, H, W, H)), _attn_pack_strides(who, "rel_w", rel_w, (BH, H, W, W))
     Np = attn_pack_rows(N, padded)
     q = (torch.empty(BH, Np, cols, dtype=torch.float16, device=rq.device), torch.empty(BH, Np, cols, dtype=torch.float16, device=rq.device))
-    rc = _lib.load().hipie_attn_pack_q(rq.data_ptr(), rel_h.data_ptr(), *sh, rel_w.data_ptr(), *sw, q[0].data_ptr(), q[1].data_ptr(), BH // heads, heads,
-                                       H, W, Np, cols, ATTN_PACK_HD ** -0.5, _stream())
-    _lib.check(rc, "hipie_attn_pack_q")
+    _call("hipie_attn_pack_q", rq.data_ptr(), rel_h.data_ptr(), *sh, rel_w.data_ptr(), *sw, q[0].data_ptr(), q[1].data_ptr(), BH // heads, heads,
+          H, W, Np, cols, ATTN_PACK_HD ** -0.5)
     return q
 
 
@@ -1790,8 +1687,7 @@ def attn_grad_amax(go):
     _attn_pack_dev("attn_grad_amax", (("go", go),))
     _attn_pack_dense("attn_grad_amax", "go", go, go.shape)
     amax = torch.empty(1, dtype=torch.float32, device=go.device)
-    rc = _lib.load().hipie_attn_grad_amax(go.data_ptr(), go.numel(), amax.data_ptr(), _stream())
-    _lib.check(rc, "hipie_attn_grad_amax")
+    _call("hipie_attn_grad_amax", go.data_ptr(), go.numel(), amax.data_ptr())
     return amax
 
 
@@ -1816,9 +1712,8 @@ def attn_pack_grad(go, out, v_pair, scale, heads, H, W):
     do = (torch.empty(BH, Np, 96, dtype=torch.float16, device=dev), torch.empty(BH, Np, 96, dtype=torch.float16, device=dev))
     v96 = (torch.empty(BH, Np, 96, dtype=torch.float16, device=dev), torch.empty(BH, Np, 96, dtype=torch.float16, device=dev))
     delta = torch.empty(BH, Np, dtype=torch.float32, device=dev)
-    rc = _lib.load().hipie_attn_pack_grad(go.data_ptr(), out.data_ptr(), vp[0], vp[1], scale.data_ptr(), do[0].data_ptr(), do[1].data_ptr(),
-                                          v96[0].data_ptr(), v96[1].data_ptr(), delta.data_ptr(), B, heads, H, W, Np, _stream())
-    _lib.check(rc, "hipie_attn_pack_grad")
+    _call("hipie_attn_pack_grad", go.data_ptr(), out.data_ptr(), vp[0], vp[1], scale.data_ptr(), do[0].data_ptr(), do[1].data_ptr(),
+          v96[0].data_ptr(), v96[1].data_ptr(), delta.data_ptr(), B, heads, H, W, Np)
     return do, v96, delta
 
 
@@ -1847,10 +1742,9 @@ def attn_unpack_grad(dq, dk, dv, dq_h, dq_w, inv, heads, H, W):
     if inv.numel() != 1:
         raise RuntimeError("%s: inv must have one element" % who)
     dqkv = torch.empty(BH // heads, N, 3 * heads * ATTN_PACK_HD, dtype=torch.float32, device=dq.device)
-    rc = _lib.load().hipie_attn_unpack_grad(dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), dq_h.data_ptr(), *strides[0],
-                                            None if dq_w is None else dq_w.data_ptr(), *strides[1], inv.data_ptr(), dqkv.data_ptr(), BH // heads, heads,
-                                            H, W, Np, cols, ATTN_PACK_HD ** -0.5, _stream())
-    _lib.check(rc, "hipie_attn_unpack_grad")
+    _call("hipie_attn_unpack_grad", dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), dq_h.data_ptr(), *strides[0],
+          None if dq_w is None else dq_w.data_ptr(), *strides[1], inv.data_ptr(), dqkv.data_ptr(), BH // heads, heads,
+          H, W, Np, cols, ATTN_PACK_HD ** -0.5)
     return dqkv
 
 
@@ -1858,12 +1752,10 @@ def attn_unpack_grad(dq, dk, dv, dq_h, dq_w, inv, heads, H, W):
 def fill_rows(dst, rows, src_row):
     """dst[rows[i]] = src_row for every i (hipie_fill_rows): dst (R, W) contiguous device tensor, rows int32 (n,), src_row (W,) of dst's
     dtype; row bytes a multiple of 16.  In place; returns dst."""
-    lib = _lib.load()
     if dst.dim() != 2 or not dst.is_cuda or src_row.dtype != dst.dtype or src_row.numel() != dst.shape[1]:
         raise RuntimeError("fill_rows: dst (R, W) on the device, src_row (W,) of the same dtype")
-    rc = lib.hipie_fill_rows(_chk(dst, "dst"), dst.stride(0) * dst.element_size(), _chk(rows, "rows", torch.int32), rows.numel(),
-                             _chk(src_row, "src_row"), dst.shape[1] * dst.element_size(), _stream())
-    _lib.check(rc, "hipie_fill_rows")
+    _call("hipie_fill_rows", _chk(dst, "dst"), dst.stride(0) * dst.element_size(), _chk(rows, "rows", torch.int32), rows.numel(),
+          _chk(src_row, "src_row"), dst.shape[1] * dst.element_size())
     return dst
 
 
@@ -1888,7 +1780,6 @@ def gemm(a, w, bias=None, resid=None, out_fmt=F32, act=ACT_NONE, alpha=1.0, osca
     `split` tells which (default: inferred -- pass it when K is ambiguous).  With split=True a may also be PLAIN fp32 (..., K) rows
     (16-byte aligned): the kernel splits them after the LDS read -- no hipie_to_hl8 launch.  a may be a row-strided 2-d view.  bias (N) f32,
     resid (..., N) f32.  out_fmt F32 | F16 | HL8 -> (..., N) f32 / f16 or (..., 2N) fp16 HL8."""
-    lib = _lib.load()
     a_f32 = a.dtype == torch.float32 and bool(split)
     if (a.dtype != torch.float16 and not a_f32) or w.dtype != torch.float16 or not a.is_cuda:
         raise RuntimeError("gemm: operands must be fp16 (plain or HL8) device tensors (a may be fp32 against HL8 weights)")
@@ -1933,16 +1824,15 @@ def gemm(a, w, bias=None, resid=None, out_fmt=F32, act=ACT_NONE, alpha=1.0, osca
     if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous()):
         raise RuntimeError("gemm: bias must be contiguous fp32")
     if a_row is not None:
-        rc = lib.hipie_gemm_gather(a2.data_ptr(), a2.stride(0), a2.shape[0], a_row.data_ptr(), _chk(w, "w"), w.shape[1],
-                                   None if bias is None else bias.data_ptr(), None if r2 is None else r2.data_ptr(), 0 if r2 is None else r2.stride(0),
-                                   o2.data_ptr(), o2.stride(0), None if out_row is None else out_row.data_ptr(), M, N, Kw,
-                                   F32 if a_f32 else HL8, int(out_fmt), int(act), float(alpha), float(oscale), _stream())
-        _lib.check(rc, "hipie_gemm_gather")
+        _call("hipie_gemm_gather", a2.data_ptr(), a2.stride(0), a2.shape[0], a_row.data_ptr(), _chk(w, "w"), w.shape[1],
+              None if bias is None else bias.data_ptr(), None if r2 is None else r2.data_ptr(), 0 if r2 is None else r2.stride(0),
+              o2.data_ptr(), o2.stride(0), None if out_row is None else out_row.data_ptr(), M, N, Kw,
+              F32 if a_f32 else HL8, int(out_fmt), int(act), float(alpha), float(oscale))
         return out
-    rc = lib.hipie_gemm(a2.data_ptr(), a2.stride(0), _chk(w, "w"), w.shape[1], None if bias is None else bias.data_ptr(),
-                        None if r2 is None else r2.data_ptr(), 0 if r2 is None else r2.stride(0), o2.data_ptr(), o2.stride(0),
-                        None if out_row is None else out_row.data_ptr(), M, N, Kw, F32 if a_f32 else (HL8 if split else F16), int(out_fmt), int(act), float(alpha), float(oscale), _stream())
-    _lib.check(rc, "hipie_gemm")
+    _call("hipie_gemm", a2.data_ptr(), a2.stride(0), _chk(w, "w"), w.shape[1], None if bias is None else bias.data_ptr(),
+          None if r2 is None else r2.data_ptr(), 0 if r2 is None else r2.stride(0), o2.data_ptr(), o2.stride(0),
+          None if out_row is None else out_row.data_ptr(), M, N, Kw, F32 if a_f32 else (HL8 if split else F16), int(out_fmt), int(act),
+          float(alpha), float(oscale))
     return out
 
 
@@ -1950,15 +1840,13 @@ def gemm(a, w, bias=None, resid=None, out_fmt=F32, act=ACT_NONE, alpha=1.0, osca
 def vit_attn_split(qkv, tab_h, tab_w, grid_hw, heads):
     """hipie_vit_attn_split: qkv (B, gh*gw, 2 * 3*heads*hd) fp16 HL8 rows (q pre-scaled by scale*log2 e), tab_h (2*gh-1, 2*hd),
     tab_w (2*gw-1, 2*hd) HL8 (tables / scale) -> (B, N, 2 * heads*hd) HL8."""
-    lib = _lib.load()
     gh, gw = grid_hw
     B, N, C6 = qkv.shape
     hd = C6 // (6 * heads)
     if qkv.dtype != torch.float16 or tab_h.dtype != torch.float16 or tab_w.dtype != torch.float16:
         raise RuntimeError("vit_attn_split: HL8 (fp16) operands expected")
     out = torch.empty(B, N, 2 * heads * hd, dtype=torch.float16, device=qkv.device)
-    rc = lib.hipie_vit_attn_split(_chk(qkv, "qkv"), _chk(tab_h, "tab_h"), _chk(tab_w, "tab_w"), out.data_ptr(), B, gh, gw, heads, hd, _stream())
-    _lib.check(rc, "hipie_vit_attn_split")
+    _call("hipie_vit_attn_split", _chk(qkv, "qkv"), _chk(tab_h, "tab_h"), _chk(tab_w, "tab_w"), out.data_ptr(), B, gh, gw, heads, hd)
     return out
 
 
@@ -1967,7 +1855,6 @@ def gemm_split_k(a_hl8, w_hl8, nk):
     """a . w^T for HL8 operands a (M, 2K), w (N, 2K) with the contraction cut into nk chunks (K / nk a multiple of 32): one problem per
     chunk in ONE hipie_gemm_batched launch, partial products summed -> (M, N) fp32.  For products whose M x N is a few tiles and whose K is
     long (the weight gradients of the training step)."""
-    lib = _lib.load()
     M, K2 = a_hl8.shape
     N = w_hl8.shape[0]
     K = K2 // 2
@@ -1977,9 +1864,8 @@ def gemm_split_k(a_hl8, w_hl8, nk):
         raise RuntimeError("gemm_split_k: N must be a multiple of 8")
     Kc = K // nk
     part = torch.empty(nk, M, N, dtype=torch.float32, device=a_hl8.device)
-    rc = lib.hipie_gemm_batched(a_hl8.data_ptr(), K2, 0, 2 * Kc, w_hl8.data_ptr(), K2, 0, 2 * Kc, part.data_ptr(), N, 0, M * N, 1, nk, M, N, Kc,
-                                F32, 1.0, _stream())
-    _lib.check(rc, "hipie_gemm_batched")
+    _call("hipie_gemm_batched", a_hl8.data_ptr(), K2, 0, 2 * Kc, w_hl8.data_ptr(), K2, 0, 2 * Kc, part.data_ptr(), N, 0, M * N, 1, nk, M, N, Kc,
+          F32, 1.0)
     return part.sum(0)
 
 
@@ -1988,7 +1874,6 @@ def matmul_nt_batched(a, w, alpha=1.0):
     """out[b] = alpha * a[b] . w[b]^T at fp32-class accuracy on hipie_gemm_batched: a (B, M, K), w (B, N, K) fp32 device tensors,
     K % 32 == 0 -> (B, M, N) fp32.  The operands are split to HL8 on the way in; N is padded to a multiple of 8 with zero rows.  For the
     per-image products of the heads (class logits = queries . token embeddings^T, VL_Align: deformable_detr.py:55-73)."""
-    lib = _lib.load()
     B, M, K = a.shape
     N = w.shape[1]
     if w.shape[0] != B or w.shape[2] != K or K % 32 or not a.is_cuda:
@@ -2000,9 +1885,8 @@ def matmul_nt_batched(a, w, alpha=1.0):
         w = wp
     ah, wh = to_hl8(a.float().contiguous()), to_hl8(w.float().contiguous())
     out = torch.empty(B, M, Np, dtype=torch.float32, device=a.device)
-    rc = lib.hipie_gemm_batched(ah.data_ptr(), 2 * K, M * 2 * K, 0, wh.data_ptr(), 2 * K, Np * 2 * K, 0, out.data_ptr(), Np, M * Np, 0,
-                                B, 1, M, Np, K, F32, float(alpha), _stream())
-    _lib.check(rc, "hipie_gemm_batched")
+    _call("hipie_gemm_batched", ah.data_ptr(), 2 * K, M * 2 * K, 0, wh.data_ptr(), 2 * K, Np * 2 * K, 0, out.data_ptr(), Np, M * Np, 0,
+          B, 1, M, Np, K, F32, float(alpha))
     return out if Np == N else out[..., :N]
 
 
@@ -2057,7 +1941,6 @@ def conv3x3_split(x, conv, act=ACT_NONE):
     """conv(x) for a 3 x 3 / stride 1 / padding 1 nn.Conv2d at the split policy's accuracy (hipie_conv3x3_split: implicit GEMM, K = 9 C).
     x (B, C, H, W) in any memory format -> (B, N, H, W) fp32 in channels-last memory.  The input is copied once onto a zero-padded pixel grid
     (with guard rows), the kernel computes on that grid and the interior is cropped."""
-    lib = _lib.load()
     B, C, H, W = x.shape
     N = conv.out_channels
     Hp, Wp = H + 2, W + 2
@@ -2076,9 +1959,8 @@ def conv3x3_split(x, conv, act=ACT_NONE):
                            lambda: conv.weight.permute(0, 2, 3, 1).reshape(N, 9 * C), (lambda: conv.bias) if conv.bias is not None else None)
     out = torch.empty(rows, N, dtype=torch.float32, device=x.device)
     xin = buf[guard:]
-    rc = lib.hipie_conv3x3_split(xin.data_ptr(), C, w.data_ptr(), None if b is None else b.data_ptr(), out.data_ptr(), N, rows, Wp, C, N,
-                                 F32, F32, int(act), _stream())
-    _lib.check(rc, "hipie_conv3x3_split")
+    _call("hipie_conv3x3_split", xin.data_ptr(), C, w.data_ptr(), None if b is None else b.data_ptr(), out.data_ptr(), N, rows, Wp, C, N,
+          F32, F32, int(act))
     return out.view(B, Hp, Wp, N)[:, 1:-1, 1:-1].permute(0, 3, 1, 2).contiguous(memory_format=torch.channels_last)
 
 
@@ -2096,7 +1978,6 @@ def ffn_fused(x_hl8, lin1, lin2):
     """linear2(relu(linear1(x))) in ONE launch at the split policy's accuracy (hipie_ffn_fused): x (..., 2*256) HL8 -> (..., 256) fp32.
     The hidden activations stay in registers; W2's columns are permuted once per parameter version into the order the MFMA C layout
     hands them over (rows 0-3, 8-11, 4-7, 12-15 of every 16)."""
-    lib = _lib.load()
     w1, b1, _ = split_weight(lin1, "w", [lin1.weight, lin1.bias], lambda: lin1.weight, lambda: lin1.bias)
     F_ = lin2.weight.shape[1]
     perm = _FFN_PERM.get(F_)
@@ -2110,9 +1991,8 @@ def ffn_fused(x_hl8, lin1, lin2):
         raise RuntimeError("ffn_fused: x must be HL8 rows of 2 * 256 fp16 values")
     M = x2.shape[0]
     out = torch.empty(M, 256, dtype=torch.float32, device=x2.device)
-    rc = lib.hipie_ffn_fused(x2.data_ptr(), x2.stride(0), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), out.data_ptr(), 256,
-                             M, 256, F_, _stream())
-    _lib.check(rc, "hipie_ffn_fused")
+    _call("hipie_ffn_fused", x2.data_ptr(), x2.stride(0), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), out.data_ptr(), 256,
+          M, 256, F_)
     return out.view(*lead, 256)
 
 
@@ -2151,7 +2031,6 @@ def split_linear(x, owner, key, weight, bias=None, act=ACT_NONE, out_fmt=F32, re
 def to_f8x(x_hl8):
     """HL8 rows (rows, 2K) fp16 on the device -> (q (rows, 2K) uint8: per 32-element block [q8(hi) | q8(lo)] e4m3, scale (rows, K/32, 2) uint8
     E8M0 [hi, lo]) with the quantiser hipie_gemm_f8x applies to its activations (hipie_to_f8x)."""
-    lib = _lib.load()
     if x_hl8.dtype != torch.float16 or not x_hl8.is_cuda or x_hl8.shape[-1] % 64:
         raise RuntimeError("to_f8x: HL8 rows (fp16, 2K columns with K a multiple of 32) on the device")
     x2 = x_hl8.reshape(-1, x_hl8.shape[-1])
@@ -2160,8 +2039,7 @@ def to_f8x(x_hl8):
     R, K = x2.shape[0], x2.shape[1] // 2
     q = torch.empty(R, 2 * K, dtype=torch.uint8, device=x_hl8.device)
     sc = torch.empty(R, K // 32, 2, dtype=torch.uint8, device=x_hl8.device)
-    rc = lib.hipie_to_f8x(x2.data_ptr(), x2.stride(0), q.data_ptr(), 2 * K, sc.data_ptr(), R, K, _stream())
-    _lib.check(rc, "hipie_to_f8x")
+    _call("hipie_to_f8x", x2.data_ptr(), x2.stride(0), q.data_ptr(), 2 * K, sc.data_ptr(), R, K)
     return q, sc
 
 
@@ -2182,7 +2060,6 @@ def f8x_weight(owner, key, params, weight_fn, bias_fn=None):
 def gemm_f8x(a, w8, wsc, bias=None, resid=None, out_fmt=F32, act=ACT_NONE, alpha=1.0, oscale=1.0, out=None, out_row=None, out_rows=None):
     """ops.gemm's split form with the cross terms on block-scaled e4m3 (hipie_gemm_f8x): a (..., 2K) HL8 rows against the f8x weight
     (w8 (N, 4K) uint8, wsc (N, K/32, 2) uint8, from f8x_weight or fp8x.pack_weight); epilogue, output formats and row maps as ops.gemm."""
-    lib = _lib.load()
     if a.dtype != torch.float16 or w8.dtype != torch.uint8 or wsc.dtype != torch.uint8 or not a.is_cuda:
         raise RuntimeError("gemm_f8x: a HL8 (fp16) rows, w8 / wsc uint8, on the device")
     N, K = w8.shape[0], w8.shape[1] // 4
@@ -2207,10 +2084,9 @@ def gemm_f8x(a, w8, wsc, bias=None, resid=None, out_fmt=F32, act=ACT_NONE, alpha
             raise RuntimeError("gemm_f8x: resid must be fp32 with contiguous rows")
     if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous()):
         raise RuntimeError("gemm_f8x: bias must be contiguous fp32")
-    rc = lib.hipie_gemm_f8x(a2.data_ptr(), a2.stride(0), _chk(w8, "w8"), 2 * K, _chk(wsc, "wsc"), None if bias is None else bias.data_ptr(),
-                            None if r2 is None else r2.data_ptr(), 0 if r2 is None else r2.stride(0), o2.data_ptr(), o2.stride(0),
-                            None if out_row is None else out_row.data_ptr(), M, N, K, HL8, int(out_fmt), int(act), float(alpha), float(oscale), _stream())
-    _lib.check(rc, "hipie_gemm_f8x")
+    _call("hipie_gemm_f8x", a2.data_ptr(), a2.stride(0), _chk(w8, "w8"), 2 * K, _chk(wsc, "wsc"), None if bias is None else bias.data_ptr(),
+          None if r2 is None else r2.data_ptr(), 0 if r2 is None else r2.stride(0), o2.data_ptr(), o2.stride(0),
+          None if out_row is None else out_row.data_ptr(), M, N, K, HL8, int(out_fmt), int(act), float(alpha), float(oscale))
     return out
 
 
@@ -2232,7 +2108,6 @@ def split_linear_ln_ok(x, weight, norm_weight):
 def split_linear_ln(x, owner, key, weight, bias, resid, norm_weight, norm_bias, eps, x_hl8=False, want_hl8=True):
     """LayerNorm(resid + F.linear(x, weight, bias)) over 256 features as ONE launch (hipie_gemm_ln): returns (n fp32, n as HL8 or None).
     x (..., K) fp32 rows or HL8 (x_hl8); resid (..., 256) fp32; the HL8 copy of `weight` is cached on `owner` under `key` (split_weight)."""
-    lib = _lib.load()
     w, b, N = split_weight(owner, key, [weight] + ([bias] if bias is not None else []), lambda: weight, (lambda: bias) if bias is not None else None)
     if N != 256 or w.shape[0] != 256:
         raise RuntimeError("split_linear_ln: 256 output features expected")
@@ -2249,10 +2124,9 @@ def split_linear_ln(x, owner, key, weight, bias, resid, norm_weight, norm_bias, 
         raise RuntimeError("split_linear_ln: resid must be (rows, 256) fp32 on the device")
     out = torch.empty(*resid.shape[:-1], 256, dtype=torch.float32, device=x.device)
     o16 = torch.empty(*resid.shape[:-1], 512, dtype=torch.float16, device=x.device) if want_hl8 else None
-    rc = lib.hipie_gemm_ln(a2.data_ptr(), a2.stride(0), _chk(w, "w"), w.shape[1], None if b is None else b.data_ptr(), r2.data_ptr(), r2.stride(0),
-                           _chk(norm_weight, "norm_weight", torch.float32), _chk(norm_bias, "norm_bias", torch.float32), float(eps),
-                           out.data_ptr(), 256, None if o16 is None else o16.data_ptr(), 512, M, K, F32 if a_f32 else HL8, 1.0, _stream())
-    _lib.check(rc, "hipie_gemm_ln")
+    _call("hipie_gemm_ln", a2.data_ptr(), a2.stride(0), _chk(w, "w"), w.shape[1], None if b is None else b.data_ptr(), r2.data_ptr(), r2.stride(0),
+          _chk(norm_weight, "norm_weight", torch.float32), _chk(norm_bias, "norm_bias", torch.float32), float(eps),
+          out.data_ptr(), 256, None if o16 is None else o16.data_ptr(), 512, M, K, F32 if a_f32 else HL8, 1.0)
     return out, o16
 
 
@@ -2297,14 +2171,12 @@ def convt2x2_split(rows, owner, key, weight, bias, B, H, W):
 def topk(x, k, want_values=False):
     """row-wise top-k of a (rows, n) fp32 device tensor (row stride may exceed n), k <= 1024 -> indices (rows, k) int64 in descending value
     order (ties: ascending index) [, values].  hipie_topk: one launch, hipGraph-replay safe (torch.topk on this stack is neither)."""
-    lib = _lib.load()
     if x.dim() != 2 or x.dtype != torch.float32 or not x.is_cuda or x.stride(1) != 1:
         raise RuntimeError("topk: (rows, n) fp32 device tensor with contiguous rows expected")
     rows, n = x.shape
     idx = torch.empty(rows, k, dtype=torch.int64, device=x.device)
     val = torch.empty(rows, k, dtype=torch.float32, device=x.device) if want_values else None
-    rc = lib.hipie_topk(x.data_ptr(), x.stride(0), rows, n, int(k), idx.data_ptr(), None if val is None else val.data_ptr(), _stream())
-    _lib.check(rc, "hipie_topk")
+    _call("hipie_topk", x.data_ptr(), x.stride(0), rows, n, int(k), idx.data_ptr(), None if val is None else val.data_ptr())
     return (idx, val) if want_values else idx
 
 
