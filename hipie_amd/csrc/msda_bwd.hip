@@ -130,6 +130,8 @@ static int launch_msda_bwd(const void* value, const int64_t* shapes, const int64
 //             shuffles per sum instead of the five of the 32-lane form
 // Summation order inside a destination follows the slot order (arrival order of step 3): as with the atomics, and as in the reference,
 // grad_value is not bit-reproducible between runs; the other two outputs are.
+// hipie_msda_raw_backward (the backward of hipie_msda_fused_forward) runs the same five passes with (x, y, A) recomputed from the raw
+// projections in passes 1, 3 and 5 (template parameter SRC below) and one more small kernel that adds the per-head partials of grad_ref.
 
 struct BwdRec {
   int row;      // b * Lq + q: the grad_out row (and image) the sample came from
@@ -166,17 +168,67 @@ __device__ __forceinline__ BwdCorners bwd_corners(float x, float y, int H, int W
   return r;
 }
 
+// ---- where a point's (x, y, A) comes from ------------------------------------------------------------------------------------------------
+// kSrcLocAttn: the loc / attn tensors of the reference operator.  kSrcRaw: the raw projections of hipie_msda_fused_forward -- the location
+// from (ref, offsets) and A from the softmax over the item's L*P logits are recomputed in the count, fill and coefficient kernels, so
+// neither tensor exists in HBM.  Count and fill must then agree BIT FOR BIT on which corners are inside (a slot would run past its
+// segment otherwise): the location is written once, below, with contraction off -- every operation rounds once whatever the compiler
+// would fuse in one instantiation and not in another -- in publish_records' operation order (msda.hip).  The same holds for A.
+constexpr int kSrcLocAttn = 0, kSrcRaw = 1;
+constexpr int kBwdMaxLP = 32;                          // = kMaxLP of msda.hip: L*P of the fused forward's softmax
+
+struct BwdRaw {
+  const float* ref;                 // (B, Lq, L, ref_dim)
+  float* gref_part;                 // (B*Lq, M, L, ref_dim) per-head partials of grad_ref in the workspace, or nullptr
+  float2* stats;                    // (B*Lq, M) softmax (max, 1 / sum) in the workspace: written by the count pass
+  long off_stride, logit_stride;    // input rows (b, q): offsets (M, L, P, 2), logits (M, L*P)
+  long goff_stride, glogit_stride;  // output rows
+  long nrec;                        // corner records the workspace was sized for
+  int ref_dim;
+};
+
+__device__ __forceinline__ float2 raw_location(const float* r, int ref_dim, float ox, float oy, int H, int W, int P) {
+#pragma clang fp contract(off)
+  float2 xy;
+  if (ref_dim == 2) {                                  // ref + off / (W_l, H_l)
+    xy.x = r[0] + ox / (float)W;
+    xy.y = r[1] + oy / (float)H;
+  } else {                                             // ref_xy + off / P * ref_wh * 0.5
+    xy.x = r[0] + ox / (float)P * r[2] * 0.5f;
+    xy.y = r[1] + oy / (float)P * r[3] * 0.5f;
+  }
+  return xy;
+}
+
+// softmax over the LP logits of one item, max-subtracted as the forward's: (max, 1 / sum) in index order, then A_i = exp(z_i - max) / sum.
+// The count pass computes the pair once per item (a thread per item of its slice) and leaves it in the workspace -- 8 bytes per
+// (b, q, head) -- so the fill pass and the coefficient kernel pay one exp per point and see the same A.
+__device__ __forceinline__ float2 raw_softmax_stats(const float* lg, int LP) {
+#pragma clang fp contract(off)
+  float mx = lg[0];
+  for (int i = 1; i < LP; ++i) mx = fmaxf(mx, lg[i]);
+  float sm = 0.f;
+  for (int i = 0; i < LP; ++i) sm = sm + expf(lg[i] - mx);
+  return make_float2(mx, 1.f / sm);
+}
+__device__ __forceinline__ float raw_weight(float z, float2 stats) {
+#pragma clang fp contract(off)
+  return expf(z - stats.x) * stats.y;
+}
+
 // steps 1 and 3.  Scattered global integer atomics are no cheaper than the float ones (measured: 22 M of them = 1.2 ms; the atomic units
 // take ~15 G REQUESTS per second, a 128-byte row of 32 floats being one request), so the bins live in LDS: workgroup (plane = b*M + m,
 // slice) handles the queries [slice * per, (slice + 1) * per) of image b for head m with one LDS counter per pixel row of the image
 // (S ints <= 160 KB).  Counting pass: ds_add_u32, then the slice's counts are stored to bins[plane][slice][0:S].  After the scan the
 // same array holds the first slot of every (destination, slice) segment; the fill pass loads it back into LDS and every corner takes its
 // slot with a returning LDS add.
-template <bool FILL>
+// SRC == kSrcRaw: loc / attn are the offsets / logits rows and `raw` says how to read them; a record is written only below raw.nrec; the
+// counting pass also leaves the softmax pair of every item of its slice in raw.stats (a thread per item).
+template <bool FILL, int SRC>
 __global__ __launch_bounds__(1024) void msda_bwd_bin_kernel(const int64_t* __restrict__ shapes, const int64_t* __restrict__ lstart,
                                                             const float* __restrict__ loc, const float* __restrict__ attn,
                                                             int* __restrict__ bins, BwdRec* __restrict__ recs, int S, int M, int L, int Lq,
-                                                            int P, int K) {
+                                                            int P, int K, BwdRaw raw) {
   extern __shared__ int bwd_lds[];
   const int tid = threadIdx.x;
   const int slice = (int)(blockIdx.x % K), plane = (int)(blockIdx.x / K);
@@ -192,10 +244,24 @@ __global__ __launch_bounds__(1024) void msda_bwd_bin_kernel(const int64_t* __res
     const int i = (int)(t % LP), l = i / P;
     const long row = (long)b * Lq + q0 + t / LP;
     const long sidx = (row * M + m) * LP + i;
-    const float2 xy = *reinterpret_cast<const float2*>(loc + 2 * sidx);
+    float2 xy;
+    if constexpr (SRC == kSrcRaw) {
+      const float* op = loc + row * raw.off_stride + ((long)m * LP + i) * 2;
+      xy = raw_location(raw.ref + (row * L + l) * raw.ref_dim, raw.ref_dim, op[0], op[1], (int)shapes[2 * l], (int)shapes[2 * l + 1], P);
+    } else {
+      xy = *reinterpret_cast<const float2*>(loc + 2 * sidx);
+    }
     const BwdCorners g = bwd_corners(xy.x, xy.y, (int)shapes[2 * l], (int)shapes[2 * l + 1], (long)lstart[l]);
     if (!g.inside) continue;
-    const float a = FILL ? attn[sidx] : 0.f;
+    float a = 0.f;
+    if constexpr (SRC == kSrcRaw) {
+      if (FILL) {
+        const float* lg = attn + row * raw.logit_stride + (long)m * LP;
+        a = raw_weight(lg[i], raw.stats[row * M + m]);
+      }
+    } else {
+      a = FILL ? attn[sidx] : 0.f;
+    }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       if (!g.ok[k]) continue;
@@ -204,13 +270,23 @@ __global__ __launch_bounds__(1024) void msda_bwd_bin_kernel(const int64_t* __res
         BwdRec r;
         r.row = (int)row;
         r.w = g.c[k] * a;
-        recs[slot] = r;
+        if constexpr (SRC == kSrcRaw) {
+          if (slot >= 0 && slot < raw.nrec) recs[slot] = r;
+        } else {
+          recs[slot] = r;
+        }
       } else {
         atomicAdd(&bwd_lds[g.pix[k]], 1);
       }
     }
   }
   if (!FILL) {
+    if constexpr (SRC == kSrcRaw) {
+      for (int q = q0 + tid; q < q1; q += 1024) {
+        const long row = (long)b * Lq + q;
+        raw.stats[row * M + m] = raw_softmax_stats(attn + row * raw.logit_stride + (long)m * LP, LP);
+      }
+    }
     __syncthreads();
     for (int s = tid; s < S; s += 1024) mine[s] = bwd_lds[s];
   }
@@ -350,11 +426,17 @@ __global__ __launch_bounds__(256) void msda_bwd_gather_kernel(const float* __res
 }
 
 // step 5: item = (b, q, head) on 8 lanes, lane `sub` holds channels 4 sub .. 4 sub + 3
+// SRC == kSrcRaw: loc / attn are the offsets / logits rows, gloc / gattn the grad_offsets / grad_logits rows (strides in `raw`).  The chain
+// rule through the location is applied per point; gA of point i is parked in lane i % 8 (slot i / 8: kBwdMaxLP / 8 registers), and after the
+// point loop the 8 lanes finish the softmax backward, grad_logits[i] = A_i (gA_i - sum_j A_j gA_j), with one store of 8 adjacent floats per
+// slot.  grad_ref: the sums over a level's P points go to raw.gref_part per head (the heads of a query live in different workgroups);
+// msda_bwd_ref_kernel adds them in head order.  No atomics: all three outputs are bit-reproducible.
+template <int SRC>
 __global__ __launch_bounds__(256) void msda_bwd_coef_kernel(const float* __restrict__ value, const int64_t* __restrict__ shapes,
                                                             const int64_t* __restrict__ lstart, const float* __restrict__ loc,
                                                             const float* __restrict__ attn, const float* __restrict__ gout,
                                                             float* __restrict__ gloc, float* __restrict__ gattn, int S, int M, int L,
-                                                            int Lq, int P, long items) {
+                                                            int Lq, int P, long items, BwdRaw raw) {
   const int sub = threadIdx.x & 7;
   long bq;
   int m;
@@ -365,9 +447,21 @@ __global__ __launch_bounds__(256) void msda_bwd_coef_kernel(const float* __restr
   const long row = (long)M * 32;
   const float* vb = value + (long)b * S * row + (long)m * 32 + sub * 4;
   const float4 g4 = *reinterpret_cast<const float4*>(gout + item * 32 + sub * 4);
-  const float* lp = loc + item * (long)LP * 2;
-  const float* wp = attn + item * (long)LP;
+  constexpr bool RAW = SRC == kSrcRaw;
+  const float* lp = RAW ? loc + bq * raw.off_stride + (long)m * LP * 2 : loc + item * (long)LP * 2;
+  const float* wp = RAW ? attn + bq * raw.logit_stride + (long)m * LP : attn + item * (long)LP;
   const float gc[4] = {g4.x, g4.y, g4.z, g4.w};
+  float2 stats = make_float2(0.f, 0.f);
+  float ga[kBwdMaxLP / 8] = {0.f, 0.f, 0.f, 0.f};       // gA of the points sub, sub + 8, ...
+  float av[kBwdMaxLP / 8] = {0.f, 0.f, 0.f, 0.f};       // A of the same points: every lane computes its own, the point loop fetches them
+  float rx = 0.f, ry = 0.f, rw = 0.f, rh = 0.f;         // grad_ref of the level being walked
+  const float hp = 0.5f / (float)P;
+  if constexpr (RAW) {
+    stats = raw.stats[item];
+#pragma unroll
+    for (int k = 0; k < kBwdMaxLP / 8; ++k)
+      if (sub + 8 * k < LP) av[k] = raw_weight(wp[sub + 8 * k], stats);
+  }
   // branch-free body (masked corners and outside points read a legal address and are weighted 0), four points at a time so that their 16
   // corner reads are in flight together
   constexpr int U = 4;                                // 136 VGPRs; 1 / 2 / 8 points at a time: 0.39 / 0.34 / 0.33 ms against 0.28
@@ -375,11 +469,21 @@ __global__ __launch_bounds__(256) void msda_bwd_coef_kernel(const float* __restr
     BwdCorners g[U];
     float a[U];
     float4 v[U][4];
+    float2 off[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int i = min(i0 + u, LP - 1), l = i / P;
-      a[u] = wp[i];
-      g[u] = bwd_corners(lp[2 * i], lp[2 * i + 1], (int)shapes[2 * l], (int)shapes[2 * l + 1], (long)lstart[l]);
+      if constexpr (RAW) {
+        const int slot = i >> 3;
+        a[u] = __shfl(slot == 0 ? av[0] : slot == 1 ? av[1] : slot == 2 ? av[2] : av[3], i & 7, 8);
+        off[u] = make_float2(lp[2 * i], lp[2 * i + 1]);
+        const float2 xy = raw_location(raw.ref + (bq * L + l) * raw.ref_dim, raw.ref_dim, off[u].x, off[u].y, (int)shapes[2 * l],
+                                       (int)shapes[2 * l + 1], P);
+        g[u] = bwd_corners(xy.x, xy.y, (int)shapes[2 * l], (int)shapes[2 * l + 1], (long)lstart[l]);
+      } else {
+        a[u] = wp[i];
+        g[u] = bwd_corners(lp[2 * i], lp[2 * i + 1], (int)shapes[2 * l], (int)shapes[2 * l + 1], (long)lstart[l]);
+      }
 #pragma unroll
       for (int k = 0; k < 4; ++k) v[u][k] = *reinterpret_cast<const float4*>(vb + g[u].pix[k] * row);
     }
@@ -405,13 +509,71 @@ __global__ __launch_bounds__(256) void msda_bwd_coef_kernel(const float* __restr
         sy += __shfl_xor(sy, sft);
       }
       const int i = i0 + u;
-      if (live && sub == 0 && i < LP) {
-        gattn[item * LP + i] = sa;
-        gloc[(item * LP + i) * 2] = (float)g[u].W * sx;
-        gloc[(item * LP + i) * 2 + 1] = (float)g[u].H * sy;
+      if constexpr (RAW) {
+        if (i < LP) {
+          const int l = i / P;
+          const float gx = (float)g[u].W * sx, gy = (float)g[u].H * sy;             // gloc
+          const float* r = raw.ref + (bq * L + l) * raw.ref_dim;
+          // ref_dim 2: gloc / (W, H) = (W sx) / W: sx itself, without the two roundings
+          const float ox = raw.ref_dim == 2 ? sx : gx * r[2] * hp;
+          const float oy = raw.ref_dim == 2 ? sy : gy * r[3] * hp;
+#pragma unroll
+          for (int k = 0; k < kBwdMaxLP / 8; ++k) ga[k] = (sub == (i & 7) && (i >> 3) == k) ? sa : ga[k];
+          if (live && sub == 0) {
+            float* go = gloc + bq * raw.goff_stride + ((long)m * LP + i) * 2;
+            go[0] = ox;
+            go[1] = oy;
+          }
+          rx += gx;
+          ry += gy;
+          rw += gx * off[u].x * hp;
+          rh += gy * off[u].y * hp;
+          if (i - l * P == P - 1) {                      // the level's last point: its sums leave, per head
+            if (live && sub == 0 && raw.gref_part != nullptr) {
+              float* part = raw.gref_part + (item * L + l) * raw.ref_dim;
+              part[0] = rx;
+              part[1] = ry;
+              if (raw.ref_dim == 4) {
+                part[2] = rw;
+                part[3] = rh;
+              }
+            }
+            rx = ry = rw = rh = 0.f;
+          }
+        }
+      } else {
+        if (live && sub == 0 && i < LP) {
+          gattn[item * LP + i] = sa;
+          gloc[(item * LP + i) * 2] = (float)g[u].W * sx;
+          gloc[(item * LP + i) * 2 + 1] = (float)g[u].H * sy;
+        }
       }
     }
   }
+  if constexpr (RAW) {
+    float dot = 0.f;
+#pragma unroll
+    for (int k = 0; k < kBwdMaxLP / 8; ++k) dot += av[k] * ga[k];
+#pragma unroll
+    for (int sft = 4; sft > 0; sft >>= 1) dot += __shfl_xor(dot, sft);
+    float* gl = gattn + bq * raw.glogit_stride + (long)m * LP;
+#pragma unroll
+    for (int k = 0; k < kBwdMaxLP / 8; ++k) {
+      const int i = sub + 8 * k;
+      if (live && i < LP) gl[i] = av[k] * (ga[k] - dot);
+    }
+  }
+}
+
+// grad_ref[b, q, l, :] = sum over the heads, in head order, of the per-head partials the coefficient kernel left
+__global__ __launch_bounds__(256) void msda_bwd_ref_kernel(const float* __restrict__ part, float* __restrict__ gref, long n, int M, int width) {
+  const long j = (long)blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const long bq = j / width;
+  const int k = (int)(j % width);
+  float s = 0.f;
+  for (int m = 0; m < M; ++m) s += part[(bq * M + m) * width + k];
+  gref[j] = s;
 }
 
 constexpr long kBwdMaxRows = 160 * 1024 / 4;           // pixel rows per image whose counters fit the LDS of a CU
@@ -439,9 +601,12 @@ static BwdWorkspace bwd_workspace(long B, long S, long M, long L, long Lq, long 
   return w;
 }
 
-static int launch_msda_bwd_gather(const void* value, const int64_t* shapes, const int64_t* lstart, const void* loc, const void* attn,
-                                  const void* gout, void* gvalue, void* gloc, void* gattn, int B, int S, int M, int L, int Lq, int P,
-                                  void* workspace, hipStream_t st) {
+// the five passes for either source of (x, y, A): a0 / a1 are loc / attn (SRC = kSrcLocAttn, o0 / o1 = grad_sampling_loc / grad_attn_weight) or
+// the offsets / logits rows (kSrcRaw, o0 / o1 = grad_offsets / grad_logits, `raw` filled in)
+template <int SRC>
+static void launch_bwd_passes(const void* value, const int64_t* shapes, const int64_t* lstart, const void* a0, const void* a1, const void* gout,
+                              void* gvalue, void* o0, void* o1, int B, int S, int M, int L, int Lq, int P, void* workspace, const BwdRaw& raw,
+                              hipStream_t st) {
   const BwdWorkspace w = bwd_workspace(B, S, M, L, Lq, P);
   char* ws = (char*)workspace;
   int* bins = (int*)(ws + w.bins);
@@ -451,21 +616,33 @@ static int launch_msda_bwd_gather(const void* value, const int64_t* shapes, cons
   const dim3 block(256), bin_grid((unsigned)(B * M * w.K)), bin_block(1024);
   const size_t lds = (size_t)S * 4;
   static LdsLimit limit[2];              // the whole 160 KiB once, whatever this call's S needs
-  limit[0].raise((const void*)msda_bwd_bin_kernel<false>, 160 * 1024);
-  limit[1].raise((const void*)msda_bwd_bin_kernel<true>, 160 * 1024);
-  hipLaunchKernelGGL((msda_bwd_bin_kernel<false>), bin_grid, bin_block, lds, st, shapes, lstart, (const float*)loc, (const float*)attn, bins,
-                     recs, S, M, L, Lq, P, w.K);
+  limit[0].raise((const void*)msda_bwd_bin_kernel<false, SRC>, 160 * 1024);
+  limit[1].raise((const void*)msda_bwd_bin_kernel<true, SRC>, 160 * 1024);
+  hipLaunchKernelGGL((msda_bwd_bin_kernel<false, SRC>), bin_grid, bin_block, lds, st, shapes, lstart, (const float*)a0, (const float*)a1, bins,
+                     recs, S, M, L, Lq, P, w.K, raw);
   hipLaunchKernelGGL(msda_bwd_scan_totals_kernel, dim3((unsigned)w.nblocks), block, 0, st, bins, totals, w.nbins, S, w.K);
   hipLaunchKernelGGL(msda_bwd_scan_top_kernel, dim3(1), block, 0, st, totals, (int)w.nblocks);
   hipLaunchKernelGGL(msda_bwd_scan_apply_kernel, dim3((unsigned)w.nblocks), block, 0, st, bins, starts, totals, w.nbins, S, w.K);
-  hipLaunchKernelGGL((msda_bwd_bin_kernel<true>), bin_grid, bin_block, lds, st, shapes, lstart, (const float*)loc, (const float*)attn, bins,
-                     recs, S, M, L, Lq, P, w.K);
+  hipLaunchKernelGGL((msda_bwd_bin_kernel<true, SRC>), bin_grid, bin_block, lds, st, shapes, lstart, (const float*)a0, (const float*)a1, bins,
+                     recs, S, M, L, Lq, P, w.K, raw);
   hipLaunchKernelGGL(msda_bwd_gather_kernel, dim3(bwd_group_grid((long)B * S, M)), block, 0, st, (const float*)gout, starts, recs,
                      (float*)gvalue, B, S, M);
   const long items = (long)B * Lq * M;
-  hipLaunchKernelGGL(msda_bwd_coef_kernel, dim3(bwd_group_grid((long)B * Lq, M)), block, 0, st, (const float*)value, shapes, lstart,
-                     (const float*)loc, (const float*)attn, (const float*)gout, (float*)gloc, (float*)gattn, S, M, L, Lq, P, items);
+  hipLaunchKernelGGL(msda_bwd_coef_kernel<SRC>, dim3(bwd_group_grid((long)B * Lq, M)), block, 0, st, (const float*)value, shapes, lstart,
+                     (const float*)a0, (const float*)a1, (const float*)gout, (float*)o0, (float*)o1, S, M, L, Lq, P, items, raw);
+}
+
+static int launch_msda_bwd_gather(const void* value, const int64_t* shapes, const int64_t* lstart, const void* loc, const void* attn,
+                                  const void* gout, void* gvalue, void* gloc, void* gattn, int B, int S, int M, int L, int Lq, int P,
+                                  void* workspace, hipStream_t st) {
+  launch_bwd_passes<kSrcLocAttn>(value, shapes, lstart, loc, attn, gout, gvalue, gloc, gattn, B, S, M, L, Lq, P, workspace, BwdRaw{}, st);
   return check_launch("msda_backward_ws");
+}
+
+// the raw form's workspace: the gather form's, then the softmax pairs, then the per-head partials of grad_ref
+static size_t raw_stats_bytes(long B, long M, long Lq) { return ((size_t)(B * Lq * M) * sizeof(float2) + 255) & ~(size_t)255; }
+static size_t raw_part_bytes(long B, long M, long L, long Lq, int ref_dim, bool want_ref) {
+  return want_ref ? (((size_t)(B * Lq * M * L * ref_dim) * 4 + 255) & ~(size_t)255) : 0;
 }
 
 }  // namespace hipie
@@ -511,4 +688,62 @@ extern "C" int hipie_msda_backward_ws(const void* value, const int64_t* spatial_
   HIPIE_REQUIRE(((uintptr_t)workspace & 15) == 0, "msda_backward_ws: workspace must be 16-byte aligned");
   return launch_msda_bwd_gather(value, spatial_shapes, level_start, sampling_loc, attn_weight, grad_output, grad_value, grad_sampling_loc,
                                 grad_attn_weight, B, S, M, L, Lq, P, workspace, (hipStream_t)stream);
+}
+
+extern "C" int64_t hipie_msda_raw_backward_ws_bytes(int B, int S, int M, int L, int Lq, int P, int ref_dim, int want_grad_ref) {
+  using namespace hipie;
+  if (B <= 0 || S <= 0 || S > kBwdMaxRows || M <= 0 || L <= 0 || Lq < 0 || P <= 0 || (ref_dim != 2 && ref_dim != 4) || (long)L * P > kBwdMaxLP)
+    return 0;
+  return (int64_t)(bwd_workspace(B, S, M, L, Lq, P).bytes + raw_stats_bytes(B, M, Lq) + raw_part_bytes(B, M, L, Lq, ref_dim, want_grad_ref != 0));
+}
+
+extern "C" int hipie_msda_raw_backward(const void* value, const int64_t* spatial_shapes, const int64_t* level_start, const float* ref,
+                                       const void* offsets, const void* logits, const void* grad_output, void* grad_value,
+                                       void* grad_offsets, void* grad_logits, void* grad_ref, int B, int S, int M, int D, int L, int Lq, int P,
+                                       int ref_dim, int64_t off_row_stride, int64_t logit_row_stride, int64_t goff_row_stride,
+                                       int64_t glogit_row_stride, void* workspace, int64_t workspace_bytes, void* stream) {
+  using namespace hipie;
+  HIPIE_REQUIRE(B >= 0 && S > 0 && M > 0 && D > 0 && L > 0 && Lq >= 0 && P > 0, "msda_raw_backward: bad shape");
+  HIPIE_REQUIRE(D == 32, "msda_raw_backward: D=%d (the gather form is written for D = 32)", D);
+  HIPIE_REQUIRE(S <= kBwdMaxRows, "msda_raw_backward: S=%d pixel rows per image, the LDS counters hold %ld", S, kBwdMaxRows);
+  HIPIE_REQUIRE((long)L * P <= kBwdMaxLP, "msda_raw_backward: L*P=%ld > %d", (long)L * P, kBwdMaxLP);
+  HIPIE_REQUIRE(ref_dim == 2 || ref_dim == 4, "msda_raw_backward: ref_dim must be 2 or 4 (got %d)", ref_dim);
+  const long offw = (long)M * L * P * 2, logw = (long)M * L * P;
+  HIPIE_REQUIRE(off_row_stride >= offw && goff_row_stride >= offw, "msda_raw_backward: offsets row stride %lld / %lld below the row's %ld",
+                (long long)off_row_stride, (long long)goff_row_stride, offw);
+  HIPIE_REQUIRE(logit_row_stride >= logw && glogit_row_stride >= logw, "msda_raw_backward: logits row stride %lld / %lld below the row's %ld",
+                (long long)logit_row_stride, (long long)glogit_row_stride, logw);
+  if (B == 0) return HIPIE_OK;
+  HIPIE_REQUIRE(value && spatial_shapes && level_start && grad_value, "msda_raw_backward: null pointer");
+  HIPIE_REQUIRE(Lq == 0 || (ref && offsets && logits && grad_output && grad_offsets && grad_logits), "msda_raw_backward: null pointer");
+  const BwdWorkspace w = bwd_workspace(B, S, M, L, Lq, P);
+  HIPIE_REQUIRE(w.samples * 4 < (1L << 31) && (long)B * Lq < (1L << 31), "msda_raw_backward: more than 2^31 corner records");
+  const size_t need = w.bytes + raw_stats_bytes(B, M, Lq) + raw_part_bytes(B, M, L, Lq, ref_dim, grad_ref != nullptr);
+  HIPIE_REQUIRE(workspace && workspace_bytes >= (int64_t)need, "msda_raw_backward: workspace of %lld bytes, %lld needed (hipie_msda_raw_backward_ws_bytes)",
+                (long long)workspace_bytes, (long long)need);
+  HIPIE_REQUIRE(((uintptr_t)workspace & 15) == 0, "msda_raw_backward: workspace must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  if (Lq == 0) {                                        // no sample reaches any pixel
+    if (hipMemsetAsync(grad_value, 0, (size_t)B * S * M * D * sizeof(float), st) != hipSuccess)
+      return set_err(HIPIE_ELAUNCH, "msda_raw_backward: memset failed");
+    return HIPIE_OK;
+  }
+  BwdRaw raw;
+  raw.ref = ref;
+  raw.stats = (float2*)((char*)workspace + w.bytes);
+  raw.gref_part = grad_ref ? (float*)((char*)workspace + w.bytes + raw_stats_bytes(B, M, Lq)) : nullptr;
+  raw.off_stride = off_row_stride;
+  raw.logit_stride = logit_row_stride;
+  raw.goff_stride = goff_row_stride;
+  raw.glogit_stride = glogit_row_stride;
+  raw.nrec = w.samples * 4;
+  raw.ref_dim = ref_dim;
+  launch_bwd_passes<kSrcRaw>(value, spatial_shapes, level_start, offsets, logits, grad_output, grad_value, grad_offsets, grad_logits, B, S, M, L,
+                             Lq, P, workspace, raw, st);
+  if (grad_ref) {
+    const long n = (long)B * Lq * L * ref_dim;
+    hipLaunchKernelGGL(msda_bwd_ref_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)raw.gref_part, (float*)grad_ref, n,
+                       M, L * ref_dim);
+  }
+  return check_launch("msda_raw_backward");
 }

@@ -219,6 +219,51 @@ def msda_fused(value, spatial_shapes, level_start_index, ref, offsets, logits):
     return out
 
 
+def _raw_rows(t, name, B, Lq, inner):
+    """row stride of offsets / logits or of their gradients: dense (M,L,P,2) / (M,L*P) blocks at a common distance, fp32, on the device"""
+    if not t.is_cuda:
+        raise RuntimeError("Not implemented on the CPU (%s)" % name)
+    if t.dtype != torch.float32:
+        raise RuntimeError("%s must be torch.float32, got %s" % (name, t.dtype))
+    if tuple(t.shape[:2]) != (B, Lq) or tuple(t[0, 0].stride()) != inner or t.stride(0) != Lq * t.stride(1):
+        raise RuntimeError("msda_raw_backward: %s rows must be dense blocks of one (B, Lq, k) tensor" % name)
+    return t.stride(1)
+
+
+@_timed("msda_bwd")
+def msda_raw_backward(value, spatial_shapes, level_start_index, ref, offsets, logits, grad_output, want_grad_ref=True,
+                      grad_offsets=None, grad_logits=None):
+    """backward of msda_fused for fp32 and D = 32 (hipie_msda_raw_backward): value (B,S,M,D) dense; ref (B,Lq,L,2|4); offsets (B,Lq,M,L,P,2)
+    and logits (B,Lq,M,L*P), which may be column blocks of one projection output; grad_output (B,Lq,M*D) ->
+    (grad_value, grad_offsets, grad_logits, grad_ref | None).  grad_offsets / grad_logits may be given: column blocks of one (B, Lq, k)
+    buffer, written in place.  The workspace (bins, corner records, per-head partials of grad_ref) lives for this call."""
+    B, S, M, D = value.shape
+    _, Lq, _, L, P, _ = offsets.shape
+    dev = value.device
+    gv = torch.empty(B, S, M, D, dtype=torch.float32, device=dev)
+    if grad_offsets is None:
+        grad_offsets = torch.empty(B, Lq, M, L, P, 2, dtype=torch.float32, device=dev)
+    if grad_logits is None:
+        grad_logits = torch.empty(B, Lq, M, L * P, dtype=torch.float32, device=dev)
+    gref = torch.empty(B, Lq, L, ref.shape[-1], dtype=torch.float32, device=dev) if want_grad_ref else None
+    if B == 0:
+        return gv, grad_offsets, grad_logits, gref
+    if Lq == 0:
+        return gv.zero_(), grad_offsets, grad_logits, gref
+    off_in, lg_in = (L * P * 2, P * 2, 2, 1), (L * P, 1)
+    strides = (_raw_rows(offsets, "offsets", B, Lq, off_in), _raw_rows(logits, "logits", B, Lq, lg_in),
+               _raw_rows(grad_offsets, "grad_offsets", B, Lq, off_in), _raw_rows(grad_logits, "grad_logits", B, Lq, lg_in))
+    rd = int(ref.shape[-1])
+    need = _size("hipie_msda_raw_backward_ws_bytes", B, S, M, L, Lq, P, rd, int(bool(want_grad_ref)))
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    go = grad_output.contiguous()
+    _call("hipie_msda_raw_backward", _chk(value, "value", torch.float32), _chk(spatial_shapes, "spatial_shapes", torch.int64),
+          _chk(level_start_index, "level_start_index", torch.int64), _chk(ref, "ref", torch.float32), offsets.data_ptr(), logits.data_ptr(),
+          _chk(go, "grad_output", torch.float32), gv.data_ptr(), grad_offsets.data_ptr(), grad_logits.data_ptr(),
+          gref.data_ptr() if want_grad_ref else None, B, S, M, D, L, Lq, P, rd, *strides, ws.data_ptr(), need)
+    return gv, grad_offsets, grad_logits, gref
+
+
 @_timed("flash_attn")
 def flash_attn(q, k, v, scale, bias_h=None, bias_w=None, key_mask=None, clamp=0.0, out_f32=False, k_hl8=False):
     """q (B,Nq,H,hd), k,v (B,Nk,H,hd) 16-bit (may be strided views with hd contiguous) -> (B,Nq,H*hd) in the operand dtype, or

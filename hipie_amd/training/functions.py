@@ -55,6 +55,57 @@ def dynamic_mask(mask_feats, ref_points, params, num_queries, stride=8, up=2):
     return DynamicMaskFunction.apply(mask_feats, ref_points, params, num_queries, stride, up)
 
 
+class DeformSampleFunction(torch.autograd.Function):
+    """MSDeformAttn's sampling from the RAW projections as one node (ops/modules/ms_deform_attn.py:99-114 + the operator): forward =
+    hipie_msda_fused_forward (locations and the softmax in the kernel), backward = hipie_msda_raw_backward (the gather form; the chain rule
+    through the location and the softmax in its coefficient kernel).  value (B,S,M,32) dense; ss / ls: the level tensors; ref (B,Lq,L,2|4);
+    offsets (B,Lq,M,L,P,2) and logits (B,Lq,M,L*P), views of the projections' outputs -> (B,Lq,M*32).  Saved: value, ref, offsets, logits --
+    no location, no softmax output.  grad_ref is computed only when ref needs it."""
+
+    @staticmethod
+    def forward(ctx, value, ss, ls, ref, offsets, logits):
+        ref = ref.contiguous()
+        ctx.save_for_backward(value, ref, offsets, logits)
+        ctx.levels = (ss, ls)                        # the pyramid's cached constants (net.level_tensors)
+        return ops.msda_fused(value, ss, ls, ref, offsets, logits)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        value, ref, offsets, logits = ctx.saved_tensors
+        ss, ls = ctx.levels
+        gv, goff, glog, gref = ops.msda_raw_backward(value, ss, ls, ref, offsets, logits, grad_out, want_grad_ref=ctx.needs_input_grad[3])
+        return gv, None, None, gref, goff, glog
+
+
+MSDA_RAW_MAX_ROWS = 160 * 1024 // 4           # kBwdMaxRows of csrc/msda_bwd.hip: pixel rows whose counters fit the LDS of a CU
+MSDA_RAW_MAX_POINTS = 32                      # kMaxLP: L * P of the in-kernel softmax
+
+
+def deform_sample_ok(value, ref, offsets, logits):
+    """what hipie_msda_raw_backward takes, checked on the host before anything is launched"""
+    if value.dim() != 4 or offsets.dim() != 6 or logits.dim() != 4 or ref.dim() != 4:
+        return False
+    B, S, M, D = value.shape
+    _, Lq, _, L, P, _ = offsets.shape
+    if D != 32 or S > MSDA_RAW_MAX_ROWS or L * P > MSDA_RAW_MAX_POINTS or ref.shape[-1] not in (2, 4) or B == 0 or Lq == 0:
+        return False
+    if not all(t.is_cuda and t.dtype == torch.float32 for t in (value, ref, offsets, logits)) or not value.is_contiguous():
+        return False
+    return (tuple(offsets[0, 0].stride()) == (L * P * 2, P * 2, 2, 1) and offsets.stride(0) == Lq * offsets.stride(1)
+            and tuple(logits[0, 0].stride()) == (L * P, 1) and logits.stride(0) == Lq * logits.stride(1))
+
+
+def deform_sample(value, shapes, ref, offsets, logits):
+    """DeformSampleFunction on value (B,S,M,D), shapes [(H,W)], ref (B,Lq,L,2|4), offsets (B,Lq,M,L,P,2), logits (B,Lq,M,L*P) -> (B,Lq,M*D),
+    or None -- before any launch -- for what the backward entry would refuse (D != 32, more pixel rows than the LDS counters hold, L*P > 32,
+    anything but fp32 device tensors): the caller's composition then runs"""
+    if not deform_sample_ok(value, ref, offsets, logits):
+        return None
+    from .net import level_tensors
+    ss, ls = level_tensors(shapes, value.device)
+    return DeformSampleFunction.apply(value, ss, ls, ref, offsets, logits)
+
+
 def _weight_grad(g2, x2):
     """dW = dy^T . x  (N x K, the contraction over the M token rows) on the split GEMM.  N x K is 25-100 tiles of 256 x 256 for the ViT-H
     linears -- a fraction of the 256 CUs -- so the M rows are cut into nk chunks, one problem each in ONE hipie_gemm_batched launch, and

@@ -160,6 +160,20 @@ class HipBackendAll(HipBackendNorms, HipBackendMlp, HipBackendWindows):
     """the three opt-in groups: the hand-written LayerNorm pair, the one-node MLP and the fused windowed attention"""
 
 
+class HipBackendDeformable(HipBackend):
+    """HipBackend + every MSDeformAttn module's sampling as ONE autograd node from the raw sampling_offsets / attention_weights projections
+    (functions.DeformSampleFunction: hipie_msda_fused_forward / hipie_msda_raw_backward): no location tensor, no softmax output and none of
+    the torch passes between the projections and the operator, forward or backward.  The value mask fill and the three linears stay torch
+    nodes.  Opt-in: TrainStep's default stays HipBackend."""
+
+    @staticmethod
+    def msda_raw(value, shapes, ref, offsets, logits):
+        """value (B,S,M,D), shapes [(H,W)], ref (B,Lq,L,2|4), offsets (B,Lq,M,L,P,2), logits (B,Lq,M,L*P) -> (B,Lq,M*D), or None: msda_module's
+        own composition runs (functions.deform_sample names what is covered)"""
+        from .functions import deform_sample
+        return deform_sample(value, shapes, ref, offsets, logits)
+
+
 class HipBackendLosses(HipBackend):
     """HipBackend + the element-wise losses of both criteria on csrc/point_loss.hip: the point-sampled mask losses of a criterion call as one
     node that indexes the un-gathered targets (functions.PointMaskLossFunction) and the token focal loss with the pad tokens dropped inside
@@ -535,7 +549,15 @@ def msda_module(query, ref_points, src, shapes, pad_mask, sd, p, be, heads=8, le
         value = value.masked_fill(pad_mask[..., None], 0.0)
     value = value.view(N, S, heads, C // heads)
     off = lin(query, sd, p + "sampling_offsets.").view(N, Lq, heads, levels, points, 2)
-    aw = F.softmax(lin(query, sd, p + "attention_weights.").view(N, Lq, heads, levels * points), -1).view(N, Lq, heads, levels, points)
+    raw = getattr(be, "msda_raw", None)             # HipBackendDeformable: locations, softmax and sampling as one node from the raw projections
+    if raw is not None:
+        logits = lin(query, sd, p + "attention_weights.").view(N, Lq, heads, levels * points)
+        out = raw(value, shapes, ref_points, off, logits)
+        if out is not None:
+            return lin(out, sd, p + "output_proj.")
+        aw = F.softmax(logits, -1).view(N, Lq, heads, levels, points)
+    else:
+        aw = F.softmax(lin(query, sd, p + "attention_weights.").view(N, Lq, heads, levels * points), -1).view(N, Lq, heads, levels, points)
     if ref_points.shape[-1] == 2:
         loc = ref_points[:, :, None, :, None, :] + off / level_tensors(shapes, query.device, "wh")[None, None, None, :, None, :]
     else:

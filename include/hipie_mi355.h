@@ -128,6 +128,33 @@ int hipie_msda_fused_forward_strided(const void* value, int64_t value_row_stride
                                      int aux_dtype, int64_t off_row_stride, int64_t logit_row_stride, void* stream);
 
 /*
+ * Backward of hipie_msda_fused_forward for fp32 and D = 32 (training only): the gather form of hipie_msda_backward_ws with the location and the
+ * softmax recomputed in its count, fill and coefficient kernels from (ref, offsets, logits), and the chain rule through both applied in
+ * the coefficient kernel -- no (B,Lq,M,L,P,.) tensor other than the two gradient outputs and the corner records reaches HBM.
+ * Replaces: the autograd chain of MSDeformAttn.forward lines 99-114 (ops/modules/ms_deform_attn.py) + MSDeformAttnFunction.backward.
+ *   value, spatial_shapes, level_start, ref, offsets, logits, the two input row strides: as hipie_msda_fused_forward, all fp32, value dense
+ *   grad_output  (B, Lq, M*D)
+ *   grad_value   (B, S, M, D)   every row written (no zeroing needed; rows no level covers are zero), summed in slot (arrival) order
+ *   grad_offsets row (b,q) at grad_offsets + (b*Lq+q)*goff_row_stride holds (M, L, P, 2):  ref_dim 2: gloc / (W_l, H_l);
+ *                ref_dim 4: gloc * ref_wh * 0.5 / P          (gloc, gA, A: grad_sampling_loc, grad_attn_weight, softmax(logits))
+ *   grad_logits  row (b,q) at grad_logits + (b*Lq+q)*glogit_row_stride holds (M, L*P):  A_i (gA_i - sum_j A_j gA_j)
+ *                (the two output strides let both be column blocks of one (B, Lq, k) buffer)
+ *   grad_ref     (B, Lq, L, ref_dim) or NULL:  xy: sum_{m,p} gloc;  wh (ref_dim 4): sum_{m,p} gloc * off * 0.5 / P -- per-head partials in
+ *                the workspace, added in head order
+ * grad_offsets, grad_logits and grad_ref are bit-reproducible (no floating-point atomics anywhere).  workspace: at least
+ * hipie_msda_raw_backward_ws_bytes(..., grad_ref != NULL) bytes, 16-byte aligned: the gather form's bins and corner records, the softmax's
+ * (max, 1 / sum) per (b, q, head) -- computed once, by the count pass -- and, with grad_ref, its per-head partials.  Refused (HIPIE_EINVAL, nothing launched): D != 32, S above
+ * the 40960 pixel rows whose counters fit the LDS, L*P > 32, ref_dim not 2 | 4, a row stride below the row's width, null pointers, a
+ * workspace that is too small (the message names the size needed).  The size query answers 0 for shapes the entry refuses.
+ */
+int64_t hipie_msda_raw_backward_ws_bytes(int B, int S, int M, int L, int Lq, int P, int ref_dim, int want_grad_ref);
+int hipie_msda_raw_backward(const void* value, const int64_t* spatial_shapes, const int64_t* level_start, const float* ref,
+                            const void* offsets, const void* logits, const void* grad_output, void* grad_value, void* grad_offsets,
+                            void* grad_logits, void* grad_ref, int B, int S, int M, int D, int L, int Lq, int P, int ref_dim,
+                            int64_t off_row_stride, int64_t logit_row_stride, int64_t goff_row_stride, int64_t glogit_row_stride,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+
+/*
  * Fused (flash-style) attention core shared by the ViT blocks and the VL fusion:
  *     out[b,i,h,:] = softmax_j( clamp(scale * q[b,i,h,:].k[b,j,h,:], +-clamp) + bias_h[bh,j / kw,i] + bias_w[bh,i,j % kw]
  *                               + (key_mask[b,j] ? 0 : -inf) ) . v[b,j,h,:]

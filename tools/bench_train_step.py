@@ -3,7 +3,7 @@
 GPU (configs/training/vit_huge_32g.yaml:1 -- 32 GPUs x 2), the 80-class caption, 8 synthetic targets per image (6 things, 2 stuff), DN_NUMBER 100,
 12544 mask points, random-init weights.  Prints ms for the forward (loss dictionary), the backward, and the peak memory.
     python tools/bench_train_step.py [batch] [steps] [--hand-norms] [--fused-mlp] [--fused-windows] [--fused-losses] [--fused-criteria] [--fused-matching]
-                                                            [--fused-hungarian] [--fused-assign] [--packed-attention] [--packed-windows]
+                                                            [--fused-hungarian] [--fused-assign] [--packed-attention] [--packed-windows] [--fused-msda]
 --hand-norms: net.HipBackendNorms (the ViT / encoder LayerNorms on hipie_add_layernorm / hipie_layernorm_backward) instead of HipBackend
 --fused-mlp:  net.HipBackendMlp (the ViT MLPs / encoder FFNs as one autograd node, the activation recomputed by hipie_act_backward); with
               --hand-norms: net.HipBackendNormsMlp
@@ -22,6 +22,8 @@ GPU (configs/training/vit_huge_32g.yaml:1 -- 32 GPUs x 2), the 80-class caption,
 --packed-attention: net.HipBackendPackedAttention (the attention of the global ViT blocks as one autograd node, its operands packed and unpacked
               by hipie_attn_pack_*); composes with all of the above
 --packed-windows: net.HipBackendPackedWindows (--packed-attention + the same node over hipie_attn_train_win_* for the windowed blocks)
+--fused-msda: net.HipBackendDeformable (every MSDeformAttn module's locations, softmax and sampling as one autograd node from the raw projections:
+              hipie_msda_fused_forward / hipie_msda_raw_backward); composes with all of the above
 env: LIB_LINEAR=1 (library fp32 linears), PHASES=1 (synchronised forward phases), TORCH_PROF=1 (top kernels), COUNTS=1 (device launches and host
 waits of one step), HOSTPROF=1 (cProfile of a forward)"""
 import os
@@ -61,7 +63,7 @@ def targets_for(batch, n_things, n_stuff, size, L, dev, seed=0):
 
 def main():
     argv = [a for a in sys.argv[1:] if a not in ("--hand-norms", "--fused-mlp", "--fused-windows", "--fused-losses", "--fused-criteria", "--fused-matching",
-                                                   "--fused-hungarian", "--fused-assign", "--packed-attention", "--packed-windows")]
+                                                   "--fused-hungarian", "--fused-assign", "--packed-attention", "--packed-windows", "--fused-msda")]
     fused_assign = "--fused-assign" in sys.argv[1:]
     fused_hungarian = "--fused-hungarian" in sys.argv[1:] or fused_assign
     fused_matching = "--fused-matching" in sys.argv[1:] or fused_hungarian
@@ -94,6 +96,9 @@ def main():
             step.be = type(step.be.__name__ + "Windows", (step.be, net.HipBackendWindows), {})
     if "--packed-attention" in sys.argv[1:] or "--packed-windows" in sys.argv[1:]:
         top = net.HipBackendPackedWindows if "--packed-windows" in sys.argv[1:] else net.HipBackendPackedAttention
+        step.be = top if step.be is net.HipBackend else type(step.be.__name__ + top.__name__[10:], (top, step.be), {})
+    if "--fused-msda" in sys.argv[1:]:
+        top = net.HipBackendDeformable
         step.be = top if step.be is net.HipBackend else type(step.be.__name__ + top.__name__[10:], (top, step.be), {})
     if fused_losses:                                         # the criteria were built with the default backend: hand them the new one
         step.be = net.HipBackendLosses if step.be is net.HipBackend else type(step.be.__name__ + "Losses", (step.be, net.HipBackendLosses), {})
