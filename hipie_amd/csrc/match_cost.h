@@ -8,45 +8,61 @@
 
 namespace hipie {
 
-struct BoxXYXY {
-  float x0, y0, x1, y1;
+// T: float (the matching costs, in torch's fp32 operation order) or double (pair_loss.hip, which rounds once at the end)
+template <typename T>
+struct BoxCorners {
+  T x0, y0, x1, y1;
 };
+typedef BoxCorners<float> BoxXYXY;
+
+__device__ __forceinline__ float box_max(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ float box_min(float a, float b) { return fminf(a, b); }
+__device__ __forceinline__ double box_max(double a, double b) { return fmax(a, b); }
+__device__ __forceinline__ double box_min(double a, double b) { return fmin(a, b); }
+__device__ __forceinline__ float box_eps(float) { return 1e-7f; }
+__device__ __forceinline__ double box_eps(double) { return 1e-7; }
 
 // boxes.box_cxcywh_to_xyxy: c - 0.5 s, c + 0.5 s
-__device__ __forceinline__ BoxXYXY box_xyxy(const float* __restrict__ b) {
+template <typename T = float>
+__device__ __forceinline__ BoxCorners<T> box_xyxy(const float* __restrict__ b) {
 #pragma clang fp contract(off)
-  const float hw = 0.5f * b[2], hh = 0.5f * b[3];
-  BoxXYXY r;
-  r.x0 = b[0] - hw;
-  r.y0 = b[1] - hh;
-  r.x1 = b[0] + hw;
-  r.y1 = b[1] + hh;
+  const T hw = (T)0.5f * (T)b[2], hh = (T)0.5f * (T)b[3];
+  BoxCorners<T> r;
+  r.x0 = (T)b[0] - hw;
+  r.y0 = (T)b[1] - hh;
+  r.x1 = (T)b[0] + hw;
+  r.y1 = (T)b[1] + hh;
   return r;
 }
 
 // the check of boxes.generalized_box_iou: a corner pair out of order -- or a NaN -- is a caller error
-__device__ __forceinline__ bool box_degenerate(const BoxXYXY& a) { return !(a.x1 >= a.x0) || !(a.y1 >= a.y0); }
+template <typename T>
+__device__ __forceinline__ bool box_degenerate(const BoxCorners<T>& a) { return !(a.x1 >= a.x0) || !(a.y1 >= a.y0); }
 
-__device__ __forceinline__ float box_area(const BoxXYXY& a) {
+template <typename T>
+__device__ __forceinline__ T box_area(const BoxCorners<T>& a) {
 #pragma clang fp contract(off)
   return (a.x1 - a.x0) * (a.y1 - a.y0);
 }
 
-struct BoxPair {
-  float inter, uni, giou;                    // boxes._pairwise_inter_union, boxes.generalized_box_iou; IoU = inter / uni
+template <typename T>
+struct BoxPairTerms {
+  T inter, uni, giou;                        // boxes._pairwise_inter_union, boxes.generalized_box_iou; IoU = inter / uni
 };
+typedef BoxPairTerms<float> BoxPair;
 
-__device__ __forceinline__ BoxPair box_pair(const BoxXYXY& a, const BoxXYXY& b) {
+template <typename T>
+__device__ __forceinline__ BoxPairTerms<T> box_pair(const BoxCorners<T>& a, const BoxCorners<T>& b) {
 #pragma clang fp contract(off)
-  BoxPair p;
-  const float iw = fmaxf(fminf(a.x1, b.x1) - fmaxf(a.x0, b.x0), 0.f);
-  const float ih = fmaxf(fminf(a.y1, b.y1) - fmaxf(a.y0, b.y0), 0.f);
+  BoxPairTerms<T> p;
+  const T iw = box_max(box_min(a.x1, b.x1) - box_max(a.x0, b.x0), (T)0);
+  const T ih = box_max(box_min(a.y1, b.y1) - box_max(a.y0, b.y0), (T)0);
   p.inter = iw * ih;
   p.uni = (box_area(a) + box_area(b)) - p.inter;
-  const float hw = fmaxf(fmaxf(a.x1, b.x1) - fminf(a.x0, b.x0), 0.f);
-  const float hh = fmaxf(fmaxf(a.y1, b.y1) - fminf(a.y0, b.y0), 0.f);
-  const float hull = hw * hh;
-  p.giou = p.inter / p.uni - (hull - p.uni) / (hull + 1e-7f);
+  const T hw = box_max(box_max(a.x1, b.x1) - box_min(a.x0, b.x0), (T)0);
+  const T hh = box_max(box_max(a.y1, b.y1) - box_min(a.y0, b.y0), (T)0);
+  const T hull = hw * hh;
+  p.giou = p.inter / p.uni - (hull - p.uni) / (hull + box_eps((T)0));
   return p;
 }
 

@@ -43,24 +43,34 @@ __device__ __forceinline__ void ln_affine(const float (&v)[4], float mean, float
 // ---- ws (nparts, ncols) -> the column sums, columns < split into out_a and the rest into out_b ------------------------------------------
 // A workgroup owns COLS columns; thread (group, col) adds the partial rows group, group + GROUPS, ... in order, the GROUPS group sums are
 // added in order by the threads of group 0.  No atomics: GROUPS and COLS fix the order of the additions, and so the bits.
-template <int GROUPS, int COLS>
-__global__ __launch_bounds__(256) void partial_rows_sum_kernel(const float* __restrict__ ws, float* __restrict__ out_a,
-                                                               float* __restrict__ out_b, int split, int nparts, int ncols) {
-  static_assert(GROUPS * COLS == 256, "one thread per (group, column)");
-  __shared__ float red[GROUPS][COLS];
+// the sum of column `col` of ws (nparts, ncols), valid in the threads of group 0 (T: float, or double partials -- pair_loss.hip)
+template <int GROUPS, int COLS, typename T>
+__device__ __forceinline__ T partial_rows_column(const T* __restrict__ ws, int nparts, int ncols, int col, T (*red)[COLS]) {
   const int cx = threadIdx.x % COLS, grp = threadIdx.x / COLS;
-  const int col = blockIdx.x * COLS + cx;
-  float acc = 0.f;
+  T acc = 0;
   if (col < ncols) {
 #pragma unroll 8
     for (int p = grp; p < nparts; p += GROUPS) acc += ws[(long)p * ncols + col];
   }
   red[grp][cx] = acc;
   __syncthreads();
+  T t = 0;
   if (grp == 0 && col < ncols) {
-    float t = red[0][cx];
+    t = red[0][cx];
 #pragma unroll
     for (int k = 1; k < GROUPS; ++k) t += red[k][cx];
+  }
+  return t;
+}
+
+template <int GROUPS, int COLS>
+__global__ __launch_bounds__(256) void partial_rows_sum_kernel(const float* __restrict__ ws, float* __restrict__ out_a,
+                                                               float* __restrict__ out_b, int split, int nparts, int ncols) {
+  static_assert(GROUPS * COLS == 256, "one thread per (group, column)");
+  __shared__ float red[GROUPS][COLS];
+  const int col = blockIdx.x * COLS + threadIdx.x % COLS;
+  const float t = partial_rows_column<GROUPS, COLS, float>(ws, nparts, ncols, col, red);
+  if (threadIdx.x / COLS == 0 && col < ncols) {
     if (col < split) out_a[col] = t;
     else out_b[col - split] = t;
   }

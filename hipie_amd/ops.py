@@ -1182,6 +1182,116 @@ def hungarian_assign(costs, n_tgt, t_off, sum_t, Q, Tmax, ws=None):
     return pairs[0], pairs[1], status
 
 
+PAIR_MAX_B, PAIR_MAX_K = 64, 65536            # the limits of csrc/pair_loss.hip (the pair lists live in the kernel arguments)
+PAIR_STATUS = ((1, "boxes with x1 < x0 or y1 < y0 (or a NaN)"), (2, "a query or target index out of range"))
+
+
+def pair_box_loss_ws_bytes(K):
+    return _size("hipie_pair_box_loss_ws_bytes", int(K))
+
+
+def _pair_lists(who, pairs, with_t=True):
+    """the matched pairs of a batch -- per image (query idx, target idx), int64 contiguous DEVICE tensors -- as the HOST arrays of the C entries:
+    (addresses of the query lists, of the target lists | None, lengths, K).  Nothing is copied; the layout is checked before the device."""
+    B = len(pairs)
+    qs, ts, ns = (ctypes.c_void_p * B)(), (ctypes.c_void_p * B)(), (ctypes.c_int64 * B)()
+    for b, (q, t) in enumerate(pairs):
+        for name, x in (("query", q), ("target", t)):
+            if x.dtype != torch.int64 or x.dim() != 1 or not x.is_contiguous():
+                raise RuntimeError("%s: the %s indices of image %d must be a contiguous 1-d torch.int64 tensor, got %s %s"
+                                   % (who, name, b, x.dtype, tuple(x.shape)))
+        if q.shape != t.shape:
+            raise RuntimeError("%s: image %d has %d query and %d target indices" % (who, b, q.numel(), t.numel()))
+        _on_device(pair_q=q, pair_t=t)
+        ns[b] = q.numel()
+        if q.numel():
+            qs[b], ts[b] = q.data_ptr(), t.data_ptr()
+    return qs, (ts if with_t else None), ns, sum(ns)
+
+
+def _rows_f32(t, name, shape, inner):
+    """refuses t unless it is an fp32 tensor of that shape whose last `inner` elements are dense (the image and row strides are the caller's)"""
+    if t.dtype != torch.float32:
+        raise RuntimeError("%s must be torch.float32, got %s" % (name, t.dtype))
+    if tuple(t.shape) != tuple(shape):
+        raise RuntimeError("%s must be %s, got %s" % (name, tuple(shape), tuple(t.shape)))
+    if inner > 1 and t.stride(-1) != 1:
+        raise RuntimeError("%s: the last dimension has to be dense" % name)
+
+
+@_timed("pair_box_loss_fwd")
+def pair_box_loss_forward(boxes, iou, pairs, tgt_boxes, is_thing, count, mode):
+    """the box losses of the matched pairs of one criterion call (hipie_pair_box_loss_forward): boxes (B,Q,4) fp32 cxcywh -- any image and row
+    stride, e.g. a slice of the query axis --, iou None or the (B,Q) box-IoU logits (strided too), pairs: per image (query idx, target idx) int64
+    on the device, tgt_boxes (B,Tmax,4) fp32 and is_thing (B,Tmax) uint8 or None (functions.pack_match_targets), count: the normaliser;
+    mode 0 = DetCriterion.loss_boxes, 1 = MaskCriterion.loss_boxes -> (out (8,) fp32: loss_bbox, loss_giou, loss_boxiou and the factors of the
+    backward; pair_grad (K,9); status (1,) int32, PAIR_STATUS).  Two launches, no host wait, bit-reproducible.  Without pairs nothing is
+    launched and out is all zero.  Nothing is copied: another dtype or layout, B > 64 or more than 65536 pairs is refused."""
+    B, Q = boxes.shape[0], boxes.shape[1] if boxes.dim() == 3 else -1
+    _rows_f32(boxes, "boxes", (B, Q, 4), 4)
+    if iou is not None:
+        _rows_f32(iou, "iou", (B, Q), 1)
+    Tmax = tgt_boxes.shape[1] if tgt_boxes.dim() == 3 else -1
+    _layout_as(tgt_boxes, "tgt_boxes", torch.float32, (B, Tmax, 4))
+    if is_thing is not None:
+        _layout_as(is_thing, "is_thing", torch.uint8, (B, Tmax))
+    if len(pairs) != B or B > PAIR_MAX_B:
+        raise RuntimeError("pair_box_loss: %d pair lists for B=%d images (at most %d)" % (len(pairs), B, PAIR_MAX_B))
+    qs, ts, ns, K = _pair_lists("pair_box_loss", pairs)
+    if K > PAIR_MAX_K:
+        raise RuntimeError("pair_box_loss: K=%d pairs, at most %d" % (K, PAIR_MAX_K))
+    _on_device(boxes=boxes, iou=iou, tgt_boxes=tgt_boxes, is_thing=is_thing)
+    out = boxes.new_zeros(8)
+    pair_grad = boxes.new_empty(K, 9)
+    status = torch.zeros(1, dtype=torch.int32, device=boxes.device)
+    ws_bytes = _size("hipie_pair_box_loss_ws_bytes", K)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=boxes.device)
+    _call("hipie_pair_box_loss_forward", boxes.data_ptr(), boxes.stride(0), boxes.stride(1), None if iou is None else iou.data_ptr(),
+          0 if iou is None else iou.stride(0), 0 if iou is None else iou.stride(1), qs, ts, ns, tgt_boxes.data_ptr(),
+          None if is_thing is None else is_thing.data_ptr(), out.data_ptr(), pair_grad.data_ptr(), status.data_ptr(), ws.data_ptr(), ws_bytes, B, Q,
+          Tmax, int(mode), float(count))
+    return out, pair_grad, status
+
+
+@_timed("pair_box_loss_bwd")
+def pair_box_loss_backward(pairs, out, pair_grad, g_bbox, g_giou, g_boxiou, B, Q, with_iou):
+    """(d_boxes (B,Q,4), d_iou (B,Q) | None) of pair_box_loss_forward for the gradients of its three scalars, DEVICE tensors of one fp32 element
+    each (hipie_pair_box_loss_backward): both results are zero-filled and every pair adds its stored gradient with an fp32 atomic -- duplicates
+    of an (image, query) sum; one target per (image, query): bit-reproducible.  No host wait."""
+    qs, _, ns, K = _pair_lists("pair_box_loss_backward", pairs, with_t=False)
+    _layout_as(out, "out", torch.float32, (8,))
+    _layout_as(pair_grad, "pair_grad", torch.float32, (K, 9))
+    gs = (g_bbox, g_giou) + ((g_boxiou,) if with_iou else ())
+    for g in gs:
+        if g.dtype != torch.float32 or g.numel() != 1:
+            raise RuntimeError("pair_box_loss_backward: an upstream gradient must hold one torch.float32 value, got %s %s" % (g.dtype, tuple(g.shape)))
+    _on_device(out=out, pair_grad=pair_grad, **{"g%d" % i: g for i, g in enumerate(gs)})
+    d_boxes = out.new_empty(B, Q, 4)
+    d_iou = out.new_empty(B, Q) if with_iou else None
+    _call("hipie_pair_box_loss_backward", qs, ns, out.data_ptr(), pair_grad.data_ptr(), g_bbox.data_ptr(), g_giou.data_ptr(),
+          g_boxiou.data_ptr() if with_iou else None, d_boxes.data_ptr(), None if d_iou is None else d_iou.data_ptr(), B, Q)
+    return d_boxes, d_iou
+
+
+@_timed("positive_onehot")
+def positive_onehot(pairs, pos_map, Q):
+    """criterion._positive_onehot on hipie_positive_onehot: pairs as in pair_box_loss_forward, pos_map (B,Tmax,L) uint8 -> onehot (B,Q,L) fp32,
+    zero but onehot[b, q_i] = (pos_map[b, t_i] != 0).  A fill and one launch, no host wait."""
+    if pos_map.dim() != 3:
+        raise RuntimeError("positive_onehot: pos_map must be (B, Tmax, L), got %s" % (tuple(pos_map.shape),))
+    B, Tmax, L = pos_map.shape
+    _layout_as(pos_map, "pos_map", torch.uint8, (B, Tmax, L))
+    if len(pairs) != B or B > PAIR_MAX_B:
+        raise RuntimeError("positive_onehot: %d pair lists for B=%d images (at most %d)" % (len(pairs), B, PAIR_MAX_B))
+    qs, ts, ns, K = _pair_lists("positive_onehot", pairs)
+    if K > PAIR_MAX_K:
+        raise RuntimeError("positive_onehot: K=%d pairs, at most %d" % (K, PAIR_MAX_K))
+    _on_device(pos_map=pos_map)
+    onehot = torch.empty(B, int(Q), L, dtype=torch.float32, device=pos_map.device)
+    _call("hipie_positive_onehot", qs, ts, ns, pos_map.data_ptr(), onehot.data_ptr(), B, int(Q), Tmax, L)
+    return onehot
+
+
 OPTIM_MAX_GROUPS = 8
 OPTIM_SEGMENT_WORDS = 6          # int64 words of a segment record: p, g, m, v, numel, group
 

@@ -21,7 +21,16 @@ tokens inside the kernel instead of by boolean indexing (a host wait).  The rand
 An `ops` that also has
     uncertain_points(src (N,H,W), cand (N,C,2), rest (N,P-k,2) | None, k, num_points=None) -> pts (N,P,2)
 (net.HipBackendCriteria: functions.uncertain_points on csrc/point_select.hip) selects the importance points of those two calls: the same
-two draws, the chosen candidates in ascending candidate index instead of sorted by score."""
+two draws, the chosen candidates in ascending candidate index instead of sorted by score.
+An `ops` that also has
+    pair_box_loss(pred_boxes (B,Q,4), pred_iou | None, indices, packed, count, mode, use_thing) -> (loss_bbox, loss_giou, loss_boxiou | None, status) | None
+    positive_onehot(logits (B,Q,L), indices, packed) -> onehot (B,Q,L) | None
+    pack_pair_targets(targets, device) -> the padded targets those two read (tgt_boxes, is_thing, pos_map), packed without a host -> device copy
+(net.HipBackendPairLosses: functions.pair_box_loss / positive_onehot on csrc/pair_loss.hip) computes `loss_boxes` of both criteria as one node
+from the pairs where the matcher left them -- the final scalars, no host wait -- and the one-hot of the token focal loss as a fill and one
+scatter.  The targets are packed once per forward (or taken from the matcher's packing).  An answer None (a shape or dtype outside the
+kernels' limits) runs the code below.  The status word of a loss_boxes call (a degenerate box in MaskCriterion's: the ValueError of
+boxes.generalized_box_iou) stays on the device in `pending` until check() -- or HungarianMatcher.check_all, which TrainStep calls -- reads it."""
 import copy
 
 import torch
@@ -110,6 +119,63 @@ def _positive_onehot(logits, targets, indices):
     return onehot
 
 
+PAIR_STATUS = ((1, "generalized_box_iou: boxes with x1 < x0 or y1 < y0"), (2, "a query or target index out of range"))
+
+
+class _PairOps:
+    """what the two criteria share of the `pair_box_loss` / `positive_onehot` ops: the targets packed once per target list, the one-hot, and
+    the status words of the loss_boxes calls that nobody has read yet"""
+
+    def _init_pair_ops(self):
+        self._packs = []                                   # (target list, its packing) of the forward in flight, `ops` path only
+        self.pending = []                                  # (status (1,) int32 on the device, label, what, messages) per unchecked loss_boxes call
+        self.box_calls = 0
+
+    def _pair_targets(self, targets, device, packed=None):
+        """the packing of `targets` for the pair ops, made once per list (every layer and de-noising part of a forward passes the same one);
+        packed: a packing the caller already has (the matcher's) -- it is kept instead"""
+        for t, p in self._packs:
+            if t is targets:
+                return p
+        if packed is None:
+            packed = self.ops.pack_pair_targets(targets, device)
+        self._packs = self._packs[-3:] + [(targets, packed)]
+        return packed
+
+    def _onehot(self, logits, targets, indices):
+        """_positive_onehot, through the `positive_onehot` op when every positive map is bool / uint8: the packed map ((map != 0) as bytes) then
+        holds the entries the loop would write"""
+        op = getattr(self.ops, "positive_onehot", None)
+        if op is not None and all(t.get("positive_map") is not None and t["positive_map"].dtype in (torch.bool, torch.uint8) for t in targets):
+            got = op(logits, indices, self._pair_targets(targets, logits.device))
+            if got is not None:
+                return got
+        return _positive_onehot(logits, targets, indices)
+
+    def _pair_boxes(self, out, targets, indices, count, mode, use_thing):
+        """loss_boxes through the `pair_box_loss` op -> its dict, or None: no such op, no pair (the torch expression runs: `src.sum() * 0.0`, no
+        launch of the op) or the op declined"""
+        op = getattr(self.ops, "pair_box_loss", None)
+        if op is None or sum(len(p[0]) for p in indices) == 0:
+            return None
+        boxes = out["pred_boxes"]
+        got = op(boxes, out.get("pred_boxious") if mode == 0 else None, indices, self._pair_targets(targets, boxes.device), count, mode, use_thing)
+        if got is None:
+            return None
+        lb, lg, li, status = got
+        self.box_calls += 1
+        self.pending.append((status, "%s.loss_boxes call %d" % (type(self).__name__, self.box_calls), "loss_boxes", PAIR_STATUS))
+        res = {"loss_bbox": lb, "loss_giou": lg}
+        if li is not None:
+            res["loss_boxiou"] = li
+        return res
+
+    def check(self):
+        """reads the status words of the pending loss_boxes calls in one copy, clears the list and raises ValueError for the first non-zero one"""
+        from .matcher import HungarianMatcher
+        HungarianMatcher.check_all((self,))
+
+
 def _pad_masks(masks, divisor=0):
     """per-image (n_i, h_i, w_i) masks -> (B, max n, H, W) zero padded at the bottom / right (nested_tensor_from_tensor_list), H and W rounded
     up to a multiple of `divisor`"""
@@ -125,7 +191,7 @@ def _pad_masks(masks, divisor=0):
 
 
 # ---- detection branch ---------------------------------------------------------------------------------------------------------------
-class DetCriterion(nn.Module):
+class DetCriterion(nn.Module, _PairOps):
     """losses: any of "labelsVL", "boxes", "masks".  matcher: only its ``forward_boxes_only`` is called here (the encoder proposals,
     deformable_detr.py:693-716); the assignments of the decoder layers are computed by the caller (ddetrs_dn.py coco_forward) and
     passed as `indices_per_layer` (last entry = last layer)."""
@@ -135,6 +201,7 @@ class DetCriterion(nn.Module):
                  ops=None):
         super().__init__()
         self.ops = ops
+        self._init_pair_ops()
         self.ota = ota                                     # one-to-many assignments: every loss is per MATCHED PAIR (deformable_detr.py:362, 430, 481)
         self.matcher, self.losses = matcher, tuple(losses)
         self.focal_alpha, self.mask_out_stride = focal_alpha, mask_out_stride
@@ -151,13 +218,18 @@ class DetCriterion(nn.Module):
             count = sum(len(p[0]) for p in indices)
         if count == 0:
             return {"loss_ce": logits.sum() * 0.0}
-        onehot = _positive_onehot(logits, targets, indices)
+        onehot = self._onehot(logits, targets, indices)
         if self.ops is not None:
             return {"loss_ce": self.ops.token_focal_sum(logits, onehot, out["text_masks"], self.focal_alpha) / count}
         return {"loss_ce": token_focal_loss(logits, onehot, out["text_masks"], self.focal_alpha) / count}
 
     def loss_boxes(self, out, targets, indices, count):
         """deformable_detr.py:397-450: stuff targets carry no box -- they are masked out and the rest re-weighted to the full count"""
+        # the `pair_box_loss` op has no "no thing among the pairs" branch: every masked sum is then exactly 0, so the losses and their
+        # gradients are exactly 0 -- what the branch below returns
+        fused = self._pair_boxes(out, targets, indices, sum(len(p[0]) for p in indices) if self.ota else count, 0, self.panoptic_box_loss)
+        if fused is not None:
+            return fused
         bi, si = _perm(indices, 0)
         src = out["pred_boxes"][bi, si]
         tgt = torch.cat([t["boxes"][j] for t, (_, j) in zip(targets, indices)])
@@ -232,6 +304,7 @@ class DetCriterion(nn.Module):
         ``cdn_queries`` extended by the caller with "output_known_lbs_bboxes" = the de-noising part's outputs (+ its "aux_outputs").
         -> {name: scalar} with the reference's key suffixes (_i aux layer, _enc, _dn, _dn_i)."""
         count = _target_count(targets, outputs["pred_logits"].device)
+        self._packs = []
         losses = {}
         for name in self.losses:
             losses.update(self._one(name, outputs, targets, indices_per_layer[-1], count))
@@ -252,10 +325,13 @@ class DetCriterion(nn.Module):
                 idx = self.matcher.forward_boxes_only(enc["pred_logits"], enc["pred_boxes"], bin_targets)
             else:
                 idx = self.matcher.forward_boxes_only(enc["pred_logits"], enc["pred_boxes"], bin_targets, packed=packed)
+                if getattr(self.ops, "pair_box_loss", None) is not None:               # the pair ops read the matcher's packing of the binary targets:
+                    self._pair_targets(bin_targets, enc["pred_logits"].device, packed)  # their all-ones (T, 1) maps are packed, this call is not left out
             for name in self.losses:
                 if name != "masks":
                     losses.update({k + "_enc": v for k, v in self._one(name, enc, bin_targets, idx, count).items()})
         losses.update(self.dn_losses(dn_meta, targets, len(outputs.get("aux_outputs", ())), count, outputs["pred_logits"].device))
+        self._packs = []
         return losses
 
     def dn_losses(self, dn_meta, targets, n_aux, count, device):
@@ -278,7 +354,7 @@ class DetCriterion(nn.Module):
 
 
 # ---- MaskDINO ------------------------------------------------------------------------------------------------------------------------
-class MaskCriterion(nn.Module):
+class MaskCriterion(nn.Module, _PairOps):
     """losses: any of "labels", "masks", "boxes"; vl_loss: labels against positive maps (token focal loss) instead of class ids;
     dn: "no" | "standard" | "seg" with dn_losses the families applied to the de-noising part (maskdino/criterion.py:136-166)."""
 
@@ -286,6 +362,7 @@ class MaskCriterion(nn.Module):
                  dn="no", dn_losses=(), panoptic_on=False, focal_alpha=0.25, draw=None, ops=None):
         super().__init__()
         self.ops = ops
+        self._init_pair_ops()
         self._padded = None                                # (targets, their padded masks) of the forward in flight, `ops` path only
         self.num_classes, self.matcher, self.losses = num_classes, matcher, tuple(losses)
         self.vl_loss, self.dn, self.dn_losses_names, self.panoptic_on, self.focal_alpha = vl_loss, dn, tuple(dn_losses), panoptic_on, focal_alpha
@@ -297,7 +374,7 @@ class MaskCriterion(nn.Module):
         if self.vl_loss:                                   # maskdino/criterion.py:209-238
             if count == 0:
                 return {"loss_ce": logits.sum() * 0.0}
-            onehot = _positive_onehot(logits, targets, indices).detach()
+            onehot = self._onehot(logits, targets, indices).detach()
             if self.ops is not None:
                 return {"loss_ce": self.ops.token_focal_sum(logits, onehot, out["text_masks"].detach(), self.focal_alpha) / count}
             return {"loss_ce": token_focal_loss(logits, onehot, out["text_masks"].detach(), self.focal_alpha) / count}
@@ -309,6 +386,9 @@ class MaskCriterion(nn.Module):
 
     def loss_boxes(self, out, targets, indices, count):
         """:240-284: L1 and 1 - GIoU of the matched pairs; panoptic: things only"""
+        fused = self._pair_boxes(out, targets, indices, count, 1, self.panoptic_on)
+        if fused is not None:
+            return fused
         bi, si = _perm(indices, 0)
         src = out["pred_boxes"][bi, si]
         tgt = torch.cat([t["boxes"][j] for t, (_, j) in zip(targets, indices)])
@@ -365,6 +445,9 @@ class MaskCriterion(nn.Module):
             dn_idx = dn_match_indices(targets, {"dn_num": groups, "single_padding": mask_dict["pad_size"] // groups}, dev)
         pack = getattr(self.matcher, "pack", None)                                      # the targets as the matcher's Hungarian cost kernel reads them,
         packed = pack(targets, dev) if pack else None                                   # once for every output of this call; None without that kernel
+        self._packs = []
+        if packed is not None and getattr(self.ops, "pair_box_loss", None) is not None:
+            self._pair_targets(targets, dev, packed)                                    # the pair ops read the same packing
         idx = self._match(main, targets, packed)
         count = _target_count(targets, dev)
         losses = {}
@@ -393,4 +476,5 @@ class MaskCriterion(nn.Module):
             for name in self.losses:
                 losses.update({k + "_interm": v for k, v in self._one(name, outputs["interm_outputs"], targets, iidx, count).items()})
         self._padded = None                                # the graph holds what it needs
+        self._packs = []
         return losses

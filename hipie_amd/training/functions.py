@@ -611,13 +611,14 @@ MatchTargets = collections.namedtuple("MatchTargets", "tgt_boxes pos_map labels 
 
 
 @torch.no_grad()
-def pack_match_targets(targets, device, with_masks=True):
+def pack_match_targets(targets, device, with_masks=True, with_counts=True):
     """the targets of a Hungarian matcher as hipie_hungarian_cost reads them, packed ONCE for many calls (every decoder level, every output of a
     criterion call): per-image dicts with "boxes" (T_i, 4) cxcywh, "positive_map" (T_i, L) and / or "labels" (T_i,), optionally "is_thing"
     (T_i,; absent: every target is a thing) and "masks" (T_i, H_i, W_i) -> MatchTargets(tgt_boxes (B,Tmax,4) fp32, pos_map (B,Tmax,L) uint8 or
     None when no image has a map, labels (B,Tmax) int32 or None when an image with targets has none, is_thing (B,Tmax) uint8 -- all zero behind
     T_i; n_tgt and t_off (B,) int32 on the device, t_off the exclusive prefix sum; counts: the T_i as a host list; tgt_masks: per image the
-    fp32 dense masks on the device, or None (with_masks=False, or an image with targets has none))."""
+    fp32 dense masks on the device, or None (with_masks=False, or an image with targets has none)).  with_counts=False: n_tgt and t_off are
+    None and NOTHING is copied from the host -- the packing of pack_pair_targets, whose readers take the counts from the pair lists."""
     counts = [int(t["boxes"].shape[0]) for t in targets]
     B, Tmax = len(targets), max(counts, default=0)
     has_map = any("positive_map" in t for t in targets)
@@ -642,7 +643,10 @@ def pack_match_targets(targets, device, with_masks=True):
     for n in counts[:-1]:
         offs.append(offs[-1] + n)
     # one host -> device copy for the two count vectors
-    both = torch.tensor([counts, offs[:B]], dtype=torch.int32).to(device) if B else torch.zeros(2, 0, dtype=torch.int32, device=device)
+    if not with_counts:
+        both = (None, None)
+    else:
+        both = torch.tensor([counts, offs[:B]], dtype=torch.int32).to(device) if B else torch.zeros(2, 0, dtype=torch.int32, device=device)
     tgt_masks = None
     if with_masks and all("masks" in t for t, n in zip(targets, counts) if n):
         tgt_masks = [t["masks"].to(device).float().contiguous() if n else None for t, n in zip(targets, counts)]
@@ -740,3 +744,88 @@ def hungarian_match(logits, boxes, packed, w, masks=None, coords=None, stuff_tak
     pair_q, pair_t, status = ops.hungarian_assign(out, packed.n_tgt, packed.t_off, sum(packed.counts), Q, packed.tgt_boxes.shape[1])
     return [(pair_q[b, :min(Q, n)], pair_t[b, :min(Q, n)]) for b, n in enumerate(packed.counts)], status
 
+
+
+class PairBoxLossFunction(torch.autograd.Function):
+    """the box losses of the matched pairs of ONE criterion call as one node (criterion.DetCriterion.loss_boxes: mode 0, MaskCriterion.loss_boxes:
+    mode 1): pred_boxes (B,Q,4) -- a slice of the query axis is read through its strides, never copied --, pred_iou None | (B,Q) logits, pairs:
+    per image (query idx, target idx) int64 on the device, tgt_boxes / is_thing of pack_match_targets, the normaliser `count` -> (loss_bbox,
+    loss_giou, loss_boxiou, status): the FINAL scalars (views of one 8-element buffer) and the (1,) int32 status word (ops.PAIR_STATUS), which
+    nobody reads here.  forward = ops.pair_box_loss_forward, backward = ops.pair_box_loss_backward with the three upstream scalars taken from
+    the device.  Kept for the backward: that buffer, the (K,9) per-pair gradients and the pair lists -- no operand.  Gradients for pred_boxes
+    and pred_iou only."""
+
+    @staticmethod
+    def forward(ctx, pred_boxes, pred_iou, pairs, tgt_boxes, is_thing, count, mode):
+        out, pair_grad, status = ops.pair_box_loss_forward(pred_boxes, pred_iou, pairs, tgt_boxes, is_thing, count, mode)
+        ctx.save_for_backward(out, pair_grad)
+        ctx.pairs, ctx.shape, ctx.iou_shape = pairs, pred_boxes.shape, None if pred_iou is None else pred_iou.shape
+        ctx.mark_non_differentiable(status)
+        return out[0], out[1], out[2], status
+
+    @staticmethod
+    def backward(ctx, g_bbox, g_giou, g_boxiou, _):
+        want_iou = ctx.iou_shape is not None and ctx.needs_input_grad[1]
+        if not (ctx.needs_input_grad[0] or want_iou):
+            return (None,) * 7
+        out, pair_grad = ctx.saved_tensors
+        d_boxes, d_iou = ops.pair_box_loss_backward(ctx.pairs, out, pair_grad, g_bbox.float(), g_giou.float(), g_boxiou.float(), ctx.shape[0],
+                                                    ctx.shape[1], want_iou)
+        return (d_boxes if ctx.needs_input_grad[0] else None, d_iou.reshape(ctx.iou_shape) if want_iou else None) + (None,) * 5
+
+
+def pack_pair_targets(targets, device):
+    """the targets of a criterion call as pair_box_loss / positive_onehot read them: pack_match_targets without masks and without the count
+    vectors, whose host -> device copy is a host wait (tgt_boxes, is_thing, pos_map, the counts as a host list).  A packing the matcher
+    already made (pack_match_targets) serves as well."""
+    return pack_match_targets(targets, device, with_masks=False, with_counts=False)
+
+
+def _device_pairs(pairs, device):
+    """the pairs as the kernels read them: int64, contiguous, on `device` (what the device matchers and dn_match_indices return is passed on
+    as it is; host pairs -- a matcher that ran its torch path -- are copied over)"""
+    def one(x):
+        if x.device != device or x.dtype != torch.int64:
+            x = x.to(device=device, dtype=torch.int64)
+        return x.reshape(-1) if x.is_contiguous() and x.dim() == 1 else x.reshape(-1).contiguous()
+    return [(one(q), one(t)) for q, t in pairs]
+
+
+def _pairs_fit(pairs, B):
+    return len(pairs) == B and B <= ops.PAIR_MAX_B and sum(int(q.shape[0]) for q, _ in pairs) <= ops.PAIR_MAX_K
+
+
+def pair_box_loss(pred_boxes, pred_iou, pairs, packed, count, mode, use_thing=True):
+    """loss_boxes of a criterion call on hipie_pair_box_loss_forward / _backward: pred_boxes (B,Q,4), pred_iou None | (B,Q) | (B,Q,1) logits (mode
+    0 only), pairs: per image (query idx, target idx), packed = pack_pair_targets(targets, device) (or a pack_match_targets packing), count: the normaliser the
+    criterion divides by (under `ota` the number of pairs), mode 0 = DetCriterion, 1 = MaskCriterion, use_thing: weight (mode 0) / keep (mode 1)
+    the pairs by the targets' is_thing -> (loss_bbox, loss_giou, loss_boxiou | None, status (1,) int32 on the device), or None: the criterion's
+    torch path runs.  The limits: fp32 operands whose last dimension is dense, B <= 64 images, 1 <= K <= 65536 pairs (K = 0 is the criterion's
+    own `src.sum() * 0.0`: no launch), targets packed for the same B.  No host wait and no host -> device copy."""
+    if pred_boxes.dim() != 3 or pred_boxes.shape[2] != 4 or pred_boxes.dtype != torch.float32 or pred_boxes.stride(2) != 1:
+        return None
+    B, Q = pred_boxes.shape[:2]
+    if pred_iou is not None:
+        if mode != 0 or pred_iou.dtype != torch.float32 or tuple(pred_iou.shape) not in ((B, Q), (B, Q, 1)):
+            return None
+        pred_iou = pred_iou.reshape(B, Q) if pred_iou.dim() == 2 else pred_iou[:, :, 0]
+    if not _pairs_fit(pairs, B) or sum(int(q.shape[0]) for q, _ in pairs) == 0 or packed.tgt_boxes.shape[0] != B:
+        return None
+    lb, lg, li, status = PairBoxLossFunction.apply(pred_boxes, pred_iou, _device_pairs(pairs, pred_boxes.device), packed.tgt_boxes,
+                                                   packed.is_thing if use_thing else None, float(count), int(mode))
+    return lb, lg, (li if pred_iou is not None else None), status
+
+
+@torch.no_grad()
+def positive_onehot(logits, pairs, packed):
+    """criterion._positive_onehot on hipie_positive_onehot: logits (B,Q,L) fp32, pairs as above, packed.pos_map (B,Tmax,L) uint8 -> onehot (B,Q,L)
+    of exact 0 / 1, or None: the criterion's loop runs (logits of another dtype, targets packed without maps or for another B or L, B > 64, more
+    than 65536 pairs).  The CALLER decides from the dtype of the targets' maps whether the packed map ((map != 0) as bytes) equals them."""
+    if logits.dim() != 3 or logits.dtype != torch.float32 or packed.pos_map is None:
+        return None
+    B, Q, L = logits.shape
+    if not _pairs_fit(pairs, B) or packed.pos_map.shape[0] != B or (packed.pos_map.shape[1] and packed.pos_map.shape[2] != L):
+        return None
+    if packed.pos_map.shape[1] == 0:                           # no image has a target: nothing to scatter (pack_match_targets then has no L)
+        return torch.zeros_like(logits)
+    return ops.positive_onehot(_device_pairs(pairs, logits.device), packed.pos_map, Q)

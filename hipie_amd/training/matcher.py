@@ -187,12 +187,15 @@ class HungarianMatcher(nn.Module):
         return self.ops.pack_match_targets(targets, device, masks)
 
     @staticmethod
-    def _status_error(words, label):
-        """the ValueError of the first non-zero status word of a call (ops.HUNGARIAN_STATUS), naming the image; None: all zero"""
-        from ..ops import HUNGARIAN_STATUS
+    def _status_error(words, label, what="hungarian_match", messages=None):
+        """the ValueError of the first non-zero status word of a call (ops.HUNGARIAN_STATUS, or the `messages` of another kind of call), naming
+        the image (the word, where a call has one for the batch); None: all zero"""
+        if messages is None:
+            from ..ops import HUNGARIAN_STATUS as messages
         for b, s in enumerate(words):
             if s:
-                return ValueError("hungarian_match: %s: image %d: %s" % (label, b, "; ".join(msg for bit, msg in HUNGARIAN_STATUS if s & bit)))
+                return ValueError("%s: %s: %s %d: %s" % (what, label, "image" if what == "hungarian_match" else "word", b,
+                                                         "; ".join(msg for bit, msg in messages if s & bit)))
         return None
 
     def check(self):
@@ -201,16 +204,17 @@ class HungarianMatcher(nn.Module):
 
     @staticmethod
     def check_all(matchers):
-        """check() for several matchers with ONE copy for all of them (TrainStep: its three matchers, one host read per step)"""
+        """check() for several matchers with ONE copy for all of them (TrainStep: its three matchers, one host read per step).  Anything with
+        a `pending` list takes part: the criteria keep the status words of their `pair_box_loss` calls as (status, label, what, messages)"""
         pending = [p for m in matchers for p in m.pending]
         for m in matchers:
             m.pending = []
         if not pending:
             return
-        words = torch.cat([s for s, _ in pending]).cpu().tolist()
+        words = torch.cat([p[0] for p in pending]).cpu().tolist()
         at = 0
-        for s, label in pending:
-            err = HungarianMatcher._status_error(words[at:at + s.numel()], label)
+        for s, *label in pending:
+            err = HungarianMatcher._status_error(words[at:at + s.numel()], *label)
             if err is not None:
                 raise err
             at += s.numel()

@@ -12,7 +12,8 @@ the token focal loss of the two criteria on hipie_point_mask_loss_* / hipie_toke
 importance point selection of the criteria and the mask costs of the matchers on hipie_uncertain_points / hipie_mask_match_cost; opt-in, HipBackendMatching: on top of those
 the SimOTA matching of the foreground queries on hipie_ota_cost / hipie_ota_assign; opt-in, HipBackendHungarian: on top of those the cost
 matrices of the one-to-one Hungarian matchers on hipie_hungarian_cost; opt-in, HipBackendAssign: on top of those the assignment itself on
-hipie_hungarian_assign, the pairs staying on the device).
+hipie_hungarian_assign, the pairs staying on the device; opt-in, HipBackendPairLosses: on top of those the box losses of the matched pairs and
+the positive one-hot of the label losses on hipie_pair_box_loss_* / hipie_positive_onehot).
 
 Functional style over a dict ``sd`` of LIVE parameters (model.named_parameters() + buffers, reference key names), so gradients land in the
 model's own parameters.  Every function cites the reference code it follows.  Training-mode differences from the inference path:
@@ -270,6 +271,35 @@ class HipBackendAssign(HipBackendHungarian):
         or None outside the kernels' limits"""
         from .functions import hungarian_match
         return hungarian_match(logits, boxes, packed, w, masks, coords, stuff_takes_mean, with_boxes, class_mode)
+
+
+class HipBackendPairLosses(HipBackendAssign):
+    """HipBackendAssign + what the criteria do with the matched pairs, on csrc/pair_loss.hip: loss_boxes of both criteria as one node that
+    reads the pairs where the matchers left them (functions.PairBoxLossFunction: two launches forward, one backward, the final scalars; no
+    gather, no `thing.sum() == 0` / degenerate-box read on the host) and the positive one-hot in front of every token focal loss as a fill and
+    one scatter (functions.positive_onehot).  The criteria keep the status words of their loss_boxes calls pending; TrainStep reads them with
+    the matchers' in the one copy at the end of loss_dict.
+    Opt-in: TrainStep's default stays HipBackend; HipBackendAssign and HipBackendAll do not include it."""
+
+    @staticmethod
+    def pack_pair_targets(targets, device):
+        """per-image target dicts -> functions.MatchTargets without masks and count vectors: no host -> device copy (the matcher's own
+        packing serves the two ops as well)"""
+        from .functions import pack_pair_targets
+        return pack_pair_targets(targets, device)
+
+    @staticmethod
+    def pair_box_loss(pred_boxes, pred_iou, pairs, packed, count, mode, use_thing=True):
+        """pred_boxes (B,Q,4), pred_iou None | (B,Q[,1]), pairs, packed targets -> (loss_bbox, loss_giou, loss_boxiou | None, status), or None
+        outside the kernels' limits"""
+        from .functions import pair_box_loss
+        return pair_box_loss(pred_boxes, pred_iou, pairs, packed, count, mode, use_thing)
+
+    @staticmethod
+    def positive_onehot(logits, pairs, packed):
+        """logits (B,Q,L), pairs, packed targets -> onehot (B,Q,L), or None outside the kernel's limits"""
+        from .functions import positive_onehot
+        return positive_onehot(logits, pairs, packed)
 
 
 # ------------------------------------------------------------------------------------------------ small helpers

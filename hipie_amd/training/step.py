@@ -57,6 +57,7 @@ class TrainStep:
         # (net.HipBackendHungarian): the matchers get the backend the same way
         match_ops = self.be if (getattr(self.be, "mask_match_costs", None) or getattr(self.be, "ota_match", None)
                                 or getattr(self.be, "hungarian_costs", None)) else None
+        # (net.HipBackendPairLosses: the criteria find `pair_box_loss` / `positive_onehot` on the same `ops` object themselves)
         # the opt-in assignment kernel (net.HipBackendAssign): the matchers' pairs stay on the device and the status words of their calls are
         # read once, at the end of loss_dict
         defer = getattr(self.be, "hungarian_match", None) is not None
@@ -286,8 +287,10 @@ class TrainStep:
         lang = {"hidden": lang["hidden"].float(), "masks": lang["masks"]}
         targets = [{k: (v.to(x.device) if torch.is_tensor(v) else v) for k, v in t.items()} for t in targets]
         raw, _ = self.coco_forward(x, pad, sizes, targets, lang, task)
-        HungarianMatcher.check_all(self.matchers)                                       # check() of the three matchers as one read: the deferred status
-                                                                                        # words of the assignment kernel; nothing pending without it
+        # check() of the three matchers as one read: the deferred status words of the assignment kernel; nothing pending without it.  The
+        # same copy carries the status words of the criteria's `pair_box_loss` calls (net.HipBackendPairLosses: a degenerate box in
+        # MaskCriterion.loss_boxes raises the ValueError of boxes.generalized_box_iou here)
+        HungarianMatcher.check_all(self.matchers + (self.criterion, self.md_criterion))
         out = {}
         for k, v in raw.items():
             if "_maskdino" in k:

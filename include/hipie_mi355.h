@@ -545,6 +545,49 @@ int hipie_hungarian_assign(const float* C, const int* cost_status, const int* n_
 int64_t hipie_hungarian_assign_ws_bytes(int64_t Q, int64_t sum_t);
 
 /*
+ * What the training criteria do with the matched (query, target) pairs of one call (csrc/pair_loss.hip; fp32 operands, a pair is evaluated
+ * in float64 and rounded once), forward and backward.
+ * Replaces: SetCriterion.loss_boxes (models/deformable_detr/deformable_detr.py:397-450, mode 0) and models/maskdino/criterion.py:240-284
+ *           (mode 1): the gathers of the matched boxes, box_cxcywh_to_xyxy, l1_loss, giou_loss / generalized_box_iou, the box-IoU BCE, the
+ *           thing mask and its re-weighting with their autograd mirrors, and the host wait of `thing.sum() == 0` / the degenerate-box assert;
+ *           the loop over the images in front of every loss_labelsVL that writes the matched rows of the positive maps into the one-hot.
+ *   The pairs: pair_q, pair_t are HOST arrays of B device addresses -- per image the int64 query and target indices of its pairs, as the
+ *     matchers return them --, pair_n the HOST array of their lengths.  They are placed in the kernel arguments: B <= 64, at most 65536 pairs;
+ *     nothing is copied to the device and nothing waits.  A pair with an index outside [0, Q) x [0, Tmax) is left out and sets status bit 2.
+ *   boxes (B, Q, 4) cxcywh by element strides (box_stride_b, box_stride_q; the 4 coordinates dense): a slice of the query axis needs no copy.
+ *   iou: NULL or the (B, Q) box-IoU logits by element strides.   tgt_boxes (B, Tmax, 4), is_thing (B, Tmax) bytes or NULL (every pair counts).
+ *   mode 0: w = is_thing != 0 (or 1), reweight = K / (sum w + 1e-6);  loss_bbox = reweight sum w |src - tgt|_1 / count;  loss_giou = reweight
+ *     sum w (1 - GIoU) / count with the intersection counted only where the boxes overlap and 1e-7 in both quotients (fvcore giou_loss);
+ *     loss_boxiou = reweight mean w BCE_with_logits(iou logit, IoU), the IoU target without gradient.  With no thing among the pairs the three
+ *     losses and every gradient are exactly 0.
+ *   mode 1: the pairs with is_thing == 0 are left out;  loss_bbox = sum |src - tgt|_1 / count;  loss_giou = sum (1 - GIoU) / count with every
+ *     extent clamped at 0 and 1e-7 in the hull quotient only (util/box_ops.py generalized_box_iou).  A box with x1 < x0 or y1 < y0 (or a NaN)
+ *     among the evaluated pairs sets status bit 1 -- the reference's assert; the outputs are still those of the formula.
+ *   Ties of max / min give half the gradient to each side, |x| has gradient 0 at 0, a clamp passes the gradient at exactly 0 (torch).
+ * hipie_pair_box_loss_forward:  out (8 floats, 8-byte aligned) = loss_bbox, loss_giou, loss_boxiou, 0 and two float64 factors for the
+ *     backward;  pair_grad (K, 9) the weighted per-pair gradients;  status (1) int32.  A workgroup per 256 pairs, float64 partial sums in `ws`
+ *     (hipie_pair_box_loss_ws_bytes(K), 8-byte aligned), added by one workgroup in a fixed order.  No atomics: bit-reproducible.  Two launches.
+ * hipie_pair_box_loss_backward: d_boxes (B, Q, 4) and d_iou (B, Q; NULL without iou), dense, are zero-filled here and every pair adds
+ *     g x factor x its stored gradient with a global fp32 atomic: duplicates of an (image, query) sum; with one target per (image, query)
+ *     every element receives one addition and the result is bit-reproducible.  g_bbox, g_giou, g_boxiou: DEVICE scalars.  One launch.
+ * hipie_positive_onehot: onehot (B, Q, L) fp32 is zero-filled, then onehot[b, q_i] = (pos_map[b, t_i] != 0) for every pair; pos_map
+ *     (B, Tmax, L) bytes.  One launch.
+ * Refused (-22): mode outside {0, 1}, iou with mode 1, count <= 0 or not finite, B > 64, more than 65536 pairs, a negative size or length,
+ *     pairs with Q == 0 or Tmax == 0, strides that do not describe the rows, null pointers, a workspace that is too small or misaligned.
+ *     No pairs: the forward returns 0 without a launch and writes nothing, the backward and the one-hot only zero-fill; null pointers allowed.
+ */
+int hipie_pair_box_loss_forward(const float* boxes, int64_t box_stride_b, int64_t box_stride_q, const float* iou, int64_t iou_stride_b,
+                                int64_t iou_stride_q, const int64_t* const* pair_q, const int64_t* const* pair_t, const int64_t* pair_n,
+                                const float* tgt_boxes, const uint8_t* is_thing, float* out, float* pair_grad, int* status, void* ws,
+                                int64_t ws_bytes, int B, int Q, int Tmax, int mode, double count, void* stream);
+int64_t hipie_pair_box_loss_ws_bytes(int64_t K);
+int hipie_pair_box_loss_backward(const int64_t* const* pair_q, const int64_t* pair_n, const float* out, const float* pair_grad,
+                                 const float* g_bbox, const float* g_giou, const float* g_boxiou, float* d_boxes, float* d_iou, int B, int Q,
+                                 void* stream);
+int hipie_positive_onehot(const int64_t* const* pair_q, const int64_t* const* pair_t, const int64_t* pair_n, const uint8_t* pos_map,
+                          float* onehot, int B, int Q, int Tmax, int L, void* stream);
+
+/*
  * The tail of a training iteration behind backward() as two passes over memory (csrc/optim_step.hip): the total gradient norm, and the clip
  * and the AdamW update of EVERY parameter tensor in one launch; fp32, nothing is read by the host, bit-reproducible from call to call.
  * Replaces: torch.nn.utils.clip_grad_norm_ inside FullModelGradientClippingOptimizer.step (projects/HIPIE/train_net.py:199-228, with

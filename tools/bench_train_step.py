@@ -3,7 +3,7 @@
 GPU (configs/training/vit_huge_32g.yaml:1 -- 32 GPUs x 2), the 80-class caption, 8 synthetic targets per image (6 things, 2 stuff), DN_NUMBER 100,
 12544 mask points, random-init weights.  Prints ms for the forward (loss dictionary), the backward, and the peak memory.
     python tools/bench_train_step.py [batch] [steps] [--hand-norms] [--fused-mlp] [--fused-windows] [--fused-losses] [--fused-criteria] [--fused-matching]
-                                                            [--fused-hungarian] [--fused-assign] [--packed-attention] [--packed-windows] [--fused-msda]
+                                                            [--fused-hungarian] [--fused-assign] [--fused-pair-losses] [--packed-attention] [--packed-windows] [--fused-msda]
 --hand-norms: net.HipBackendNorms (the ViT / encoder LayerNorms on hipie_add_layernorm / hipie_layernorm_backward) instead of HipBackend
 --fused-mlp:  net.HipBackendMlp (the ViT MLPs / encoder FFNs as one autograd node, the activation recomputed by hipie_act_backward); with
               --hand-norms: net.HipBackendNormsMlp
@@ -19,6 +19,8 @@ GPU (configs/training/vit_huge_32g.yaml:1 -- 32 GPUs x 2), the 80-class caption,
               device -> host copy per matcher call, the targets packed once per step / criterion call); composes with the other three
 --fused-assign: net.HipBackendAssign (--fused-hungarian + the one-to-one assignment itself on hipie_hungarian_assign: the pairs stay on the device,
               no host wait per matcher call, the status words of all calls read once per step); composes with the other three
+--fused-pair-losses: net.HipBackendPairLosses (--fused-assign + loss_boxes of both criteria and the positive one-hot of the label losses on
+              hipie_pair_box_loss_* / hipie_positive_onehot: no gather and no host wait per loss_boxes call); composes with the other three
 --packed-attention: net.HipBackendPackedAttention (the attention of the global ViT blocks as one autograd node, its operands packed and unpacked
               by hipie_attn_pack_*); composes with all of the above
 --packed-windows: net.HipBackendPackedWindows (--packed-attention + the same node over hipie_attn_train_win_* for the windowed blocks)
@@ -63,8 +65,10 @@ def targets_for(batch, n_things, n_stuff, size, L, dev, seed=0):
 
 def main():
     argv = [a for a in sys.argv[1:] if a not in ("--hand-norms", "--fused-mlp", "--fused-windows", "--fused-losses", "--fused-criteria", "--fused-matching",
-                                                   "--fused-hungarian", "--fused-assign", "--packed-attention", "--packed-windows", "--fused-msda")]
-    fused_assign = "--fused-assign" in sys.argv[1:]
+                                                   "--fused-hungarian", "--fused-assign", "--fused-pair-losses", "--packed-attention", "--packed-windows",
+                                                   "--fused-msda")]
+    fused_pairs = "--fused-pair-losses" in sys.argv[1:]
+    fused_assign = "--fused-assign" in sys.argv[1:] or fused_pairs
     fused_hungarian = "--fused-hungarian" in sys.argv[1:] or fused_assign
     fused_matching = "--fused-matching" in sys.argv[1:] or fused_hungarian
     fused_criteria = "--fused-criteria" in sys.argv[1:] and not fused_matching
@@ -108,8 +112,8 @@ def main():
         step.criterion.ops = step.md_criterion.ops = step.be
         step.matcher.ops = step.matcher_bg.ops = step.md_criterion.matcher.ops = step.be
     if fused_matching:                                       # the criteria, the matchers' mask costs and the SimOTA matching
-        # the second: + the Hungarian matchers' cost matrices; the third: + their assignment
-        top = net.HipBackendAssign if fused_assign else net.HipBackendHungarian if fused_hungarian else net.HipBackendMatching
+        # the second: + the Hungarian matchers' cost matrices; the third: + their assignment; the fourth: + the criteria's box losses and one-hot
+        top = net.HipBackendPairLosses if fused_pairs else net.HipBackendAssign if fused_assign else net.HipBackendHungarian if fused_hungarian else net.HipBackendMatching
         step.be = top if step.be is net.HipBackend else type(step.be.__name__ + top.__name__[10:], (step.be, top), {})
         step.criterion.ops = step.md_criterion.ops = step.be
         step.matcher.ops = step.matcher_bg.ops = step.md_criterion.matcher.ops = step.be
