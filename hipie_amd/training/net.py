@@ -3,17 +3,8 @@ state_dict layout as the reference, hipie_amd/hipie_img.py), written for autogra
 kernels have no backward.  What is hand-written HIP here is what has a backward kernel: multi-scale deformable attention
 (hipie_msda_forward / hipie_msda_backward), the mask contraction and the CondInst dynamic mask head (training/functions.py); the dense
 linears, LayerNorm / GroupNorm, the softmax attentions and the convolutions run on the library kernels PyTorch-ROCm dispatches to, with
-torch.autograd providing their backward (opt-in, HipBackendNorms: the LayerNorms of the ViT blocks and of the encoder layers on
-hipie_add_layernorm / hipie_layernorm_backward; opt-in, HipBackendMlp: their MLPs / FFNs as one node with the activation on
-hipie_act_forward / hipie_act_backward; opt-in, HipBackendWindows: the attention of the windowed ViT blocks on
-hipie_attn_train_win_forward / _backward; opt-in, HipBackendPackedAttention / HipBackendPackedWindows: the attention of a ViT block between its
-two linears as one node, its operands packed and unpacked by hipie_attn_pack_*; opt-in, HipBackendLosses: the point-sampled mask losses and
-the token focal loss of the two criteria on hipie_point_mask_loss_* / hipie_token_focal_*; opt-in, HipBackendCriteria: on top of those the
-importance point selection of the criteria and the mask costs of the matchers on hipie_uncertain_points / hipie_mask_match_cost; opt-in, HipBackendMatching: on top of those
-the SimOTA matching of the foreground queries on hipie_ota_cost / hipie_ota_assign; opt-in, HipBackendHungarian: on top of those the cost
-matrices of the one-to-one Hungarian matchers on hipie_hungarian_cost; opt-in, HipBackendAssign: on top of those the assignment itself on
-hipie_hungarian_assign, the pairs staying on the device; opt-in, HipBackendPairLosses: on top of those the box losses of the matched pairs and
-the positive one-hot of the label losses on hipie_pair_box_loss_* / hipie_positive_onehot).
+torch.autograd providing their backward.  More of the step runs on hand-written kernels opt-in, one HipBackend* class per kernel group:
+GROUPS below names them, backend(*names) composes any of them into the class TrainStep takes.
 
 Functional style over a dict ``sd`` of LIVE parameters (model.named_parameters() + buffers, reference key names), so gradients land in the
 model's own parameters.  Every function cites the reference code it follows.  Training-mode differences from the inference path:
@@ -300,6 +291,31 @@ class HipBackendPairLosses(HipBackendAssign):
         """logits (B,Q,L), pairs, packed targets -> onehot (B,Q,L), or None outside the kernel's limits"""
         from .functions import positive_onehot
         return positive_onehot(logits, pairs, packed)
+
+
+# the opt-in kernel groups by name; a composed class lists its bases in this order
+GROUPS = {"norms": HipBackendNorms, "mlp": HipBackendMlp, "windows": HipBackendWindows, "packed_attention": HipBackendPackedAttention,
+          "packed_windows": HipBackendPackedWindows, "deformable": HipBackendDeformable, "losses": HipBackendLosses, "criteria": HipBackendCriteria,
+          "matching": HipBackendMatching, "hungarian": HipBackendHungarian, "assign": HipBackendAssign, "pair_losses": HipBackendPairLosses}
+_COMPOSED = {("norms", "mlp"): HipBackendNormsMlp, ("norms", "mlp", "windows"): HipBackendAll}
+
+
+def backend(*names):
+    """the backend class with the named opt-in groups (keys of GROUPS); none: HipBackend.  A group another named group inherits from is
+    implied by it and dropped ("losses" beside "matching", "windows" and "packed_attention" beside "packed_windows"): what is left is
+    unrelated by inheritance, so its classes compose as bases in any order, and no op is defined by two of them (tests/
+    test_backend_compose_cpu.py, every subset).  One group left: its own class; several: one class per set of groups, built once."""
+    unknown = sorted(set(names) - set(GROUPS))
+    if unknown:
+        raise ValueError("unknown backend group(s) %s; known: %s" % (", ".join(map(repr, unknown)), ", ".join(GROUPS)))
+    named = [GROUPS[n] for n in names]
+    left = tuple(n for n, c in GROUPS.items() if c in named and not any(o is not c and issubclass(o, c) for o in named))
+    if len(left) < 2:
+        return GROUPS[left[0]] if left else HipBackend
+    if left not in _COMPOSED:
+        bases = tuple(GROUPS[n] for n in left)
+        _COMPOSED[left] = type("HipBackend" + "".join(c.__name__[len("HipBackend"):] for c in bases), bases, {"__doc__": "the opt-in groups " + ", ".join(left)})
+    return _COMPOSED[left]
 
 
 # ------------------------------------------------------------------------------------------------ small helpers

@@ -306,7 +306,8 @@ def test_vit_backbone_under_the_new_backends(case, nodes, monkeypatch):
     applied = []
     real = functions.VitAttentionFunction.apply
     monkeypatch.setattr(functions.VitAttentionFunction, "apply", lambda *a: applied.append(a[4:6]) or real(*a))
-    for be, n in zip((net.HipBackendPackedAttention, net.HipBackendPackedWindows), nodes):
+    composed = net.backend("norms", "mlp", "packed_windows")      # the node beside two unrelated opt-in groups: the same rule, HipBackendPackedWindows' count
+    for be, n in zip((net.HipBackendPackedAttention, net.HipBackendPackedWindows, composed), nodes + nodes[1:]):
         applied.clear()
         got = run(DEV, torch.float32, be)
         assert len(applied) == n, applied

@@ -303,7 +303,7 @@ def test_train_step_with_the_assignment_kernel_matches_the_hungarian_backend(mon
     which moves `loss_mask` by one ulp (72.2514572 / 72.2514648) whichever backend runs; with it ten alternated runs agree in every stage
     and every entry (docs/measurements.md)."""
     from hipie_amd.training import net
-    from test_gpu_point_loss import _train_step_case
+    from _train_step_cases import train_step_case as _train_step_case
     seen = []
     for name in ("forward", "forward_boxes_only"):
         def recorded(self, *a, _f=getattr(HungarianMatcher, name), **k):

@@ -249,7 +249,7 @@ def test_train_step_with_the_hungarian_kernel_matches_the_matching_backend(monke
     recorded reference too, and the same matched pairs in every Hungarian matcher call (every level of the background queries, the encoder
     proposals, every MaskDINO output)."""
     from hipie_amd.training import net
-    from test_gpu_point_loss import _train_step_case
+    from _train_step_cases import train_step_case as _train_step_case
     seen = []
     for name in ("forward", "forward_boxes_only"):
         def recorded(self, *a, _f=getattr(HungarianMatcher, name), **k):

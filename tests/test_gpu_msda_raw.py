@@ -5,7 +5,6 @@ Yardstick: torch.autograd.grad in float64 through the plain composition over ora
 gradients with respect to value, offsets, logits and ref, measured with util.rel_err.  Bound: 2e-5 for each -- the project's bound for
 grad_sampling_loc / grad_attn_weight; grad_value gets it too (not the 3e-6 of the loc-fed kernel) because the location is now computed in
 fp32 from ref and offsets.  The same composition in fp32 on the CPU stays below 1e-5 on these inputs (test_msda_raw_cpu.py)."""
-import json
 
 import pytest
 import torch
@@ -203,9 +202,9 @@ def test_train_step_with_the_deformable_node_matches_the_reference(monkeypatch):
     """test_training.test_train_step_losses_and_gradients_match_the_reference with backend=net.HipBackendDeformable: the same fixture, the same
     assertions and bounds for cuda (loss entries 2e-3, the three gradient classes 5e-3 / 5e-3 / 8e-2, the same random draws), and every
     msda_module call of the step answered by the node, at both reference-point widths"""
-    from test_gpu_point_loss import _train_step_case
+    from _train_step_cases import check_step_against_golden, train_step_case
     from hipie_amd.training import functions, net
-    z, meta, model, step, batch, targets = _train_step_case("cuda", net.HipBackendDeformable)
+    z, meta, model, step, batch, targets = train_step_case("cuda", net.HipBackendDeformable)
     modules, answered = [], []
 
     def counted_module(*a, _f=net.msda_module, **k):
@@ -221,36 +220,7 @@ def test_train_step_with_the_deformable_node_matches_the_reference(monkeypatch):
     losses = step.loss_dict(batch, targets)
     total = sum(losses.values())
     total.backward()
-    assert step.draws.calls == int(z["n_rand"])                               # the same random draws, in the same order
     widths = sorted(set(w for w, _ in answered))
     print("MSDA_RAW step: %d msda_module calls, %d answered by the node, reference-point widths %s" % (len(modules), sum(ok for _, ok in answered), widths))
     assert len(modules) > 0 and len(answered) == len(modules) and all(ok for _, ok in answered) and widths == [2, 4]
-    want = {k[5:]: float(z[k]) * float(z["weight/" + k[5:]]) for k in z.files if k.startswith("loss/")}
-    assert sorted(losses) == sorted(want)
-    tol = 2e-3
-    worst_l = max((abs(float(losses[k]) - want[k]) / max(1.0, abs(want[k])), k) for k in want)
-    assert worst_l[0] < tol, worst_l
-    assert abs(float(total) - float(z["total"])) < tol * float(z["total"])
-    steps = json.loads(bytes(z["grad_steps"]).decode())
-    params = dict(model.named_parameters(remove_duplicate=False))
-    errs = []
-    for k in z.files:
-        if not k.startswith("grad/"):
-            continue
-        name = k[5:]
-        p = params[name]
-        g = (torch.zeros_like(p) if p.grad is None else p.grad).reshape(-1).cpu()
-        if name in steps:
-            g = g[::steps[name]]
-        w = torch.from_numpy(z[k])
-        errs.append((float((g - w).abs().max() / (w.abs().max() + 1e-12)), name))
-    errs.sort(reverse=True)
-    border = [e for e in errs if e[1].startswith("detr.mask_head.")]
-    offsets = [e for e in errs if "sampling_offsets" in e[1]]
-    rest = [e for e in errs if not e[1].startswith("detr.mask_head.") and "sampling_offsets" not in e[1]]
-    print("MSDA_RAW step: total %.5f (reference %.5f), worst loss entry %.1e (%s), worst of %d parameter gradients %.1e (%s); offsets %.1e; mask-head "
-          "convolutions %.1e (%s)" % (float(total), float(z["total"]), worst_l[0], worst_l[1], len(rest), rest[0][0], rest[0][1], offsets[0][0],
-                                      border[0][0], border[0][1]))
-    assert offsets and offsets[0][0] < 5e-3, offsets[:5]
-    assert len(errs) > 400 and rest[0][0] < 5e-3, rest[:5]
-    assert border[0][0] < 8e-2, border[:5]
+    check_step_against_golden(z, model, step, losses, total, "cuda", "MSDA_RAW step")

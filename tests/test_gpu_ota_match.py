@@ -6,7 +6,6 @@ masks first; every case prints its figures (lines starting with OTA) before it a
 a copy of the kernel's own cost and iou, no tolerance -- pairs, best, repair rounds and the final cost bit for bit.  Each case runs the two
 kernels once (`_run`) and the tests share what they returned."""
 import functools
-import json
 
 import pytest
 import torch
@@ -206,43 +205,14 @@ def test_train_step_with_the_matching_kernels_matches_the_reference(monkeypatch)
     same assertions and bounds (loss entries 2e-3, the three gradient classes 5e-3 / 5e-3 / 8e-2, the same random draws); the SimOTA matching
     of every decoder level goes through the kernels."""
     from hipie_amd.training import net
-    from test_gpu_point_loss import _train_step_case
-    z, meta, model, step, batch, targets = _train_step_case("cuda", net.HipBackendMatching)
+    from _train_step_cases import check_step_against_golden, train_step_case
+    z, meta, model, step, batch, targets = train_step_case("cuda", net.HipBackendMatching)
     assert step.matcher.ops is net.HipBackendMatching and step.criterion.ops is net.HipBackendMatching
     answers = _spy(monkeypatch)
     with torch.enable_grad():
         losses = step.loss_dict(batch, targets)
         total = sum(losses.values())
         total.backward()
-    assert step.draws.calls == int(z["n_rand"])                               # the same random draws, in the same order
     assert len(answers) == step.cfg["dec_layers"] and all(a is not None for a in answers)
     print("OTA step: %d matching calls, pairs per call %s" % (len(answers), [sum(len(p[0]) for p in a[0]) for a in answers]))
-    want = {k[5:]: float(z[k]) * float(z["weight/" + k[5:]]) for k in z.files if k.startswith("loss/")}
-    assert sorted(losses) == sorted(want)
-    tol = 2e-3
-    worst_l = max((abs(float(losses[k]) - want[k]) / max(1.0, abs(want[k])), k) for k in want)
-    assert worst_l[0] < tol, worst_l
-    assert abs(float(total) - float(z["total"])) < tol * float(z["total"])
-    steps = json.loads(bytes(z["grad_steps"]).decode())
-    params = dict(model.named_parameters(remove_duplicate=False))
-    errs = []
-    for k in z.files:
-        if not k.startswith("grad/"):
-            continue
-        name = k[5:]
-        p = params[name]
-        g = (torch.zeros_like(p) if p.grad is None else p.grad).reshape(-1).cpu()
-        if name in steps:
-            g = g[::steps[name]]
-        w = torch.from_numpy(z[k])
-        errs.append((float((g - w).abs().max() / (w.abs().max() + 1e-12)), name))
-    errs.sort(reverse=True)
-    border = [e for e in errs if e[1].startswith("detr.mask_head.")]
-    offsets = [e for e in errs if "sampling_offsets" in e[1]]
-    rest = [e for e in errs if not e[1].startswith("detr.mask_head.") and "sampling_offsets" not in e[1]]
-    print("OTA step: total %.5f (reference %.5f), worst loss entry %.1e (%s), worst of %d parameter gradients %.1e (%s); offsets %.1e; mask-head "
-          "convolutions %.1e (%s)" % (float(total), float(z["total"]), worst_l[0], worst_l[1], len(rest), rest[0][0], rest[0][1], offsets[0][0],
-                                      border[0][0], border[0][1]))
-    assert offsets and offsets[0][0] < 5e-3, offsets[:5]
-    assert len(errs) > 400 and rest[0][0] < 5e-3, rest[:5]
-    assert border[0][0] < 8e-2, border[:5]
+    check_step_against_golden(z, model, step, losses, total, "cuda", "OTA step")

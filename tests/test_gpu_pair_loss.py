@@ -273,7 +273,7 @@ def test_train_step_with_the_pair_kernels_matches_the_assign_backend(monkeypatch
     entries against today's formula evaluated in float64 on the CPU on the arguments of every loss_boxes call of the parent run -- the new
     entry's error within max(1e-6, 4 x the parent entry's error); and the host waits of loss_dict."""
     from hipie_amd.training import net
-    from test_gpu_point_loss import _train_step_case
+    from _train_step_cases import train_step_case as _train_step_case
     seen = []
     for name in ("forward", "forward_boxes_only", "forward_ota"):
         def recorded(self, *a, _f=getattr(HungarianMatcher, name), _n=name, **k):

@@ -5,15 +5,11 @@ step.
 Reference, metric and bound: tests/_loss_cases.py -- today's criterion.py / matcher.point_sample formulas on the CPU in float64 (reference)
 and float32 (e_lib); max|got - ref64| / max|ref64| per output tensor against max(1e-6, 4 x e_lib).  Every case prints its figures (lines
 starting with LOSS) before it asserts."""
-import json
-import os
-import sys
-
-import numpy as np
 import pytest
 import torch
 
 from _loss_cases import (POINT_NAMES, _special_points, bound_of, check, point_case, point_reference, point_yardsticks, token_case, token_reference)
+from _train_step_cases import check_step_against_golden, train_step_case
 
 
 @pytest.fixture(autouse=True)
@@ -25,7 +21,6 @@ def _grad_enabled():
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 MODES = [pytest.param(0, -1.0, id="bce"), pytest.param(1, 0.25, id="focal"), pytest.param(1, -1.0, id="focal-no-alpha")]
 
 
@@ -212,32 +207,6 @@ def test_token_focal_function_matches_the_criterion_formula():
 
 
 # ------------------------------------------------------------------------------------------------ the step
-def _train_step_case(dev, backend):
-    """the recipe of test_training._train_step_case with the backend under test"""
-    sys.path.insert(0, GOLD)
-    import _synth
-    from hipie_amd.config import HipieConfig, Precision
-    from hipie_amd.hipie_img import HIPIE_IMG
-    from hipie_amd.training.step import TrainStep
-    z = np.load(os.path.join(GOLD, "train_step_tiny.npz"))
-    meta = json.loads(bytes(z["cfg_json"]).decode())
-    model = HIPIE_IMG(HipieConfig.from_dict(meta["cfg"]), Precision.parity(), device=dev)
-    model.load_state_dict(_synth.synth_full_state_dict({k: tuple(v) for k, v in meta["manifest"].items()}), strict=True)
-    model.finalize()
-    sizes = [tuple(s) for s in meta["sizes"]]
-    imgs = _synth.synth_images(sizes, seed=73)
-    ids, mask, _ = _synth.synth_token_ids(2, meta["n_classes"], meta["max_len"], seed=74)
-    targets = []
-    for i in range(len(sizes)):
-        t = {k: torch.from_numpy(z["t%d_%s" % (i, k)]) for k in ("labels", "boxes", "positive_map", "is_thing", "masks", "image_size")}
-        t["masks"] = t["masks"].float()
-        targets.append(t)
-    step = TrainStep(model, backend=backend, draws=_synth.HashDraws(), dn_number=meta["dn_number"], num_points=meta["num_points"],
-                     md_num_points=meta["num_points"], fusion_dropout=0.0)
-    batch = [{"image": im, "input_ids": ids[i], "attention_mask": mask[i]} for i, im in enumerate(imgs)]
-    return z, meta, model, step, batch, targets
-
-
 def _spy_on_the_criteria(monkeypatch, step):
     """counts, per loss_masks / loss_labels call of the two criteria that has matched instances, how often the Function under it was applied"""
     from hipie_amd.training import functions
@@ -264,43 +233,13 @@ def test_train_step_with_the_loss_kernels_matches_the_reference(monkeypatch):
     """test_training.test_train_step_losses_and_gradients_match_the_reference with backend=net.HipBackendLosses: the same fixture, the same
     assertions and bounds (loss entries 2e-3, the three gradient classes 5e-3 / 5e-3 / 8e-2, the same random draws)."""
     from hipie_amd.training import net
-    z, meta, model, step, batch, targets = _train_step_case("cuda", net.HipBackendLosses)
+    z, meta, model, step, batch, targets = train_step_case("cuda", net.HipBackendLosses)
     assert step.criterion.ops is net.HipBackendLosses and step.md_criterion.ops is net.HipBackendLosses
     seen = _spy_on_the_criteria(monkeypatch, step)
     with torch.enable_grad():
         losses = step.loss_dict(batch, targets)
         total = sum(losses.values())
         total.backward()
-    assert step.draws.calls == int(z["n_rand"])                               # the same random draws, in the same order
     print("LOSS step: %d mask-loss calls and %d label-loss calls with matched instances" % (len(seen["point"]), len(seen["token"])))
     assert len(seen["point"]) >= 4 and len(seen["token"]) >= 4 and set(seen["point"]) == {1} and set(seen["token"]) == {1}
-    want = {k[5:]: float(z[k]) * float(z["weight/" + k[5:]]) for k in z.files if k.startswith("loss/")}
-    assert sorted(losses) == sorted(want)
-    tol = 2e-3
-    worst_l = max((abs(float(losses[k]) - want[k]) / max(1.0, abs(want[k])), k) for k in want)
-    assert worst_l[0] < tol, worst_l
-    assert abs(float(total) - float(z["total"])) < tol * float(z["total"])
-    steps = json.loads(bytes(z["grad_steps"]).decode())
-    params = dict(model.named_parameters(remove_duplicate=False))
-    errs = []
-    for k in z.files:
-        if not k.startswith("grad/"):
-            continue
-        name = k[5:]
-        p = params[name]
-        g = (torch.zeros_like(p) if p.grad is None else p.grad).reshape(-1).cpu()
-        if name in steps:
-            g = g[::steps[name]]
-        w = torch.from_numpy(z[k])
-        errs.append((float((g - w).abs().max() / (w.abs().max() + 1e-12)), name))
-    errs.sort(reverse=True)
-    # the three gradient classes of the test this one follows: the mask-head convolutions (padded tokens), the sampling offsets, the rest
-    border = [e for e in errs if e[1].startswith("detr.mask_head.")]
-    offsets = [e for e in errs if "sampling_offsets" in e[1]]
-    rest = [e for e in errs if not e[1].startswith("detr.mask_head.") and "sampling_offsets" not in e[1]]
-    print("LOSS step: total %.5f (reference %.5f), worst loss entry %.1e (%s), worst of %d parameter gradients %.1e (%s); offsets %.1e; mask-head "
-          "convolutions %.1e (%s)" % (float(total), float(z["total"]), worst_l[0], worst_l[1], len(rest), rest[0][0], rest[0][1], offsets[0][0],
-                                      border[0][0], border[0][1]))
-    assert offsets and offsets[0][0] < 5e-3, offsets[:5]
-    assert len(errs) > 400 and rest[0][0] < 5e-3, rest[:5]
-    assert border[0][0] < 8e-2, border[:5]
+    check_step_against_golden(z, model, step, losses, total, "cuda", "LOSS step")

@@ -2,30 +2,12 @@
 """forward + backward time of ONE TRAINING STEP (hipie_amd/training/step.py) at the reference's training batch: ViT-H, 1024 x 1024, 2 images per
 GPU (configs/training/vit_huge_32g.yaml:1 -- 32 GPUs x 2), the 80-class caption, 8 synthetic targets per image (6 things, 2 stuff), DN_NUMBER 100,
 12544 mask points, random-init weights.  Prints ms for the forward (loss dictionary), the backward, and the peak memory.
-    python tools/bench_train_step.py [batch] [steps] [--hand-norms] [--fused-mlp] [--fused-windows] [--fused-losses] [--fused-criteria] [--fused-matching]
-                                                            [--fused-hungarian] [--fused-assign] [--fused-pair-losses] [--packed-attention] [--packed-windows] [--fused-msda]
---hand-norms: net.HipBackendNorms (the ViT / encoder LayerNorms on hipie_add_layernorm / hipie_layernorm_backward) instead of HipBackend
---fused-mlp:  net.HipBackendMlp (the ViT MLPs / encoder FFNs as one autograd node, the activation recomputed by hipie_act_backward); with
-              --hand-norms: net.HipBackendNormsMlp
---fused-windows: net.HipBackendWindows (the attention of the windowed ViT blocks on hipie_attn_train_win_*); composes with the other two
-              (all three: net.HipBackendAll)
---fused-losses: net.HipBackendLosses (the point-sampled mask losses and the token focal loss of both criteria on hipie_point_mask_loss_* /
-              hipie_token_focal_*); composes with the other three
---fused-criteria: net.HipBackendCriteria (--fused-losses + the importance point selection of the criteria and the mask costs of the matchers on
-              hipie_uncertain_points / hipie_mask_match_cost); composes with the other three
---fused-matching: net.HipBackendMatching (--fused-criteria + the SimOTA matching of the foreground queries on hipie_ota_cost / hipie_ota_assign,
-              the targets packed once per step); composes with the other three
---fused-hungarian: net.HipBackendHungarian (--fused-matching + the cost matrices of the one-to-one Hungarian matchers on hipie_hungarian_cost, one
-              device -> host copy per matcher call, the targets packed once per step / criterion call); composes with the other three
---fused-assign: net.HipBackendAssign (--fused-hungarian + the one-to-one assignment itself on hipie_hungarian_assign: the pairs stay on the device,
-              no host wait per matcher call, the status words of all calls read once per step); composes with the other three
---fused-pair-losses: net.HipBackendPairLosses (--fused-assign + loss_boxes of both criteria and the positive one-hot of the label losses on
-              hipie_pair_box_loss_* / hipie_positive_onehot: no gather and no host wait per loss_boxes call); composes with the other three
---packed-attention: net.HipBackendPackedAttention (the attention of the global ViT blocks as one autograd node, its operands packed and unpacked
-              by hipie_attn_pack_*); composes with all of the above
---packed-windows: net.HipBackendPackedWindows (--packed-attention + the same node over hipie_attn_train_win_* for the windowed blocks)
---fused-msda: net.HipBackendDeformable (every MSDeformAttn module's locations, softmax and sampling as one autograd node from the raw projections:
-              hipie_msda_fused_forward / hipie_msda_raw_backward); composes with all of the above
+    python tools/bench_train_step.py [batch] [steps] [--hand-norms] [--fused-mlp] [--fused-windows] [--packed-attention] [--packed-windows] [--fused-msda]
+                                                            [--fused-losses] [--fused-criteria] [--fused-matching] [--fused-hungarian] [--fused-assign] [--fused-pair-losses]
+Each flag names one opt-in kernel group of hipie_amd/training/net.py (FLAGS below; the classes' docstrings say what each puts on which kernels);
+the step runs on net.backend(*groups), no flag: net.HipBackend.  Any set of flags composes.  A flag whose group another flag's group builds on
+adds nothing: --packed-windows includes --packed-attention and --fused-windows, and each of --fused-losses < --fused-criteria < --fused-matching <
+--fused-hungarian < --fused-assign < --fused-pair-losses includes the ones before it.
 env: LIB_LINEAR=1 (library fp32 linears), PHASES=1 (synchronised forward phases), TORCH_PROF=1 (top kernels), COUNTS=1 (device launches and host
 waits of one step), HOSTPROF=1 (cProfile of a forward)"""
 import os
@@ -63,17 +45,26 @@ def targets_for(batch, n_things, n_stuff, size, L, dev, seed=0):
     return out
 
 
+# flag -> group of net.GROUPS
+FLAGS = {"--hand-norms": "norms", "--fused-mlp": "mlp", "--fused-windows": "windows", "--packed-attention": "packed_attention",
+         "--packed-windows": "packed_windows", "--fused-msda": "deformable", "--fused-losses": "losses", "--fused-criteria": "criteria",
+         "--fused-matching": "matching", "--fused-hungarian": "hungarian", "--fused-assign": "assign", "--fused-pair-losses": "pair_losses"}
+
+
+def backend_names(argv):
+    """the command line -> (the groups its flags name, for net.backend; what is left: [batch] [steps])"""
+    return [FLAGS[a] for a in argv if a in FLAGS], [a for a in argv if a not in FLAGS]
+
+
 def main():
-    argv = [a for a in sys.argv[1:] if a not in ("--hand-norms", "--fused-mlp", "--fused-windows", "--fused-losses", "--fused-criteria", "--fused-matching",
-                                                   "--fused-hungarian", "--fused-assign", "--fused-pair-losses", "--packed-attention", "--packed-windows",
-                                                   "--fused-msda")]
-    fused_pairs = "--fused-pair-losses" in sys.argv[1:]
-    fused_assign = "--fused-assign" in sys.argv[1:] or fused_pairs
-    fused_hungarian = "--fused-hungarian" in sys.argv[1:] or fused_assign
-    fused_matching = "--fused-matching" in sys.argv[1:] or fused_hungarian
-    fused_criteria = "--fused-criteria" in sys.argv[1:] and not fused_matching
-    fused_losses = "--fused-losses" in sys.argv[1:] and not fused_criteria and not fused_matching
-    hand_norms, fused_mlp, fused_windows = "--hand-norms" in sys.argv[1:], "--fused-mlp" in sys.argv[1:], "--fused-windows" in sys.argv[1:]
+    from hipie_amd.training import net
+    names, argv = backend_names(sys.argv[1:])
+    be = net.backend(*names)
+    if os.environ.get("LIB_LINEAR") == "1":                  # A/B: the big linears on the library instead of the split GEMM Function
+
+        class LibBackend(be):
+            linear = None
+        be = LibBackend
     B = int(argv[0]) if len(argv) > 0 else 2
     steps = int(argv[1]) if len(argv) > 1 else 3
     dev = torch.device("cuda", 0)
@@ -87,43 +78,7 @@ def main():
     size, L = 1024, 194
     batch = bench.synth_batch(cfg, B, size, 80, L, dev)
     targets = targets_for(B, 6, 2, size, L, dev)
-    step = TrainStep(model)
-    from hipie_amd.training import net
-    if hand_norms or fused_mlp:
-        step.be = net.HipBackendNormsMlp if hand_norms and fused_mlp else net.HipBackendNorms if hand_norms else net.HipBackendMlp
-    if fused_windows:
-        if hand_norms and fused_mlp:
-            step.be = net.HipBackendAll
-        elif step.be is net.HipBackend:
-            step.be = net.HipBackendWindows
-        else:                                                    # one of the other two groups + the windows
-            step.be = type(step.be.__name__ + "Windows", (step.be, net.HipBackendWindows), {})
-    if "--packed-attention" in sys.argv[1:] or "--packed-windows" in sys.argv[1:]:
-        top = net.HipBackendPackedWindows if "--packed-windows" in sys.argv[1:] else net.HipBackendPackedAttention
-        step.be = top if step.be is net.HipBackend else type(step.be.__name__ + top.__name__[10:], (top, step.be), {})
-    if "--fused-msda" in sys.argv[1:]:
-        top = net.HipBackendDeformable
-        step.be = top if step.be is net.HipBackend else type(step.be.__name__ + top.__name__[10:], (top, step.be), {})
-    if fused_losses:                                         # the criteria were built with the default backend: hand them the new one
-        step.be = net.HipBackendLosses if step.be is net.HipBackend else type(step.be.__name__ + "Losses", (step.be, net.HipBackendLosses), {})
-        step.criterion.ops = step.md_criterion.ops = step.be
-    if fused_criteria:                                       # the criteria AND the matchers
-        step.be = net.HipBackendCriteria if step.be is net.HipBackend else type(step.be.__name__ + "Criteria", (step.be, net.HipBackendCriteria), {})
-        step.criterion.ops = step.md_criterion.ops = step.be
-        step.matcher.ops = step.matcher_bg.ops = step.md_criterion.matcher.ops = step.be
-    if fused_matching:                                       # the criteria, the matchers' mask costs and the SimOTA matching
-        # the second: + the Hungarian matchers' cost matrices; the third: + their assignment; the fourth: + the criteria's box losses and one-hot
-        top = net.HipBackendPairLosses if fused_pairs else net.HipBackendAssign if fused_assign else net.HipBackendHungarian if fused_hungarian else net.HipBackendMatching
-        step.be = top if step.be is net.HipBackend else type(step.be.__name__ + top.__name__[10:], (step.be, top), {})
-        step.criterion.ops = step.md_criterion.ops = step.be
-        step.matcher.ops = step.matcher_bg.ops = step.md_criterion.matcher.ops = step.be
-        for m in step.matchers:                              # as TrainStep builds them with such a backend: one status read per step
-            m.defer_status = fused_assign
-    if os.environ.get("LIB_LINEAR") == "1":                  # A/B: the big linears on the library instead of the split GEMM Function
-
-        class LibBackend(step.be):
-            linear = None
-        step.be = LibBackend
+    step = TrainStep(model, backend=be)                      # the criteria and the matchers get the backend from TrainStep
     phases = {}
     if os.environ.get("PHASES") == "1":                      # synchronised wall time of the forward's phases
         def wrap(mod, name):
