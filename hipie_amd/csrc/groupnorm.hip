@@ -9,29 +9,13 @@
 // The sums are SHIFTED: every value has K = (first value of its group, pre-bias included) subtracted before it is accumulated --
 // var = E[(a-K)^2] - (E[a-K])^2 is then free of the cancellation that E[a^2] - mean^2 suffers when |mean| >> std (real
 // convolution biases folded in as pre-bias), at the cost of one extra scalar load per block.
+// For the training step (hipie_group_norm_train_forward): the same two NCHW launches, then a finisher that writes the (mean, rstd) the
+// apply pass used per (image, group) for groupnorm_bwd.hip.
 #include "common.h"
+#include "groupnorm.h"
 #include "wave.h"
 
 namespace hipie {
-
-constexpr int GN_CPG = 8;          // channels per group
-constexpr int GN_MAXK = 512;       // partials per (image, group)
-
-template <typename T> struct V8 {
-  static __device__ __forceinline__ void ld(const T* p, float (&v)[8]) {
-    typedef T t8 __attribute__((ext_vector_type(8)));
-    const t8 r = *reinterpret_cast<const t8*>(p);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (float)r[i];
-  }
-  static __device__ __forceinline__ void st(T* p, const float (&v)[8]) {
-    typedef T t8 __attribute__((ext_vector_type(8)));
-    t8 r;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r[i] = (T)v[i];
-    *reinterpret_cast<t8*>(p) = r;
-  }
-};
 
 // ---- channels-last: x (B, HW, C), C = 8 G.  thread -> (group = t % G, pixel lane = t / G) ----
 template <typename T>
@@ -223,6 +207,26 @@ __global__ __launch_bounds__(256) void gn_apply_nchw_kernel(const T* __restrict_
   }
 }
 
+// NCHW, the training forward: stat (B, G, 2) = the (mean, rstd) of every (image, group).  One wave per (image, group) runs the statements
+// of wave 0 of gn_apply_nchw_kernel on the same partials -- the same additions in the same order, so the bits the apply pass normalised with.
+template <typename T>
+__global__ __launch_bounds__(64) void gn_stat_nchw_kernel(const T* __restrict__ x, const float* __restrict__ part, float* __restrict__ stat_out,
+                                                          int HW, int C, int nchunk, float eps) {
+  const int G = C / GN_CPG, g = blockIdx.x % G, b = blockIdx.x / G, K = nchunk * GN_CPG;
+  const float* pp = part + ((long)b * G + g) * K * 2;
+  float s = 0.f, ss = 0.f;
+  for (int k = threadIdx.x; k < K; k += 64) { s += pp[2 * k]; ss += pp[2 * k + 1]; }
+  s = wave_sum(s);
+  ss = wave_sum(ss);
+  if (threadIdx.x == 0) {
+    const float K0 = (float)x[((long)b * C + g * GN_CPG) * HW];
+    float mean, rstd;
+    gn_mean_rstd(s, ss, (float)HW * GN_CPG, K0, eps, mean, rstd);
+    stat_out[(long)blockIdx.x * 2] = mean;
+    stat_out[(long)blockIdx.x * 2 + 1] = rstd;
+  }
+}
+
 template <typename T, typename OutT>
 static int launch_gn(const void* x, const float* prebias, const float* gamma, const float* beta, void* out, float* part, int B,
                      int C, int HW, int nhwc, float eps, int relu, hipStream_t st) {
@@ -245,10 +249,8 @@ static int launch_gn(const void* x, const float* prebias, const float* gamma, co
     hipLaunchKernelGGL((gn_apply_nhwc_kernel<T, OutT>), dim3(nchunk, B), dim3(256), 0, st, (const T*)x, prebias, part, gamma, beta,
                        (OutT*)out, HW, G, nchunk, per, eps, relu);
   } else {
-    int nchunk = max(1, min(GN_MAXK / GN_CPG, HW / 8192));
-    int per = (HW + nchunk - 1) / nchunk;
-    per = (per + 7) / 8 * 8;
-    nchunk = (HW + per - 1) / per;
+    int nchunk, per;
+    gn_nchw_chunks(HW, nchunk, per);
     hipLaunchKernelGGL((gn_stats_nchw_kernel<T>), dim3(nchunk, B * C), dim3(256), 0, st, (const T*)x, prebias, part, HW, C, nchunk, per);
     hipLaunchKernelGGL((gn_apply_nchw_kernel<T, OutT>), dim3(nchunk, B * C), dim3(256), 0, st, (const T*)x, prebias, part, gamma,
                        beta, (OutT*)out, HW, C, nchunk, per, eps, relu);
@@ -276,4 +278,22 @@ extern "C" int hipie_group_norm(const void* x, const float* prebias, const float
       return launch_gn<decltype(tx), decltype(to)>(x, prebias, gamma, beta, out, workspace, B, C, HW, channels_last, eps, relu, st);
     });
   });
+}
+
+extern "C" int hipie_group_norm_train_forward(const float* x, const float* gamma, const float* beta, float* y, float* stat,
+                                              float* workspace, int B, int C, int HW, int groups, float eps, int relu, void* stream) {
+  using namespace hipie;
+  HIPIE_REQUIRE(x && gamma && beta && y && stat && workspace, "group_norm_train: null pointer");
+  HIPIE_REQUIRE(B >= 0 && C > 0 && HW > 0, "group_norm_train: bad shape");
+  HIPIE_REQUIRE(groups > 0 && C == groups * GN_CPG && groups <= 64 && 256 % groups == 0,
+                "group_norm_train: %d channels in %d groups unsupported (8 channels per group, 256 %% groups == 0)", C, groups);
+  HIPIE_REQUIRE(HW % 8 == 0, "group_norm_train: NCHW needs H*W %% 8 == 0 (got %d)", HW);
+  if (B == 0) return HIPIE_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = launch_gn<float, float>(x, nullptr, gamma, beta, y, workspace, B, C, HW, 0, eps, relu, st);
+  if (rc != HIPIE_OK) return rc;
+  int nchunk, per;
+  gn_nchw_chunks(HW, nchunk, per);
+  hipLaunchKernelGGL((gn_stat_nchw_kernel<float>), dim3(B * groups), dim3(64), 0, st, x, (const float*)workspace, stat, HW, C, nchunk, eps);
+  return check_launch("group_norm_train (statistics)");
 }

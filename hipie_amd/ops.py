@@ -1424,6 +1424,55 @@ def group_norm(x, groups, weight, bias, eps, relu=False, prebias=None, out_dtype
     return out
 
 
+def _gn_train_args(who, x, weight, bias, others=()):
+    """(B, C, HW) of a dense NCHW fp32 map for the training GroupNorm pair; host tensors and other layouts / types are refused"""
+    for n, t in (("x", x), ("weight", weight), ("bias", bias)) + tuple(others):
+        if not t.is_cuda:
+            raise RuntimeError("Not implemented on the CPU (%s must be a CUDA/HIP tensor)" % n)
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise RuntimeError("%s: x must be a dense NCHW fp32 tensor" % who)
+    B, C, H, W = x.shape
+    if weight.numel() != C or bias.numel() != C:
+        raise RuntimeError("%s: weight and bias must have x's %d channels" % (who, C))
+    return B, C, H * W
+
+
+@_timed("group_norm_train")
+def group_norm_train_forward(x, groups, weight, bias, eps, relu=False):
+    """GroupNorm(groups, C = 8 * groups)(x) (+ ReLU) of a dense NCHW fp32 map for the training step (hipie_group_norm_train_forward) ->
+    (y, stat): y has the bits of group_norm(x, ...) on the same arguments, stat (B, groups, 2) = the (mean, rstd) it normalised with, what
+    group_norm_backward takes.  The workspace lives for the call (its size is the library's query)."""
+    B, C, HW = _gn_train_args("group_norm_train_forward", x, weight, bias)
+    y = torch.empty_like(x)
+    stat = torch.empty(B, groups, 2, dtype=torch.float32, device=x.device)
+    ws = torch.empty(_size("hipie_group_norm_backward_ws_bytes", B, C, HW), dtype=torch.uint8, device=x.device)
+    _call("hipie_group_norm_train_forward", x.data_ptr(), _chk(weight, "weight", torch.float32), _chk(bias, "bias", torch.float32),
+          y.data_ptr(), stat.data_ptr(), ws.data_ptr(), B, C, HW, int(groups), float(eps), 1 if relu else 0)
+    return y, stat
+
+
+@_timed("group_norm_bwd")
+def group_norm_backward(x, dy, stat, groups, weight, bias, relu=False, want_dx=True, want_param_grads=True):
+    """backward of group_norm_train_forward (hipie_group_norm_backward, fp32 NCHW): dy = gradient of y, stat = the forward's ->
+    (dx | None, dgamma | None, dbeta | None); with relu the mask is recomputed from x and stat (the forward's y > 0 bit for bit).
+    Without want_dx the second pass is not launched, without want_param_grads the parameter sums are not; the sums are added in a fixed
+    order (bit-reproducible).  Nothing is cached: the workspace lives for the call."""
+    B, C, HW = _gn_train_args("group_norm_backward", x, weight, bias, (("dy", dy), ("stat", stat)))
+    if dy.shape != x.shape or stat.shape != (B, groups, 2):
+        raise RuntimeError("group_norm_backward: dy must have the shape of x %s and stat be (B, groups, 2)" % (tuple(x.shape),))
+    dx = torch.empty_like(x) if want_dx else None
+    dgamma = dbeta = None
+    if want_param_grads:
+        dgamma, dbeta = (torch.empty(C, dtype=torch.float32, device=x.device) for _ in range(2))
+    ws_bytes = _size("hipie_group_norm_backward_ws_bytes", B, C, HW)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    _call("hipie_group_norm_backward", x.data_ptr(), _chk(dy, "dy", torch.float32), _chk(stat, "stat", torch.float32),
+          _chk(weight, "weight", torch.float32), _chk(bias, "bias", torch.float32), None if dx is None else dx.data_ptr(),
+          None if dgamma is None else dgamma.data_ptr(), None if dbeta is None else dbeta.data_ptr(), ws.data_ptr(), ws_bytes,
+          B, C, HW, int(groups), 1 if relu else 0)
+    return dx, dgamma, dbeta
+
+
 @_timed("add_cast")
 def add_cast(a, b):
     """(a f32 + b 16-bit) rounded once to b's dtype; same shapes, numel % 4 == 0."""

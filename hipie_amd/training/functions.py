@@ -478,6 +478,42 @@ def add_layer_norm(x, delta, weight, bias, eps):
     return AddLayerNormFunction.apply(x, delta, weight, bias, eps)
 
 
+class GroupNormFunction(torch.autograd.Function):
+    """y = GroupNorm(groups, C = 8 * groups)(x) [then ReLU] of a dense NCHW fp32 map: the conv + GN blocks after the backbone (input_proj of
+    both heads, deformable_detr.py:139-160; adapter_1 / layer_1 / mask_features of the pixel decoder, maskdino_encoder.py:262-300) as ONE node
+    of the graph.  forward = hipie_group_norm_train_forward (the inference path's two NCHW launches + the statistics), backward =
+    hipie_group_norm_backward.  Saved: x, stat (B, groups, 2), weight, bias -- nothing else of x's size: with ReLU the mask is recomputed."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, groups, eps, relu):
+        y, stat = ops.group_norm_train_forward(x, groups, weight.detach(), bias.detach(), eps, relu)
+        ctx.save_for_backward(x, stat, weight, bias)
+        ctx.groups, ctx.relu = int(groups), bool(relu)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, stat, weight, bias = ctx.saved_tensors
+        want_x, want_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        if not (want_x or want_p):
+            return None, None, None, None, None, None
+        dx, dg, db = ops.group_norm_backward(x, dy.contiguous(), stat, ctx.groups, weight, bias, ctx.relu, want_dx=want_x, want_param_grads=want_p)
+        return dx, dg if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None, None, None, None
+
+
+def group_norm_ok(x, groups):
+    """the limits of the training GroupNorm kernels: a dense NCHW fp32 device map, C = 8 * groups, groups a power of two <= 64, H*W % 8 == 0"""
+    return (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous() and 0 < groups <= 64 and 256 % groups == 0
+            and x.shape[1] == 8 * groups and x.shape[0] > 0 and x.shape[2] * x.shape[3] > 0 and (x.shape[2] * x.shape[3]) % 8 == 0)
+
+
+def group_norm(x, groups, weight, bias, eps, relu=False):
+    """GroupNorm (+ ReLU) with a hand-written backward (GroupNormFunction), or None outside the kernels' limits: the caller's torch form runs"""
+    if not group_norm_ok(x, groups) or weight.dtype != torch.float32 or bias.dtype != torch.float32:
+        return None
+    return GroupNormFunction.apply(x, weight, bias, groups, eps, relu)
+
+
 class PointMaskLossFunction(torch.autograd.Function):
     """the point-sampled mask losses of ONE criterion call as one node (criterion.loss_masks: point_sample of the predictions and of the
     targets, focal / sigmoid-CE + dice): src (N,H,W) logits, tgt_maps (T,Ht,Wt) ALL padded targets -- indexed by tgt_index (N,) inside the

@@ -4,7 +4,7 @@ kernels have no backward.  What is hand-written HIP here is what has a backward 
 (hipie_msda_forward / hipie_msda_backward), the mask contraction and the CondInst dynamic mask head (training/functions.py); the dense
 linears, LayerNorm / GroupNorm, the softmax attentions and the convolutions run on the library kernels PyTorch-ROCm dispatches to, with
 torch.autograd providing their backward.  More of the step runs on hand-written kernels opt-in, one HipBackend* class per kernel group:
-GROUPS below names them, backend(*names) composes any of them into the class TrainStep takes.
+GROUPS and EXTRA_GROUPS below name them, backend(*names) composes any of them into the class TrainStep takes.
 
 Functional style over a dict ``sd`` of LIVE parameters (model.named_parameters() + buffers, reference key names), so gradients land in the
 model's own parameters.  Every function cites the reference code it follows.  Training-mode differences from the inference path:
@@ -293,27 +293,46 @@ class HipBackendPairLosses(HipBackendAssign):
         return positive_onehot(logits, pairs, packed)
 
 
+class HipBackendGroupNorms(HipBackend):
+    """HipBackend + the GroupNorm (+ ReLU) of the 11 conv + GN blocks of a step -- input_proj.0-3 of the detection head and of the MaskDINO
+    pixel decoder, its adapter_1, layer_1 and mask_features, the last two with their ReLU -- as ONE autograd node each on
+    hipie_group_norm_train_forward / hipie_group_norm_backward (functions.GroupNormFunction; opt-in: TrainStep's default stays HipBackend).
+    NCHW fp32 as the convolutions hand it over.  Not here: channels-last maps, 16-bit operands, the transposed convolution's bias as a
+    pre-bias (it keeps its bias), writing the normalised levels straight into the token stream."""
+
+    @staticmethod
+    def group_norm(x, groups, weight, bias, eps, relu):
+        """GroupNorm(groups)(x) * weight + bias (+ ReLU), or None outside the kernels' limits (gn then runs F.group_norm).  A map the
+        convolution left in another layout (the library picks channels-last outputs for the 1 x 1 / strided projections when the other ViT
+        groups are composed in) is copied to NCHW first, the kernels' training layout; no copy where the map is NCHW already"""
+        from .functions import group_norm
+        return group_norm(x.contiguous(), groups, weight, bias, eps, relu)
+
+
 # the opt-in kernel groups by name; a composed class lists its bases in this order
 GROUPS = {"norms": HipBackendNorms, "mlp": HipBackendMlp, "windows": HipBackendWindows, "packed_attention": HipBackendPackedAttention,
           "packed_windows": HipBackendPackedWindows, "deformable": HipBackendDeformable, "losses": HipBackendLosses, "criteria": HipBackendCriteria,
           "matching": HipBackendMatching, "hungarian": HipBackendHungarian, "assign": HipBackendAssign, "pair_losses": HipBackendPairLosses}
+# the groups that joined after GROUPS' keys and order were pinned (tests/test_backend_compose_cpu.py): a composed class lists them last
+EXTRA_GROUPS = {"group_norms": HipBackendGroupNorms}
 _COMPOSED = {("norms", "mlp"): HipBackendNormsMlp, ("norms", "mlp", "windows"): HipBackendAll}
 
 
 def backend(*names):
-    """the backend class with the named opt-in groups (keys of GROUPS); none: HipBackend.  A group another named group inherits from is
+    """the backend class with the named opt-in groups (keys of GROUPS and EXTRA_GROUPS); none: HipBackend.  A group another named group inherits from is
     implied by it and dropped ("losses" beside "matching", "windows" and "packed_attention" beside "packed_windows"): what is left is
     unrelated by inheritance, so its classes compose as bases in any order, and no op is defined by two of them (tests/
     test_backend_compose_cpu.py, every subset).  One group left: its own class; several: one class per set of groups, built once."""
-    unknown = sorted(set(names) - set(GROUPS))
+    known = {**GROUPS, **EXTRA_GROUPS}
+    unknown = sorted(set(names) - set(known))
     if unknown:
-        raise ValueError("unknown backend group(s) %s; known: %s" % (", ".join(map(repr, unknown)), ", ".join(GROUPS)))
-    named = [GROUPS[n] for n in names]
-    left = tuple(n for n, c in GROUPS.items() if c in named and not any(o is not c and issubclass(o, c) for o in named))
+        raise ValueError("unknown backend group(s) %s; known: %s" % (", ".join(map(repr, unknown)), ", ".join(known)))
+    named = [known[n] for n in names]
+    left = tuple(n for n, c in known.items() if c in named and not any(o is not c and issubclass(o, c) for o in named))
     if len(left) < 2:
-        return GROUPS[left[0]] if left else HipBackend
+        return known[left[0]] if left else HipBackend
     if left not in _COMPOSED:
-        bases = tuple(GROUPS[n] for n in left)
+        bases = tuple(known[n] for n in left)
         _COMPOSED[left] = type("HipBackend" + "".join(c.__name__[len("HipBackend"):] for c in bases), bases, {"__doc__": "the opt-in groups " + ", ".join(left)})
     return _COMPOSED[left]
 
@@ -340,8 +359,15 @@ def conv(x, sd, p, stride=1, padding=0):
     return F.conv2d(x, sd[p + "weight"], sd.get(p + "bias"), stride=stride, padding=padding)
 
 
-def gn(x, sd, p, groups=32):
-    return F.group_norm(x, groups, sd[p + "weight"], sd[p + "bias"], 1e-5)
+def gn(x, sd, p, groups=32, be=None, relu=False):
+    """GroupNorm (+ ReLU) of a conv + GN block; a backend with a `group_norm` op is asked first (None: outside its kernels' limits)"""
+    op = getattr(be, "group_norm", None)
+    y = op(x, groups, sd[p + "weight"], sd[p + "bias"], 1e-5, relu) if op is not None else None
+    if y is None:
+        y = F.group_norm(x, groups, sd[p + "weight"], sd[p + "bias"], 1e-5)
+        if relu:
+            y = F.relu(y)
+    return y
 
 
 def inverse_sigmoid(x, eps=1e-5):
@@ -746,8 +772,8 @@ def hipie_transformer(srcs, masks, poses, lang, sd, p, cfg, be, query_label=None
 def maskdino_pixel_decoder(feats, sd, p, cfg, be):
     """MaskDINOEncoder.forward_features (maskdino/pixel_decoder/maskdino_encoder.py:368-434), low2high, masks None"""
     f3, f4, f5 = feats["res3"], feats["res4"], feats["res5"]
-    extra = gn(conv(f5, sd, p + "input_proj.3.0.", stride=2, padding=1), sd, p + "input_proj.3.1.")
-    srcs = [gn(conv(f, sd, "%sinput_proj.%d.0." % (p, i)), sd, "%sinput_proj.%d.1." % (p, i)) for i, f in enumerate((f3, f4, f5))] + [extra]
+    extra = gn(conv(f5, sd, p + "input_proj.3.0.", stride=2, padding=1), sd, p + "input_proj.3.1.", be=be)
+    srcs = [gn(conv(f, sd, "%sinput_proj.%d.0." % (p, i)), sd, "%sinput_proj.%d.1." % (p, i), be=be) for i, f in enumerate((f3, f4, f5))] + [extra]
     B, dev = f3.shape[0], f3.device
     zero = [torch.zeros(B, s.shape[2], s.shape[3], dtype=torch.bool, device=dev) for s in srcs]
     poses = [pos_sine(z, 128, offset=0.0) for z in zero]
@@ -763,10 +789,10 @@ def maskdino_pixel_decoder(feats, sd, p, cfg, be):
     for (H, W) in shapes:
         outs.append(src[:, st:st + H * W].transpose(1, 2).reshape(B, -1, H, W))
         st += H * W
-    cur = gn(F.conv2d(f3, sd[p + "adapter_1.weight"]), sd, p + "adapter_1.norm.")
+    cur = gn(F.conv2d(f3, sd[p + "adapter_1.weight"]), sd, p + "adapter_1.norm.", be=be)
     y = cur + F.interpolate(outs[0], size=cur.shape[-2:], mode="bilinear", align_corners=False)
-    y = F.relu(gn(F.conv2d(y, sd[p + "layer_1.weight"], padding=1), sd, p + "layer_1.norm."))
-    mf = F.relu(gn(F.conv_transpose2d(y, sd[p + "mask_features.0.weight"], sd[p + "mask_features.0.bias"], stride=2), sd, p + "mask_features.1."))
+    y = gn(F.conv2d(y, sd[p + "layer_1.weight"], padding=1), sd, p + "layer_1.norm.", be=be, relu=True)
+    mf = gn(F.conv_transpose2d(y, sd[p + "mask_features.0.weight"], sd[p + "mask_features.0.bias"], stride=2), sd, p + "mask_features.1.", be=be, relu=True)
     return conv(mf, sd, p + "mask_features.3."), outs
 
 
@@ -841,7 +867,7 @@ def backbone_and_projections(x, pad, sd, cfg, be=None):
     names = ["res3", "res4", "res5"]
     fmasks = [down_mask(pad, feats[n].shape[-2:]) for n in names]
     poses = [pos_sine(m, cfg["hidden_dim"] // 2) for m in fmasks]
-    srcs = [gn(conv(feats[n], sd, "%sinput_proj.%d.0." % (p, i)), sd, "%sinput_proj.%d.1." % (p, i)) for i, n in enumerate(names)]
-    s4 = gn(conv(feats["res5"], sd, p + "input_proj.3.0.", stride=2, padding=1), sd, p + "input_proj.3.1.")
+    srcs = [gn(conv(feats[n], sd, "%sinput_proj.%d.0." % (p, i)), sd, "%sinput_proj.%d.1." % (p, i), be=be) for i, n in enumerate(names)]
+    s4 = gn(conv(feats["res5"], sd, p + "input_proj.3.0.", stride=2, padding=1), sd, p + "input_proj.3.1.", be=be)
     m4 = down_mask(fmasks[0], s4.shape[-2:])
     return feats, srcs + [s4], fmasks + [m4], poses + [pos_sine(m4, cfg["hidden_dim"] // 2)]

@@ -713,6 +713,38 @@ int hipie_group_norm(const void* x, const float* prebias, const float* gamma, co
                      int B, int C, int HW, int groups, int channels_last, float eps, int relu, int x_dtype, int out_dtype,
                      void* stream);
 
+/*
+ * hipie_group_norm for the training step: NCHW, fp32, no pre-bias, with the statistics the apply pass used as a second output.
+ * Replaces: the forward of torch.nn.GroupNorm(32, 256) (+ F.relu) as the conv + GN blocks use it in training (deformable_detr.py:139-160,
+ *           maskdino_encoder.py:262-300), and the mean / rstd tensors torch.native_group_norm saves for its backward.
+ *   x, y (B, C, H*W) f32;  y: the bits hipie_group_norm(channels_last 0, f32 -> f32, prebias NULL) writes for the same arguments;
+ *   stat (B, groups, 2) f32 = (mean, rstd) per (image, group), written by a third small launch from the same partial sums;
+ *   workspace: hipie_group_norm_backward_ws_bytes(B, C, HW) bytes (2 floats per image, channel and chunk of a row).
+ *   C == 8 * groups, 256 % groups == 0, H*W % 8 == 0.  B == 0: returns 0.
+ */
+int hipie_group_norm_train_forward(const float* x, const float* gamma, const float* beta, float* y, float* stat, float* workspace,
+                                   int B, int C, int HW, int groups, float eps, int relu, void* stream);
+
+/*
+ * Backward of hipie_group_norm_train_forward: the input gradient and the parameter gradients of GroupNorm (+ ReLU) in two passes over
+ * x and dy and a partial-row sum.
+ * Replaces: torch.autograd through torch.nn.GroupNorm(32, 256) and the F.relu behind it in the conv + GN blocks (input_proj of both heads,
+ *           deformable_detr.py:139-160; adapter_1 / layer_1 / mask_features of the pixel decoder, maskdino_encoder.py:262-300): the
+ *           library's group-norm backward, the ReLU backward in front of it and the pre-ReLU map autograd keeps for the two.
+ *   x, dy (B, C, H*W) f32;  stat (B, groups, 2): the forward's (mean, rstd);  gamma, beta (C).
+ *   xhat = (x - mean) * rstd;  g = dy, with relu g = dy * [fmaf(x, sc, sh) > 0] from the forward's own scale / shift -- the forward's y > 0
+ *   bit for bit, no mask is saved;  n = 8 H*W;  s1 = sum_group gamma_c g,  s2 = sum_group gamma_c g xhat:
+ *   dx (B, C, H*W) = rstd * (gamma_c g - (s1 + xhat s2) / n), or NULL (frozen input: the second pass is not launched);
+ *   dgamma (C) = sum g xhat,  dbeta (C) = sum g over images and pixels: overwritten; both NULL = input gradient only; all three NULL:
+ *   nothing is launched.  No atomics, fixed order of the additions: bit-reproducible from call to call.
+ *   ws: at least hipie_group_norm_backward_ws_bytes(B, C, HW) bytes = B x chunks x 2 C floats, chunks = the runs a row of H*W values is
+ *   cut into (one below 16384 values, at most 64).  C == 8 * groups, 256 % groups == 0, H*W % 8 == 0.  B == 0: returns 0.
+ */
+int hipie_group_norm_backward(const float* x, const float* dy, const float* stat, const float* gamma, const float* beta, float* dx,
+                              float* dgamma, float* dbeta, void* ws, int64_t ws_bytes, int B, int C, int HW, int groups, int relu,
+                              void* stream);
+int64_t hipie_group_norm_backward_ws_bytes(int B, int C, int HW);
+
 /* out = (dtype)(a + b): a (n) f32, b (n) `dtype` f16 | bf16 -- `tgt + query_pos` rounded once to the GEMM operand type. */
 int hipie_add_cast(const float* a, const void* b, void* out, int64_t n, int dtype, void* stream);
 

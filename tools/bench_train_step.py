@@ -4,7 +4,8 @@ GPU (configs/training/vit_huge_32g.yaml:1 -- 32 GPUs x 2), the 80-class caption,
 12544 mask points, random-init weights.  Prints ms for the forward (loss dictionary), the backward, and the peak memory.
     python tools/bench_train_step.py [batch] [steps] [--hand-norms] [--fused-mlp] [--fused-windows] [--packed-attention] [--packed-windows] [--fused-msda]
                                                             [--fused-losses] [--fused-criteria] [--fused-matching] [--fused-hungarian] [--fused-assign] [--fused-pair-losses]
-Each flag names one opt-in kernel group of hipie_amd/training/net.py (FLAGS below; the classes' docstrings say what each puts on which kernels);
+                                                            [--fused-group-norms]
+Each flag names one opt-in kernel group of hipie_amd/training/net.py (FLAGS and EXTRA_FLAGS below; the classes' docstrings say what each puts on which kernels);
 the step runs on net.backend(*groups), no flag: net.HipBackend.  Any set of flags composes.  A flag whose group another flag's group builds on
 adds nothing: --packed-windows includes --packed-attention and --fused-windows, and each of --fused-losses < --fused-criteria < --fused-matching <
 --fused-hungarian < --fused-assign < --fused-pair-losses includes the ones before it.
@@ -51,9 +52,14 @@ FLAGS = {"--hand-norms": "norms", "--fused-mlp": "mlp", "--fused-windows": "wind
          "--fused-matching": "matching", "--fused-hungarian": "hungarian", "--fused-assign": "assign", "--fused-pair-losses": "pair_losses"}
 
 
+# flag -> group of net.EXTRA_GROUPS
+EXTRA_FLAGS = {"--fused-group-norms": "group_norms"}
+
+
 def backend_names(argv):
     """the command line -> (the groups its flags name, for net.backend; what is left: [batch] [steps])"""
-    return [FLAGS[a] for a in argv if a in FLAGS], [a for a in argv if a not in FLAGS]
+    flags = {**FLAGS, **EXTRA_FLAGS}
+    return [flags[a] for a in argv if a in flags], [a for a in argv if a not in flags]
 
 
 def main():
