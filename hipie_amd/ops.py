@@ -448,6 +448,56 @@ def attn_f32_ok(hd):
     return hd in (32, 64)
 
 
+def _query_attn_args(who, qk, v, blocked, heads, others=()):
+    """(B, N, mask pointer) of the training query self-attention: qk (B, N, 2 heads 32), v (B, N, heads 32) fp32 device rows (column blocks of
+    wider buffers are fine), blocked None | (N, N) bool / uint8 dense; host tensors and other layouts / types are refused"""
+    for n, t in (("qk", qk), ("v", v)) + tuple(others) + ((("blocked", blocked),) if blocked is not None else ()):
+        if not t.is_cuda:
+            raise RuntimeError("Not implemented on the CPU (%s must be a CUDA/HIP tensor)" % n)
+    B, N = qk.shape[0], qk.shape[1]
+    C = heads * 32
+    for n, t, width in (("qk", qk, 2 * C), ("v", v, C)) + tuple((n, t, C) for n, t in others):
+        if t.dtype != torch.float32 or tuple(t.shape) != (B, N, width) or t.stride(2) != 1:
+            raise RuntimeError("%s: %s must be fp32 (%d, %d, %d) rows with contiguous columns, got %s %s" % (who, n, B, N, width, t.dtype, tuple(t.shape)))
+    if blocked is None:
+        return B, N, None
+    if blocked.dtype not in (torch.bool, torch.uint8) or tuple(blocked.shape) != (N, N) or not blocked.is_contiguous():
+        raise RuntimeError("%s: blocked must be a dense (N, N) bool / uint8 tensor, got %s %s" % (who, blocked.dtype, tuple(blocked.shape)))
+    return B, N, blocked.data_ptr()
+
+
+@_timed("query_attn_train")
+def query_attn_train_forward(qk, v, blocked, heads, scale):
+    """hipie_attn_f32_train_forward: the decoders' query self-attention in exact fp32 for the training step.  qk (B, N, 2 heads 32) rows of the
+    q | k in-projection, v (B, N, heads 32) rows, blocked None | (N, N) bool (True = may NOT attend, torch's attn_mask; its own storage is
+    passed) -> (out (B, N, heads 32), lse (B, heads, N) in log2 units: what query_attn_train_backward takes)."""
+    B, N, mp = _query_attn_args("query_attn_train_forward", qk, v, blocked, heads)
+    out = torch.empty(B, N, heads * 32, dtype=torch.float32, device=qk.device)
+    lse = torch.empty(B, heads, N, dtype=torch.float32, device=qk.device)
+    _call("hipie_attn_f32_train_forward", qk.data_ptr(), v.data_ptr(), mp, out.data_ptr(), lse.data_ptr(), B, int(heads), N, 32,
+          qk.stride(0), qk.stride(1), v.stride(0), v.stride(1), 0, float(scale))
+    return out, lse
+
+
+@_timed("query_attn_bwd")
+def query_attn_train_backward(qk, v, blocked, out, lse, d_out, heads, scale, want_qk=True, want_v=True):
+    """backward of query_attn_train_forward (hipie_attn_f32_train_backward): out, lse = the forward's, d_out (B, N, heads 32) rows ->
+    (d_qk (B, N, 2 heads 32) | None, d_v (B, N, heads 32) | None); the probabilities are recomputed from lse, the sums run in a fixed
+    order (bit-reproducible).  Without want_qk the dQ pass and the dK half are not launched, without want_v the dV half, without both
+    nothing.  Nothing is cached: the workspace lives for the call."""
+    B, N, mp = _query_attn_args("query_attn_train_backward", qk, v, blocked, heads, (("out", out), ("d_out", d_out)))
+    if tuple(lse.shape) != (B, heads, N):
+        raise RuntimeError("query_attn_train_backward: lse must be (B, heads, N), got %s" % (tuple(lse.shape),))
+    d_qk = torch.empty(B, N, 2 * heads * 32, dtype=torch.float32, device=qk.device) if want_qk else None
+    d_v = torch.empty(B, N, heads * 32, dtype=torch.float32, device=qk.device) if want_v else None
+    ws_bytes = _size("hipie_attn_f32_train_backward_ws_bytes", B, int(heads), N)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=qk.device)
+    _call("hipie_attn_f32_train_backward", qk.data_ptr(), v.data_ptr(), mp, _chk(out, "out", torch.float32), _chk(lse, "lse", torch.float32),
+          d_out.data_ptr(), None if d_qk is None else d_qk.data_ptr(), None if d_v is None else d_v.data_ptr(), ws.data_ptr(), ws_bytes,
+          B, int(heads), N, 32, qk.stride(0), qk.stride(1), v.stride(0), v.stride(1), 0, d_out.stride(0), d_out.stride(1), float(scale))
+    return d_qk, d_v
+
+
 @_timed(lambda qkv, rel_h, rel_w, grid_hw, heads, scale: "vit_attn_global" if grid_hw[0] * grid_hw[1] > 256 else "vit_attn_window")
 def vit_attn(qkv, rel_h, rel_w, grid_hw, heads, scale):
     """qkv (B, gh*gw, 3*heads*hd) 16-bit packed as (3, heads, hd); rel_h (B*heads, gh, N) f32 (key-row major),

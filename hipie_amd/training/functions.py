@@ -514,6 +514,60 @@ def group_norm(x, groups, weight, bias, eps, relu=False):
     return GroupNormFunction.apply(x, weight, bias, groups, eps, relu)
 
 
+def _rows_ok(t):
+    """rows the query-attention kernels read in place: contiguous columns, strides multiples of 4 elements, a 16-byte boundary"""
+    return t.stride(2) == 1 and t.stride(0) % 4 == 0 and t.stride(1) % 4 == 0 and t.data_ptr() % 16 == 0
+
+
+class QueryAttentionFunction(torch.autograd.Function):
+    """the core of the decoder layers' query self-attention (nn.MultiheadAttention with q = k = tgt + query_pos, v = tgt, heads of 32 and the
+    de-noising attn_mask: deformable_transformer_dino.py:418-436, dino_decoder.py:222-248) as ONE node between the in-projection and
+    out_proj: qk (B, N, 2 C) rows of the q | k linear, v (B, N, C) rows, mask None | (N, N) bool (True = blocked) -> (B, N, C).
+    forward = hipie_attn_f32_train_forward, backward = hipie_attn_f32_train_backward, exact fp32 (csrc/attn_f32_train.hip).
+    Saved: qk, v, out, lse (B, heads, N) and the mask -- nothing of N x N elements besides the mask the caller owns.  The backward writes
+    ONE d_qk buffer for both column blocks; a frozen input skips its launches."""
+
+    @staticmethod
+    def forward(ctx, qk, v, mask, heads):
+        scale = 32 ** -0.5
+        out, lse = ops.query_attn_train_forward(qk, v, mask, heads, scale)
+        ctx.save_for_backward(qk, v, out, lse, mask)
+        ctx.heads, ctx.scale = int(heads), scale
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        want_qk, want_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (want_qk or want_v):
+            return None, None, None, None
+        qk, v, out, lse, mask = ctx.saved_tensors
+        if d_out.dtype != torch.float32 or not _rows_ok(d_out):
+            d_out = d_out.float().contiguous()
+        d_qk, d_v = ops.query_attn_train_backward(qk, v, mask, out, lse, d_out, ctx.heads, ctx.scale, want_qk=want_qk, want_v=want_v)
+        return d_qk, d_v, None, None
+
+
+def query_attention_ok(qk, v, attn_mask, heads):
+    """the limits of the training query-attention kernels: fp32 device rows qk (B, N, 2 C) and v (B, N, C) with C = heads * 32, read in
+    place (contiguous columns, strides multiples of 4 elements, 16-byte boundaries); attn_mask None or an (N, N) bool on the same device"""
+    if not (torch.is_tensor(qk) and torch.is_tensor(v) and qk.is_cuda and v.is_cuda and qk.dtype == torch.float32 and v.dtype == torch.float32):
+        return False
+    if qk.dim() != 3 or v.dim() != 3 or heads <= 0 or qk.shape[0] == 0 or qk.shape[1] == 0:
+        return False
+    B, N, C = v.shape
+    if C != heads * 32 or tuple(qk.shape) != (B, N, 2 * C) or not _rows_ok(qk) or not _rows_ok(v):
+        return False
+    return attn_mask is None or (attn_mask.is_cuda and attn_mask.dtype == torch.bool and tuple(attn_mask.shape) == (N, N))
+
+
+def query_attention(qk, v, attn_mask, heads):
+    """softmax(q k^T / sqrt(32) with attn_mask) v of the decoders' query self-attention with a hand-written backward
+    (QueryAttentionFunction) -> (B, N, C), or None outside the kernels' limits: the caller's materialised formulation runs"""
+    if not query_attention_ok(qk, v, attn_mask, heads):
+        return None
+    return QueryAttentionFunction.apply(qk, v, None if attn_mask is None else attn_mask.contiguous(), heads)
+
+
 class PointMaskLossFunction(torch.autograd.Function):
     """the point-sampled mask losses of ONE criterion call as one node (criterion.loss_masks: point_sample of the predictions and of the
     targets, focal / sigmoid-CE + dice): src (N,H,W) logits, tgt_maps (T,Ht,Wt) ALL padded targets -- indexed by tgt_index (N,) inside the

@@ -4,7 +4,7 @@ kernels have no backward.  What is hand-written HIP here is what has a backward 
 (hipie_msda_forward / hipie_msda_backward), the mask contraction and the CondInst dynamic mask head (training/functions.py); the dense
 linears, LayerNorm / GroupNorm, the softmax attentions and the convolutions run on the library kernels PyTorch-ROCm dispatches to, with
 torch.autograd providing their backward.  More of the step runs on hand-written kernels opt-in, one HipBackend* class per kernel group:
-GROUPS and EXTRA_GROUPS below name them, backend(*names) composes any of them into the class TrainStep takes.
+GROUPS, EXTRA_GROUPS and LATER_GROUPS below name them, backend(*names) composes any of them into the class TrainStep takes.
 
 Functional style over a dict ``sd`` of LIVE parameters (model.named_parameters() + buffers, reference key names), so gradients land in the
 model's own parameters.  Every function cites the reference code it follows.  Training-mode differences from the inference path:
@@ -309,21 +309,40 @@ class HipBackendGroupNorms(HipBackend):
         return group_norm(x.contiguous(), groups, weight, bias, eps, relu)
 
 
+class HipBackendQueryAttention(HipBackend):
+    """HipBackend + the query self-attention of every decoder layer -- 6 in the thing branch, 9 in MaskDINO: nn.MultiheadAttention with
+    q = k = tgt + query_pos, v = tgt, 8 heads of 32 and the de-noising attn_mask -- as ONE autograd node between the in-projection and
+    out_proj on hipie_attn_f32_train_forward / hipie_attn_f32_train_backward (functions.QueryAttentionFunction, csrc/attn_f32_train.hip):
+    exact fp32 as the inference path's attn_f32, no (B, 8, N, N) tensor in HBM forward or backward, q | k from one linear.
+    Opt-in: TrainStep's default stays HipBackend.  Not here: the layers' LayerNorms and FFN, the vision-language fusion attention, head
+    widths other than 32, dropout."""
+
+    @staticmethod
+    def query_attention(qk, v, attn_mask, heads):
+        """qk (B, N, 2 C) rows of the q | k in-projection, v (B, N, C) rows, attn_mask None | (N, N) bool (True = blocked) -> (B, N, C), or
+        None outside the kernels' limits (mha then runs its materialised formulation; functions.query_attention_ok names the limits)"""
+        from .functions import query_attention
+        return query_attention(qk, v, attn_mask, heads)
+
+
 # the opt-in kernel groups by name; a composed class lists its bases in this order
 GROUPS = {"norms": HipBackendNorms, "mlp": HipBackendMlp, "windows": HipBackendWindows, "packed_attention": HipBackendPackedAttention,
           "packed_windows": HipBackendPackedWindows, "deformable": HipBackendDeformable, "losses": HipBackendLosses, "criteria": HipBackendCriteria,
           "matching": HipBackendMatching, "hungarian": HipBackendHungarian, "assign": HipBackendAssign, "pair_losses": HipBackendPairLosses}
 # the groups that joined after GROUPS' keys and order were pinned (tests/test_backend_compose_cpu.py): a composed class lists them last
 EXTRA_GROUPS = {"group_norms": HipBackendGroupNorms}
+# the table every later group joins, at its end: a composed class lists these after the GROUPS and EXTRA_GROUPS classes, in this order.
+# It GROWS: a test may assert that a name is in it and where it stands relative to another name, never the table's full contents.
+LATER_GROUPS = {"query_attention": HipBackendQueryAttention}
 _COMPOSED = {("norms", "mlp"): HipBackendNormsMlp, ("norms", "mlp", "windows"): HipBackendAll}
 
 
 def backend(*names):
-    """the backend class with the named opt-in groups (keys of GROUPS and EXTRA_GROUPS); none: HipBackend.  A group another named group inherits from is
+    """the backend class with the named opt-in groups (keys of GROUPS, EXTRA_GROUPS and LATER_GROUPS); none: HipBackend.  A group another named group inherits from is
     implied by it and dropped ("losses" beside "matching", "windows" and "packed_attention" beside "packed_windows"): what is left is
     unrelated by inheritance, so its classes compose as bases in any order, and no op is defined by two of them (tests/
     test_backend_compose_cpu.py, every subset).  One group left: its own class; several: one class per set of groups, built once."""
-    known = {**GROUPS, **EXTRA_GROUPS}
+    known = {**GROUPS, **EXTRA_GROUPS, **LATER_GROUPS}
     unknown = sorted(set(names) - set(known))
     if unknown:
         raise ValueError("unknown backend group(s) %s; known: %s" % (", ".join(map(repr, unknown)), ", ".join(known)))
@@ -647,11 +666,18 @@ def encoder_layer(src, pos, refs, shapes, pad_mask, sd, p, be):
     return ln(src + _bmlp(src, sd, p + "linear1.", p + "linear2.", "relu", be), sd, p + "norm2.")
 
 
-def mha(x_qk, x_v, sd, p, attn_mask=None, heads=8):
-    """nn.MultiheadAttention (q = k = tgt + pos, v = tgt), batch first; attn_mask (Nq, Nq) bool, True = blocked"""
+def mha(x_qk, x_v, sd, p, attn_mask=None, heads=8, be=None):
+    """nn.MultiheadAttention (q = k = tgt + pos, v = tgt), batch first; attn_mask (Nq, Nq) bool, True = blocked.  A backend with a
+    `query_attention` op (HipBackendQueryAttention) is asked first, with q | k from ONE linear over in_proj_weight[:2 C] as the inference
+    module computes them (None: outside its kernels' limits, the materialised formulation below runs)"""
     B, N, C = x_qk.shape
     w, b = sd[p + "in_proj_weight"], sd[p + "in_proj_bias"]
     hd = C // heads
+    op = getattr(be, "query_attention", None)
+    if op is not None:
+        o = op(F.linear(x_qk, w[:2 * C], b[:2 * C]), F.linear(x_v, w[2 * C:], b[2 * C:]), attn_mask, heads)
+        if o is not None:
+            return lin(o, sd, p + "out_proj.")
 
     def sp(t):
         return t.view(B, N, heads, hd).transpose(1, 2)
@@ -664,7 +690,7 @@ def mha(x_qk, x_v, sd, p, attn_mask=None, heads=8):
 
 def decoder_layer(tgt, qpos, refs_in, src, shapes, pad_mask, sd, p, be, attn_mask=None):
     """DeformableTransformerDecoderLayer.forward (deformable_transformer_dino.py:432-450; maskdino dino_decoder.py:221-270)"""
-    tgt = ln(tgt + mha(tgt + qpos, tgt, sd, p + "self_attn.", attn_mask), sd, p + "norm2.")
+    tgt = ln(tgt + mha(tgt + qpos, tgt, sd, p + "self_attn.", attn_mask, be=be), sd, p + "norm2.")
     tgt = ln(tgt + msda_module(tgt + qpos, refs_in, src, shapes, pad_mask, sd, p + "cross_attn.", be), sd, p + "norm1.")
     return ln(tgt + lin(F.relu(lin(tgt, sd, p + "linear1.")), sd, p + "linear2."), sd, p + "norm3.")
 

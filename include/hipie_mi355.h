@@ -1073,6 +1073,48 @@ int hipie_attn_split(const float* q, const float* k, const float* v, const unsig
                    void* stream);
 
 /*
+ * hipie_attn_f32 for the TRAINING step: the decoders' query self-attention (q = k rows, Nq = Nk = N, head_dim 32) with the log-sum-exp of
+ * every row as a second output and a mask per (query, key) pair.  Exact fp32 FMA chains in a fixed order, no atomics: deterministic.
+ *   qk (B, N, 2 H 32) f32 rows of the q | k in-projection: q of head h at column h * 32, k at H * 32 + h * 32; batch / row strides
+ *   qk_sb / qk_st in elements;  v (B, N, H 32) f32 rows, strides v_sb / v_st (both may be column blocks of wider buffers);
+ *   blocked (N, N) uint8, 1 = query i may NOT see key j (torch's attn_mask convention: a bool tensor's own storage), image b's mask at
+ *   blocked + b * mask_sb (0: one mask for every image and head); NULL = no mask;
+ *   out (B, N, H 32) f32 contiguous = softmax_j(scale q_i . k_j) v_j;  lse (B, H, N) f32 = max_j s_ij + log2 sum_j 2^(s_ij - max) with
+ *   s = scale * log2(e) * q . k, i.e. in log2 units.  A row with every key blocked gives zeros and lse = -inf.
+ * Refused (HIPIE_EINVAL, nothing launched): null pointers, head_dim != 32, B, H or N < 1, qk / v / out off a 16-byte boundary, strides
+ * that are no multiple of 4, a row stride below the row's width.
+ * Replaces: the forward of nn.MultiheadAttention's core under torch.autograd in the decoder layers -- scale, masked_fill(attn_mask, -inf),
+ *           softmax, two batched products and the (B, 8, N, N) logits and probabilities they keep
+ *           (models/deformable_detr/deformable_transformer_dino.py:418-436, models/maskdino/transformer_decoder/dino_decoder.py:222-248).
+ */
+int hipie_attn_f32_train_forward(const float* qk, const float* v, const unsigned char* blocked, float* out, float* lse, int B, int H, int N,
+                                 int head_dim, int64_t qk_sb, int64_t qk_st, int64_t v_sb, int64_t v_st, int64_t mask_sb, float scale,
+                                 void* stream);
+
+/*
+ * Backward of hipie_attn_f32_train_forward in two passes that recompute the probabilities from lse: nothing of N x N elements is read or
+ * written.  p_ij = 2^(s_ij - lse_i) with s from the forward's own chains, delta_i = d_out_i . out_i, dp_ij = d_out_i . v_j,
+ * ds_ij = p_ij (dp_ij - delta_i):
+ *   pass 1, one thread per query row:  d_qk[b, i, h * 32 ..]         = scale sum_j ds_ij k_j, and delta into the workspace;
+ *   pass 2, one thread per key row:    d_qk[b, j, H * 32 + h * 32 ..] = scale sum_i ds_ij q_i,  d_v[b, j, h * 32 ..] = sum_i p_ij d_out_i,
+ *   summed in query order.  d_qk (B, N, 2 H 32) and d_v (B, N, H 32) f32 contiguous, every element overwritten.
+ *   qk, v, blocked, out, lse, the strides and scale: the forward's;  d_out (B, N, H 32) f32 with strides do_sb / do_st.
+ *   d_qk NULL (frozen q | k rows): pass 1 and the dK half of pass 2 are skipped;  d_v NULL: the dV half;  both NULL: nothing is launched.
+ *   ws: at least hipie_attn_f32_train_backward_ws_bytes(B, H, N) bytes = (B, H, N) floats.
+ * A row with lse = -inf contributes exactly zero to every gradient.  Fixed order of the additions, no atomics: bit-reproducible.
+ * Refused (HIPIE_EINVAL, nothing launched): what the forward refuses, d_out / d_qk / d_v off a 16-byte boundary, do_sb / do_st no
+ * multiple of 4, a workspace that is too small (the message names the size needed).
+ * Replaces: torch.autograd through the same code -- the softmax backward over the saved (B, 8, N, N) probabilities, four batched products,
+ *           the transposing copies and the zero-filled slice gradients of the three in-projection slices
+ *           (models/deformable_detr/deformable_transformer_dino.py:418-436, models/maskdino/transformer_decoder/dino_decoder.py:222-248).
+ */
+int hipie_attn_f32_train_backward(const float* qk, const float* v, const unsigned char* blocked, const float* out, const float* lse,
+                                  const float* d_out, float* d_qk, float* d_v, void* ws, int64_t ws_bytes, int B, int H, int N, int head_dim,
+                                  int64_t qk_sb, int64_t qk_st, int64_t v_sb, int64_t v_st, int64_t mask_sb, int64_t do_sb, int64_t do_st,
+                                  float scale, void* stream);
+int64_t hipie_attn_f32_train_backward_ws_bytes(int B, int H, int N);
+
+/*
  * The FFN of a deformable encoder layer in ONE launch at the split policy's accuracy:  out = W2 . relu(W1 . x + b1) + b2.
  *   x    (M, 2 D) HIPIE_HL8 rows (row stride ldx in fp16 elements);  w1 (F, 2 D) HL8;  b1 (F) fp32;
  *   w2p  (D, 2 F) HL8 of W2 with its COLUMNS permuted inside every block of 16 into the order 0-3, 8-11, 4-7, 12-15 (the order in which

@@ -4,8 +4,8 @@ GPU (configs/training/vit_huge_32g.yaml:1 -- 32 GPUs x 2), the 80-class caption,
 12544 mask points, random-init weights.  Prints ms for the forward (loss dictionary), the backward, and the peak memory.
     python tools/bench_train_step.py [batch] [steps] [--hand-norms] [--fused-mlp] [--fused-windows] [--packed-attention] [--packed-windows] [--fused-msda]
                                                             [--fused-losses] [--fused-criteria] [--fused-matching] [--fused-hungarian] [--fused-assign] [--fused-pair-losses]
-                                                            [--fused-group-norms]
-Each flag names one opt-in kernel group of hipie_amd/training/net.py (FLAGS and EXTRA_FLAGS below; the classes' docstrings say what each puts on which kernels);
+                                                            [--fused-group-norms] [--fused-query-attention]
+Each flag names one opt-in kernel group of hipie_amd/training/net.py (FLAGS, EXTRA_FLAGS and LATER_FLAGS below; the classes' docstrings say what each puts on which kernels);
 the step runs on net.backend(*groups), no flag: net.HipBackend.  Any set of flags composes.  A flag whose group another flag's group builds on
 adds nothing: --packed-windows includes --packed-attention and --fused-windows, and each of --fused-losses < --fused-criteria < --fused-matching <
 --fused-hungarian < --fused-assign < --fused-pair-losses includes the ones before it.
@@ -56,9 +56,13 @@ FLAGS = {"--hand-norms": "norms", "--fused-mlp": "mlp", "--fused-windows": "wind
 EXTRA_FLAGS = {"--fused-group-norms": "group_norms"}
 
 
+# flag -> group of net.LATER_GROUPS: the table later flags join (tests assert membership in it, not its full contents)
+LATER_FLAGS = {"--fused-query-attention": "query_attention"}
+
+
 def backend_names(argv):
     """the command line -> (the groups its flags name, for net.backend; what is left: [batch] [steps])"""
-    flags = {**FLAGS, **EXTRA_FLAGS}
+    flags = {**FLAGS, **EXTRA_FLAGS, **LATER_FLAGS}
     return [flags[a] for a in argv if a in flags], [a for a in argv if a not in flags]
 
 
