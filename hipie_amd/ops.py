@@ -498,6 +498,65 @@ def query_attn_train_backward(qk, v, blocked, out, lse, d_out, heads, scale, wan
     return d_qk, d_v
 
 
+def _bi_attn_args(who, q, k, vv, vl, att, heads, vis=(), txt=()):
+    """(B, Nv, L) of the training fusion attention: q, vv (B, Nv, heads 256) and k, vl (B, L, heads 256) fp32 device rows (column blocks of
+    wider buffers are fine), att (B, L) dense bool / uint8; `vis` / `txt`: further (name, tensor) rows of either side.  Host tensors and
+    other layouts / types are refused"""
+    B, Nv, L, E = q.shape[0], q.shape[1], k.shape[1], heads * 256
+    for n, t, rows in (("q", q, Nv), ("vv", vv, Nv), ("k", k, L), ("vl", vl, L)) + tuple((n, t, Nv) for n, t in vis) + tuple((n, t, L) for n, t in txt):
+        if not t.is_cuda:
+            raise RuntimeError("Not implemented on the CPU (%s must be a CUDA/HIP tensor)" % n)
+        if t.dtype != torch.float32 or tuple(t.shape) != (B, rows, E) or t.stride(2) != 1:
+            raise RuntimeError("%s: %s must be fp32 (%d, %d, %d) rows with contiguous columns, got %s %s" % (who, n, B, rows, E, t.dtype, tuple(t.shape)))
+    if not att.is_cuda:
+        raise RuntimeError("Not implemented on the CPU (att must be a CUDA/HIP tensor)")
+    if att.dtype not in (torch.bool, torch.uint8) or tuple(att.shape) != (B, L) or not att.is_contiguous():
+        raise RuntimeError("%s: att must be a dense (B, L) bool / uint8 tensor, got %s %s" % (who, att.dtype, tuple(att.shape)))
+    return B, Nv, L
+
+
+@_timed("bi_attn_train")
+def bi_attn_train_forward(q, k, vv, vl, att, heads, dropout=0.0, seed=0):
+    """hipie_bi_attn_train_forward: the core of the vision-language fusion attention in exact fp32 for the training step, both directions.
+    q (UNSCALED v_proj rows), vv (B, Nv, heads 256), k, vl (B, L, heads 256), att (B, L) bool (True = attended), dropout in [0, 1) with the
+    64-bit `seed` of the library's stateless keep function -> (out_v (B, Nv, E), out_l (B, L, E), lse_v (B, heads, Nv), lse_l (B, heads, L)
+    in log2 units, stat_v (B, heads, Nv, 2), stat_l (B, heads, L, 2): what bi_attn_train_backward takes).  The workspace lives for the call."""
+    B, Nv, L = _bi_attn_args("bi_attn_train_forward", q, k, vv, vl, att, heads)
+    dev, E = q.device, heads * 256
+    out_v = torch.empty(B, Nv, E, dtype=torch.float32, device=dev)
+    out_l = torch.empty(B, L, E, dtype=torch.float32, device=dev)
+    lse_v = torch.empty(B, heads, Nv, dtype=torch.float32, device=dev)
+    lse_l = torch.empty(B, heads, L, dtype=torch.float32, device=dev)
+    stat_v = torch.empty(B, heads, Nv, 2, dtype=torch.float32, device=dev)
+    stat_l = torch.empty(B, heads, L, 2, dtype=torch.float32, device=dev)
+    ws_bytes = _size("hipie_bi_attn_train_forward_ws_bytes", B, int(heads), Nv, L)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    _call("hipie_bi_attn_train_forward", q.data_ptr(), k.data_ptr(), vv.data_ptr(), vl.data_ptr(), att.data_ptr(), out_v.data_ptr(),
+          out_l.data_ptr(), lse_v.data_ptr(), lse_l.data_ptr(), stat_v.data_ptr(), stat_l.data_ptr(), ws.data_ptr(), ws_bytes, B, int(heads), Nv, L,
+          256, q.stride(0), q.stride(1), k.stride(0), k.stride(1), vv.stride(0), vv.stride(1), vl.stride(0), vl.stride(1), float(dropout), int(seed))
+    return out_v, out_l, lse_v, lse_l, stat_v, stat_l
+
+
+@_timed("bi_attn_bwd")
+def bi_attn_train_backward(q, k, vv, vl, att, out_v, out_l, stat_v, stat_l, d_out_v, d_out_l, heads, dropout=0.0, seed=0, want=(True, True, True, True)):
+    """backward of bi_attn_train_forward (hipie_bi_attn_train_backward): out_*, stat_* = the forward's, d_out_v (B, Nv, E) and d_out_l (B, L, E)
+    rows, the forward's dropout and seed -> (d_q, d_k, d_vv, d_vl), None where `want` (in that order) is False: the work that serves only
+    that gradient is not launched, and nothing at all without any.  Fixed order of every sum (bit-reproducible)."""
+    B, Nv, L = _bi_attn_args("bi_attn_train_backward", q, k, vv, vl, att, heads, (("out_v", out_v), ("d_out_v", d_out_v)), (("out_l", out_l), ("d_out_l", d_out_l)))
+    if tuple(stat_v.shape) != (B, heads, Nv, 2) or tuple(stat_l.shape) != (B, heads, L, 2):
+        raise RuntimeError("bi_attn_train_backward: stat_v / stat_l must be (B, heads, Nv, 2) / (B, heads, L, 2), got %s %s" % (tuple(stat_v.shape), tuple(stat_l.shape)))
+    dev, E = q.device, heads * 256
+    grads = [torch.empty(B, n, E, dtype=torch.float32, device=dev) if w else None for w, n in zip(want, (Nv, L, Nv, L))]
+    ws_bytes = _size("hipie_bi_attn_train_backward_ws_bytes", B, int(heads), Nv, L)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    _call("hipie_bi_attn_train_backward", q.data_ptr(), k.data_ptr(), vv.data_ptr(), vl.data_ptr(), att.data_ptr(), _chk(out_v, "out_v", torch.float32),
+          _chk(out_l, "out_l", torch.float32), _chk(stat_v, "stat_v", torch.float32), _chk(stat_l, "stat_l", torch.float32), d_out_v.data_ptr(),
+          d_out_l.data_ptr(), *[None if g is None else g.data_ptr() for g in grads], ws.data_ptr(), ws_bytes, B, int(heads), Nv, L, 256,
+          q.stride(0), q.stride(1), k.stride(0), k.stride(1), vv.stride(0), vv.stride(1), vl.stride(0), vl.stride(1),
+          d_out_v.stride(0), d_out_v.stride(1), d_out_l.stride(0), d_out_l.stride(1), float(dropout), int(seed))
+    return tuple(grads)
+
+
 @_timed(lambda qkv, rel_h, rel_w, grid_hw, heads, scale: "vit_attn_global" if grid_hw[0] * grid_hw[1] > 256 else "vit_attn_window")
 def vit_attn(qkv, rel_h, rel_w, grid_hw, heads, scale):
     """qkv (B, gh*gw, 3*heads*hd) 16-bit packed as (3, heads, hd); rel_h (B*heads, gh, N) f32 (key-row major),

@@ -568,6 +568,70 @@ def query_attention(qk, v, attn_mask, heads):
     return QueryAttentionFunction.apply(qk, v, None if attn_mask is None else attn_mask.contiguous(), heads)
 
 
+class FusionAttentionFunction(torch.autograd.Function):
+    """the core of the vision-language fusion attention (BiMultiHeadAttention.forward, fuse_helper.py:54-139) as ONE node between the four
+    input projections and the two output projections, both directions: q (UNSCALED v_proj rows), vv (B, Nv, E), k, vl (B, L, E), att (B, L)
+    bool (True = attended), heads of 256, the attention dropout rate and its 64-bit seed -> (out_v (B, Nv, E), out_l (B, L, E)).
+    forward = hipie_bi_attn_train_forward, backward = hipie_bi_attn_train_backward, exact fp32 (csrc/bi_attn_train.hip).
+    Saved: the four operands, out_v, out_l, the two (maximum, log2 sum) statistics (B, heads, Nv | L, 2), att; the seed and the rate in ctx --
+    nothing of Nv x L elements.  The dropout masks are a stateless function of (seed, direction, b, h, i, j), recomputed in the backward;
+    they are NOT F.dropout's random stream.  A frozen input skips the launches that serve only it.
+    An image with no attended token is outside the contract: its out_v rows are 0 and that direction gives it no gradient (the reference
+    gives a uniform row).  Not here: the folded form of the inference path, 16-bit operands, L > 256, a pad mask on the visual side
+    (the reference has none), the block's LayerNorms and projections."""
+
+    @staticmethod
+    def forward(ctx, q, k, vv, vl, att, heads, dropout, seed):
+        out_v, out_l, _, _, stat_v, stat_l = ops.bi_attn_train_forward(q, k, vv, vl, att, heads, dropout, seed)
+        ctx.save_for_backward(q, k, vv, vl, att, out_v, out_l, stat_v, stat_l)
+        ctx.heads, ctx.dropout, ctx.seed = int(heads), float(dropout), int(seed)
+        return out_v, out_l
+
+    @staticmethod
+    def backward(ctx, d_out_v, d_out_l):
+        want = tuple(ctx.needs_input_grad[:4])
+        if not any(want):
+            return (None,) * 8
+        q, k, vv, vl, att, out_v, out_l, stat_v, stat_l = ctx.saved_tensors
+        if d_out_v.dtype != torch.float32 or not _rows_ok(d_out_v):
+            d_out_v = d_out_v.float().contiguous()
+        if d_out_l.dtype != torch.float32 or not _rows_ok(d_out_l):
+            d_out_l = d_out_l.float().contiguous()
+        grads = ops.bi_attn_train_backward(q, k, vv, vl, att, out_v, out_l, stat_v, stat_l, d_out_v, d_out_l, ctx.heads, ctx.dropout, ctx.seed, want)
+        return grads + (None, None, None, None)
+
+
+def fusion_attention_ok(q, k, vv, vl, text_mask, heads, dropout):
+    """the limits of the training fusion-attention kernels: fp32 device rows q, vv (B, Nv, E) and k, vl (B, L, E) with E = heads * 256, read in
+    place (contiguous columns, strides multiples of 4 elements, 16-byte boundaries), 1 <= L <= 256, Nv >= 1, text_mask (B, L) on the same
+    device, 0 <= dropout < 1"""
+    ts = (q, k, vv, vl)
+    if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 for t in ts):
+        return False
+    if not (torch.is_tensor(text_mask) and text_mask.is_cuda) or not 0.0 <= float(dropout) < 1.0 or heads <= 0:
+        return False
+    B, Nv, E = q.shape
+    L = k.shape[1]
+    if E != heads * 256 or B == 0 or Nv == 0 or not 1 <= L <= 256:
+        return False
+    if tuple(vv.shape) != (B, Nv, E) or tuple(k.shape) != (B, L, E) or tuple(vl.shape) != (B, L, E) or tuple(text_mask.shape) != (B, L):
+        return False
+    return all(_rows_ok(t) for t in ts)
+
+
+def fusion_attention(q, k, vv, vl, text_mask, heads, dropout=0.0, seed=None):
+    """both directions of the fusion attention from the UNSCALED v_proj rows q, the l_proj rows k and the two value projections, with a
+    hand-written backward (FusionAttentionFunction) -> (out_v, out_l), or None outside the kernels' limits: the caller's materialised
+    formulation runs.  seed None: with dropout > 0 one 64-bit seed per call from torch's default CPU generator (no device work; reproduces
+    under torch.manual_seed), none drawn at dropout 0"""
+    if not fusion_attention_ok(q, k, vv, vl, text_mask, heads, dropout):
+        return None
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item()) if dropout > 0 else 0
+    att = (text_mask != 0).contiguous()
+    return FusionAttentionFunction.apply(q, k, vv, vl, att, heads, float(dropout), seed)
+
+
 class PointMaskLossFunction(torch.autograd.Function):
     """the point-sampled mask losses of ONE criterion call as one node (criterion.loss_masks: point_sample of the predictions and of the
     targets, focal / sigmoid-CE + dice): src (N,H,W) logits, tgt_maps (T,Ht,Wt) ALL padded targets -- indexed by tgt_index (N,) inside the

@@ -325,6 +325,27 @@ class HipBackendQueryAttention(HipBackend):
         return query_attention(qk, v, attn_mask, heads)
 
 
+class HipBackendFusionAttention(HipBackend):
+    """HipBackend + the vision-language fusion attention of every vl layer -- BiMultiHeadAttention.forward (fuse_helper.py:54-139), 8 heads of
+    256, both directions, with the block's attention dropout -- as ONE autograd node between the four input projections and the two output
+    projections on hipie_bi_attn_train_forward / hipie_bi_attn_train_backward (functions.FusionAttentionFunction, csrc/bi_attn_train.hip):
+    exact fp32, no (B 8, Nv, L) tensor in HBM forward or backward, the 256^-0.5 scale folded into the kernels.  The dropout masks are a
+    stateless function of a per-call 64-bit seed (torch's default CPU generator) and the element's indices, not F.dropout's random stream.
+    An image with NO attended text token is outside the contract: its out_v rows are 0 and that direction gives no gradient, where the
+    reference gives a uniform row.
+    Opt-in: TrainStep's default stays HipBackend.  Not here: the folded form of the inference path (no (B, Nv, 2048) projection at all),
+    16-bit operands, L > 256 (declined), a pad mask on the visual side (the reference has none), the block's LayerNorms and projections,
+    making the group the default."""
+
+    @staticmethod
+    def fusion_attention(q, k, vv, vl, text_mask, heads, dropout):
+        """q (B, Nv, E) UNSCALED v_proj rows, k (B, L, E) l_proj rows, vv / vl the value projections, text_mask (B, L) (non-zero = attended),
+        the dropout rate -> (out_v (B, Nv, E), out_l (B, L, E)), or None outside the kernels' limits (bi_attention_block then runs its
+        materialised formulation; functions.fusion_attention_ok names the limits)"""
+        from .functions import fusion_attention
+        return fusion_attention(q, k, vv, vl, text_mask, heads, dropout)
+
+
 # the opt-in kernel groups by name; a composed class lists its bases in this order
 GROUPS = {"norms": HipBackendNorms, "mlp": HipBackendMlp, "windows": HipBackendWindows, "packed_attention": HipBackendPackedAttention,
           "packed_windows": HipBackendPackedWindows, "deformable": HipBackendDeformable, "losses": HipBackendLosses, "criteria": HipBackendCriteria,
@@ -333,7 +354,7 @@ GROUPS = {"norms": HipBackendNorms, "mlp": HipBackendMlp, "windows": HipBackendW
 EXTRA_GROUPS = {"group_norms": HipBackendGroupNorms}
 # the table every later group joins, at its end: a composed class lists these after the GROUPS and EXTRA_GROUPS classes, in this order.
 # It GROWS: a test may assert that a name is in it and where it stands relative to another name, never the table's full contents.
-LATER_GROUPS = {"query_attention": HipBackendQueryAttention}
+LATER_GROUPS = {"query_attention": HipBackendQueryAttention, "fusion_attention": HipBackendFusionAttention}
 _COMPOSED = {("norms", "mlp"): HipBackendNormsMlp, ("norms", "mlp", "windows"): HipBackendAll}
 
 
@@ -715,15 +736,22 @@ def gen_proposals(memory, pad_mask, shapes):
 
 
 # ------------------------------------------------------------------------------------------------ vision-language fusion (fuse_helper.py)
-def bi_attention_block(v, l, text_mask, sd, p, heads=8, dropout=0.0):
+def bi_attention_block(v, l, text_mask, sd, p, heads=8, dropout=0.0, be=None):
     """BiAttentionBlockForCheckpoint.forward (fuse_helper.py:170-179) + BiMultiHeadAttention.forward (:54-139).  dropout: the functional
-    attention dropout of :111-112 (0.1 in vlfusion.py:81; 0 reproduces the deterministic fixture)"""
+    attention dropout of :111-112 (0.1 in vlfusion.py:81; 0 reproduces the deterministic fixture).  A backend with a `fusion_attention` op
+    (HipBackendFusionAttention) is asked first, with the UNSCALED v_proj rows (None: outside its kernels' limits, the materialised
+    formulation below runs)"""
     v, l = ln(v, sd, p + "layer_norm_v."), ln(l, sd, p + "layer_norm_l.")
     a = p + "attn."
     B, Nv, _ = v.shape
     L = l.shape[1]
     E = sd[a + "v_proj.weight"].shape[0]
     hd = E // heads
+    op = getattr(be, "fusion_attention", None)
+    if op is not None:
+        o = op(lin(v, sd, a + "v_proj."), lin(l, sd, a + "l_proj."), lin(v, sd, a + "values_v_proj."), lin(l, sd, a + "values_l_proj."), text_mask, heads, dropout)
+        if o is not None:
+            return v + sd[p + "gamma_v"] * lin(o[0], sd, a + "out_v_proj."), l + sd[p + "gamma_l"] * lin(o[1], sd, a + "out_l_proj.")
 
     def split(t, n):
         return t.view(B, n, heads, hd).transpose(1, 2).reshape(B * heads, n, hd)
@@ -758,7 +786,7 @@ def hipie_transformer(srcs, masks, poses, lang, sd, p, cfg, be, query_label=None
     hidden, lmask = lang["hidden"], lang["masks"]
     for i in range(cfg["enc_layers"]):
         if i < cfg["num_vl_layers"]:
-            src, hidden = bi_attention_block(src, hidden, lmask, sd, "%sencoder.vl_layers.%d.b_attn." % (p, i), dropout=fusion_dropout)
+            src, hidden = bi_attention_block(src, hidden, lmask, sd, "%sencoder.vl_layers.%d.b_attn." % (p, i), dropout=fusion_dropout, be=be)
         src = encoder_layer(src, pos, refs, shapes, mask, sd, "%sencoder.layers.%d." % (p, i), be)
     memory = src
     lang_pool = agg_lang_feat(hidden, lmask)

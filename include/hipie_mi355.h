@@ -1115,6 +1115,55 @@ int hipie_attn_f32_train_backward(const float* qk, const float* v, const unsigne
 int64_t hipie_attn_f32_train_backward_ws_bytes(int B, int H, int N);
 
 /*
+ * The core of the vision-language fusion attention for the TRAINING step, both directions in one call, exact fp32 on the f32-input MFMA
+ * (bitwise fmaf chains in a fixed order, no atomics: deterministic), with the block's attention dropout.  Head width 256, L <= 256.
+ *   q, vv (B, Nv, H 256) f32 rows of v_proj (UNSCALED: scale = 256^-0.5 is applied here) and values_v_proj; k, vl (B, L, H 256) f32 rows
+ *   of l_proj and values_l_proj; head h at column h * 256; batch / row strides *_sb / *_st in elements (column blocks of wider buffers
+ *   are read in place);  att (B, L) uint8, 1 = attended text token.
+ *   raw_ij = scale q_i . k_j, s_ij = clamp(raw_ij, -50000, 50000);  pv = softmax of s over the ATTENDED j (0 elsewhere);  pl = softmax of s
+ *   over ALL i per column j (no mask);  out_v (B, Nv, H 256) = sum_j pv_ij kv_ij vl_j;  out_l (B, L, H 256) = sum_i pl_ij kl_ij vv_i.
+ *   kv, kl: dropout keep factors, 0 or 1 / (1 - dropout), from a stateless hash of (seed, direction, b, h, i, j) -- the same function in
+ *   the forward and the backward, independent of the launch geometry; not torch's random stream.  dropout = 0 keeps everything.
+ *   lse_v (B, H, Nv) and lse_l (B, H, L): log-sum-exp of the rows / columns in LOG2 units (s * log2 e);  stat_v (B, H, Nv, 2) and
+ *   stat_l (B, H, L, 2): the same as a pair (maximum, log2 of the sum of 2^(s - maximum)) -- what the backward reads: a clamped row's
+ *   logits are 72135 in log2 units, where a single float's ulp of 0.008 would cost 0.5 % in every probability.
+ *   An image with NO attended token is outside the contract: out_v = 0, lse_v = -inf, and its image -> text direction gives zero gradient.
+ *   ws: at least hipie_bi_attn_train_forward_ws_bytes(B, H, Nv, L) bytes: the partial column statistics and out_l rows of at most 8
+ *   segments of the visual rows, folded in segment order.  Nothing of Nv x L elements is written.
+ * Refused (HIPIE_EINVAL, nothing launched): null pointers, head_dim != 256, L outside 1 .. 256, B, H or Nv < 1, pointers off a 16-byte
+ * boundary, strides that are no multiple of 4, a row stride below the row's width, dropout outside [0, 1), a workspace that is too small.
+ * Replaces: the forward of BiMultiHeadAttention.forward between the four input and two output projections under torch.autograd -- two
+ *           batched products, four clamps, a max, two softmaxes, the int64 mask, two dropouts and the dozen (B 8, Nv, L) tensors they
+ *           keep (models/fuse_helper.py:54-139).
+ */
+int hipie_bi_attn_train_forward(const float* q, const float* k, const float* vv, const float* vl, const unsigned char* att, float* out_v,
+                                float* out_l, float* lse_v, float* lse_l, float* stat_v, float* stat_l, void* ws, int64_t ws_bytes, int B,
+                                int H, int Nv, int L, int head_dim, int64_t q_sb, int64_t q_st, int64_t k_sb, int64_t k_st, int64_t vv_sb,
+                                int64_t vv_st, int64_t vl_sb, int64_t vl_st, double dropout, int64_t seed, void* stream);
+int64_t hipie_bi_attn_train_forward_ws_bytes(int B, int H, int Nv, int L);
+
+/*
+ * Backward of hipie_bi_attn_train_forward; the probabilities of both directions are recomputed from stat_v / stat_l with the forward's
+ * own logit chains and keep function.  With dv_i = d_out_v_i . out_v_i and dl_j = d_out_l_j . out_l_j:
+ *   ds_ij = (pv_ij (kv_ij d_out_v_i . vl_j - dv_i) + pl_ij (kl_ij vv_i . d_out_l_j - dl_j)) [|raw_ij| <= 50000]
+ *   d_q_i = scale sum_j ds_ij k_j,  d_k_j = scale sum_i ds_ij q_i,  d_vl_j = sum_i pv_ij kv_ij d_out_v_i,  d_vv_i = sum_j pl_ij kl_ij d_out_l_j
+ *   d_q, d_vv (B, Nv, H 256) and d_k, d_vl (B, L, H 256) f32 contiguous, every element overwritten;  d_out_v (B, Nv, H 256) and
+ *   d_out_l (B, L, H 256) f32 with strides dov_* / dol_*.  A NULL gradient pointer skips the work that serves only it; all four NULL:
+ *   nothing is launched.  The sums over the visual rows run per segment in row order, the segments are folded in order: bit-reproducible.
+ *   ws: at least hipie_bi_attn_train_backward_ws_bytes(B, H, Nv, L) bytes.
+ * Refused (HIPIE_EINVAL, nothing launched): what the forward refuses, gradients off a 16-byte boundary, dov_* / dol_* no multiple of 4,
+ * a workspace that is too small (the message names the size needed).
+ * Replaces: torch.autograd through the same code (models/fuse_helper.py:54-139).
+ */
+int hipie_bi_attn_train_backward(const float* q, const float* k, const float* vv, const float* vl, const unsigned char* att,
+                                 const float* out_v, const float* out_l, const float* stat_v, const float* stat_l, const float* d_out_v,
+                                 const float* d_out_l, float* d_q, float* d_k, float* d_vv, float* d_vl, void* ws, int64_t ws_bytes, int B,
+                                 int H, int Nv, int L, int head_dim, int64_t q_sb, int64_t q_st, int64_t k_sb, int64_t k_st, int64_t vv_sb,
+                                 int64_t vv_st, int64_t vl_sb, int64_t vl_st, int64_t dov_sb, int64_t dov_st, int64_t dol_sb,
+                                 int64_t dol_st, double dropout, int64_t seed, void* stream);
+int64_t hipie_bi_attn_train_backward_ws_bytes(int B, int H, int Nv, int L);
+
+/*
  * The FFN of a deformable encoder layer in ONE launch at the split policy's accuracy:  out = W2 . relu(W1 . x + b1) + b2.
  *   x    (M, 2 D) HIPIE_HL8 rows (row stride ldx in fp16 elements);  w1 (F, 2 D) HL8;  b1 (F) fp32;
  *   w2p  (D, 2 F) HL8 of W2 with its COLUMNS permuted inside every block of 16 into the order 0-3, 8-11, 4-7, 12-15 (the order in which
