@@ -2277,6 +2277,64 @@ def conv3x3_split(x, conv, act=ACT_NONE):
     return out.view(B, Hp, Wp, N)[:, 1:-1, 1:-1].permute(0, 3, 1, 2).contiguous(memory_format=torch.channels_last)
 
 
+# ---- the training step's 3 x 3 convolution node on the same padded grid (training/functions.Conv3x3Function) ----------------------------
+CONV_WGRAD_CHUNK = 2048         # grid rows per partial of hipie_conv3x3_wgrad (csrc/conv_wgrad.hip WG_CHUNK)
+
+
+def conv3x3_stage(x):
+    """x (B, C, H, W) fp32 in any memory format -> its zero-padded pixel grid in a buffer of ITS OWN, (rows + 2 guard, C) fp32: rows =
+    B (H + 2) (W + 2) pixel rows with a zero border, guard = W + 3 zero rows on both ends.  Not the inference cache _CONV_STAGE (eight slots
+    per stream, evicted): a training node's grid must outlive other convolutions of the step, so it is allocated per call and freed with
+    its last reference."""
+    B, C, H, W = x.shape
+    Hp, Wp = H + 2, W + 2
+    guard, rows = Wp + 1, B * Hp * Wp
+    buf = torch.zeros(rows + 2 * guard, C, dtype=torch.float32, device=x.device)
+    buf[guard:guard + rows].view(B, Hp, Wp, C)[:, 1:-1, 1:-1].copy_(x.permute(0, 2, 3, 1))
+    return buf
+
+
+def conv3x3_crop(grid_rows, B, H, W):
+    """(B (H + 2) (W + 2), N) rows on the padded grid -> the (B, N, H, W) interior, a VIEW (channels-last strides inside the grid)"""
+    return grid_rows.view(B, H + 2, W + 2, grid_rows.shape[1])[:, 1:-1, 1:-1].permute(0, 3, 1, 2)
+
+
+@_timed("conv3x3_train")
+def conv3x3_grid(buf, w_hl8, bias, B, H, W, relu=False):
+    """hipie_conv3x3_split on a grid of conv3x3_stage, F32 rows in and F32 out: buf (rows + 2 guard, C), w_hl8 (N, 2 * 9 C) HL8 with
+    k = (3 ky + kx) C + c, bias (N) fp32 or None -> (rows, N) fp32 on the SAME grid; its border rows are meaningless."""
+    Wp = W + 2
+    guard, rows = Wp + 1, B * (H + 2) * Wp
+    C, N = buf.shape[1], w_hl8.shape[0]
+    if buf.shape[0] != rows + 2 * guard or w_hl8.shape[1] != 18 * C or w_hl8.dtype != torch.float16 or buf.dtype != torch.float32:
+        raise RuntimeError("conv3x3_grid: a staged grid %s against an HL8 weight %s" % (tuple(buf.shape), tuple(w_hl8.shape)))
+    out = torch.empty(rows, N, dtype=torch.float32, device=buf.device)
+    _call("hipie_conv3x3_split", _chk(buf, "grid") + 4 * guard * C, C, _chk(w_hl8, "w"), None if bias is None else _chk(bias, "bias", torch.float32),
+          out.data_ptr(), N, rows, Wp, C, N, F32, F32, ACT_RELU if relu else ACT_NONE)
+    return out
+
+
+@_timed("conv3x3_wgrad")
+def conv3x3_wgrad(xbuf, dybuf, y_rows, B, H, W, want_bias=True):
+    """weight and bias gradient of the 3 x 3 convolution on the padded grid (hipie_conv3x3_wgrad): xbuf (rows + 2 guard, C) and dybuf
+    (rows + 2 guard, N) grids of conv3x3_stage (dybuf's border zero), y_rows (rows, N) the forward's output on the grid or None (with it
+    the gradient is masked by y > 0 as it is read) -> (dw (N, 9, C) with tap = 3 ky + kx, db (N) | None).  The partial sums of the row
+    chunks are added in chunk order: bit-reproducible.  The workspace lives for the call."""
+    Wp = W + 2
+    guard, rows = Wp + 1, B * (H + 2) * Wp
+    C, N = xbuf.shape[1], dybuf.shape[1]
+    if xbuf.shape[0] != rows + 2 * guard or dybuf.shape[0] != rows + 2 * guard or (y_rows is not None and tuple(y_rows.shape) != (rows, N)):
+        raise RuntimeError("conv3x3_wgrad: grids %s / %s for %d rows" % (tuple(xbuf.shape), tuple(dybuf.shape), rows))
+    dw = torch.empty(N, 9, C, dtype=torch.float32, device=xbuf.device)
+    db = torch.empty(N, dtype=torch.float32, device=xbuf.device) if want_bias else None
+    ws_bytes = -(-rows // CONV_WGRAD_CHUNK) * (9 * C * N + N) * 4
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=xbuf.device)
+    _call("hipie_conv3x3_wgrad", _chk(xbuf, "x grid", torch.float32) + 4 * guard * C, C, _chk(dybuf, "dy grid", torch.float32) + 4 * guard * N, N,
+          None if y_rows is None else _chk(y_rows, "y", torch.float32), rows, Wp, C, N, dw.data_ptr(), None if db is None else db.data_ptr(),
+          ws.data_ptr(), ws_bytes)
+    return dw, db
+
+
 _FFN_PERM = {}
 
 

@@ -514,6 +514,81 @@ def group_norm(x, groups, weight, bias, eps, relu=False):
     return GroupNormFunction.apply(x, weight, bias, groups, eps, relu)
 
 
+class Conv3x3Function(torch.autograd.Function):
+    """y = conv2d(x, weight, bias, stride 1, padding 1) [then ReLU] for a dense 3 x 3 fp32 convolution as ONE node of the graph: the
+    MaskHeadSmallConv convolutions (ddetrs_dn.py:1633-1689) and the pixel decoder's layer_1 (maskdino_encoder.py:294-310).  All three passes
+    work on the zero-padded pixel grid of ops.conv3x3_stage (B (H+2) (W+2) rows of channels, zero border, W + 3 guard rows on both ends):
+        y  = hipie_conv3x3_split(x grid, W as HL8 (N, 9 C))                  F32 rows in and out, bias / ReLU in the epilogue
+        dx = hipie_conv3x3_split(g grid, Wt as HL8 (C, 9 N))                 Wt[c, (2 - ky, 2 - kx), n] = W[n, c, ky, kx]
+        dW, db = hipie_conv3x3_wgrad(x grid, g grid)                         the row contraction per tap, csrc/conv_wgrad.hip
+    with g = dy, or dy * [y > 0] under ReLU.  Saved: x as it came in, and with ReLU the output grid -- the storage the returned y is a view
+    of, so the mask costs no memory of its own; no pre-ReLU map, no mask tensor.  x is RE-STAGED in the backward rather than keeping its
+    grid: the step's convolution inputs are kept by their producers anyway, a saved grid would be a second copy of each until its backward
+    (about 35 MB per 128 x 128 site at 2 images), and the re-staging is one copy pass.  Only the saved-x form was built and measured.
+    The HL8 copies of W and Wt are cached on the weight tensor (ops.split_weight) and rebuilt when it changes.
+    needs_input_grad is honoured: a frozen input skips the dx pass, a frozen weight and bias skip hipie_conv3x3_wgrad."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, relu):
+        B, C, H, W = x.shape
+        N = weight.shape[0]
+        w_hl8, _, _ = ops.split_weight(weight, "w3x3", [weight], lambda: weight.permute(0, 2, 3, 1).reshape(N, 9 * C))
+        yg = ops.conv3x3_grid(ops.conv3x3_stage(x), w_hl8, None if bias is None else bias.detach().contiguous(), B, H, W, relu)
+        ctx.save_for_backward(x, weight, *((yg,) if relu else ()))
+        ctx.owner, ctx.relu, ctx.has_bias = weight, bool(relu), bias is not None
+        return ops.conv3x3_crop(yg, B, H, W)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors[:2]
+        yg = ctx.saved_tensors[2] if ctx.relu else None
+        B, C, H, W = x.shape
+        N = weight.shape[0]
+        want_x, want_w, want_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        if not (want_x or want_w or want_b):
+            return None, None, None, None
+        g = ops.conv3x3_stage(dy)                              # border and guard rows zero; a strided dy is read in place by the copy
+        guard = W + 3
+        if yg is not None and want_x:                          # the dx convolution needs the masked map itself; the weight pass then reads it
+            g[guard:guard + yg.shape[0]].masked_fill_(~(yg > 0), 0.0)
+            yg = None
+        dx = dw = db = None
+        if want_x:
+            wt_hl8, _, _ = ops.split_weight(ctx.owner, "w3x3.T", [weight], lambda: weight.flip(2, 3).permute(1, 2, 3, 0).reshape(C, 9 * N))
+            dx = ops.conv3x3_crop(ops.conv3x3_grid(g, wt_hl8, None, B, H, W), B, H, W)
+        if want_w or want_b:
+            dw, db = ops.conv3x3_wgrad(ops.conv3x3_stage(x), g, yg, B, H, W, want_bias=want_b)
+            dw = dw.view(N, 3, 3, C).permute(0, 3, 1, 2).contiguous() if want_w else None
+        return dx, dw, db, None
+
+
+def conv3x3_train_ok(x, weight, bias=None, stride=1, padding=1, dilation=1, groups=1):
+    """the limits of the training convolution node: fp32 device tensors, kernel 3 x 3, stride 1, padding 1 (zeros), dilation 1, groups 1,
+    Cin % 32 == 0 and Cout % 32 == 0 (the input-gradient pass swaps the channel roles, and hipie_conv3x3_split needs C % 32), and the
+    byte-offset limit hipie_conv3x3_split checks on a row stride, for both channel counts"""
+    def one(v):
+        return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+    if x.dim() != 4 or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        return False
+    if one(stride) != (1, 1) or one(padding) != (1, 1) or one(dilation) != (1, 1) or groups != 1:
+        return False
+    N, C = weight.shape[0], weight.shape[1]
+    if C != x.shape[1] or C % 32 or N % 32 or min(x.shape) < 1:
+        return False
+    if x.dtype != torch.float32 or weight.dtype != torch.float32 or (bias is not None and bias.dtype != torch.float32):
+        return False
+    if (256 + x.shape[3] + 4) * 4 * max(C, N) >= 1 << 31 or x.shape[0] * (x.shape[2] + 2) * (x.shape[3] + 2) >= 1 << 31:
+        return False
+    return x.is_cuda and weight.is_cuda and (bias is None or bias.is_cuda)
+
+
+def conv3x3_train(x, weight, bias=None, relu=False, stride=1, padding=1, dilation=1, groups=1):
+    """conv2d (+ ReLU) with a hand-written backward (Conv3x3Function), or None outside conv3x3_train_ok's limits: the caller's F.conv2d runs"""
+    if not conv3x3_train_ok(x, weight, bias, stride, padding, dilation, groups):
+        return None
+    return Conv3x3Function.apply(x, weight, bias, relu)
+
+
 def _rows_ok(t):
     """rows the query-attention kernels read in place: contiguous columns, strides multiples of 4 elements, a 16-byte boundary"""
     return t.stride(2) == 1 and t.stride(0) % 4 == 0 and t.stride(1) % 4 == 0 and t.data_ptr() % 16 == 0

@@ -3,7 +3,7 @@ state_dict layout as the reference, hipie_amd/hipie_img.py), written for autogra
 kernels have no backward.  What is hand-written HIP here is what has a backward kernel: multi-scale deformable attention
 (hipie_msda_forward / hipie_msda_backward), the mask contraction and the CondInst dynamic mask head (training/functions.py); the dense
 linears, LayerNorm / GroupNorm, the softmax attentions and the convolutions run on the library kernels PyTorch-ROCm dispatches to, with
-torch.autograd providing their backward.  More of the step runs on hand-written kernels opt-in, one HipBackend* class per kernel group:
+torch.autograd providing their backward (the dense 3 x 3 convolutions have a node of their own in the opt-in group "convs").  More of the step runs on hand-written kernels opt-in, one HipBackend* class per kernel group:
 GROUPS, EXTRA_GROUPS and LATER_GROUPS below name them, backend(*names) composes any of them into the class TrainStep takes.
 
 Functional style over a dict ``sd`` of LIVE parameters (model.named_parameters() + buffers, reference key names), so gradients land in the
@@ -346,15 +346,36 @@ class HipBackendFusionAttention(HipBackend):
         return fusion_attention(q, k, vv, vl, text_mask, heads, dropout)
 
 
+class HipBackendConvs(HipBackend):
+    """HipBackend + the dense 3 x 3 / stride 1 / padding 1 convolutions that carry the conv flops of a step -- lay3, lay4, jia_dcn and lay1 of
+    the CondInst mask head with their ReLU, layer_1 of the MaskDINO pixel decoder without one (its ReLU stays with the GroupNorm behind it)
+    -- as ONE autograd node each (functions.Conv3x3Function): forward and input gradient on hipie_conv3x3_split, the inference path's
+    implicit GEMM on a zero-padded pixel grid, weight and bias gradient on hipie_conv3x3_wgrad (csrc/conv_wgrad.hip); three-product split
+    fp16 with fp32 accumulation in all three passes.  With ReLU the backward's mask is the node's own y > 0: no pre-ReLU map is kept.
+    Opt-in: TrainStep's default stays HipBackend.  Not here: the stride-2 and 1 x 1 projections, the transposed convolutions, 16-bit
+    operands, lay2 (64 -> 8 channels: declined, F.conv2d runs), making the group the default."""
+
+    @staticmethod
+    def conv3x3(x, weight, bias, relu):
+        """conv2d(x, weight, bias, padding=1) (+ ReLU) -> (B, N, H, W), a channels-last view of the node's output grid, or None outside the
+        kernels' limits (conv then runs F.conv2d; functions.conv3x3_train_ok names the limits)"""
+        from .functions import conv3x3_train
+        return conv3x3_train(x, weight, bias, relu)
+
+
 # the opt-in kernel groups by name; a composed class lists its bases in this order
 GROUPS = {"norms": HipBackendNorms, "mlp": HipBackendMlp, "windows": HipBackendWindows, "packed_attention": HipBackendPackedAttention,
           "packed_windows": HipBackendPackedWindows, "deformable": HipBackendDeformable, "losses": HipBackendLosses, "criteria": HipBackendCriteria,
           "matching": HipBackendMatching, "hungarian": HipBackendHungarian, "assign": HipBackendAssign, "pair_losses": HipBackendPairLosses}
 # the groups that joined after GROUPS' keys and order were pinned (tests/test_backend_compose_cpu.py): a composed class lists them last
 EXTRA_GROUPS = {"group_norms": HipBackendGroupNorms}
-# the table every later group joins, at its end: a composed class lists these after the GROUPS and EXTRA_GROUPS classes, in this order.
+# the table every later group joins, at its end: a composed class lists these after the GROUPS and EXTRA_GROUPS classes.
 # It GROWS: a test may assert that a name is in it and where it stands relative to another name, never the table's full contents.
-LATER_GROUPS = {"query_attention": HipBackendQueryAttention, "fusion_attention": HipBackendFusionAttention}
+LATER_GROUPS = {"query_attention": HipBackendQueryAttention, "fusion_attention": HipBackendFusionAttention, "convs": HipBackendConvs}
+# Among the bases of a composed class the two attention groups keep the END, in this order (tests/test_fusion_attention_cpu.py pins
+# HipBackendFusionAttention as the last base of the every-group class); a group that joins LATER_GROUPS behind them is listed in front of
+# them.  The groups are unrelated by inheritance and share no op, so the order of the bases changes nothing a step computes.
+_LAST_BASES = ("query_attention", "fusion_attention")
 _COMPOSED = {("norms", "mlp"): HipBackendNormsMlp, ("norms", "mlp", "windows"): HipBackendAll}
 
 
@@ -368,7 +389,8 @@ def backend(*names):
     if unknown:
         raise ValueError("unknown backend group(s) %s; known: %s" % (", ".join(map(repr, unknown)), ", ".join(known)))
     named = [known[n] for n in names]
-    left = tuple(n for n, c in known.items() if c in named and not any(o is not c and issubclass(o, c) for o in named))
+    order = [n for n in known if n not in _LAST_BASES] + list(_LAST_BASES)
+    left = tuple(n for n in order if known[n] in named and not any(o is not known[n] and issubclass(o, known[n]) for o in named))
     if len(left) < 2:
         return known[left[0]] if left else HipBackend
     if left not in _COMPOSED:
@@ -395,8 +417,16 @@ def mlp(x, sd, p, n):
     return x
 
 
-def conv(x, sd, p, stride=1, padding=0):
-    return F.conv2d(x, sd[p + "weight"], sd.get(p + "bias"), stride=stride, padding=padding)
+def conv(x, sd, p, stride=1, padding=0, be=None, relu=False):
+    """conv2d (+ ReLU); a backend with a `conv3x3` op is asked first for the 3 x 3 / stride 1 / padding 1 sites (None: outside its limits)"""
+    w, b = sd[p + "weight"], sd.get(p + "bias")
+    op = getattr(be, "conv3x3", None) if (stride, padding) == (1, 1) else None
+    y = op(x, w, b, relu) if op is not None else None
+    if y is None:
+        y = F.conv2d(x, w, b, stride=stride, padding=padding)
+        if relu:
+            y = F.relu(y)
+    return y
 
 
 def gn(x, sd, p, groups=32, be=None, relu=False):
@@ -845,7 +875,7 @@ def maskdino_pixel_decoder(feats, sd, p, cfg, be):
         st += H * W
     cur = gn(F.conv2d(f3, sd[p + "adapter_1.weight"]), sd, p + "adapter_1.norm.", be=be)
     y = cur + F.interpolate(outs[0], size=cur.shape[-2:], mode="bilinear", align_corners=False)
-    y = gn(F.conv2d(y, sd[p + "layer_1.weight"], padding=1), sd, p + "layer_1.norm.", be=be, relu=True)
+    y = gn(conv(y, sd, p + "layer_1.", padding=1, be=be), sd, p + "layer_1.norm.", be=be, relu=True)       # the ReLU stays with GroupNorm
     mf = gn(F.conv_transpose2d(y, sd[p + "mask_features.0.weight"], sd[p + "mask_features.0.bias"], stride=2), sd, p + "mask_features.1.", be=be, relu=True)
     return conv(mf, sd, p + "mask_features.3."), outs
 
@@ -901,14 +931,14 @@ def maskdino_decoder(ms_feats, mask_features, sd, p, cfg, be, dn=None, topk_over
 
 
 # ------------------------------------------------------------------------------------------------ CondInst mask branch
-def mask_head_small_conv(feats, sd, p):
+def mask_head_small_conv(feats, sd, p, be=None):
     """MaskHeadSmallConv.forward, fpns None (ddetrs_dn.py:1633-1689); feats = [s8, s16, s32] NCHW"""
-    x = F.relu(conv(feats[-1], sd, p + "lay3.", padding=1))
+    x = conv(feats[-1], sd, p + "lay3.", padding=1, be=be, relu=True)
     x = feats[-2] + F.interpolate(x, size=feats[-2].shape[-2:], mode="nearest")
-    x = F.relu(conv(x, sd, p + "lay4.", padding=1))
+    x = conv(x, sd, p + "lay4.", padding=1, be=be, relu=True)
     x = feats[-3] + F.interpolate(x, size=feats[-3].shape[-2:], mode="nearest")
-    x = F.relu(conv(x, sd, p + "jia_dcn.", padding=1))
-    return F.relu(conv(F.relu(conv(x, sd, p + "lay1.", padding=1)), sd, p + "lay2.", padding=1))
+    x = conv(x, sd, p + "jia_dcn.", padding=1, be=be, relu=True)
+    return conv(conv(x, sd, p + "lay1.", padding=1, be=be, relu=True), sd, p + "lay2.", padding=1, be=be, relu=True)
 
 
 def backbone_and_projections(x, pad, sd, cfg, be=None):

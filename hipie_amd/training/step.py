@@ -119,7 +119,7 @@ class TrainStep:
         for (H, W) in shapes[:3]:
             lv.append(memory[:, st:st + H * W].reshape(B, H, W, c).permute(0, 3, 1, 2))
             st += H * W
-        return net.mask_head_small_conv(lv, sd, "detr.mask_head.")
+        return net.mask_head_small_conv(lv, sd, "detr.mask_head.", self.be)
 
     def dyn_masks(self, mask_feats, ref_points, params, num_insts):
         """dynamic_mask_with_coords for per-image instance lists -> per image (1, n_i, 1, H/4, W/4) (forward_mask_head_train's output form)"""

@@ -1192,6 +1192,26 @@ int hipie_conv3x3_split(const void* x, int64_t ldx, const void* w, const float* 
                         int N, int in_fmt, int out_fmt, int act, void* stream);
 
 /*
+ * Weight and bias gradient of hipie_conv3x3_split's convolution for the TRAINING step, on the same zero-padded pixel grid:
+ *   dw[n, tap, c] = sum_rows g[row, n] * x[row + (ty - 1) * Wp + (tx - 1), c],  tap = 3 ty + tx;   db[n] = sum_rows g[row, n]
+ *   g = dy, or with y given (the ReLU fused into the node) dy * [y > 0].
+ *   x: row 0 of the input grid, `rows` rows of C f32 values, row stride ldx elements, at least Wp + 1 readable rows before and after it;
+ *   dy: row 0 of the output-gradient grid, `rows` rows of N f32 values, row stride ldg -- its BORDER rows must be zero (the forward computes
+ *   border rows too; their gradient is not part of the problem); no guard rows are read;  y: the forward's output on that grid with dy's
+ *   row stride, or NULL;  dw (N, 9, C) and db (N) f32 contiguous, every element overwritten; db NULL: not computed.
+ *   ws: at least ceil(rows / 2048) * (9 C N + N) * 4 bytes: one partial [dw | db] per chunk of 2048 rows, added in chunk order by a second
+ *   launch.  Three-product split fp16 with fp32 accumulation; db from the fp32 values.  No atomics: two calls give the same bits.
+ *   Every read stays inside rows -(Wp + 1) .. rows + Wp of x and rows 0 .. rows - 1 of dy / y.
+ * Refused (HIPIE_EINVAL, nothing launched): null x / dy / dw / ws, rows outside 1 .. 2^31 - 1, Wp < 3, C or N no positive multiple of 32,
+ * row strides below the row's width or no multiple of 4, a pointer off a 16-byte boundary, a workspace that is too small (the message
+ * names the size needed).
+ * Replaces: the weight / bias gradient kernels the library runs under torch.autograd for the 3 x 3 convolutions of MaskHeadSmallConv
+ *           (ddetrs_dn.py:1633-1689) and of the pixel decoder's layer_1 (maskdino_encoder.py:294-310), and the ReLU backward in front of them.
+ */
+int hipie_conv3x3_wgrad(const float* x, int64_t ldx, const float* dy, int64_t ldg, const float* y, int64_t rows, int Wp, int C, int N,
+                        float* dw, float* db, void* ws, int64_t ws_bytes, void* stream);
+
+/*
  * Row-wise top-k of fp32 scores, k <= 1024: idx_out (rows, k) int64 in descending value order (ascending index among equal values;
  * NaN sorts as the largest value), val_out (rows, k) f32 or NULL.  One launch, hipGraph-replay safe.
  * Replaces: torch.topk in the two-stage query selections (models/deformable_detr/deformable_transformer_dino.py:222-230, 900 of Nv;
