@@ -95,7 +95,7 @@ static inline bool gemm_mfma16() {
 
 static int gemm_impl(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, const float* resid, int64_t ldr,
                      void* out, int64_t ldo, const int32_t* out_row, const int32_t* a_row, int64_t a_rows, int M, int N, int K, int in_fmt,
-                     int out_fmt, int act, float alpha, float oscale, void* stream) {
+                     int out_fmt, int act, float alpha, float oscale, void* stream, const float* alpha_dev = nullptr) {
   HIPIE_REQUIRE(A && W && out, "gemm: null pointer");
   HIPIE_REQUIRE(in_fmt == HIPIE_F16 || in_fmt == HIPIE_HL8 || in_fmt == HIPIE_F32, "gemm: operand format %d (HIPIE_F16 | HIPIE_HL8 | HIPIE_F32)",
                 in_fmt);
@@ -115,7 +115,7 @@ static int gemm_impl(const void* A, int64_t lda, const void* W, int64_t ldw, con
   GemmParams p;
   gm_set_operands(p, A, lda, W, ldw, M, N, K, kq);
   p.bias = bias; p.resid = resid; p.ldr = ldr; p.out = (char*)out; p.ldo = ldo; p.out_row = out_row; p.a_row = a_row;
-  p.out_fmt = out_fmt; p.act = act; p.alpha = alpha; p.oscale = oscale;
+  p.out_fmt = out_fmt; p.act = act; p.alpha = alpha; p.oscale = oscale; p.alpha_dev = alpha_dev;
   hipStream_t st = (hipStream_t)stream;
   // K = 256 linears over many rows with a plain fp32 result: the thin-K kernel (gemm_k256.hip: X rows live in registers, the weight
   // streams through LDS in 32-feature chunks) where it is faster than the 256-column tiles -- N >= 384 (tools/bench_gemm_k256.py: -20 % at
@@ -125,7 +125,7 @@ static int gemm_impl(const void* A, int64_t lda, const void* W, int64_t ldw, con
   const bool k256_on = k256_mode == 1 || (k256_mode == 2 && N >= 384);
   // the thin-K kernel addresses X rows with 32-bit offsets from the base of the whole matrix: M rows must stay below 4 GiB
   if (k256_on && split && K == 256 && out_fmt == HIPIE_F32 && act == 0 && resid == nullptr && out_row == nullptr && a_row == nullptr &&
-      alpha == 1.f && oscale == 1.f && N % 32 == 0 && M >= 8192 && ldw * 2 == 1024 && (long)M * p.lda_b < (1L << 32))
+      alpha == 1.f && oscale == 1.f && alpha_dev == nullptr && N % 32 == 0 && M >= 8192 && ldw * 2 == 1024 && (long)M * p.lda_b < (1L << 32))
     return launch_gemm_k256(A, p.lda_b, a_f32 ? 1 : 0, W, p.ldw_b, bias, (float*)out, ldo, M, N, st);
   const bool wide = (N % 320 == 0);
   // problems that fill less than 3/8 of the CUs with 256-row tiles go to the 64 x 128 tile kernel (HIPIE_GEMM_SMALL=0: never; A/B timing)
@@ -166,6 +166,15 @@ extern "C" int hipie_gemm(const void* A, int64_t lda, const void* W, int64_t ldw
                           void* out, int64_t ldo, const int32_t* out_row, int M, int N, int K, int in_fmt, int out_fmt, int act, float alpha,
                           float oscale, void* stream) {
   return gemm_impl(A, lda, W, ldw, bias, resid, ldr, out, ldo, out_row, nullptr, 0, M, N, K, in_fmt, out_fmt, act, alpha, oscale, stream);
+}
+
+// hipie_gemm + a device factor of alpha.  The thin-K kernel (gemm_k256.hip) has no alpha at all, so a call WITH the pointer never goes there
+// (gemm_impl); every tile kernel reads it (gm_alpha_dev).  NULL: hipie_gemm, dispatch and bits.
+extern "C" int hipie_gemm_scaled(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, const float* resid, int64_t ldr,
+                                 void* out, int64_t ldo, const int32_t* out_row, int M, int N, int K, int in_fmt, int out_fmt, int act, float alpha,
+                                 float oscale, const float* alpha_dev, void* stream) {
+  HIPIE_REQUIRE(((uintptr_t)alpha_dev % 4) == 0, "gemm_scaled: alpha_dev must be 4-byte aligned");
+  return gemm_impl(A, lda, W, ldw, bias, resid, ldr, out, ldo, out_row, nullptr, 0, M, N, K, in_fmt, out_fmt, act, alpha, oscale, stream, alpha_dev);
 }
 
 extern "C" int hipie_gemm_gather(const void* A, int64_t lda, int64_t a_rows, const int32_t* a_row, const void* W, int64_t ldw, const float* bias,

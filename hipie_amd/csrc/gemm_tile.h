@@ -82,7 +82,15 @@ struct GemmParams {
   char* out2 = nullptr; long ldo2 = 0;
   int variant = 0;            // timing experiments (HIPIE_GEMM_VARIANTS builds only)
   int prio_mode = 0;          // gemm2: 0 none, 1 blocks 256..511 at low priority (phase offset), 2 by dispatch-round parity
+  // optional DEVICE factor of alpha (hipie_gemm_scaled: 1 / s of a gradient operand that was scaled by the power of two s, grad_pack.hip); a
+  // kernel reads it once per block, in front of its k loop (gm_alpha_dev).  NULL = off: alpha is used as it stands, today's bits.
+  const float* alpha_dev = nullptr;
 };
+
+// the epilogue's alpha of this block: the host's value, times the device factor when there is one
+__device__ __forceinline__ void gm_alpha_dev(GemmParams& p) {
+  if (p.alpha_dev != nullptr) p.alpha *= *p.alpha_dev;
+}
 
 __device__ __forceinline__ unsigned int gm_pack2(float a, float b) {
   typedef _Float16 h2 __attribute__((ext_vector_type(2)));
@@ -428,6 +436,7 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel(const GemmParams pin) {
   static_assert(MS == 32 || (MS == 16 && BN == 320 && SPLIT && (VAR == 0 || VAR == 2)),
                 "the 16x16x32 form exists for the wide split instances (HL8 and fp32 A rows) only");
   GemmParams p = pin;
+  gm_alpha_dev(p);
   int vtile = -1;
   if (VAR == 8) {
     // batched with the INNER index fastest (grid: tiles * n_inner x n_outer): the n_inner problems of one row tile share their A operand (the
@@ -848,7 +857,9 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel(const GemmParams pin) {
 // two workgroups per CU), one barrier per step: M = 2400, N = 256 becomes 76 workgroups of 8 short steps instead of 10 of them, and
 // M = 1552, N = 768, K = 3072 (BERT's output dense) 150 instead of 21.  Same operand formats, swizzle and epilogue as gemm_kernel.
 template <int VAR>
-__global__ __launch_bounds__(256, 2) void gemm_small_kernel(const GemmParams p) {
+__global__ __launch_bounds__(256, 2) void gemm_small_kernel(const GemmParams pin) {
+  GemmParams p = pin;
+  gm_alpha_dev(p);
   constexpr int BM = 64, BN = 128, ROWS = BM + BN, STAGE = ROWS * 128, NI = ROWS / 32;      // NI: DMA instructions per wave and stage
   typedef Mfma32<f16_t>::frag frag;
   extern __shared__ __attribute__((aligned(128))) char smem[];

@@ -2085,9 +2085,12 @@ def _gemm_tag(a, w, *args, **kw):
     return tag
 
 
+_NO_ALPHA_DEV = object()          # gemm's alpha_dev left out: hipie_gemm.  Given (a device tensor, or None for NULL): hipie_gemm_scaled
+
+
 @_timed(_gemm_tag)
 def gemm(a, w, bias=None, resid=None, out_fmt=F32, act=ACT_NONE, alpha=1.0, oscale=1.0, split=None, out=None, tag="gemm", out_row=None,
-         out_rows=None, a_row=None):
+         out_rows=None, a_row=None, alpha_dev=_NO_ALPHA_DEV):
     """out = ((act(alpha * a . w^T + bias)) + resid) * oscale on hipie_gemm.
     a (..., K) fp16 and w (N, K) fp16 (one product), or both HL8: a (..., 2K), w (N, 2K) fp16 (three products, fp32-class);
     `split` tells which (default: inferred -- pass it when K is ambiguous).  With split=True a may also be PLAIN fp32 (..., K) rows
@@ -2142,11 +2145,39 @@ def gemm(a, w, bias=None, resid=None, out_fmt=F32, act=ACT_NONE, alpha=1.0, osca
               o2.data_ptr(), o2.stride(0), None if out_row is None else out_row.data_ptr(), M, N, Kw,
               F32 if a_f32 else HL8, int(out_fmt), int(act), float(alpha), float(oscale))
         return out
+    if alpha_dev is not _NO_ALPHA_DEV:       # gemm_scaled: the same call plus the device factor of alpha (None: NULL, hipie_gemm's bits)
+        _call("hipie_gemm_scaled", a2.data_ptr(), a2.stride(0), _chk(w, "w"), w.shape[1], None if bias is None else bias.data_ptr(),
+              None if r2 is None else r2.data_ptr(), 0 if r2 is None else r2.stride(0), o2.data_ptr(), o2.stride(0),
+              None if out_row is None else out_row.data_ptr(), M, N, Kw, F32 if a_f32 else (HL8 if split else F16), int(out_fmt), int(act),
+              float(alpha), float(oscale), None if alpha_dev is None else alpha_dev.data_ptr())
+        return out
     _call("hipie_gemm", a2.data_ptr(), a2.stride(0), _chk(w, "w"), w.shape[1], None if bias is None else bias.data_ptr(),
           None if r2 is None else r2.data_ptr(), 0 if r2 is None else r2.stride(0), o2.data_ptr(), o2.stride(0),
           None if out_row is None else out_row.data_ptr(), M, N, Kw, F32 if a_f32 else (HL8 if split else F16), int(out_fmt), int(act),
           float(alpha), float(oscale))
     return out
+
+
+def _alpha_dev(who, alpha_dev):
+    """a one-element fp32 device tensor (a view into a scale block), or None"""
+    if alpha_dev is None:
+        return None
+    if not alpha_dev.is_cuda:
+        raise RuntimeError("Not implemented on the CPU (%s: alpha_dev must be a CUDA/HIP tensor)" % who)
+    if alpha_dev.dtype != torch.float32 or alpha_dev.numel() != 1:
+        raise RuntimeError("%s: alpha_dev must be one torch.float32 element, got %s %s" % (who, alpha_dev.dtype, tuple(alpha_dev.shape)))
+    return alpha_dev
+
+
+def gemm_scaled(a, w, alpha_dev, **kw):
+    """gemm (hipie_gemm_scaled) whose alpha is multiplied by the DEVICE scalar alpha_dev (one fp32 element, e.g. grad_scale(dy)[1:]) in the
+    kernel that writes the product: no host wait, no extra pass.  alpha_dev None: the NULL pointer, i.e. gemm's dispatch and bits.  The
+    a_row (gather) form has no scaled entry."""
+    if not a.is_cuda:
+        raise RuntimeError("Not implemented on the CPU (gemm_scaled: a must be a CUDA/HIP tensor)")
+    if kw.get("a_row") is not None:
+        raise RuntimeError("gemm_scaled: the gather form (a_row) has no scaled entry")
+    return gemm(a, w, alpha_dev=_alpha_dev("gemm_scaled", alpha_dev), **kw)
 
 
 @_timed(lambda qkv, tab_h, tab_w, grid_hw, heads: "vit_attn_global" if grid_hw[0] * grid_hw[1] > 256 else "vit_attn_window")
@@ -2180,6 +2211,87 @@ def gemm_split_k(a_hl8, w_hl8, nk):
     _call("hipie_gemm_batched", a_hl8.data_ptr(), K2, 0, 2 * Kc, w_hl8.data_ptr(), K2, 0, 2 * Kc, part.data_ptr(), N, 0, M * N, 1, nk, M, N, Kc,
           F32, 1.0)
     return part.sum(0)
+
+
+@_timed("gemm_split_k")
+def gemm_split_k_scaled(a_hl8, w_hl8, nk, alpha_dev):
+    """gemm_split_k whose partial products are added in chunk order and multiplied by the device scalar alpha_dev (None: 1) in ONE pass
+    (hipie_splitk_finish) instead of part.sum(0): the weight gradient of the scaled-gradient nodes.  M * N a multiple of 4."""
+    if not a_hl8.is_cuda or not w_hl8.is_cuda:
+        raise RuntimeError("Not implemented on the CPU (gemm_split_k_scaled: operands must be CUDA/HIP tensors)")
+    alpha_dev = _alpha_dev("gemm_split_k_scaled", alpha_dev)
+    if a_hl8.dim() != 2 or w_hl8.dim() != 2 or a_hl8.dtype != torch.float16 or w_hl8.dtype != torch.float16:
+        raise RuntimeError("gemm_split_k_scaled: HL8 (fp16) operands (M, 2K) / (N, 2K)")
+    M, K2 = a_hl8.shape
+    N = w_hl8.shape[0]
+    K = K2 // 2
+    if w_hl8.shape[1] != K2 or nk < 1 or nk > 64 or K % (32 * nk) or not a_hl8.is_contiguous() or not w_hl8.is_contiguous():
+        raise RuntimeError("gemm_split_k_scaled: contiguous operands (M, 2K) / (N, 2K), K a multiple of 32 * nk, nk <= 64")
+    if N % 8 or a_hl8.data_ptr() % 16 or w_hl8.data_ptr() % 16:
+        raise RuntimeError("gemm_split_k_scaled: N must be a multiple of 8, the operands 16-byte aligned")
+    Kc = K // nk
+    part = torch.empty(nk, M, N, dtype=torch.float32, device=a_hl8.device)
+    out = torch.empty(M, N, dtype=torch.float32, device=a_hl8.device)
+    _call("hipie_gemm_batched", a_hl8.data_ptr(), K2, 0, 2 * Kc, w_hl8.data_ptr(), K2, 0, 2 * Kc, part.data_ptr(), N, 0, M * N, 1, nk, M, N, Kc,
+          F32, 1.0)
+    _call("hipie_splitk_finish", part.data_ptr(), nk, M * N, None if alpha_dev is None else alpha_dev.data_ptr(), out.data_ptr())
+    return out
+
+
+def _grad_rows(who, dy):
+    """dy as the kernels of csrc/grad_pack.hip take it: 2-D fp32 on the device, contiguous rows, row stride a multiple of 4, 16-byte aligned"""
+    if not dy.is_cuda:
+        raise RuntimeError("Not implemented on the CPU (%s: dy must be a CUDA/HIP tensor)" % who)
+    if dy.dtype != torch.float32:
+        raise RuntimeError("%s: dy must be torch.float32, got %s" % (who, dy.dtype))
+    if dy.dim() != 2 or dy.shape[0] == 0 or dy.shape[1] == 0:
+        raise RuntimeError("%s: dy must be a non-empty 2-D tensor, got %s" % (who, tuple(dy.shape)))
+    if dy.stride(1) != 1 or (dy.shape[0] > 1 and (dy.stride(0) < dy.shape[1] or dy.stride(0) % 4)):
+        raise RuntimeError("%s: dy rows must be contiguous with a row stride that is a multiple of 4, got strides %s" % (who, tuple(dy.stride())))
+    if dy.data_ptr() % 16:
+        raise RuntimeError("%s: dy must be 16-byte aligned" % who)
+    return dy.stride(0) if dy.shape[0] > 1 else dy.shape[1]
+
+
+@_timed("grad_scale")
+def grad_scale(dy):
+    """hipie_grad_scale: dy (rows, N) fp32 device rows (N % 4 == 0; any row stride that is a multiple of 4) -> the device block {s, 1 / s},
+    a (2,) fp32 tensor: s = 2^e with max|dy| * 2^e in [2^14, 2^15), {1, 1} for an all-zero or non-finite dy.  No host wait."""
+    ldx = _grad_rows("grad_scale", dy)
+    if dy.shape[1] % 4:
+        raise RuntimeError("grad_scale: N=%d must be a multiple of 4" % dy.shape[1])
+    block = torch.empty(2, dtype=torch.float32, device=dy.device)
+    _call("hipie_grad_scale", dy.data_ptr(), ldx, dy.shape[0], dy.shape[1], block.data_ptr())
+    return block
+
+
+@_timed("grad_pack")
+def grad_pack(dy, scale, want_rows=True, want_t=True, want_bias=False, rows_p=None):
+    """hipie_grad_pack: ONE pass over dy (rows, N) fp32 with the device block `scale` = {s, 1 / s} of grad_scale ->
+    (the HL8 rows of s dy, (rows, 2N) fp16 | None,  the HL8 rows of (s dy)^T, (N, 2 rows_p) fp16 with zero pad columns | None,
+     db = dy.sum(0) of the UNSCALED values, (N,) fp32, summed in a fixed order | None).  N % 8 == 0; rows_p (default: rows rounded up to 32)
+    a multiple of 32.  Everything is refused before a launch."""
+    ldx = _grad_rows("grad_pack", dy)
+    if not scale.is_cuda:
+        raise RuntimeError("Not implemented on the CPU (grad_pack: scale must be a CUDA/HIP tensor)")
+    if scale.dtype != torch.float32 or scale.numel() != 2 or not scale.is_contiguous():
+        raise RuntimeError("grad_pack: scale must be the contiguous {s, 1 / s} block of grad_scale (2 x torch.float32)")
+    rows, N = dy.shape
+    if N % 8:
+        raise RuntimeError("grad_pack: N=%d must be a multiple of 8" % N)
+    rows_p = -(-rows // 32) * 32 if rows_p is None else int(rows_p)
+    if rows_p < rows or rows_p % 32:
+        raise RuntimeError("grad_pack: rows_p=%d must be a multiple of 32 and at least rows=%d (rows_p %% 32)" % (rows_p, rows))
+    out_r = torch.empty(rows, 2 * N, dtype=torch.float16, device=dy.device) if want_rows else None
+    out_t = torch.empty(N, 2 * rows_p, dtype=torch.float16, device=dy.device) if want_t else None
+    db = ws = None
+    if want_bias:
+        db = torch.empty(N, dtype=torch.float32, device=dy.device)
+        ws = torch.empty(_size("hipie_grad_pack_ws_bytes", rows_p, N), dtype=torch.uint8, device=dy.device)
+    _call("hipie_grad_pack", dy.data_ptr(), ldx, scale.data_ptr(), None if out_r is None else out_r.data_ptr(), 2 * N,
+          None if out_t is None else out_t.data_ptr(), 2 * rows_p, None if db is None else db.data_ptr(), None if ws is None else ws.data_ptr(),
+          rows, N, rows_p)
+    return out_r, out_t, db
 
 
 @_timed("gemm_batched")

@@ -111,16 +111,21 @@ def _weight_grad(g2, x2):
     linears -- a fraction of the 256 CUs -- so the M rows are cut into nk chunks, one problem each in ONE hipie_gemm_batched launch, and
     the partial products are summed (the 64 x 128-tile kernel the single problem fell to ran at 160 TFLOP/s: 0.51 ms per linear)."""
     M, N = g2.shape
-    K = x2.shape[1]
+    nk = _weight_grad_chunks(M, N, x2.shape[1])
+    gt, xt = ops.to_hl8_t(g2, 32), ops.to_hl8_t(x2, 32)                                           # (N | K, 2 Mp) fp16 pairs, one pass each
+    if nk == 1:
+        return ops.gemm(gt, xt, None, split=True, out_fmt=ops.F32, tag="train_dw")
+    return ops.gemm_split_k(gt, xt, nk)
+
+
+def _weight_grad_chunks(M, N, K):
+    """the chunks _weight_grad cuts the M rows into: doubled while the N x K tiles leave CUs idle and the 32-row groups divide evenly"""
     Mp = -(-M // 32) * 32
     tiles = -(-N // 256) * -(-K // 256)
     nk = 1
     while nk < 16 and tiles * nk < 256 and (Mp // 32) % (2 * nk) == 0:
         nk *= 2
-    gt, xt = ops.to_hl8_t(g2, 32), ops.to_hl8_t(x2, 32)                                           # (N | K, 2 Mp) fp16 pairs, one pass each
-    if nk == 1:
-        return ops.gemm(gt, xt, None, split=True, out_fmt=ops.F32, tag="train_dw")
-    return ops.gemm_split_k(gt, xt, nk)
+    return nk
 
 
 class SplitLinearFunction(torch.autograd.Function):
@@ -236,6 +241,142 @@ def split_mlp(x, w1, b1, w2, b2, act):
         return MlpFunction.apply(x, w1, b1, w2, b2, act)
     f = {ops.ACT_GELU: torch.nn.functional.gelu, ops.ACT_RELU: torch.nn.functional.relu}[act]
     return split_linear(f(split_linear(x, w1, b1, w1, "w")), w2, b2, w2, "w")
+
+
+# ---- the same two nodes with SCALED gradient operands (csrc/grad_pack.hip; the opt-in group "scaled_grads" of training/net.py).
+# The split hi = fp16(dy), lo = fp16(dy - hi) is 2^-22 accurate only while dy is a normal fp16 number: a gradient of 1e-6 per element
+# reaches the products above with ~1.6 % error, one of 1e-9 as zero, one above 65504 saturated.  Here every output gradient that enters a
+# split GEMM is first multiplied by a power of two chosen on the device from its largest magnitude (ops.grad_scale: amax lands in
+# [2^14, 2^15)), in the ONE pass that also writes both of its operand forms and the bias gradient (ops.grad_pack: three readers of dy
+# become one), and the products are multiplied back by the kernel that writes them (ops.gemm_scaled, ops.gemm_split_k_scaled).  All
+# factors are exact powers of two and every sum has a fixed order: the results for 2^e dy are 2^e times the results for dy, bit for bit.
+def _grad_rows(gy, N):
+    """the output gradient as the (M, N) fp32 rows ops.grad_scale / ops.grad_pack take: a view where the strides and the alignment allow"""
+    g2 = gy.reshape(-1, N).float()
+    if g2.stride(-1) != 1 or (g2.shape[0] > 1 and (g2.stride(0) < N or g2.stride(0) % 4)):
+        g2 = g2.contiguous()
+    return g2.clone() if g2.data_ptr() % 16 else g2
+
+
+def _scaled_weight_grad(gt, x2, inv):
+    """_weight_grad for a gradient that arrives PACKED: gt = (s dy)^T as HL8 (N, 2 Mp) from ops.grad_pack, inv = the device scalar 1 / s.
+    The same chunks; the partial products are added in chunk order and multiplied by inv in one pass (or, one chunk, in the GEMM's store)."""
+    nk = _weight_grad_chunks(x2.shape[0], gt.shape[0], x2.shape[1])
+    xt = ops.to_hl8_t(x2, 32)
+    if nk == 1:
+        return ops.gemm_scaled(gt, xt, inv, split=True, out_fmt=ops.F32, tag="train_dw")
+    return ops.gemm_split_k_scaled(gt, xt, nk, inv)
+
+
+class ScaledSplitLinearFunction(SplitLinearFunction):
+    """SplitLinearFunction (its forward, unchanged) with a backward on scaled operands:
+        {s, 1/s} = grad_scale(dy)       (s dy) rows, (s dy)^T, db = grad_pack(dy)        one pass over dy; a frozen input skips its form
+        dx = (1/s) (s dy) . W           dW = (1/s) (s dy)^T . x                          the factor is applied where the product is stored"""
+
+    @staticmethod
+    def backward(ctx, gy):
+        x2, weight = ctx.saved_tensors
+        N, K = weight.shape
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_b = ctx.has_bias and ctx.needs_input_grad[2]
+        gx = gw = gb = None
+        if not (need_x or need_w or need_b):
+            return None, None, None, None, None
+        g2 = _grad_rows(gy, N)
+        scale = ops.grad_scale(g2)
+        ga, gt, gb = ops.grad_pack(g2, scale, want_rows=need_x, want_t=need_w, want_bias=need_b)
+        inv = scale[1:]
+        if need_x:
+            wt_hl8, _, _ = ops.split_weight(ctx.owner, ctx.key + ".T", [weight], lambda: weight.t().contiguous())
+            gx = ops.gemm_scaled(ga, wt_hl8, inv, split=True, out_fmt=ops.F32, tag="train_dx").view(*ctx.lead, K)
+        if need_w:
+            gw = _scaled_weight_grad(gt, x2, inv)
+        return gx, gw, gb, None, None
+
+
+class ScaledMaskEinsumFunction(MaskEinsumFunction):
+    """MaskEinsumFunction (its forward, unchanged) whose backward scales the output gradient the same way: its two hipie_gemm_batched products
+    split grad_out into fp16 pairs too, and the per-pixel gradient of a mask loss is the smallest of the step (with the loss multiplied by
+    2^-20 every gradient behind the mask logits of the tiny fixture came out as zero).  The scale is the device block of ops.grad_scale; the
+    two multiplications are library passes over grad_out and the results (the products have no device-side alpha), not part of the linears'
+    pack.  A grad_out whose size is not a multiple of 4 runs the unscaled backward."""
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        go = grad_out.float().contiguous()
+        if go.numel() % 4 or go.data_ptr() % 16 or go.numel() == 0:
+            return MaskEinsumFunction.backward(ctx, grad_out)
+        e, f = ctx.saved_tensors
+        hw = go.shape[2] * go.shape[3]
+        scale = ops.grad_scale(go.view(-1, hw) if hw % 4 == 0 else go.view(1, -1))
+        ge, gf = ops.mask_einsum_backward(e, f, go * scale[0])
+        gb = grad_out.sum((2, 3)) if ctx.has_bias else None
+        return (ge * scale[1]).to(e.dtype), (gf * scale[1]).to(f.dtype), gb
+
+
+def mask_einsum_scaled(mask_embed, mask_features, row_bias=None):
+    return ScaledMaskEinsumFunction.apply(mask_embed, mask_features, row_bias)
+
+
+def split_linear_scaled(x, weight, bias, owner, key):
+    """split_linear with the scaled-gradient backward (ScaledSplitLinearFunction); the same shapes, the same fall-through to the library"""
+    if _split_linear_ok(x, weight, x.numel() // weight.shape[1] if weight.shape[1] else 0):
+        return ScaledSplitLinearFunction.apply(x, weight, bias, owner, key)
+    return torch.nn.functional.linear(x, weight, bias)
+
+
+class ScaledMlpFunction(MlpFunction):
+    """MlpFunction (its forward, unchanged) with a backward on scaled operands; dy and du each get a scale of their own:
+        {sy, 1/sy} = grad_scale(dy)     (sy dy) rows, (sy dy)^T, db2 = grad_pack(dy)
+        da = (1/sy) (sy dy) . W2        dW2 = (1/sy) (sy dy)^T . a
+        du, a, db1 = act_backward       (unscaled: du = da * act'(u) is a product, so a power of two in da passes through it exactly)
+        {su, 1/su} = grad_scale(du)     (su du) rows, (su du)^T = grad_pack(du)
+        dW1 = (1/su) (su du)^T . x      dx = (1/su) (su du) . W1"""
+
+    @staticmethod
+    def backward(ctx, gy):
+        x2, u, w1, w2 = ctx.saved_tensors
+        need_x, need_w1, need_b1, need_w2, need_b2 = ctx.needs_input_grad[:5]
+        need_b1, need_b2 = need_b1 and ctx.has_b1, need_b2 and ctx.has_b2
+        gx = gw1 = gb1 = gw2 = gb2 = du = a = None
+        if not (need_x or need_w1 or need_b1 or need_w2 or need_b2):
+            return None, None, None, None, None, None
+        need_da = need_x or need_w1 or need_b1
+        g2 = _grad_rows(gy, w2.shape[0])
+        sy = ops.grad_scale(g2)
+        ga, gt, gb2 = ops.grad_pack(g2, sy, want_rows=need_da, want_t=need_w2, want_bias=need_b2)
+        del g2
+        if need_da:
+            w2t_hl8, _, _ = ops.split_weight(w2, "w.T", [w2], lambda: w2.t().contiguous())
+            da = ops.gemm_scaled(ga, w2t_hl8, sy[1:], split=True, out_fmt=ops.F32, tag="train_dx")
+            ga = None
+            du, a, gb1 = ops.act_backward(u, da, ctx.act, want_a=need_w2, want_bias_grad=need_b1, out=da)
+            del da
+        elif need_w2:
+            a = ops.act_forward(u, ctx.act)
+        if need_w2:
+            gw2 = _scaled_weight_grad(gt, a, sy[1:])
+        a = gt = None
+        if need_x or need_w1:
+            su = ops.grad_scale(du)
+            ua, ut, _ = ops.grad_pack(du, su, want_rows=need_x, want_t=need_w1)
+            del du
+            if need_w1:
+                gw1 = _scaled_weight_grad(ut, x2, su[1:])
+            if need_x:
+                w1t_hl8, _, _ = ops.split_weight(w1, "w.T", [w1], lambda: w1.t().contiguous())
+                gx = ops.gemm_scaled(ua, w1t_hl8, su[1:], split=True, out_fmt=ops.F32, tag="train_dx").view(*ctx.lead, w1.shape[1])
+        return gx, gw1, gb1, gw2, gb2, None
+
+
+def split_mlp_scaled(x, w1, b1, w2, b2, act):
+    """split_mlp with the scaled-gradient backward (ScaledMlpFunction) under the same conditions; any other shape runs the three-node
+    composition over split_linear_scaled, so nothing is refused"""
+    rows = x.numel() // w1.shape[1] if w1.shape[1] else 0
+    if _split_linear_ok(x, w1, rows) and _split_linear_ok(x, w2, rows) and act in (ops.ACT_GELU, ops.ACT_RELU):
+        return ScaledMlpFunction.apply(x, w1, b1, w2, b2, act)
+    f = {ops.ACT_GELU: torch.nn.functional.gelu, ops.ACT_RELU: torch.nn.functional.relu}[act]
+    return split_linear_scaled(f(split_linear_scaled(x, w1, b1, w1, "w")), w2, b2, w2, "w")
 
 
 def _attention_forward(ctx, qa, ka, v, cols, forward_op):

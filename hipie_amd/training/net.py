@@ -363,6 +363,42 @@ class HipBackendConvs(HipBackend):
         return conv3x3_train(x, weight, bias, relu)
 
 
+class HipBackendScaledGrads(HipBackend):
+    """HipBackend + SCALED gradient operands in the backward of the split linears -- the ViT qkv / proj / fc1 / fc2 and the encoder FFNs: every
+    output gradient that enters a split GEMM is first multiplied by a power of two chosen on the device from its largest magnitude, in the
+    one pass that writes both of its operand forms and the bias gradient (csrc/grad_pack.hip), and the product is multiplied back where it is
+    stored (functions.ScaledSplitLinearFunction / ScaledMlpFunction).  The raw split of HipBackend.linear is 2^-22 accurate only while dy
+    is a normal fp16 number (6.1e-5 .. 65504 per element); with the scale the accuracy does not depend on the magnitude of dy.  The
+    forward is HipBackend.linear's, bit for bit.  NEW ops, so no op is defined by two groups: _blin asks linear_scaled first, _bmlp
+    asks mlp_scaled first when the backend also has `mlp` (without it: the three nodes over _blin), and the mask logits ask
+    mask_einsum_scaled first -- the mask contraction's backward splits its output gradient too, and with a small loss it is the first to
+    lose it (tests/test_gpu_grad_scale.py, the step with the loss multiplied by 2^-20).
+    Opt-in: TrainStep's default stays HipBackend.  Not here: dy of the convolution node (functions.Conv3x3Function), the decoder / head
+    F.linear calls, loss scaling of the whole step, making the group the default."""
+
+    @staticmethod
+    def linear_scaled(x, sd, p):
+        """HipBackend.linear with the scaled-gradient backward (functions.split_linear_scaled)"""
+        from .functions import split_linear_scaled
+        w = sd[p + "weight"]
+        return split_linear_scaled(x, w, sd.get(p + "bias"), w, "w")
+
+    @staticmethod
+    def mask_einsum_scaled(mask_embed, mask_features):
+        """HipBackend.mask_einsum whose backward scales the output gradient in front of its two split products (functions.ScaledMaskEinsumFunction):
+        the per-pixel gradient of the mask losses is the smallest of the step"""
+        from .functions import mask_einsum_scaled
+        return mask_einsum_scaled(mask_embed, mask_features)
+
+    @staticmethod
+    def mlp_scaled(x, sd, p_fc1, p_fc2, act):
+        """HipBackendMlp.mlp with the scaled-gradient backward (functions.split_mlp_scaled)"""
+        from .. import ops
+        from .functions import split_mlp_scaled
+        return split_mlp_scaled(x, sd[p_fc1 + "weight"], sd.get(p_fc1 + "bias"), sd[p_fc2 + "weight"], sd.get(p_fc2 + "bias"),
+                                {"gelu": ops.ACT_GELU, "relu": ops.ACT_RELU}[act])
+
+
 # the opt-in kernel groups by name; a composed class lists its bases in this order
 GROUPS = {"norms": HipBackendNorms, "mlp": HipBackendMlp, "windows": HipBackendWindows, "packed_attention": HipBackendPackedAttention,
           "packed_windows": HipBackendPackedWindows, "deformable": HipBackendDeformable, "losses": HipBackendLosses, "criteria": HipBackendCriteria,
@@ -371,7 +407,8 @@ GROUPS = {"norms": HipBackendNorms, "mlp": HipBackendMlp, "windows": HipBackendW
 EXTRA_GROUPS = {"group_norms": HipBackendGroupNorms}
 # the table every later group joins, at its end: a composed class lists these after the GROUPS and EXTRA_GROUPS classes.
 # It GROWS: a test may assert that a name is in it and where it stands relative to another name, never the table's full contents.
-LATER_GROUPS = {"query_attention": HipBackendQueryAttention, "fusion_attention": HipBackendFusionAttention, "convs": HipBackendConvs}
+LATER_GROUPS = {"query_attention": HipBackendQueryAttention, "fusion_attention": HipBackendFusionAttention, "convs": HipBackendConvs,
+                "scaled_grads": HipBackendScaledGrads}
 # Among the bases of a composed class the two attention groups keep the END, in this order (tests/test_fusion_attention_cpu.py pins
 # HipBackendFusionAttention as the last base of the every-group class); a group that joins LATER_GROUPS behind them is listed in front of
 # them.  The groups are unrelated by inheritance and share no op, so the order of the bases changes nothing a step computes.
@@ -511,15 +548,18 @@ def get_rel_pos(q_size, k_size, rel_pos):
 
 
 def _blin(x, sd, p, be):
-    """a linear that carries flops: the backend's split-GEMM form when it has one (HipBackend.linear), else F.linear"""
-    f = getattr(be, "linear", None)
+    """a linear that carries flops: the backend's split-GEMM form when it has one (HipBackend.linear; HipBackendScaledGrads.linear_scaled
+    in front of it), else F.linear"""
+    f = getattr(be, "linear_scaled", None) or getattr(be, "linear", None)
     return f(x, sd, p) if f is not None else lin(x, sd, p)
 
 
 def _bmlp(x, sd, p_fc1, p_fc2, act, be):
-    """linear -> activation -> linear: the backend's one-node form when it has one (HipBackendMlp.mlp), else the three nodes"""
+    """linear -> activation -> linear: the backend's one-node form when it has one (HipBackendMlp.mlp; with it, HipBackendScaledGrads.mlp_scaled
+    in front of it), else the three nodes"""
     f = getattr(be, "mlp", None)
     if f is not None:
+        f = getattr(be, "mlp_scaled", None) or f
         return f(x, sd, p_fc1, p_fc2, act)
     return _blin((F.gelu if act == "gelu" else F.relu)(_blin(x, sd, p_fc1, be)), sd, p_fc2, be)
 
@@ -904,7 +944,8 @@ def maskdino_decoder(ms_feats, mask_features, sd, p, cfg, be, dn=None, topk_over
 
     def heads(x):
         d = ln(x, sd, p + "decoder_norm.")
-        return lin(d, sd, p + "class_embed."), be.mask_einsum(mlp(d, sd, p + "mask_embed.", 3), mask_features)
+        einsum = getattr(be, "mask_einsum_scaled", None) or be.mask_einsum       # HipBackendScaledGrads: the same forward, a scaled backward
+        return lin(d, sd, p + "class_embed."), einsum(mlp(d, sd, p + "mask_embed.", 3), mask_features)
     ic, im = heads(tgt_undetach)
     interm = {"pred_logits": ic, "pred_boxes": ref_undetach.sigmoid(), "pred_masks": im}
     tgt, ref_un, tgt_mask = tgt_undetach.detach(), ref_undetach.detach(), None

@@ -833,6 +833,17 @@ int hipie_gemm(const void* A, int64_t lda, const void* W, int64_t ldw, const flo
                float oscale, void* stream);
 
 /*
+ * hipie_gemm with a DEVICE factor of alpha: y = (alpha * alpha_dev[0]) * acc + bias, everything else as hipie_gemm.  alpha_dev is read once
+ * per workgroup; it is the 1 / s of hipie_grad_scale when A holds a gradient that was scaled by s (hipie_grad_pack), so the product leaves
+ * un-scaled without a pass of its own.  alpha_dev NULL: hipie_gemm, the same dispatch and the same bits.  With the pointer the call never
+ * goes to the thin-K kernel (which has no alpha); every tile kernel honours it.
+ * Replaces: a separate `dx * inv` pass over the input gradient of torch.nn.functional.linear's backward.
+ */
+int hipie_gemm_scaled(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, const float* resid, int64_t ldr,
+                      void* out, int64_t ldo, const int32_t* out_row, int M, int N, int K, int in_fmt, int out_fmt, int act, float alpha,
+                      float oscale, const float* alpha_dev, void* stream);
+
+/*
  * hipie_gemm (HIPIE_HL8 activations) with the two CROSS terms on block-scaled FP8 -- the opt-in `fp8x` precision policy:
  *     acc = W_hi . A_hi  +  q8(W_lo) . q8(A_hi)  +  q8(W_hi) . q8(A_lo)          fp32 accumulation
  * q8 = OCP e4m3 with one power-of-two (E8M0) scale per 32 k-elements: e = the largest integer with amax * 2^e <= 448 over the block (amax = 0:
@@ -980,6 +991,34 @@ int hipie_to_hl8(const void* x, int64_t ldx, void* out, int64_t ldo, int64_t row
  * The producer of both operands of the weight gradient dW = dy^T . x of a Linear (torch.nn.functional.linear's backward in the reference's
  * training step, hipie/backbone/vit.py:67-83 and every other Linear): the contraction runs over the token rows. */
 int hipie_to_hl8_t(const void* x, int64_t ldx, void* out, int64_t ldo, int64_t rows, int C, int64_t rows_p, float scale, void* stream);
+
+/*
+ * Scaled gradient operands of the training linears (csrc/grad_pack.hip; the opt-in backend group "scaled_grads"): the output gradient dy of
+ * a Linear is multiplied by a power of two s chosen ON THE DEVICE before it is split into fp16 pairs, and the products are multiplied by 1 / s
+ * where they are written.  The raw split is 2^-22 accurate only while dy is a normal fp16 number (6.1e-5 .. 65504); with s the accuracy
+ * does not depend on the magnitude of dy.  No host wait, no floating-point atomic, the same bits on every call.
+ *
+ * hipie_grad_scale:  x (rows, N) f32, row stride ldx (N and ldx multiples of 4, 16-byte aligned) -> scale = {s, 1 / s} (two device floats,
+ *   8-byte aligned): s = 2^e with max|x| * 2^e in [2^14, 2^15), e taken from the exponent bits of the maximum (an integer maximum of the bit
+ *   patterns) and clamped to +-126 so that both floats are normal; max|x| == 0, inf or NaN: {1, 1}.
+ *   Replaces: the torch.exp2(torch.floor(torch.log2(...))) chain the attention nodes form their scale with (training/functions.py).
+ * hipie_grad_pack:  ONE pass over dy (rows, N) f32 (row stride ldx; N a multiple of 8) that reads scale[0] = s and writes, each unless NULL,
+ *   out_rows (rows, 2 N) HL8 of s dy, row stride ldo: the A operand of dx = dy . W, the bits of hipie_to_hl8(dy, scale = s);
+ *   out_t    (N, 2 rows_p) HL8 of (s dy)^T, row stride ldt, columns rows <= m < rows_p zero (rows_p a multiple of 32): the operand of
+ *            dW = dy^T . x, the bits of hipie_to_hl8_t(dy, scale = s);
+ *   dbias    (N) f32 = sum over the rows of the UNSCALED dy: per-tile column sums in ws (hipie_grad_pack_ws_bytes(rows_p, N) bytes), added in
+ *            tile order.  dbias and ws come together.
+ *   Replaces: the three readers of dy in torch.nn.functional.linear's backward on the split GEMM -- the in-kernel split of hipie_gemm's
+ *   HIPIE_F32 rows, hipie_to_hl8_t and dy.sum(0) (hipie/backbone/vit.py:67-83, 193-197 and every other big Linear of the step).
+ * hipie_splitk_finish:  out (n) f32 = (part[0] + part[1] + .. + part[nk - 1]) * alpha_dev[0], part (nk, n) f32 the partial products of one
+ *   hipie_gemm_batched launch over chunks of the contraction, added in chunk order; alpha_dev NULL: 1.  n a multiple of 4, nk <= 64.
+ *   Replaces: part.sum(0) behind the split-K weight gradient, and the multiplication by 1 / s.
+ */
+int hipie_grad_scale(const void* x, int64_t ldx, int64_t rows, int N, void* scale, void* stream);
+int64_t hipie_grad_pack_ws_bytes(int64_t rows_p, int N);
+int hipie_grad_pack(const void* dy, int64_t ldx, const void* scale, void* out_rows, int64_t ldo, void* out_t, int64_t ldt, void* dbias, void* ws,
+                    int64_t rows, int N, int64_t rows_p, void* stream);
+int hipie_splitk_finish(const void* part, int nk, int64_t n, const float* alpha_dev, void* out, void* stream);
 
 /*
  * hipie_gemm on n_outer x n_inner independent problems in ONE launch (split-fp16 HL8 operands only, no bias / residual / activation):
