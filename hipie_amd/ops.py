@@ -77,6 +77,7 @@ def _timed(tag):
             return out
         wrapper.__doc__ = fn.__doc__
         wrapper.__name__ = fn.__name__
+        wrapper.__wrapped__ = fn
         return wrapper
     return deco
 
@@ -116,24 +117,70 @@ def _alloc(shape, dtype, device):
     return torch.empty(shape, dtype=dtype, device=device)
 
 
-def _chk(t, name, dtype=None):
-    if not t.is_cuda:
-        raise RuntimeError("Not implemented on the CPU (%s must be a CUDA/HIP tensor)" % name)
-    if not t.is_contiguous():
-        raise RuntimeError("%s tensor has to be contiguous" % name)
-    if dtype is not None and t.dtype != dtype:
-        raise RuntimeError("%s must be %s, got %s" % (name, dtype, t.dtype))
-    return t.data_ptr()
+# ---- the operand checks of every op below.  Each helper does one thing; only _dense_f32 may copy.  The rule: every tensor whose address
+# goes to _call is refused by _on_device while it is a host tensor, before _call and before a _size query that depends on it.
+def _on_device(op, names, *tensors):
+    """refuses host tensors: `names` = the operands' names in one string, `tensors` in that order (None: an operand that is left out)"""
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            i = [x is t for x in tensors].index(True)
+            raise RuntimeError("Not implemented on the CPU (%s: %s must be a CUDA/HIP tensor)" % (op, names.split()[i]))
 
 
-def _dense_f32(t, name, align16=False):
+_DENSE, _ROWS, _ANY = 0, 1, 2          # _layout's density: contiguous | last dimension contiguous (rows may be strided) | no requirement
+
+
+def _layout(op, name, t, dtype=None, shape=None, ndim=None, density=_DENSE, row_mult=1, align16=False):
+    """refuses t unless it has that dtype (or one of a tuple), that shape / rank, that density (with _ROWS: a row stride that is a multiple
+    of row_mult) and, with align16, a 16-byte aligned address.  Nothing is copied, the device is not looked at; returns t (None, an
+    optional operand left out, passes)"""
+    if t is None:
+        return None
+    if dtype is not None and t.dtype is not dtype and (type(dtype) is not tuple or t.dtype not in dtype):
+        raise RuntimeError("%s: %s must be %s, got %s" % (op, name, " / ".join(map(str, dtype)) if type(dtype) is tuple else dtype, t.dtype))
+    if ndim is not None and t.dim() != ndim:
+        raise RuntimeError("%s: %s must have %d dimensions, got %s" % (op, name, ndim, tuple(t.shape)))
+    if shape is not None and t.shape != shape:          # torch.Size is a tuple: it compares with the tuple the caller wrote
+        raise RuntimeError("%s: %s must be %s, got %s" % (op, name, tuple(shape), tuple(t.shape)))
+    if density == _DENSE:
+        if not t.is_contiguous():
+            raise RuntimeError("%s: %s tensor has to be contiguous" % (op, name))
+    elif density == _ROWS:
+        if t.stride(-1) != 1:
+            raise RuntimeError("%s: %s: the last dimension has to be dense (contiguous rows), got strides %s" % (op, name, tuple(t.stride())))
+        if row_mult > 1 and t.shape[-2] > 1 and t.stride(-2) % row_mult:
+            raise RuntimeError("%s: %s: the row stride must be a multiple of %d, got strides %s" % (op, name, row_mult, tuple(t.stride())))
+    if align16 and t.data_ptr() % 16:
+        raise RuntimeError("%s: %s must be 16-byte aligned" % (op, name))
+    return t
+
+
+def _dense_f32(op, name, t, align16=False):
     """t as a dense fp32 device tensor, with align16 on a 16-byte boundary: a strided view, or one at an odd storage offset, is copied"""
-    if not t.is_cuda:
-        raise RuntimeError("Not implemented on the CPU (%s must be a CUDA/HIP tensor)" % name)
-    if t.dtype != torch.float32:
-        raise RuntimeError("%s must be torch.float32, got %s" % (name, t.dtype))
+    if not t.is_cuda or t.dtype is not torch.float32:          # the refusals are the vocabulary's; the usual call pays for neither
+        _on_device(op, name, t)
+        _layout(op, name, t, torch.float32, density=_ANY)
     t = t.contiguous()
     return t.clone() if align16 and t.data_ptr() % 16 else t
+
+
+def _ptr(t):
+    """the address of an optional operand, or NULL"""
+    return t.data_ptr() if t is not None else None
+
+
+def _workspace(ws, need, device, what):
+    """the caller's byte workspace when it is given (checked), else one that lives for the call"""
+    if ws is None:
+        return torch.empty(need, dtype=torch.uint8, device=device)
+    if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need:
+        raise RuntimeError("%s: workspace of %d contiguous uint8 elements needed, got %s %s" % (what, need, ws.dtype, tuple(ws.shape)))
+    return ws
+
+
+def _f16_planes(shape, device):
+    """the (hi, lo) fp16 planes of a split operand, uninitialised (the sizes go to torch.empty one by one: a tuple is parsed twice as slowly)"""
+    return torch.empty(*shape, dtype=torch.float16, device=device), torch.empty(*shape, dtype=torch.float16, device=device)
 
 
 def _check_im2col_step(B, im2col_step):
@@ -155,10 +202,12 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
     if value.dtype not in _DT and not f64:
         raise RuntimeError("ms_deform_attn_forward: unsupported dtype %s" % value.dtype)
     aux = torch.float64 if f64 else torch.float32
+    who = "ms_deform_attn_forward"
+    _on_device(who, "value spatial_shapes level_start_index sampling_loc attn_weight", value, spatial_shapes, level_start_index, sampling_loc, attn_weight)
     out = torch.empty(B, Lq, M * D, dtype=value.dtype, device=value.device)
-    _call("hipie_msda_forward", _chk(value, "value"), _chk(spatial_shapes, "spatial_shapes", torch.int64),
-          _chk(level_start_index, "level_start_index", torch.int64), _chk(sampling_loc, "sampling_loc", aux),
-          _chk(attn_weight, "attn_weight", aux), out.data_ptr(), B, S, M, D, L, Lq, P, F64 if f64 else _DT[value.dtype])
+    _call("hipie_msda_forward", _layout(who, "value", value).data_ptr(), _layout(who, "spatial_shapes", spatial_shapes, torch.int64).data_ptr(),
+          _layout(who, "level_start_index", level_start_index, torch.int64).data_ptr(), _layout(who, "sampling_loc", sampling_loc, aux).data_ptr(),
+          _layout(who, "attn_weight", attn_weight, aux).data_ptr(), out.data_ptr(), B, S, M, D, L, Lq, P, F64 if f64 else _DT[value.dtype])
     return out
 
 
@@ -172,16 +221,17 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
     dt = value.dtype
     if dt not in (torch.float32, torch.float64):
         raise RuntimeError("ms_deform_attn_backward: float32 / float64 only (got %s)" % dt)
-    if not value.is_cuda:
-        raise RuntimeError("Not implemented on the CPU (ms_deform_attn_backward)")
+    who = "ms_deform_attn_backward"
+    _on_device(who, "value spatial_shapes level_start_index sampling_loc attn_weight grad_output", value, spatial_shapes, level_start_index, sampling_loc,
+               attn_weight, grad_output)
     gv = torch.empty_like(value, memory_format=torch.contiguous_format)
     gl = torch.empty(sampling_loc.shape, dtype=dt, device=value.device)
     ga = torch.empty(attn_weight.shape, dtype=dt, device=value.device)
     need = _size("hipie_msda_backward_workspace", B, S, M, L, Lq, P) if dt == torch.float32 and D == 32 and B * Lq > 0 else 0
-    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=value.device)      # the gather form's bins and corner records (fp32, D = 32)
-    _call("hipie_msda_backward_ws", _chk(value, "value", dt), _chk(spatial_shapes, "spatial_shapes", torch.int64),
-          _chk(level_start_index, "level_start_index", torch.int64), _chk(sampling_loc, "sampling_loc", dt),
-          _chk(attn_weight, "attn_weight", dt), _chk(grad_output.contiguous(), "grad_output", dt),
+    ws = _workspace(None, max(need, 16), value.device, who)      # the gather form's bins and corner records (fp32, D = 32)
+    _call("hipie_msda_backward_ws", _layout(who, "value", value, dt).data_ptr(), _layout(who, "spatial_shapes", spatial_shapes, torch.int64).data_ptr(),
+          _layout(who, "level_start_index", level_start_index, torch.int64).data_ptr(), _layout(who, "sampling_loc", sampling_loc, dt).data_ptr(),
+          _layout(who, "attn_weight", attn_weight, dt).data_ptr(), _layout(who, "grad_output", grad_output.contiguous(), dt).data_ptr(),
           gv.data_ptr(), gl.data_ptr(), ga.data_ptr(), B, S, M, D, L, Lq, P, F64 if dt == torch.float64 else F32, ws.data_ptr(), need)
     return gv, gl, ga
 
@@ -205,26 +255,24 @@ def msda_fused(value, spatial_shapes, level_start_index, ref, offsets, logits):
     if offsets.stride(0) != Lq * off_stride or logits.stride(0) != Lq * lg_stride or \
             offsets[0, 0].stride() != (L * P * 2, P * 2, 2, 1) or logits[0, 0].stride() != (L * P, 1):
         raise RuntimeError("msda_fused: offsets/logits rows must be dense (M,L,P,2)/(M,L*P) blocks")
-    for t, n in ((offsets, "offsets"), (logits, "logits")):
-        if not t.is_cuda:
-            raise RuntimeError("Not implemented on the CPU (%s)" % n)
+    who = "msda_fused"
+    _on_device(who, "offsets logits value spatial_shapes level_start_index ref", offsets, logits, value, spatial_shapes, level_start_index, ref)
     out = torch.empty(B, Lq, M * D, dtype=value.dtype, device=value.device)
-    if not value.is_cuda or value.dtype not in _DT:
-        raise RuntimeError("Not implemented on the CPU (value)" if not value.is_cuda else "msda_fused: bad value dtype")
+    if value.dtype not in _DT:
+        raise RuntimeError("msda_fused: bad value dtype")
+    _layout(who, "spatial_shapes", spatial_shapes, torch.int64)
+    _layout(who, "level_start_index", level_start_index, torch.int64)
+    _layout(who, "ref", ref, torch.float32)
     # dense values go in with row stride 0 (= M * D inside the library): the % 8 requirement applies to strided column blocks only
     _call("hipie_msda_fused_forward_strided", value.data_ptr(), 0 if value.is_contiguous() else vrow,
-          _chk(spatial_shapes, "spatial_shapes", torch.int64), _chk(level_start_index, "level_start_index", torch.int64),
-          _chk(ref, "ref", torch.float32), offsets.data_ptr(), logits.data_ptr(), out.data_ptr(),
+          spatial_shapes.data_ptr(), level_start_index.data_ptr(), ref.data_ptr(), offsets.data_ptr(), logits.data_ptr(), out.data_ptr(),
           B, S, M, D, L, Lq, P, ref.shape[-1], _DT[value.dtype], _DT[offsets.dtype], off_stride, lg_stride)
     return out
 
 
 def _raw_rows(t, name, B, Lq, inner):
-    """row stride of offsets / logits or of their gradients: dense (M,L,P,2) / (M,L*P) blocks at a common distance, fp32, on the device"""
-    if not t.is_cuda:
-        raise RuntimeError("Not implemented on the CPU (%s)" % name)
-    if t.dtype != torch.float32:
-        raise RuntimeError("%s must be torch.float32, got %s" % (name, t.dtype))
+    """row stride of offsets / logits or of their gradients: dense (M,L,P,2) / (M,L*P) blocks at a common distance, fp32"""
+    _layout("msda_raw_backward", name, t, torch.float32, density=_ANY)
     if tuple(t.shape[:2]) != (B, Lq) or tuple(t[0, 0].stride()) != inner or t.stride(0) != Lq * t.stride(1):
         raise RuntimeError("msda_raw_backward: %s rows must be dense blocks of one (B, Lq, k) tensor" % name)
     return t.stride(1)
@@ -250,17 +298,21 @@ def msda_raw_backward(value, spatial_shapes, level_start_index, ref, offsets, lo
         return gv, grad_offsets, grad_logits, gref
     if Lq == 0:
         return gv.zero_(), grad_offsets, grad_logits, gref
+    who = "msda_raw_backward"
+    _on_device(who, "offsets logits grad_offsets grad_logits value spatial_shapes level_start_index ref grad_output",
+               offsets, logits, grad_offsets, grad_logits, value, spatial_shapes, level_start_index, ref, grad_output)
     off_in, lg_in = (L * P * 2, P * 2, 2, 1), (L * P, 1)
     strides = (_raw_rows(offsets, "offsets", B, Lq, off_in), _raw_rows(logits, "logits", B, Lq, lg_in),
                _raw_rows(grad_offsets, "grad_offsets", B, Lq, off_in), _raw_rows(grad_logits, "grad_logits", B, Lq, lg_in))
     rd = int(ref.shape[-1])
     need = _size("hipie_msda_raw_backward_ws_bytes", B, S, M, L, Lq, P, rd, int(bool(want_grad_ref)))
-    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    ws = _workspace(None, max(need, 16), dev, who)
     go = grad_output.contiguous()
-    _call("hipie_msda_raw_backward", _chk(value, "value", torch.float32), _chk(spatial_shapes, "spatial_shapes", torch.int64),
-          _chk(level_start_index, "level_start_index", torch.int64), _chk(ref, "ref", torch.float32), offsets.data_ptr(), logits.data_ptr(),
-          _chk(go, "grad_output", torch.float32), gv.data_ptr(), grad_offsets.data_ptr(), grad_logits.data_ptr(),
-          gref.data_ptr() if want_grad_ref else None, B, S, M, D, L, Lq, P, rd, *strides, ws.data_ptr(), need)
+    _call("hipie_msda_raw_backward", _layout(who, "value", value, torch.float32).data_ptr(),
+          _layout(who, "spatial_shapes", spatial_shapes, torch.int64).data_ptr(), _layout(who, "level_start_index", level_start_index, torch.int64).data_ptr(),
+          _layout(who, "ref", ref, torch.float32).data_ptr(), offsets.data_ptr(), logits.data_ptr(),
+          _layout(who, "grad_output", go, torch.float32).data_ptr(), gv.data_ptr(), grad_offsets.data_ptr(), grad_logits.data_ptr(),
+          _ptr(gref), B, S, M, D, L, Lq, P, rd, *strides, ws.data_ptr(), need)
     return gv, grad_offsets, grad_logits, gref
 
 
@@ -276,23 +328,23 @@ def flash_attn(q, k, v, scale, bias_h=None, bias_w=None, key_mask=None, clamp=0.
         if k.dtype != torch.float16 or q.dtype != torch.float16 or not k.is_contiguous() or tuple(k.shape) != (B, Nk, 2 * H * hd):
             raise RuntimeError("flash_attn: k_hl8 expects a contiguous (B, Nk, 2*H*hd) fp16 HL8 buffer and fp16 q / v")
         ks = (Nk * 2 * H * hd, 2 * H * hd, 2 * hd)
+    _on_device("flash_attn", "q k v bias_h bias_w key_mask", q, k, v, bias_h, bias_w if bias_h is not None else None, key_mask)
     for t, n in ((q, "q"), (v, "v")) + (() if k_hl8 else ((k, "k"),)):
-        if not t.is_cuda:
-            raise RuntimeError("Not implemented on the CPU (%s)" % n)
-        if t.stride(-1) != 1 or t.dtype != q.dtype or t.dtype not in (torch.float16, torch.bfloat16):
-            raise RuntimeError("flash_attn: %s must be fp16/bf16 with contiguous head_dim" % n)
+        if t.dtype != q.dtype:
+            raise RuntimeError("flash_attn: %s must have q's dtype %s, got %s" % (n, q.dtype, t.dtype))
+        _layout("flash_attn", n, t, (torch.float16, torch.bfloat16), density=_ROWS)
     out = torch.empty(B, Nq, H * hd, dtype=torch.float32 if out_f32 else q.dtype, device=q.device)
     kh = kw = 0
-    bhp = bwp = mp = None
     if bias_h is not None:
         kh, kw = bias_h.shape[-2], bias_w.shape[-1]
-        bhp, bwp = _chk(bias_h, "bias_h", torch.float32), _chk(bias_w, "bias_w", torch.float32)
+        _layout("flash_attn", "bias_h", bias_h, torch.float32)
+        _layout("flash_attn", "bias_w", bias_w, torch.float32)
     if key_mask is not None:
         key_mask = key_mask.to(torch.uint8).contiguous()
-        mp = _chk(key_mask, "key_mask")
     _call("hipie_flash_attn", q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, H, Nq, Nk, hd,
           q.stride(0), q.stride(1), q.stride(2), *(ks if k_hl8 else (k.stride(0), k.stride(1), k.stride(2))),
-          v.stride(0), v.stride(1), v.stride(2), Nq * H * hd, H * hd, hd, bhp, bwp, kh, kw, mp, float(scale), float(clamp),
+          v.stride(0), v.stride(1), v.stride(2), Nq * H * hd, H * hd, hd, _ptr(bias_h), _ptr(bias_w) if bias_h is not None else None, kh, kw,
+          _ptr(key_mask), float(scale), float(clamp),
           _DT[q.dtype] | (OUT_F32 if out_f32 else 0) | (K_HL8_HI if k_hl8 else 0))
     return out
 
@@ -316,6 +368,7 @@ def bi_i2t_split(q_hl8, k, vl, text_mask, heads, clamp=50000.0, n_keys=None):
     Lp = (L + 31) // 32 * 32
     if q_hl8.dtype != torch.float16 or not q_hl8.is_contiguous() or k.dtype != torch.float32 or vl.dtype != torch.float32 or hd % 32:
         raise RuntimeError("bi_i2t_split: q HL8 (fp16) contiguous, k / vl fp32, head_dim a multiple of 32")
+    _on_device("bi_i2t_split", "q_hl8 k vl text_mask", q_hl8, k, vl, text_mask)
     dev = q_hl8.device
     kp = torch.zeros(B, Lp, E, dtype=torch.float32, device=dev)
     kp[:, :L] = k
@@ -367,6 +420,7 @@ def bi_i2t_folded(v_hl8, M, cb, vl, text_mask, heads, wo, bo, resid=None, clamp=
     if v_hl8.dtype != torch.float16 or not v_hl8.is_contiguous() or M.dtype != torch.float32 or vl.dtype != torch.float32 or Lp > 256 or Co % 8 \
             or tuple(M.shape) != (B, heads, L, C) or tuple(cb.shape) != (B, heads, L) or vl.shape[1] != L:
         raise RuntimeError("bi_i2t_folded: x HL8 (fp16) contiguous, M (B, H, L, C) / cb (B, H, L) / vl (B, L, E) fp32, at most 256 text columns")
+    _on_device("bi_i2t_folded", "v_hl8 M cb vl text_mask wo bo resid", v_hl8, M, cb, vl, text_mask, wo, bo, resid)
     dev = v_hl8.device
     Mp = torch.zeros(B, heads, Lp, C, dtype=torch.float32, device=dev)
     Mp[:, :, :L] = M
@@ -381,33 +435,31 @@ def bi_i2t_folded(v_hl8, M, cb, vl, text_mask, heads, wo, bo, resid=None, clamp=
     _call("hipie_gemm_batched_softmax_bias", v_hl8.data_ptr(), 2 * C, Nv * 2 * C, 0, m_hl8.data_ptr(), 2 * C, heads * Lp * 2 * C, Lp * 2 * C,
           P.data_ptr(), heads * 2 * Lp, Nv * heads * 2 * Lp, 2 * Lp, B, heads, Nv, Lp, C, mk.data_ptr(), L, cbp.data_ptr(), float(clamp), 1.0)
     out = torch.empty(B, Nv, Co, dtype=torch.float32, device=dev)
-    r = None
-    if resid is not None:
-        r = resid.reshape(B, Nv, Co)
-        if r.dtype != torch.float32 or not r.is_contiguous():
-            raise RuntimeError("bi_i2t_folded: resid must be contiguous fp32 (B, Nv, C_out)")
+    r = None if resid is None else _layout("bi_i2t_folded", "resid", resid.reshape(B, Nv, Co), torch.float32)
     bo32 = None if bo is None else bo.float().contiguous()
     KK = heads * Lp
-    _call("hipie_gemm_batched_resid", P.data_ptr(), 2 * KK, Nv * 2 * KK, 0, u_hl8.data_ptr(), 2 * KK, Co * 2 * KK, 0,
-          None if bo32 is None else bo32.data_ptr(), None if r is None else r.data_ptr(),
+    _call("hipie_gemm_batched_resid", P.data_ptr(), 2 * KK, Nv * 2 * KK, 0, u_hl8.data_ptr(), 2 * KK, Co * 2 * KK, 0, _ptr(bo32), _ptr(r),
           Co, Nv * Co, 0, out.data_ptr(), Co, Nv * Co, 0, B, 1, Nv, Co, KK, 1.0)
     return out
 
 
-def _small_attn(fn_name, q, k, v, scale, key_mask):
+def _small_attn_args(who, q, k, v, mask):
+    """(B, Nq, H, hd, Nk) of the small fp32 attentions: q, k, v fp32 device (B, N, H, hd) views with hd contiguous and heads hd apart"""
+    _on_device(who, "q k v mask", q, k, v, mask)
     B, Nq, H, hd = q.shape
-    Nk = k.shape[1]
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        if not t.is_cuda:
-            raise RuntimeError("Not implemented on the CPU (%s)" % n)
-        if t.dtype != torch.float32 or t.stride(-1) != 1 or (H > 1 and t.stride(2) != hd):
-            raise RuntimeError("%s: %s must be fp32 (B, N, H, hd) with hd contiguous and heads hd apart" % (fn_name, n))
+        _layout(who, n, t, torch.float32, density=_ROWS)
+        if H > 1 and t.stride(2) != hd:
+            raise RuntimeError("%s: %s must be fp32 (B, N, H, hd) with hd contiguous and heads hd apart" % (who, n))
+    return B, Nq, H, hd, k.shape[1]
+
+
+def _small_attn(fn_name, q, k, v, scale, key_mask):
+    B, Nq, H, hd, Nk = _small_attn_args(fn_name, q, k, v, key_mask)
     out = torch.empty(B, Nq, H * hd, dtype=torch.float32, device=q.device)
-    mp = None
     if key_mask is not None:
         key_mask = key_mask.to(torch.uint8).contiguous()
-        mp = key_mask.data_ptr()
-    _call(fn_name, q.data_ptr(), k.data_ptr(), v.data_ptr(), mp, out.data_ptr(), B, H, Nq, Nk, hd, q.stride(0), q.stride(1),
+    _call(fn_name, q.data_ptr(), k.data_ptr(), v.data_ptr(), _ptr(key_mask), out.data_ptr(), B, H, Nq, Nk, hd, q.stride(0), q.stride(1),
           k.stride(0), k.stride(1), v.stride(0), v.stride(1), float(scale))
     return out
 
@@ -423,11 +475,7 @@ def attn_f32(q, k, v, scale, key_mask=None):
 def attn_f32_rows(q, k, v, scale, query_mask, split=False):
     """hipie_attn_f32_rows (exact fp32 FMA) / hipie_attn_split_rows (split=True: matrix pipe, fp32-class): attention with a mask per query row --
     query_mask (B, Nq, Nk) bool / uint8, True = may attend"""
-    B, Nq, H, hd = q.shape
-    Nk = k.shape[1]
-    for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        if not t.is_cuda or t.dtype != torch.float32 or t.stride(-1) != 1 or (H > 1 and t.stride(2) != hd):
-            raise RuntimeError("attn_f32_rows: %s must be an fp32 device (B, N, H, hd) with hd contiguous and heads hd apart" % n)
+    B, Nq, H, hd, Nk = _small_attn_args("attn_f32_rows", q, k, v, query_mask)
     if tuple(query_mask.shape) != (B, Nq, Nk):
         raise RuntimeError("attn_f32_rows: query_mask (B, Nq, Nk), got %s" % (tuple(query_mask.shape),))
     qm = query_mask.to(torch.uint8).contiguous()
@@ -448,22 +496,19 @@ def attn_f32_ok(hd):
     return hd in (32, 64)
 
 
-def _query_attn_args(who, qk, v, blocked, heads, others=()):
+def _query_attn_args(who, qk, v, blocked, heads, out=None, d_out=None, lse=None):
     """(B, N, mask pointer) of the training query self-attention: qk (B, N, 2 heads 32), v (B, N, heads 32) fp32 device rows (column blocks of
-    wider buffers are fine), blocked None | (N, N) bool / uint8 dense; host tensors and other layouts / types are refused"""
-    for n, t in (("qk", qk), ("v", v)) + tuple(others) + ((("blocked", blocked),) if blocked is not None else ()):
-        if not t.is_cuda:
-            raise RuntimeError("Not implemented on the CPU (%s must be a CUDA/HIP tensor)" % n)
+    wider buffers are fine; the backward's out and d_out too), blocked None | (N, N) bool / uint8 dense; host tensors (lse's too) and other
+    layouts / types are refused"""
+    _on_device(who, "qk v blocked out d_out lse", qk, v, blocked, out, d_out, lse)
     B, N = qk.shape[0], qk.shape[1]
     C = heads * 32
-    for n, t, width in (("qk", qk, 2 * C), ("v", v, C)) + tuple((n, t, C) for n, t in others):
-        if t.dtype != torch.float32 or tuple(t.shape) != (B, N, width) or t.stride(2) != 1:
-            raise RuntimeError("%s: %s must be fp32 (%d, %d, %d) rows with contiguous columns, got %s %s" % (who, n, B, N, width, t.dtype, tuple(t.shape)))
-    if blocked is None:
-        return B, N, None
-    if blocked.dtype not in (torch.bool, torch.uint8) or tuple(blocked.shape) != (N, N) or not blocked.is_contiguous():
-        raise RuntimeError("%s: blocked must be a dense (N, N) bool / uint8 tensor, got %s %s" % (who, blocked.dtype, tuple(blocked.shape)))
-    return B, N, blocked.data_ptr()
+    _layout(who, "qk", qk, torch.float32, (B, N, 2 * C), None, _ROWS)
+    _layout(who, "v", v, torch.float32, (B, N, C), None, _ROWS)
+    _layout(who, "out", out, torch.float32, (B, N, C), None, _ROWS)
+    _layout(who, "d_out", d_out, torch.float32, (B, N, C), None, _ROWS)
+    _layout(who, "blocked", blocked, (torch.bool, torch.uint8), (N, N))
+    return B, N, _ptr(blocked)
 
 
 @_timed("query_attn_train")
@@ -485,15 +530,16 @@ def query_attn_train_backward(qk, v, blocked, out, lse, d_out, heads, scale, wan
     (d_qk (B, N, 2 heads 32) | None, d_v (B, N, heads 32) | None); the probabilities are recomputed from lse, the sums run in a fixed
     order (bit-reproducible).  Without want_qk the dQ pass and the dK half are not launched, without want_v the dV half, without both
     nothing.  Nothing is cached: the workspace lives for the call."""
-    B, N, mp = _query_attn_args("query_attn_train_backward", qk, v, blocked, heads, (("out", out), ("d_out", d_out)))
-    if tuple(lse.shape) != (B, heads, N):
-        raise RuntimeError("query_attn_train_backward: lse must be (B, heads, N), got %s" % (tuple(lse.shape),))
+    who = "query_attn_train_backward"
+    B, N, mp = _query_attn_args(who, qk, v, blocked, heads, out, d_out, lse)
+    _layout(who, "out", out)
+    _layout(who, "lse", lse, torch.float32, (B, heads, N))
     d_qk = torch.empty(B, N, 2 * heads * 32, dtype=torch.float32, device=qk.device) if want_qk else None
     d_v = torch.empty(B, N, heads * 32, dtype=torch.float32, device=qk.device) if want_v else None
     ws_bytes = _size("hipie_attn_f32_train_backward_ws_bytes", B, int(heads), N)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=qk.device)
-    _call("hipie_attn_f32_train_backward", qk.data_ptr(), v.data_ptr(), mp, _chk(out, "out", torch.float32), _chk(lse, "lse", torch.float32),
-          d_out.data_ptr(), None if d_qk is None else d_qk.data_ptr(), None if d_v is None else d_v.data_ptr(), ws.data_ptr(), ws_bytes,
+    ws = _workspace(None, ws_bytes, qk.device, who)
+    _call("hipie_attn_f32_train_backward", qk.data_ptr(), v.data_ptr(), mp, out.data_ptr(), lse.data_ptr(),
+          d_out.data_ptr(), _ptr(d_qk), _ptr(d_v), ws.data_ptr(), ws_bytes,
           B, int(heads), N, 32, qk.stride(0), qk.stride(1), v.stride(0), v.stride(1), 0, d_out.stride(0), d_out.stride(1), float(scale))
     return d_qk, d_v
 
@@ -503,15 +549,11 @@ def _bi_attn_args(who, q, k, vv, vl, att, heads, vis=(), txt=()):
     wider buffers are fine), att (B, L) dense bool / uint8; `vis` / `txt`: further (name, tensor) rows of either side.  Host tensors and
     other layouts / types are refused"""
     B, Nv, L, E = q.shape[0], q.shape[1], k.shape[1], heads * 256
-    for n, t, rows in (("q", q, Nv), ("vv", vv, Nv), ("k", k, L), ("vl", vl, L)) + tuple((n, t, Nv) for n, t in vis) + tuple((n, t, L) for n, t in txt):
-        if not t.is_cuda:
-            raise RuntimeError("Not implemented on the CPU (%s must be a CUDA/HIP tensor)" % n)
-        if t.dtype != torch.float32 or tuple(t.shape) != (B, rows, E) or t.stride(2) != 1:
-            raise RuntimeError("%s: %s must be fp32 (%d, %d, %d) rows with contiguous columns, got %s %s" % (who, n, B, rows, E, t.dtype, tuple(t.shape)))
-    if not att.is_cuda:
-        raise RuntimeError("Not implemented on the CPU (att must be a CUDA/HIP tensor)")
-    if att.dtype not in (torch.bool, torch.uint8) or tuple(att.shape) != (B, L) or not att.is_contiguous():
-        raise RuntimeError("%s: att must be a dense (B, L) bool / uint8 tensor, got %s %s" % (who, att.dtype, tuple(att.shape)))
+    rows = [("q", q, Nv), ("vv", vv, Nv), ("k", k, L), ("vl", vl, L)] + [(n, t, Nv) for n, t in vis] + [(n, t, L) for n, t in txt]
+    _on_device(who, " ".join([n for n, _, _ in rows] + ["att"]), *[t for _, t, _ in rows], att)
+    for n, t, r in rows:
+        _layout(who, n, t, torch.float32, (B, r, E), None, _ROWS)
+    _layout(who, "att", att, (torch.bool, torch.uint8), (B, L))
     return B, Nv, L
 
 
@@ -530,7 +572,7 @@ def bi_attn_train_forward(q, k, vv, vl, att, heads, dropout=0.0, seed=0):
     stat_v = torch.empty(B, heads, Nv, 2, dtype=torch.float32, device=dev)
     stat_l = torch.empty(B, heads, L, 2, dtype=torch.float32, device=dev)
     ws_bytes = _size("hipie_bi_attn_train_forward_ws_bytes", B, int(heads), Nv, L)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws = _workspace(None, ws_bytes, dev, "bi_attn_train_forward")
     _call("hipie_bi_attn_train_forward", q.data_ptr(), k.data_ptr(), vv.data_ptr(), vl.data_ptr(), att.data_ptr(), out_v.data_ptr(),
           out_l.data_ptr(), lse_v.data_ptr(), lse_l.data_ptr(), stat_v.data_ptr(), stat_l.data_ptr(), ws.data_ptr(), ws_bytes, B, int(heads), Nv, L,
           256, q.stride(0), q.stride(1), k.stride(0), k.stride(1), vv.stride(0), vv.stride(1), vl.stride(0), vl.stride(1), float(dropout), int(seed))
@@ -543,18 +585,33 @@ def bi_attn_train_backward(q, k, vv, vl, att, out_v, out_l, stat_v, stat_l, d_ou
     rows, the forward's dropout and seed -> (d_q, d_k, d_vv, d_vl), None where `want` (in that order) is False: the work that serves only
     that gradient is not launched, and nothing at all without any.  Fixed order of every sum (bit-reproducible)."""
     B, Nv, L = _bi_attn_args("bi_attn_train_backward", q, k, vv, vl, att, heads, (("out_v", out_v), ("d_out_v", d_out_v)), (("out_l", out_l), ("d_out_l", d_out_l)))
-    if tuple(stat_v.shape) != (B, heads, Nv, 2) or tuple(stat_l.shape) != (B, heads, L, 2):
-        raise RuntimeError("bi_attn_train_backward: stat_v / stat_l must be (B, heads, Nv, 2) / (B, heads, L, 2), got %s %s" % (tuple(stat_v.shape), tuple(stat_l.shape)))
+    who = "bi_attn_train_backward"
+    _on_device(who, "stat_v stat_l", stat_v, stat_l)
+    _layout(who, "out_v", out_v)
+    _layout(who, "out_l", out_l)
+    _layout(who, "stat_v", stat_v, torch.float32, (B, heads, Nv, 2))
+    _layout(who, "stat_l", stat_l, torch.float32, (B, heads, L, 2))
     dev, E = q.device, heads * 256
     grads = [torch.empty(B, n, E, dtype=torch.float32, device=dev) if w else None for w, n in zip(want, (Nv, L, Nv, L))]
     ws_bytes = _size("hipie_bi_attn_train_backward_ws_bytes", B, int(heads), Nv, L)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    _call("hipie_bi_attn_train_backward", q.data_ptr(), k.data_ptr(), vv.data_ptr(), vl.data_ptr(), att.data_ptr(), _chk(out_v, "out_v", torch.float32),
-          _chk(out_l, "out_l", torch.float32), _chk(stat_v, "stat_v", torch.float32), _chk(stat_l, "stat_l", torch.float32), d_out_v.data_ptr(),
-          d_out_l.data_ptr(), *[None if g is None else g.data_ptr() for g in grads], ws.data_ptr(), ws_bytes, B, int(heads), Nv, L, 256,
+    ws = _workspace(None, ws_bytes, dev, who)
+    _call("hipie_bi_attn_train_backward", q.data_ptr(), k.data_ptr(), vv.data_ptr(), vl.data_ptr(), att.data_ptr(), out_v.data_ptr(),
+          out_l.data_ptr(), stat_v.data_ptr(), stat_l.data_ptr(), d_out_v.data_ptr(),
+          d_out_l.data_ptr(), *[_ptr(g) for g in grads], ws.data_ptr(), ws_bytes, B, int(heads), Nv, L, 256,
           q.stride(0), q.stride(1), k.stride(0), k.stride(1), vv.stride(0), vv.stride(1), vl.stride(0), vl.stride(1),
           d_out_v.stride(0), d_out_v.stride(1), d_out_l.stride(0), d_out_l.stride(1), float(dropout), int(seed))
     return tuple(grads)
+
+
+def _vit_operands(who, qkv, a, b, dtype, heads, parts=3, tables=("tab_h", "tab_w")):
+    """(B, N, head dim) of the ViT attention family: qkv (B, N, parts * heads * hd) of any dtype and the two tables `a`, `b` (named by
+    `tables`) of `dtype`, dense device tensors"""
+    _on_device(who, "qkv %s %s" % tables, qkv, a, b)
+    _layout(who, "qkv", qkv)
+    _layout(who, tables[0], a, dtype)
+    _layout(who, tables[1], b, dtype)
+    B, N, C = qkv.shape
+    return B, N, C // (parts * heads)
 
 
 @_timed(lambda qkv, rel_h, rel_w, grid_hw, heads, scale: "vit_attn_global" if grid_hw[0] * grid_hw[1] > 256 else "vit_attn_window")
@@ -562,11 +619,9 @@ def vit_attn(qkv, rel_h, rel_w, grid_hw, heads, scale):
     """qkv (B, gh*gw, 3*heads*hd) 16-bit packed as (3, heads, hd); rel_h (B*heads, gh, N) f32 (key-row major),
     rel_w (B*heads, N, gw) f32 -> (B, N, heads*hd)."""
     gh, gw = grid_hw
-    B, N, C3 = qkv.shape
-    hd = C3 // (3 * heads)
+    B, N, hd = _vit_operands("vit_attn", qkv, rel_h, rel_w, torch.float32, heads, 3, ("rel_h", "rel_w"))
     out = torch.empty(B, N, heads * hd, dtype=qkv.dtype, device=qkv.device)
-    _call("hipie_vit_attn", _chk(qkv, "qkv"), _chk(rel_h, "rel_h", torch.float32), _chk(rel_w, "rel_w", torch.float32),
-          out.data_ptr(), B, gh, gw, heads, hd, float(scale), _DT[qkv.dtype])
+    _call("hipie_vit_attn", qkv.data_ptr(), rel_h.data_ptr(), rel_w.data_ptr(), out.data_ptr(), B, gh, gw, heads, hd, float(scale), _DT[qkv.dtype])
     return out
 
 
@@ -580,11 +635,9 @@ def vit_attn_fused(qkv, tab_h, tab_w, grid_hw, heads, scale):
     """global ViT attention with the decomposed rel-pos bias computed in the kernel prologue from the tables:
     qkv (B, gh*gw, 3*heads*hd) 16-bit, tab_h (2*gh-1, hd), tab_w (2*gw-1, hd) same dtype -> (B, N, heads*hd)."""
     gh, gw = grid_hw
-    B, N, C3 = qkv.shape
-    hd = C3 // (3 * heads)
+    B, N, hd = _vit_operands("vit_attn_fused", qkv, tab_h, tab_w, qkv.dtype, heads)
     out = torch.empty(B, N, heads * hd, dtype=qkv.dtype, device=qkv.device)
-    _call("hipie_vit_attn_fused", _chk(qkv, "qkv"), _chk(tab_h, "tab_h", qkv.dtype), _chk(tab_w, "tab_w", qkv.dtype),
-          out.data_ptr(), B, gh, gw, heads, hd, float(scale), _DT[qkv.dtype])
+    _call("hipie_vit_attn_fused", qkv.data_ptr(), tab_h.data_ptr(), tab_w.data_ptr(), out.data_ptr(), B, gh, gw, heads, hd, float(scale), _DT[qkv.dtype])
     return out
 
 
@@ -603,11 +656,9 @@ def vit_attn_rel(qkv, tab_h, tab_w, grid_hw, heads, fast=False):
     hipie_vit_attn_rel: qkv (B, gh*gw, 3*heads*hd) 16-bit whose q rows are PRE-SCALED by scale*log2(e); tab_h (2*gh-1, hd),
     tab_w (2*gw-1, hd) = the (re-interpolated) rel-pos tables DIVIDED by scale, same dtype -> (B, N, heads*hd)."""
     gh, gw = grid_hw
-    B, N, C3 = qkv.shape
-    hd = C3 // (3 * heads)
+    B, N, hd = _vit_operands("vit_attn_rel", qkv, tab_h, tab_w, qkv.dtype, heads)
     out = torch.empty(B, N, heads * hd, dtype=qkv.dtype, device=qkv.device)
-    _call("hipie_vit_attn_rel", _chk(qkv, "qkv"), _chk(tab_h, "tab_h", qkv.dtype), _chk(tab_w, "tab_w", qkv.dtype),
-          out.data_ptr(), B, gh, gw, heads, hd, _DT[qkv.dtype], ATTN_FAST if fast else 0)
+    _call("hipie_vit_attn_rel", qkv.data_ptr(), tab_h.data_ptr(), tab_w.data_ptr(), out.data_ptr(), B, gh, gw, heads, hd, _DT[qkv.dtype], ATTN_FAST if fast else 0)
     return out
 
 
@@ -639,14 +690,17 @@ def bi_xattn(q, k, vv, vl, text_mask, clamp=50000.0, out_f32=False):
     rows of a batch item whose text_mask is all zero are zero at every L (whichever kernel the length selects); out_l has no mask."""
     B, Nv, H, hd = q.shape
     L = k.shape[1]
+    _on_device("bi_xattn", "q k vv vl text_mask", q, k, vv, vl, text_mask)
+    for n, t in (("q", q), ("k", k), ("vv", vv), ("vl", vl)):
+        _layout("bi_xattn", n, t)
     text_mask = text_mask.to(torch.uint8).contiguous()
     odt = torch.float32 if out_f32 else q.dtype
     out_v = torch.empty(B, Nv, H * hd, dtype=odt, device=q.device)
     out_l = torch.empty(B, L, H * hd, dtype=odt, device=q.device)
     need = 0 if out_f32 else _size("hipie_bi_xattn_workspace", B, H, Nv, L, hd)          # split partials of the text -> image direction (0: none)
     ws = _XA_WS.get(need, q.device) if need > 0 else None
-    _call("hipie_bi_xattn_ws", _chk(q, "q"), _chk(k, "k"), _chk(vv, "vv"), _chk(vl, "vl"), _chk(text_mask, "text_mask"),
-          out_v.data_ptr(), out_l.data_ptr(), None if ws is None else ws.data_ptr(), need, B, H, Nv, L, hd,
+    _call("hipie_bi_xattn_ws", q.data_ptr(), k.data_ptr(), vv.data_ptr(), vl.data_ptr(), text_mask.data_ptr(),
+          out_v.data_ptr(), out_l.data_ptr(), _ptr(ws), need, B, H, Nv, L, hd,
           float(clamp), _DT[q.dtype] | (OUT_F32 if out_f32 else 0))
     return out_v, out_l
 
@@ -662,22 +716,23 @@ def mask_einsum(mask_embed, mask_features, precision=1, out_dtype=torch.float32,
     its query row; workspace=False: the workspace-free entry point hipie_mask_einsum (every workgroup splits the embedding)."""
     B, Q, C = mask_embed.shape
     _, _, Hh, Ww = mask_features.shape
+    _on_device("mask_einsum", "mask_embed mask_features row_bias", mask_embed, mask_features, row_bias)
     out = torch.empty(B, Q, Hh, Ww, dtype=out_dtype, device=mask_embed.device)
-    e, f = _chk(mask_embed, "mask_embed", torch.float32), _chk(mask_features, "mask_features", torch.float32)
+    e = _layout("mask_einsum", "mask_embed", mask_embed, torch.float32).data_ptr()
+    f = _layout("mask_einsum", "mask_features", mask_features, torch.float32).data_ptr()
     if int(precision) == 0 or not workspace:
         if row_bias is not None:
             raise RuntimeError("mask_einsum: row_bias needs precision 1 | 2 and the workspace form")
         _call("hipie_mask_einsum", e, f, out.data_ptr(), B, Q, C, Hh * Ww, int(precision), _DT[out_dtype])
     else:
-        rb = None
+        rbt = None
         if row_bias is not None:
             rbt = row_bias.float().contiguous()
             if tuple(rbt.shape) != (B, Q):
                 raise ValueError("mask_einsum: row_bias must be (B, Q) = (%d, %d), got %s" % (B, Q, tuple(rbt.shape)))
-            rb = _chk(rbt, "row_bias", torch.float32)
         need = _size("hipie_mask_einsum_workspace", B, Q, C)
         ws = _ME_WS.get(need, mask_embed.device)
-        _call("hipie_mask_einsum_ws", e, f, rb, out.data_ptr(), ws.data_ptr(), need, B, Q, C, Hh * Ww, int(precision), _DT[out_dtype])
+        _call("hipie_mask_einsum_ws", e, f, _ptr(rbt), out.data_ptr(), ws.data_ptr(), need, B, Q, C, Hh * Ww, int(precision), _DT[out_dtype])
     return out
 
 
@@ -700,10 +755,11 @@ def mask_einsum_backward(mask_embed, mask_features, grad_out):
     B, Q, C = mask_embed.shape
     _, _, Hh, Ww = mask_features.shape
     HW = Hh * Ww
-    if tuple(grad_out.shape) != (B, Q, Hh, Ww) or tuple(mask_features.shape[:2]) != (B, C) or not grad_out.is_cuda:
+    if tuple(grad_out.shape) != (B, Q, Hh, Ww) or tuple(mask_features.shape[:2]) != (B, C):
         raise RuntimeError("mask_einsum_backward: mask_embed (B,Q,C), mask_features (B,C,H,W), grad_out (B,Q,H,W) device tensors")
     if C % 8:
         raise RuntimeError("mask_einsum_backward: C must be a multiple of 8")
+    _on_device("mask_einsum_backward", "mask_embed mask_features grad_out", mask_embed, mask_features, grad_out)
     dev = grad_out.device
     G = grad_out.float().reshape(B, Q, HW)
     F_ = mask_features.float().reshape(B, C, HW)
@@ -740,13 +796,20 @@ def mask_einsum16(mask_embed, mask_features, split=True, out_dtype=None, row_bia
     _, _, Hh, Ww = mask_features.shape
     dt = mask_features.dtype
     out_dtype = out_dtype or dt
+    _on_device("mask_einsum16", "mask_embed mask_features row_bias", mask_embed, mask_features, row_bias)
+    _layout("mask_einsum16", "mask_features", mask_features)
     hi = mask_embed.to(dt).contiguous()
     lo = (mask_embed.float() - hi.float()).to(dt).contiguous() if split else None
     out = torch.empty(B, Q, Hh, Ww, dtype=out_dtype, device=mask_embed.device)
-    rb = None if row_bias is None else _chk(row_bias.float().contiguous(), "row_bias", torch.float32)
-    _call("hipie_mask_einsum16", _chk(hi, "embed_hi"), None if lo is None else _chk(lo, "embed_lo"), _chk(mask_features, "mask_features"),
-          rb, out.data_ptr(), B, Q, C, Hh * Ww, _DT[dt], _DT[out_dtype])
+    rb = None if row_bias is None else row_bias.float().contiguous()
+    _call("hipie_mask_einsum16", hi.data_ptr(), _ptr(lo), mask_features.data_ptr(), _ptr(rb), out.data_ptr(), B, Q, C, Hh * Ww, _DT[dt], _DT[out_dtype])
     return out
+
+
+def _dynamic_mask_operands(who, mask_feats, ref_points, params, grad_out):
+    _on_device(who, "mask_feats ref_points params grad_out", mask_feats, ref_points, params, grad_out)
+    for n, t in (("mask_feats", mask_feats), ("ref_points", ref_points), ("params", params)) + ((("grad_out", grad_out),) if grad_out is not None else ()):
+        _layout(who, n, t, torch.float32)
 
 
 @_timed("dynamic_mask")
@@ -759,15 +822,15 @@ def dynamic_mask(mask_feats, ref_points, params, num_queries, stride=8, up=2, ou
     if C != 8 or params.shape[-1] != 169:
         raise RuntimeError("dynamic_mask: expects 8 feature channels and 169 parameters per instance")
     n = B * num_queries
+    _dynamic_mask_operands("dynamic_mask", mask_feats, ref_points, params, None)
     out = torch.empty(n, up * H, up * W, dtype=out_dtype, device=mask_feats.device)
     split = mlp_dtype == "split" and out_dtype in (torch.float32, torch.float16)
     if (split or mlp_dtype in (torch.float16, torch.bfloat16)) and up == 2 and W % 4 == 0 and stride % 4 == 0 and stride * max(H, W) <= 8192:
-        _call("hipie_dynamic_mask16", _chk(mask_feats, "mask_feats", torch.float32), _chk(ref_points, "ref_points", torch.float32),
-              _chk(params, "params", torch.float32), out.data_ptr(), B, num_queries, H, W,
+        _call("hipie_dynamic_mask16", mask_feats.data_ptr(), ref_points.data_ptr(), params.data_ptr(), out.data_ptr(), B, num_queries, H, W,
               int(stride), HL8 if split else _DT[mlp_dtype], _DT[out_dtype])
         return out
-    _call("hipie_dynamic_mask", _chk(mask_feats, "mask_feats", torch.float32), _chk(ref_points, "ref_points", torch.float32),
-          _chk(params, "params", torch.float32), out.data_ptr(), B, num_queries, H, W, int(stride), int(up), _DT[out_dtype])
+    _call("hipie_dynamic_mask", mask_feats.data_ptr(), ref_points.data_ptr(), params.data_ptr(), out.data_ptr(), B, num_queries, H, W,
+          int(stride), int(up), _DT[out_dtype])
     return out
 
 
@@ -781,12 +844,12 @@ def dynamic_mask_backward(mask_feats, ref_points, params, grad_out, num_queries,
         raise RuntimeError("dynamic_mask_backward: expects 8 feature channels, (B*Q, 169) parameters and (B*Q, 2) reference points")
     if tuple(grad_out.shape[-2:]) != (up * H, up * W) or grad_out.numel() != n * up * up * H * W:
         raise RuntimeError("dynamic_mask_backward: grad_out must be (B*Q, up*H, up*W), got %s" % (tuple(grad_out.shape),))
+    _dynamic_mask_operands("dynamic_mask_backward", mask_feats, ref_points, params, grad_out)
     dev = mask_feats.device
     gf = torch.empty(B, 8, H, W, dtype=torch.float32, device=dev)
     gr = torch.empty(n, 2, dtype=torch.float32, device=dev)
     gp = torch.empty(n, 169, dtype=torch.float32, device=dev)
-    _call("hipie_dynamic_mask_backward", _chk(mask_feats, "mask_feats", torch.float32), _chk(ref_points, "ref_points", torch.float32),
-          _chk(params, "params", torch.float32), _chk(grad_out, "grad_out", torch.float32),
+    _call("hipie_dynamic_mask_backward", mask_feats.data_ptr(), ref_points.data_ptr(), params.data_ptr(), grad_out.data_ptr(),
           gf.data_ptr(), gr.data_ptr(), gp.data_ptr(), B, num_queries, H, W, int(stride), int(up))
     return gf, gr, gp
 
@@ -796,12 +859,10 @@ def vit_relpos(qkv, tab_h, tab_w, grid_hw, heads):
     """qkv (B, N, 3*heads*hd) 16-bit; tab_h (2gh-1, hd), tab_w (2gw-1, hd) same dtype -> rel_h (B*heads, gh, N), rel_w
     (B*heads, N, gw) f32, the bias tables of hipie_vit_attn."""
     gh, gw = grid_hw
-    B, N, C3 = qkv.shape
-    hd = C3 // (3 * heads)
+    B, N, hd = _vit_operands("vit_relpos", qkv, tab_h, tab_w, qkv.dtype, heads)
     rel_h = torch.empty(B * heads, gh, N, dtype=torch.float32, device=qkv.device)
     rel_w = torch.empty(B * heads, N, gw, dtype=torch.float32, device=qkv.device)
-    _call("hipie_vit_relpos", _chk(qkv, "qkv"), _chk(tab_h, "tab_h", qkv.dtype), _chk(tab_w, "tab_w", qkv.dtype),
-          rel_h.data_ptr(), rel_w.data_ptr(), B, gh, gw, heads, hd, _DT[qkv.dtype])
+    _call("hipie_vit_relpos", qkv.data_ptr(), tab_h.data_ptr(), tab_w.data_ptr(), rel_h.data_ptr(), rel_w.data_ptr(), B, gh, gw, heads, hd, _DT[qkv.dtype])
     return rel_h, rel_w
 
 
@@ -812,6 +873,8 @@ def add_layernorm(x, delta, weight, bias, eps, norm_dtype, want_res=True, delta_
     then has out_rows rows; ``delta_row`` (rows of x,) = row of ``delta`` that belongs to x row r."""
     C = x.shape[-1]
     rows = x.numel() // C
+    who = "add_layernorm"
+    _on_device(who, "x delta weight bias delta_row out_src", x, delta, weight, bias, delta_row, out_src)
     res = torch.empty_like(x) if (want_res and delta is not None) else None
     if out_src is None:
         out = _alloc(tuple(x.shape), norm_dtype, x.device)
@@ -819,15 +882,15 @@ def add_layernorm(x, delta, weight, bias, eps, norm_dtype, want_res=True, delta_
     else:
         out_rows = int(out_src.shape[0])
         out = _alloc((out_rows, C), norm_dtype, x.device)
-    args = (_chk(x, "x"), None if delta is None else _chk(delta, "delta"),
-            _chk(weight, "weight", torch.float32), _chk(bias, "bias", torch.float32),
-            None if res is None else res.data_ptr(), out.data_ptr(), out_rows, C, float(eps),
+    args = (_layout(who, "x", x).data_ptr(), None if delta is None else _layout(who, "delta", delta).data_ptr(),
+            _layout(who, "weight", weight, torch.float32).data_ptr(), _layout(who, "bias", bias, torch.float32).data_ptr(),
+            _ptr(res), out.data_ptr(), out_rows, C, float(eps),
             _DT[x.dtype], _DT[x.dtype if delta is None else delta.dtype], _code(norm_dtype))
     if delta_row is None and out_src is None:
         _call("hipie_add_layernorm", *args)
     else:
-        _call("hipie_add_layernorm_rows", *args, None if delta_row is None else _chk(delta_row, "delta_row", torch.int32),
-              None if out_src is None else _chk(out_src, "out_src", torch.int32))
+        _call("hipie_add_layernorm_rows", *args, None if delta_row is None else _layout(who, "delta_row", delta_row, torch.int32).data_ptr(),
+              None if out_src is None else _layout(who, "out_src", out_src, torch.int32).data_ptr())
     return (x if delta is None else res), out
 
 
@@ -837,32 +900,29 @@ def layernorm_backward(s, gy, weight, eps, gres=None, want_param_grads=True):
     gy = gradient of the LayerNorm output, gres = gradient arriving at s from the residual stream (or None) ->
     (dx = LayerNorm input gradient + gres, dgamma, dbeta); the parameter sums are skipped (None, None) without want_param_grads.
     mean / rstd are recomputed from s; dgamma / dbeta are summed in a fixed order (bit-reproducible)."""
-    for n, t in (("s", s), ("gy", gy), ("weight", weight), ("gres", gres)):
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("Not implemented on the CPU (%s must be a CUDA/HIP tensor)" % n)
+    who = "layernorm_backward"
+    _on_device(who, "s gy weight gres", s, gy, weight, gres)
     C = s.shape[-1]
     rows = s.numel() // C if C else 0
     if gy.shape != s.shape or (gres is not None and gres.shape != s.shape) or weight.numel() != C:
         raise RuntimeError("layernorm_backward: gy / gres must have the shape of s %s and weight its last dimension" % (tuple(s.shape),))
-    s, gy, weight = _dense_f32(s, "s", True), _dense_f32(gy, "gy", True), _dense_f32(weight, "weight", True)
-    gres = None if gres is None else _dense_f32(gres, "gres", True)
+    s, gy, weight = _dense_f32(who, "s", s, True), _dense_f32(who, "gy", gy, True), _dense_f32(who, "weight", weight, True)
+    gres = None if gres is None else _dense_f32(who, "gres", gres, True)
     dx = torch.empty_like(s)
     dgamma = dbeta = ws = None
     ws_bytes = 0
     if want_param_grads:
         dgamma, dbeta = torch.empty_like(weight), torch.empty_like(weight)
         ws_bytes = _size("hipie_layernorm_backward_ws_bytes", rows, C)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=s.device)
-    _call("hipie_layernorm_backward", _chk(s, "s", torch.float32), _chk(gy, "gy", torch.float32),
-          None if gres is None else _chk(gres, "gres", torch.float32), _chk(weight, "weight", torch.float32),
-          dx.data_ptr(), None if dgamma is None else dgamma.data_ptr(), None if dbeta is None else dbeta.data_ptr(),
-          None if ws is None else ws.data_ptr(), ws_bytes, rows, C, float(eps))
+        ws = _workspace(None, ws_bytes, s.device, who)
+    _call("hipie_layernorm_backward", s.data_ptr(), gy.data_ptr(), _ptr(gres), weight.data_ptr(), dx.data_ptr(), _ptr(dgamma), _ptr(dbeta),
+          _ptr(ws), ws_bytes, rows, C, float(eps))
     return dx, dgamma, dbeta
 
 
-def _act_rows16(t, name):
-    """(t as dense fp32 rows on a 16-byte boundary, rows, N)"""
-    t = _dense_f32(t, name, True)
+def _act_rows16(who, name, t):
+    """(t as dense fp32 rows on a 16-byte boundary -- copied when it is not --, rows, N)"""
+    t = _dense_f32(who, name, t, True)
     N = t.shape[-1] if t.dim() else 1
     return t, (t.numel() // N if N else 0), N
 
@@ -871,7 +931,7 @@ def _act_rows16(t, name):
 def act_forward(u, act):
     """a = act(u) on hipie_act_forward (fp32, last dimension % 4 == 0); act = ACT_GELU (the exact-erf formula of the GEMM epilogue, bit
     for bit) | ACT_RELU.  The forward half of the training step's MLP node (functions.MlpFunction)."""
-    u, rows, N = _act_rows16(u, "u")
+    u, rows, N = _act_rows16("act_forward", "u", u)
     a = torch.empty_like(u)
     _call("hipie_act_forward", u.data_ptr(), a.data_ptr(), rows, N, int(act))
     return a
@@ -883,13 +943,12 @@ def act_backward(u, g, act, want_a=False, want_bias_grad=False, out=None):
     (du = g * act'(u),  a = act(u) recomputed with the bits of act_forward | None,  dbias = du summed over the rows, (N,) | None).
     out: the buffer du is written into -- it may be g itself (in place); it is used when it is dense, 16-byte aligned fp32 of u's shape.
     dbias is summed in a fixed order (bit-reproducible).  Nothing is cached: the workspace lives for the call."""
-    u, rows, N = _act_rows16(u, "u")
+    u, rows, N = _act_rows16("act_backward", "u", u)
     if g.shape != u.shape:
         raise RuntimeError("act_backward: g %s must have the shape of u %s" % (tuple(g.shape), tuple(u.shape)))
     g_in = g
-    g, _, _ = _act_rows16(g, "g")
-    if out is not None and not out.is_cuda:
-        raise RuntimeError("Not implemented on the CPU (out must be a CUDA/HIP tensor)")
+    g, _, _ = _act_rows16("act_backward", "g", g)
+    _on_device("act_backward", "out", out)
     if out is not None and out is g_in:
         out = g                                             # in place on the operand the kernel reads (the dense copy, when one was made)
     usable = (out is not None and out.dtype == torch.float32 and out.shape == u.shape and out.is_contiguous() and out.data_ptr() % 16 == 0
@@ -899,18 +958,16 @@ def act_backward(u, g, act, want_a=False, want_bias_grad=False, out=None):
     dbias = ws = None
     if want_bias_grad:
         dbias = torch.empty(N, dtype=torch.float32, device=u.device)
-        ws = torch.empty(_size("hipie_act_backward_ws_bytes", rows, N), dtype=torch.uint8, device=u.device)
-    _call("hipie_act_backward", u.data_ptr(), g.data_ptr(), du.data_ptr(), None if a is None else a.data_ptr(),
-          None if dbias is None else dbias.data_ptr(), None if ws is None else ws.data_ptr(), rows, N, int(act))
+        ws = _workspace(None, _size("hipie_act_backward_ws_bytes", rows, N), u.device, "act_backward")
+    _call("hipie_act_backward", u.data_ptr(), g.data_ptr(), du.data_ptr(), _ptr(a), _ptr(dbias), _ptr(ws), rows, N, int(act))
     return du, a, dbias
 
 
-def _point_loss_operands(src, tgt, tgt_index, pts):
-    src, tgt, pts = _dense_f32(src, "src"), _dense_f32(tgt, "tgt"), _dense_f32(pts, "pts")
-    if not tgt_index.is_cuda:
-        raise RuntimeError("Not implemented on the CPU (tgt_index must be a CUDA/HIP tensor)")
-    if tgt_index.dtype != torch.int64:
-        raise RuntimeError("tgt_index must be torch.int64, got %s" % tgt_index.dtype)
+def _point_loss_operands(who, src, tgt, tgt_index, pts):
+    """the operands both point-loss passes share, the fp32 ones as dense copies where they are not dense"""
+    src, tgt, pts = _dense_f32(who, "src", src), _dense_f32(who, "tgt", tgt), _dense_f32(who, "pts", pts)
+    _on_device(who, "tgt_index", tgt_index)
+    _layout(who, "tgt_index", tgt_index, torch.int64, density=_ANY)
     if src.dim() != 3 or tgt.dim() != 3 or pts.dim() != 3 or pts.shape[0] != src.shape[0] or pts.shape[2] != 2 or tgt_index.shape != src.shape[:1]:
         raise RuntimeError("point_mask_loss: src (N,H,W), tgt (T,Ht,Wt), tgt_index (N,), pts (N,P,2); got %s %s %s %s"
                            % (tuple(src.shape), tuple(tgt.shape), tuple(tgt_index.shape), tuple(pts.shape)))
@@ -922,11 +979,11 @@ def point_mask_loss_forward(src, tgt, tgt_index, pts, mode, alpha=-1.0):
     """the point-sampled mask losses of one criterion call (hipie_point_mask_loss_forward, fp32): src (N,H,W) logits, tgt (T,Ht,Wt) ALL
     target masks, tgt_index (N,) int64 rows of tgt, pts (N,P,2) (x, y) in [0,1]^2; mode 0 = sigmoid CE, 1 = focal (gamma 2, alpha) ->
     (lmask (N,), ldice (N,), sums (N,3) for point_mask_loss_backward).  Bit-reproducible; the workspace lives for the call."""
-    src, tgt, tgt_index, pts = _point_loss_operands(src, tgt, tgt_index, pts)
+    src, tgt, tgt_index, pts = _point_loss_operands("point_mask_loss_forward", src, tgt, tgt_index, pts)
     N, P = src.shape[0], pts.shape[1]
     lmask, ldice, sums = src.new_empty(N), src.new_empty(N), src.new_empty(N, 3)
     ws_bytes = _size("hipie_point_mask_loss_ws_bytes", N, P)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=src.device)
+    ws = _workspace(None, ws_bytes, src.device, "point_mask_loss_forward")
     _call("hipie_point_mask_loss_forward", src.data_ptr(), tgt.data_ptr(), tgt_index.data_ptr(), pts.data_ptr(), lmask.data_ptr(), ldice.data_ptr(),
           sums.data_ptr(), ws.data_ptr(), ws_bytes, N, src.shape[1], src.shape[2], tgt.shape[0], tgt.shape[1], tgt.shape[2], P, int(mode),
           float(alpha), 2.0)
@@ -937,8 +994,9 @@ def point_mask_loss_forward(src, tgt, tgt_index, pts, mode, alpha=-1.0):
 def point_mask_loss_backward(src, tgt, tgt_index, pts, sums, g_mask, g_dice, mode, alpha=-1.0):
     """d_src (N,H,W) of point_mask_loss_forward for the gradients g_mask (N,), g_dice (N,) of its two outputs
     (hipie_point_mask_loss_backward): the samples are recomputed, the corners accumulated with fp32 atomics (not bit-reproducible)."""
-    src, tgt, tgt_index, pts = _point_loss_operands(src, tgt, tgt_index, pts)
-    sums, g_mask, g_dice = _dense_f32(sums, "sums"), _dense_f32(g_mask, "g_mask"), _dense_f32(g_dice, "g_dice")
+    who = "point_mask_loss_backward"
+    src, tgt, tgt_index, pts = _point_loss_operands(who, src, tgt, tgt_index, pts)
+    sums, g_mask, g_dice = _dense_f32(who, "sums", sums), _dense_f32(who, "g_mask", g_mask), _dense_f32(who, "g_dice", g_dice)
     N = src.shape[0]
     if sums.shape != (N, 3) or g_mask.shape != (N,) or g_dice.shape != (N,):
         raise RuntimeError("point_mask_loss_backward: sums (N,3), g_mask (N,), g_dice (N,) for N=%d" % N)
@@ -949,13 +1007,13 @@ def point_mask_loss_backward(src, tgt, tgt_index, pts, sums, g_mask, g_dice, mod
     return d_src
 
 
-def _token_focal_operands(logits, onehot, keep):
-    logits, onehot = _dense_f32(logits, "logits"), _dense_f32(onehot, "onehot")
+def _token_focal_operands(who, logits, onehot, keep):
+    """logits and onehot as dense fp32 copies where they are not dense, keep as one byte per token"""
+    logits, onehot = _dense_f32(who, "logits", logits), _dense_f32(who, "onehot", onehot)
     if logits.dim() != 3 or onehot.shape != logits.shape:
         raise RuntimeError("token_focal: logits and onehot (B,Q,T); got %s %s" % (tuple(logits.shape), tuple(onehot.shape)))
     if keep is not None:
-        if not keep.is_cuda:
-            raise RuntimeError("Not implemented on the CPU (keep must be a CUDA/HIP tensor)")
+        _on_device(who, "keep", keep)
         if keep.shape != (logits.shape[0], logits.shape[2]):
             raise RuntimeError("token_focal: keep %s must be (B,T) of logits %s" % (tuple(keep.shape), tuple(logits.shape)))
         keep = (keep if keep.dtype in (torch.uint8, torch.bool) else keep > 0).contiguous()           # one byte per token either way
@@ -966,12 +1024,12 @@ def _token_focal_operands(logits, onehot, keep):
 def token_focal_forward(logits, onehot, keep=None, alpha=0.25):
     """sum over (b, q, t) with keep[b, t] != 0 of the binary focal loss (gamma 2) of logits (B,Q,T) against onehot (B,Q,T)
     (hipie_token_focal_forward, fp32) -> 0-d tensor.  keep (B,T) or None.  Bit-reproducible, no host wait."""
-    logits, onehot, keep = _token_focal_operands(logits, onehot, keep)
+    logits, onehot, keep = _token_focal_operands("token_focal_forward", logits, onehot, keep)
     B, Q, T = logits.shape
     out = logits.new_zeros(())
     ws_bytes = _size("hipie_token_focal_ws_bytes", logits.numel())
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=logits.device)
-    _call("hipie_token_focal_forward", logits.data_ptr(), onehot.data_ptr(), None if keep is None else keep.data_ptr(), out.data_ptr(),
+    ws = _workspace(None, ws_bytes, logits.device, "token_focal_forward")
+    _call("hipie_token_focal_forward", logits.data_ptr(), onehot.data_ptr(), _ptr(keep), out.data_ptr(),
           ws.data_ptr(), ws_bytes, B, Q, T, float(alpha), 2.0)
     return out
 
@@ -980,40 +1038,15 @@ def token_focal_forward(logits, onehot, keep=None, alpha=0.25):
 def token_focal_backward(logits, onehot, keep, g, alpha=0.25):
     """dlogits (B,Q,T) = g * d focal / d logits at kept tokens, exactly 0 at dropped ones (hipie_token_focal_backward); g: 0-d DEVICE
     tensor, the gradient of token_focal_forward's output."""
-    logits, onehot, keep = _token_focal_operands(logits, onehot, keep)
-    g = _dense_f32(g, "g")
+    logits, onehot, keep = _token_focal_operands("token_focal_backward", logits, onehot, keep)
+    g = _dense_f32("token_focal_backward", "g", g)
     if g.numel() != 1:
         raise RuntimeError("token_focal_backward: g must hold one value, got %s" % (tuple(g.shape),))
     B, Q, T = logits.shape
     dlogits = torch.empty_like(logits)
-    _call("hipie_token_focal_backward", logits.data_ptr(), onehot.data_ptr(), None if keep is None else keep.data_ptr(), g.data_ptr(),
+    _call("hipie_token_focal_backward", logits.data_ptr(), onehot.data_ptr(), _ptr(keep), g.data_ptr(),
           dlogits.data_ptr(), B, Q, T, float(alpha), 2.0)
     return dlogits
-
-
-def _layout_f32(t, name, ndim):
-    """refuses t unless it is a contiguous fp32 tensor of `ndim` dimensions (nothing is copied; the device is checked by _on_device, last)"""
-    if t.dtype != torch.float32:
-        raise RuntimeError("%s must be torch.float32, got %s" % (name, t.dtype))
-    if t.dim() != ndim:
-        raise RuntimeError("%s must have %d dimensions, got %s" % (name, ndim, tuple(t.shape)))
-    if not t.is_contiguous():
-        raise RuntimeError("%s tensor has to be contiguous" % name)
-
-
-def _on_device(**tensors):
-    for name, t in tensors.items():
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("Not implemented on the CPU (%s must be a CUDA/HIP tensor)" % name)
-
-
-def _workspace(ws, need, device, what):
-    """the caller's byte workspace when it is given (checked), else one that lives for the call"""
-    if ws is None:
-        return torch.empty(need, dtype=torch.uint8, device=device)
-    if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need:
-        raise RuntimeError("%s: workspace of %d contiguous uint8 elements needed, got %s %s" % (what, need, ws.dtype, tuple(ws.shape)))
-    return ws
 
 
 def uncertain_points_ws_bytes(N, C):
@@ -1028,8 +1061,9 @@ def uncertain_points(src, cand, rest, k, num_points=None, ws=None):
     num_points: the P the caller expects; a rest that does not hold P - k points is refused.
     ws: uint8 tensor of at least uncertain_points_ws_bytes(N, C) elements, or None: allocated for the call.
     Nothing is copied: a strided or non-fp32 operand is refused; the layout is checked before the device."""
-    _layout_f32(src, "src", 3)
-    _layout_f32(cand, "cand", 3)
+    who = "uncertain_points"
+    _layout(who, "src", src, torch.float32, ndim=3)
+    _layout(who, "cand", cand, torch.float32, ndim=3)
     N, C, k = src.shape[0], cand.shape[1], int(k)
     if cand.shape[0] != N or cand.shape[2] != 2:
         raise RuntimeError("uncertain_points: cand must be (N=%d, C, 2), got %s" % (N, tuple(cand.shape)))
@@ -1037,15 +1071,15 @@ def uncertain_points(src, cand, rest, k, num_points=None, ws=None):
         raise RuntimeError("uncertain_points: k=%d must be in [0, C=%d]" % (k, C))
     n_rest = 0
     if rest is not None:
-        _layout_f32(rest, "rest", 3)
+        _layout(who, "rest", rest, torch.float32, ndim=3)
         if rest.shape[0] != N or rest.shape[2] != 2:
             raise RuntimeError("uncertain_points: rest must be (N=%d, P - k, 2), got %s" % (N, tuple(rest.shape)))
         n_rest = rest.shape[1]
     P = k + n_rest
     if num_points is not None and P != int(num_points):
         raise RuntimeError("uncertain_points: rest must hold P - k = %d points, got %d" % (int(num_points) - k, n_rest))
-    _on_device(src=src, cand=cand, rest=rest, ws=ws)
-    ws = _workspace(ws, _size("hipie_uncertain_points_ws_bytes", N, C), src.device, "uncertain_points")
+    _on_device(who, "src cand rest ws", src, cand, rest, ws)
+    ws = _workspace(ws, _size("hipie_uncertain_points_ws_bytes", N, C), src.device, who)
     pts = src.new_empty(N, P, 2)
     _call("hipie_uncertain_points", src.data_ptr(), cand.data_ptr(), rest.data_ptr() if n_rest else None, pts.data_ptr(), ws.data_ptr(), ws.numel(),
           N, src.shape[1], src.shape[2], C, P, k)
@@ -1064,19 +1098,20 @@ def mask_match_cost(pred, tgt, coords, ws=None, ce_out=None, dice_out=None):
     ce_out, dice_out: both None (the two results are allocated) or both contiguous fp32 (Q, T) tensors the results are written to and that
     are returned -- views into a caller's buffer, e.g. an image's block of the packed costs of hungarian_cost.
     Nothing is copied: a strided or non-fp32 operand is refused; the layout is checked before the device."""
-    _layout_f32(pred, "pred", 3)
-    _layout_f32(tgt, "tgt", 3)
-    _layout_f32(coords, "coords", 2)
+    who = "mask_match_cost"
+    _layout(who, "pred", pred, torch.float32, ndim=3)
+    _layout(who, "tgt", tgt, torch.float32, ndim=3)
+    _layout(who, "coords", coords, torch.float32, ndim=2)
     Q, T, P = pred.shape[0], tgt.shape[0], coords.shape[0]
     if coords.shape[1] != 2 or (P == 0 and Q * T > 0):
         raise RuntimeError("mask_match_cost: coords must be (P > 0, 2), got %s" % (tuple(coords.shape),))
     if (ce_out is None) != (dice_out is None):
         raise RuntimeError("mask_match_cost: ce_out and dice_out come together")
     if ce_out is not None:
-        _layout_as(ce_out, "ce_out", torch.float32, (Q, T))
-        _layout_as(dice_out, "dice_out", torch.float32, (Q, T))
-    _on_device(pred=pred, tgt=tgt, coords=coords, ws=ws, ce_out=ce_out, dice_out=dice_out)
-    ws = _workspace(ws, _size("hipie_mask_match_cost_ws_bytes", Q, T, P), pred.device, "mask_match_cost")
+        _layout(who, "ce_out", ce_out, torch.float32, (Q, T))
+        _layout(who, "dice_out", dice_out, torch.float32, (Q, T))
+    _on_device(who, "pred tgt coords ws ce_out dice_out", pred, tgt, coords, ws, ce_out, dice_out)
+    ws = _workspace(ws, _size("hipie_mask_match_cost_ws_bytes", Q, T, P), pred.device, who)
     ce, dice = (pred.new_empty(Q, T), pred.new_empty(Q, T)) if ce_out is None else (ce_out, dice_out)
     _call("hipie_mask_match_cost", pred.data_ptr(), tgt.data_ptr(), coords.data_ptr(), ce.data_ptr(), dice.data_ptr(), ws.data_ptr(), ws.numel(),
           Q, pred.shape[1], pred.shape[2], T, tgt.shape[1], tgt.shape[2], P)
@@ -1090,22 +1125,11 @@ def ota_match_ws_bytes(B, Q, Tmax):
     return _size("hipie_ota_match_ws_bytes", int(B), int(Q), int(Tmax))
 
 
-def _layout_as(t, name, dtype, shape):
-    """refuses t unless it is a contiguous tensor of that dtype and shape (nothing is copied)"""
-    if t.dtype != dtype:
-        raise RuntimeError("%s must be %s, got %s" % (name, dtype, t.dtype))
-    if tuple(t.shape) != tuple(shape):
-        raise RuntimeError("%s must be %s, got %s" % (name, tuple(shape), tuple(t.shape)))
-    if not t.is_contiguous():
-        raise RuntimeError("%s tensor has to be contiguous" % name)
-
-
-def _ota_results(res, B, device):
+def _ota_results(who, res, B, device):
     """the (3, B) int32 block n_pairs | status | repair rounds of one matching call: the host reads it with one copy"""
     if res is None:
         return torch.zeros(3, B, dtype=torch.int32, device=device)
-    _layout_as(res, "res", torch.int32, (3, B))
-    return res
+    return _layout(who, "res", res, torch.int32, (3, B))
 
 
 @_timed("ota_cost")
@@ -1116,18 +1140,18 @@ def ota_cost(logits, boxes, tgt_boxes, pos_map, n_tgt, center_radius=2.5, stride
     x1 < x0 or y1 < y0, bit 1: a target without a positive token).  Bit-reproducible.
     ws: uint8 tensor of at least ota_match_ws_bytes(B, Q, Tmax) elements, or None: allocated (it backs the two results).
     Nothing is copied: a strided operand or one of another dtype is refused; the layout is checked before the device."""
-    _layout_f32(logits, "logits", 3)
-    _layout_f32(boxes, "boxes", 3)
-    _layout_f32(tgt_boxes, "tgt_boxes", 3)
+    who = "ota_cost"
+    _layout(who, "logits", logits, torch.float32, ndim=3)
+    _layout(who, "tgt_boxes", tgt_boxes, torch.float32, ndim=3)
     B, Q, L = logits.shape
     Tmax = tgt_boxes.shape[1]
-    _layout_as(boxes, "boxes", torch.float32, (B, Q, 4))
-    _layout_as(tgt_boxes, "tgt_boxes", torch.float32, (B, Tmax, 4))
-    _layout_as(pos_map, "pos_map", torch.uint8, (B, Tmax, L))
-    _layout_as(n_tgt, "n_tgt", torch.int32, (B,))
-    res = _ota_results(res, B, logits.device)
-    _on_device(logits=logits, boxes=boxes, tgt_boxes=tgt_boxes, pos_map=pos_map, n_tgt=n_tgt, ws=ws, res=res)
-    ws = _workspace(ws, _size("hipie_ota_match_ws_bytes", B, Q, Tmax), logits.device, "ota_cost")
+    _layout(who, "boxes", boxes, torch.float32, (B, Q, 4))
+    _layout(who, "tgt_boxes", tgt_boxes, None, (B, Tmax, 4))
+    _layout(who, "pos_map", pos_map, torch.uint8, (B, Tmax, L))
+    _layout(who, "n_tgt", n_tgt, torch.int32, (B,))
+    res = _ota_results(who, res, B, logits.device)
+    _on_device(who, "logits boxes tgt_boxes pos_map n_tgt ws res", logits, boxes, tgt_boxes, pos_map, n_tgt, ws, res)
+    ws = _workspace(ws, _size("hipie_ota_match_ws_bytes", B, Q, Tmax), logits.device, who)
     n = B * Tmax * Q * 4
     cost, iou = ws[:n].view(torch.float32).view(B, Tmax, Q), ws[n:2 * n].view(torch.float32).view(B, Tmax, Q)
     _call("hipie_ota_cost", logits.data_ptr(), boxes.data_ptr(), tgt_boxes.data_ptr(), pos_map.data_ptr(), n_tgt.data_ptr(), cost.data_ptr(),
@@ -1142,12 +1166,13 @@ def ota_assign(cost, iou, n_tgt, res=None):
     best (B,Tmax), res): int32; image b's matched queries in ascending order are pair_q[b, :n] with the target of each in pair_t[b, :n],
     n = res[0, b]; best[b, t] the matched query of target t with the smallest cost; res (3,B): n_pairs | status (bit 2: the repair loop was
     stopped after Q rounds) | repair rounds.  One workgroup per image, bit-reproducible."""
-    _layout_f32(cost, "cost", 3)
+    who = "ota_assign"
+    _layout(who, "cost", cost, torch.float32, ndim=3)
     B, Tmax, Q = cost.shape
-    _layout_as(iou, "iou", torch.float32, (B, Tmax, Q))
-    _layout_as(n_tgt, "n_tgt", torch.int32, (B,))
-    res = _ota_results(res, B, cost.device)
-    _on_device(cost=cost, iou=iou, n_tgt=n_tgt, res=res)
+    _layout(who, "iou", iou, torch.float32, (B, Tmax, Q))
+    _layout(who, "n_tgt", n_tgt, torch.int32, (B,))
+    res = _ota_results(who, res, B, cost.device)
+    _on_device(who, "cost iou n_tgt res", cost, iou, n_tgt, res)
     pairs = torch.empty(2, B, Q, dtype=torch.int32, device=cost.device)
     best = torch.empty(B, Tmax, dtype=torch.int32, device=cost.device)
     _call("hipie_ota_assign", cost.data_ptr(), iou.data_ptr(), n_tgt.data_ptr(), pairs[0].data_ptr(), pairs[1].data_ptr(), best.data_ptr(),
@@ -1164,9 +1189,9 @@ def hungarian_cost_ws_bytes(B, Q):
 
 
 def _image_stride(t, name, row):
-    """the image stride of a fp32 (B, Q, row) tensor whose images are dense (a slice of the query dimension of a dense tensor is); nothing is copied"""
-    if t.dtype != torch.float32:
-        raise RuntimeError("%s must be torch.float32, got %s" % (name, t.dtype))
+    """the image stride of a fp32 (B, Q, row) tensor whose images are dense (a slice of the query dimension of a dense tensor is); nothing is
+    copied, and the device is the caller's to check, after the layout"""
+    _layout("hungarian_cost", name, t, torch.float32, density=_ANY)
     if t.dim() != 3 or t.shape[2] != row:
         raise RuntimeError("%s must be (B, Q, %d), got %s" % (name, row, tuple(t.shape)))
     B, Q = t.shape[:2]
@@ -1191,43 +1216,42 @@ def hungarian_cost(logits, boxes, tgt_boxes, n_tgt, t_off, sum_t, weights, pos_m
     refused; the layout is checked before the device."""
     ls = _image_stride(logits, "logits", logits.shape[2] if logits.dim() == 3 else 0)
     B, Q, L = logits.shape
-    _layout_f32(tgt_boxes, "tgt_boxes", 3)
+    who = "hungarian_cost"
+    _layout(who, "tgt_boxes", tgt_boxes, torch.float32, ndim=3)
     Tmax, sum_t = tgt_boxes.shape[1], int(sum_t)
-    _layout_as(tgt_boxes, "tgt_boxes", torch.float32, (B, Tmax, 4))
+    _layout(who, "tgt_boxes", tgt_boxes, None, (B, Tmax, 4))
     bs = 0
     if with_boxes:
         if boxes is None:
             raise RuntimeError("hungarian_cost: boxes are needed with the box costs")
         bs = _image_stride(boxes, "boxes", 4)
-        if tuple(boxes.shape) != (B, Q, 4):
-            raise RuntimeError("boxes must be %s, got %s" % ((B, Q, 4), tuple(boxes.shape)))
-    _layout_as(n_tgt, "n_tgt", torch.int32, (B,))
-    _layout_as(t_off, "t_off", torch.int32, (B,))
+        _layout(who, "boxes", boxes, None, (B, Q, 4), density=_ANY)
+    _layout(who, "n_tgt", n_tgt, torch.int32, (B,))
+    _layout(who, "t_off", t_off, torch.int32, (B,))
     if (pos_map is None) == (labels is None):
         raise RuntimeError("hungarian_cost: exactly one of pos_map and labels")
     if pos_map is not None:
-        _layout_as(pos_map, "pos_map", torch.uint8, (B, Tmax, L))
+        _layout(who, "pos_map", pos_map, torch.uint8, (B, Tmax, L))
     else:
-        _layout_as(labels, "labels", torch.int32, (B, Tmax))
+        _layout(who, "labels", labels, torch.int32, (B, Tmax))
     mean = bool(with_boxes and stuff_takes_mean)
     if mean:
         if is_thing is None:
             raise RuntimeError("hungarian_cost: is_thing is needed with the stuff mean")
-        _layout_as(is_thing, "is_thing", torch.uint8, (B, Tmax))
+        _layout(who, "is_thing", is_thing, torch.uint8, (B, Tmax))
     if (ce is None) != (dice is None):
         raise RuntimeError("hungarian_cost: ce and dice come together")
     if not 0 <= sum_t <= B * Tmax:
         raise RuntimeError("hungarian_cost: sum_t=%d outside [0, B x Tmax = %d]" % (sum_t, B * Tmax))
     if ce is not None:
-        _layout_as(ce, "ce", torch.float32, (Q * sum_t,))
-        _layout_as(dice, "dice", torch.float32, (Q * sum_t,))
+        _layout(who, "ce", ce, torch.float32, (Q * sum_t,))
+        _layout(who, "dice", dice, torch.float32, (Q * sum_t,))
     if Q > HUNGARIAN_MAX_Q or Tmax > HUNGARIAN_MAX_T or L > HUNGARIAN_MAX_L or (L < 1 and B * Q * Tmax > 0) or B > 65535:
         raise RuntimeError("hungarian_cost: B=%d, Q=%d, Tmax=%d, L=%d outside B <= 65535, Q <= %d, Tmax <= %d, 1 <= L <= %d"
                            % (B, Q, Tmax, L, HUNGARIAN_MAX_Q, HUNGARIAN_MAX_T, HUNGARIAN_MAX_L))
-    if out is not None:
-        _layout_as(out, "out", torch.float32, (Q * sum_t + B,))
-    _on_device(logits=logits, boxes=boxes if with_boxes else None, tgt_boxes=tgt_boxes, n_tgt=n_tgt, t_off=t_off, pos_map=pos_map, labels=labels,
-               is_thing=is_thing if mean else None, ce=ce, dice=dice, out=out, ws=ws)
+    _layout(who, "out", out, torch.float32, (Q * sum_t + B,))
+    _on_device(who, "logits boxes tgt_boxes n_tgt t_off pos_map labels is_thing ce dice out ws", logits, boxes if with_boxes else None, tgt_boxes,
+               n_tgt, t_off, pos_map, labels, is_thing if mean else None, ce, dice, out, ws)
     if out is None:
         out = torch.empty(Q * sum_t + B, dtype=torch.float32, device=logits.device)
     n = Q * sum_t
@@ -1236,13 +1260,12 @@ def hungarian_cost(logits, boxes, tgt_boxes, n_tgt, t_off, sum_t, weights, pos_m
         status.zero_()
         return out
     if mean:
-        ws = _workspace(ws, _size("hipie_hungarian_cost_ws_bytes", B, Q), logits.device, "hungarian_cost")
-    ptr = lambda t: None if t is None else t.data_ptr()          # noqa: E731
+        ws = _workspace(ws, _size("hipie_hungarian_cost_ws_bytes", B, Q), logits.device, who)
     w = [float(x) for x in weights]
     if len(w) != 5:
         raise RuntimeError("hungarian_cost: five weights (cls, l1, giou, mask, dice), got %d" % len(w))
-    _call("hipie_hungarian_cost", logits.data_ptr(), ls, ptr(boxes) if with_boxes else None, bs, tgt_boxes.data_ptr(), n_tgt.data_ptr(), t_off.data_ptr(),
-          ptr(pos_map), ptr(labels), ptr(is_thing) if mean else None, ptr(ce), ptr(dice), out.data_ptr() if n else None,
+    _call("hipie_hungarian_cost", logits.data_ptr(), ls, _ptr(boxes) if with_boxes else None, bs, tgt_boxes.data_ptr(), n_tgt.data_ptr(), t_off.data_ptr(),
+          _ptr(pos_map), _ptr(labels), _ptr(is_thing) if mean else None, _ptr(ce), _ptr(dice), out.data_ptr() if n else None,
           status.data_ptr(), ws.data_ptr() if mean else None, ws.numel() if mean else 0, B, Q, Tmax, L, sum_t, *w,
           1 if with_boxes else 0, 1 if stuff_takes_mean else 0)
     return out
@@ -1271,21 +1294,22 @@ def hungarian_assign(costs, n_tgt, t_off, sum_t, Q, Tmax, ws=None):
     if n_tgt.dim() != 1:
         raise RuntimeError("n_tgt must be (B,), got %s" % (tuple(n_tgt.shape),))
     B, Q, Tmax, sum_t = int(n_tgt.shape[0]), int(Q), int(Tmax), int(sum_t)
-    _layout_as(n_tgt, "n_tgt", torch.int32, (B,))
-    _layout_as(t_off, "t_off", torch.int32, (B,))
+    who = "hungarian_assign"
+    _layout(who, "n_tgt", n_tgt, torch.int32, (B,))
+    _layout(who, "t_off", t_off, torch.int32, (B,))
     if Q < 0 or Tmax < 0 or not 0 <= sum_t <= B * Tmax:
         raise RuntimeError("hungarian_assign: Q=%d, Tmax=%d, sum_t=%d outside Q >= 0, Tmax >= 0, 0 <= sum_t <= B x Tmax = %d" % (Q, Tmax, sum_t, B * Tmax))
-    _layout_as(costs, "costs", torch.float32, (Q * sum_t + B,))
+    _layout(who, "costs", costs, torch.float32, (Q * sum_t + B,))
     if Q > HUNGARIAN_MAX_Q or Tmax > HUNGARIAN_MAX_T or B > 65535:
         raise RuntimeError("hungarian_assign: B=%d, Q=%d, Tmax=%d outside B <= 65535, Q <= %d, Tmax <= %d" % (B, Q, Tmax, HUNGARIAN_MAX_Q, HUNGARIAN_MAX_T))
-    _on_device(costs=costs, n_tgt=n_tgt, t_off=t_off, ws=ws)
+    _on_device(who, "costs n_tgt t_off ws", costs, n_tgt, t_off, ws)
     K, n = min(Q, Tmax), Q * sum_t
     pairs = torch.empty(2, B, K, dtype=torch.int64, device=costs.device)
     status = torch.empty(B, dtype=torch.int32, device=costs.device)
     if B * Q * Tmax == 0:                                    # no launch: nothing to solve (K == 0 or B == 0: the pairs are empty)
         status.copy_(costs[n:].view(torch.int32))
         return pairs[0], pairs[1], status
-    ws = _workspace(ws, _size("hipie_hungarian_assign_ws_bytes", Q, sum_t), costs.device, "hungarian_assign")
+    ws = _workspace(ws, _size("hipie_hungarian_assign_ws_bytes", Q, sum_t), costs.device, who)
     _call("hipie_hungarian_assign", costs.data_ptr() if n else None, costs[n:].data_ptr(), n_tgt.data_ptr(), t_off.data_ptr(), pairs[0].data_ptr(),
           pairs[1].data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), B, Q, Tmax, sum_t)
     return pairs[0], pairs[1], status
@@ -1311,21 +1335,11 @@ def _pair_lists(who, pairs, with_t=True):
                                    % (who, name, b, x.dtype, tuple(x.shape)))
         if q.shape != t.shape:
             raise RuntimeError("%s: image %d has %d query and %d target indices" % (who, b, q.numel(), t.numel()))
-        _on_device(pair_q=q, pair_t=t)
+        _on_device(who, "pair_q pair_t", q, t)
         ns[b] = q.numel()
         if q.numel():
             qs[b], ts[b] = q.data_ptr(), t.data_ptr()
     return qs, (ts if with_t else None), ns, sum(ns)
-
-
-def _rows_f32(t, name, shape, inner):
-    """refuses t unless it is an fp32 tensor of that shape whose last `inner` elements are dense (the image and row strides are the caller's)"""
-    if t.dtype != torch.float32:
-        raise RuntimeError("%s must be torch.float32, got %s" % (name, t.dtype))
-    if tuple(t.shape) != tuple(shape):
-        raise RuntimeError("%s must be %s, got %s" % (name, tuple(shape), tuple(t.shape)))
-    if inner > 1 and t.stride(-1) != 1:
-        raise RuntimeError("%s: the last dimension has to be dense" % name)
 
 
 @_timed("pair_box_loss_fwd")
@@ -1337,27 +1351,26 @@ def pair_box_loss_forward(boxes, iou, pairs, tgt_boxes, is_thing, count, mode):
     backward; pair_grad (K,9); status (1,) int32, PAIR_STATUS).  Two launches, no host wait, bit-reproducible.  Without pairs nothing is
     launched and out is all zero.  Nothing is copied: another dtype or layout, B > 64 or more than 65536 pairs is refused."""
     B, Q = boxes.shape[0], boxes.shape[1] if boxes.dim() == 3 else -1
-    _rows_f32(boxes, "boxes", (B, Q, 4), 4)
-    if iou is not None:
-        _rows_f32(iou, "iou", (B, Q), 1)
+    who = "pair_box_loss_forward"
+    _layout(who, "boxes", boxes, torch.float32, (B, Q, 4), density=_ROWS)
+    _layout(who, "iou", iou, torch.float32, (B, Q), density=_ANY)
     Tmax = tgt_boxes.shape[1] if tgt_boxes.dim() == 3 else -1
-    _layout_as(tgt_boxes, "tgt_boxes", torch.float32, (B, Tmax, 4))
-    if is_thing is not None:
-        _layout_as(is_thing, "is_thing", torch.uint8, (B, Tmax))
+    _layout(who, "tgt_boxes", tgt_boxes, torch.float32, (B, Tmax, 4))
+    _layout(who, "is_thing", is_thing, torch.uint8, (B, Tmax))
     if len(pairs) != B or B > PAIR_MAX_B:
         raise RuntimeError("pair_box_loss: %d pair lists for B=%d images (at most %d)" % (len(pairs), B, PAIR_MAX_B))
     qs, ts, ns, K = _pair_lists("pair_box_loss", pairs)
     if K > PAIR_MAX_K:
         raise RuntimeError("pair_box_loss: K=%d pairs, at most %d" % (K, PAIR_MAX_K))
-    _on_device(boxes=boxes, iou=iou, tgt_boxes=tgt_boxes, is_thing=is_thing)
+    _on_device(who, "boxes iou tgt_boxes is_thing", boxes, iou, tgt_boxes, is_thing)
     out = boxes.new_zeros(8)
     pair_grad = boxes.new_empty(K, 9)
     status = torch.zeros(1, dtype=torch.int32, device=boxes.device)
     ws_bytes = _size("hipie_pair_box_loss_ws_bytes", K)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=boxes.device)
-    _call("hipie_pair_box_loss_forward", boxes.data_ptr(), boxes.stride(0), boxes.stride(1), None if iou is None else iou.data_ptr(),
+    ws = _workspace(None, ws_bytes, boxes.device, who)
+    _call("hipie_pair_box_loss_forward", boxes.data_ptr(), boxes.stride(0), boxes.stride(1), _ptr(iou),
           0 if iou is None else iou.stride(0), 0 if iou is None else iou.stride(1), qs, ts, ns, tgt_boxes.data_ptr(),
-          None if is_thing is None else is_thing.data_ptr(), out.data_ptr(), pair_grad.data_ptr(), status.data_ptr(), ws.data_ptr(), ws_bytes, B, Q,
+          _ptr(is_thing), out.data_ptr(), pair_grad.data_ptr(), status.data_ptr(), ws.data_ptr(), ws_bytes, B, Q,
           Tmax, int(mode), float(count))
     return out, pair_grad, status
 
@@ -1368,17 +1381,18 @@ def pair_box_loss_backward(pairs, out, pair_grad, g_bbox, g_giou, g_boxiou, B, Q
     each (hipie_pair_box_loss_backward): both results are zero-filled and every pair adds its stored gradient with an fp32 atomic -- duplicates
     of an (image, query) sum; one target per (image, query): bit-reproducible.  No host wait."""
     qs, _, ns, K = _pair_lists("pair_box_loss_backward", pairs, with_t=False)
-    _layout_as(out, "out", torch.float32, (8,))
-    _layout_as(pair_grad, "pair_grad", torch.float32, (K, 9))
-    gs = (g_bbox, g_giou) + ((g_boxiou,) if with_iou else ())
-    for g in gs:
-        if g.dtype != torch.float32 or g.numel() != 1:
+    who = "pair_box_loss_backward"
+    _layout(who, "out", out, torch.float32, (8,))
+    _layout(who, "pair_grad", pair_grad, torch.float32, (K, 9))
+    g_boxiou = g_boxiou if with_iou else None
+    for g in (g_bbox, g_giou, g_boxiou):
+        if g is not None and (g.dtype != torch.float32 or g.numel() != 1):
             raise RuntimeError("pair_box_loss_backward: an upstream gradient must hold one torch.float32 value, got %s %s" % (g.dtype, tuple(g.shape)))
-    _on_device(out=out, pair_grad=pair_grad, **{"g%d" % i: g for i, g in enumerate(gs)})
+    _on_device(who, "out pair_grad g_bbox g_giou g_boxiou", out, pair_grad, g_bbox, g_giou, g_boxiou)
     d_boxes = out.new_empty(B, Q, 4)
     d_iou = out.new_empty(B, Q) if with_iou else None
     _call("hipie_pair_box_loss_backward", qs, ns, out.data_ptr(), pair_grad.data_ptr(), g_bbox.data_ptr(), g_giou.data_ptr(),
-          g_boxiou.data_ptr() if with_iou else None, d_boxes.data_ptr(), None if d_iou is None else d_iou.data_ptr(), B, Q)
+          _ptr(g_boxiou), d_boxes.data_ptr(), _ptr(d_iou), B, Q)
     return d_boxes, d_iou
 
 
@@ -1389,13 +1403,13 @@ def positive_onehot(pairs, pos_map, Q):
     if pos_map.dim() != 3:
         raise RuntimeError("positive_onehot: pos_map must be (B, Tmax, L), got %s" % (tuple(pos_map.shape),))
     B, Tmax, L = pos_map.shape
-    _layout_as(pos_map, "pos_map", torch.uint8, (B, Tmax, L))
+    _layout("positive_onehot", "pos_map", pos_map, torch.uint8, (B, Tmax, L))
     if len(pairs) != B or B > PAIR_MAX_B:
         raise RuntimeError("positive_onehot: %d pair lists for B=%d images (at most %d)" % (len(pairs), B, PAIR_MAX_B))
     qs, ts, ns, K = _pair_lists("positive_onehot", pairs)
     if K > PAIR_MAX_K:
         raise RuntimeError("positive_onehot: K=%d pairs, at most %d" % (K, PAIR_MAX_K))
-    _on_device(pos_map=pos_map)
+    _on_device("positive_onehot", "pos_map", pos_map)
     onehot = torch.empty(B, int(Q), L, dtype=torch.float32, device=pos_map.device)
     _call("hipie_positive_onehot", qs, ts, ns, pos_map.data_ptr(), onehot.data_ptr(), B, int(Q), Tmax, L)
     return onehot
@@ -1419,8 +1433,8 @@ def _optim_tables(who, table, cmap):
     for t, name, words in ((table, "table", OPTIM_SEGMENT_WORDS), (cmap, "cmap", 2)):
         if t.dim() != 2:
             raise RuntimeError("%s must be (n, %d), got %s" % (name, words, tuple(t.shape)))
-        _layout_as(t, name, torch.int64, (int(t.shape[0]), words))
-    _on_device(table=table, cmap=cmap)
+        _layout(who, name, t, torch.int64, (int(t.shape[0]), words))
+    _on_device(who, "table cmap", table, cmap)
     if cmap.device != table.device:
         raise RuntimeError("%s: table and cmap on different devices" % who)
     return int(table.shape[0]), int(cmap.shape[0])
@@ -1437,8 +1451,8 @@ def optim_grad_norm(table, cmap, grad_scale=1.0, ws=None):
     out = torch.empty((), dtype=torch.float32, device=table.device)
     if n_seg == 0 or n_chunks == 0:
         return out.zero_()
+    _on_device("optim_grad_norm", "ws", ws)
     ws = _workspace(ws, _size("hipie_optim_norm_ws_bytes", n_chunks), table.device, "optim_grad_norm")
-    _on_device(ws=ws)
     _call("hipie_optim_grad_norm", table.data_ptr(), n_seg, cmap.data_ptr(), n_chunks, ws.data_ptr(), ws.numel(), float(grad_scale), out.data_ptr())
     return out
 
@@ -1451,18 +1465,17 @@ def optim_adamw_step(table, cmap, steps, bc, group_lr, group_wd, betas, eps, nor
     norm: the 0-dim device tensor of optim_grad_norm -- the gradients enter as g x grad_scale x min(max_norm / (norm + 1e-6), 1) -- or None: no
     clipping.  write_grads: the clipped gradients are also written back.  Nothing is read by the host.  Two launches."""
     n_seg, n_chunks = _optim_tables("optim_adamw_step", table, cmap)
-    _layout_as(steps, "steps", torch.int32, (n_seg,))
-    _layout_as(bc, "bc", torch.float32, (n_seg, 2))
-    if norm is not None:
-        _layout_as(norm, "norm", torch.float32, ())
-    _on_device(steps=steps, bc=bc, norm=norm)
+    _layout("optim_adamw_step", "steps", steps, torch.int32, (n_seg,))
+    _layout("optim_adamw_step", "bc", bc, torch.float32, (n_seg, 2))
+    _layout("optim_adamw_step", "norm", norm, torch.float32, ())
+    _on_device("optim_adamw_step", "steps bc norm", steps, bc, norm)
     n_groups = len(group_lr)
     if len(group_wd) != n_groups or not 1 <= n_groups <= OPTIM_MAX_GROUPS:
         raise RuntimeError("optim_adamw_step: %d learning rates, %d weight decays: one each for 1 to %d groups" % (n_groups, len(group_wd), OPTIM_MAX_GROUPS))
     arr = ctypes.c_double * n_groups
     lr, wd = arr(*[float(x) for x in group_lr]), arr(*[float(x) for x in group_wd])
     _call("hipie_optim_adamw_step", table.data_ptr(), n_seg, cmap.data_ptr(), n_chunks, steps.data_ptr(), bc.data_ptr(), lr, wd, n_groups,
-          float(betas[0]), float(betas[1]), float(eps), None if norm is None else norm.data_ptr(),
+          float(betas[0]), float(betas[1]), float(eps), _ptr(norm),
           float(max_norm), float(grad_scale), int(bool(write_grads)))
 
 
@@ -1473,9 +1486,12 @@ def add_layernorm_sum(x, delta, weight, bias, eps, addend):
     rows = x.numel() // C
     if addend.dtype != x.dtype or addend.shape != x.shape:
         raise RuntimeError("add_layernorm_sum: addend must match x")
+    who = "add_layernorm_sum"
+    _on_device(who, "x delta weight bias addend", x, delta, weight, bias, addend)
     out, s = torch.empty_like(x), torch.empty_like(x)
-    _call("hipie_add_layernorm_sum", _chk(x, "x"), _chk(delta, "delta"), _chk(weight, "weight", torch.float32),
-          _chk(bias, "bias", torch.float32), None, out.data_ptr(), _chk(addend, "addend"), s.data_ptr(),
+    _call("hipie_add_layernorm_sum", _layout(who, "x", x).data_ptr(), _layout(who, "delta", delta).data_ptr(),
+          _layout(who, "weight", weight, torch.float32).data_ptr(), _layout(who, "bias", bias, torch.float32).data_ptr(), None, out.data_ptr(),
+          _layout(who, "addend", addend).data_ptr(), s.data_ptr(),
           rows, C, float(eps), _DT[x.dtype], _DT[delta.dtype], _DT[x.dtype])
     return out, s
 
@@ -1486,15 +1502,18 @@ def add_layernorm_dec(x, delta, weight, bias, eps, aux_dtype, want16=False, adde
     (n + addend) in aux_dtype or None) from one launch.  x (..., C) f32; delta any of f32/f16/bf16; addend aux_dtype."""
     C = x.shape[-1]
     rows = x.numel() // C
+    who = "add_layernorm_dec"
+    _on_device(who, "x delta weight bias addend", x, delta, weight, bias, addend)
     out = torch.empty_like(x)
     n16 = _alloc(tuple(x.shape), aux_dtype, x.device) if want16 else None
     s16 = _alloc(tuple(x.shape), aux_dtype, x.device) if addend is not None else None
     if addend is not None and ((addend.dtype != aux_dtype or addend.shape != x.shape) if aux_dtype != "hl8" else
                                (addend.dtype != torch.float16 or addend.numel() != 2 * x.numel())):
         raise RuntimeError("add_layernorm_dec: addend must match x's shape in aux_dtype")
-    _call("hipie_add_layernorm_dec", _chk(x, "x", torch.float32), _chk(delta, "delta"), _chk(weight, "weight", torch.float32),
-          _chk(bias, "bias", torch.float32), out.data_ptr(), None if n16 is None else n16.data_ptr(),
-          None if addend is None else _chk(addend, "addend"), None if s16 is None else s16.data_ptr(),
+    _layout(who, "addend", addend)
+    _call("hipie_add_layernorm_dec", _layout(who, "x", x, torch.float32).data_ptr(), _layout(who, "delta", delta).data_ptr(),
+          _layout(who, "weight", weight, torch.float32).data_ptr(), _layout(who, "bias", bias, torch.float32).data_ptr(), out.data_ptr(), _ptr(n16),
+          _ptr(addend), _ptr(s16),
           rows, C, float(eps), _DT[delta.dtype], _code(aux_dtype))
     return out, n16, s16
 
@@ -1517,6 +1536,7 @@ def group_norm(x, groups, weight, bias, eps, relu=False, prebias=None, out_dtype
     nhwc = x.is_contiguous(memory_format=torch.channels_last) and not (x.is_contiguous() and C > 1 and H * W > 1)
     if not nhwc and not x.is_contiguous():
         raise RuntimeError("group_norm: x must be NCHW- or channels-last-contiguous")
+    _on_device("group_norm", "x prebias weight bias", x, prebias, weight, bias)
     out_dtype = out_dtype or x.dtype
     if out_nchw and nhwc and (H * W) % 64 == 0:
         nhwc = 2
@@ -1527,22 +1547,22 @@ def group_norm(x, groups, weight, bias, eps, relu=False, prebias=None, out_dtype
     ws = _GN_WS.get(key)
     if ws is None:
         ws = _GN_WS[key] = torch.empty(2 * B * groups * 512, dtype=torch.float32, device=x.device)
-    _call("hipie_group_norm", x.data_ptr(), None if prebias is None else _chk(prebias, "prebias", torch.float32),
-          _chk(weight, "weight", torch.float32), _chk(bias, "bias", torch.float32), out.data_ptr(),
+    _call("hipie_group_norm", x.data_ptr(), None if prebias is None else _layout("group_norm", "prebias", prebias, torch.float32).data_ptr(),
+          _layout("group_norm", "weight", weight, torch.float32).data_ptr(), _layout("group_norm", "bias", bias, torch.float32).data_ptr(), out.data_ptr(),
           ws.data_ptr(), B, C, H * W, groups, int(nhwc), float(eps), 1 if relu else 0, _DT[x.dtype], _DT[out_dtype])
     return out
 
 
-def _gn_train_args(who, x, weight, bias, others=()):
+def _gn_train_args(who, x, weight, bias, dy=None, stat=None):
     """(B, C, HW) of a dense NCHW fp32 map for the training GroupNorm pair; host tensors and other layouts / types are refused"""
-    for n, t in (("x", x), ("weight", weight), ("bias", bias)) + tuple(others):
-        if not t.is_cuda:
-            raise RuntimeError("Not implemented on the CPU (%s must be a CUDA/HIP tensor)" % n)
-    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous():
-        raise RuntimeError("%s: x must be a dense NCHW fp32 tensor" % who)
+    _on_device(who, "x weight bias dy stat", x, weight, bias, dy, stat)
+    _layout(who, "x", x, torch.float32, None, 4)
     B, C, H, W = x.shape
     if weight.numel() != C or bias.numel() != C:
         raise RuntimeError("%s: weight and bias must have x's %d channels" % (who, C))
+    if weight.dtype is not torch.float32 or bias.dtype is not torch.float32 or not weight.is_contiguous() or not bias.is_contiguous():
+        _layout(who, "weight", weight, torch.float32)          # raises for one of the two
+        _layout(who, "bias", bias, torch.float32)
     return B, C, H * W
 
 
@@ -1554,9 +1574,9 @@ def group_norm_train_forward(x, groups, weight, bias, eps, relu=False):
     B, C, HW = _gn_train_args("group_norm_train_forward", x, weight, bias)
     y = torch.empty_like(x)
     stat = torch.empty(B, groups, 2, dtype=torch.float32, device=x.device)
-    ws = torch.empty(_size("hipie_group_norm_backward_ws_bytes", B, C, HW), dtype=torch.uint8, device=x.device)
-    _call("hipie_group_norm_train_forward", x.data_ptr(), _chk(weight, "weight", torch.float32), _chk(bias, "bias", torch.float32),
-          y.data_ptr(), stat.data_ptr(), ws.data_ptr(), B, C, HW, int(groups), float(eps), 1 if relu else 0)
+    ws = _workspace(None, _size("hipie_group_norm_backward_ws_bytes", B, C, HW), x.device, "group_norm_train_forward")
+    _call("hipie_group_norm_train_forward", x.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(), stat.data_ptr(), ws.data_ptr(),
+          B, C, HW, int(groups), float(eps), 1 if relu else 0)
     return y, stat
 
 
@@ -1566,18 +1586,20 @@ def group_norm_backward(x, dy, stat, groups, weight, bias, relu=False, want_dx=T
     (dx | None, dgamma | None, dbeta | None); with relu the mask is recomputed from x and stat (the forward's y > 0 bit for bit).
     Without want_dx the second pass is not launched, without want_param_grads the parameter sums are not; the sums are added in a fixed
     order (bit-reproducible).  Nothing is cached: the workspace lives for the call."""
-    B, C, HW = _gn_train_args("group_norm_backward", x, weight, bias, (("dy", dy), ("stat", stat)))
-    if dy.shape != x.shape or stat.shape != (B, groups, 2):
-        raise RuntimeError("group_norm_backward: dy must have the shape of x %s and stat be (B, groups, 2)" % (tuple(x.shape),))
+    who = "group_norm_backward"
+    B, C, HW = _gn_train_args(who, x, weight, bias, dy, stat)
+    if dy.shape != x.shape or stat.shape != (B, groups, 2) or dy.dtype is not torch.float32 or stat.dtype is not torch.float32 \
+            or not dy.is_contiguous() or not stat.is_contiguous():
+        _layout(who, "dy", dy, torch.float32, x.shape)          # raises for one of the two
+        _layout(who, "stat", stat, torch.float32, (B, groups, 2))
     dx = torch.empty_like(x) if want_dx else None
     dgamma = dbeta = None
     if want_param_grads:
         dgamma, dbeta = (torch.empty(C, dtype=torch.float32, device=x.device) for _ in range(2))
     ws_bytes = _size("hipie_group_norm_backward_ws_bytes", B, C, HW)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-    _call("hipie_group_norm_backward", x.data_ptr(), _chk(dy, "dy", torch.float32), _chk(stat, "stat", torch.float32),
-          _chk(weight, "weight", torch.float32), _chk(bias, "bias", torch.float32), None if dx is None else dx.data_ptr(),
-          None if dgamma is None else dgamma.data_ptr(), None if dbeta is None else dbeta.data_ptr(), ws.data_ptr(), ws_bytes,
+    ws = _workspace(None, ws_bytes, x.device, who)
+    _call("hipie_group_norm_backward", x.data_ptr(), dy.data_ptr(), stat.data_ptr(), weight.data_ptr(), bias.data_ptr(), _ptr(dx),
+          _ptr(dgamma), _ptr(dbeta), ws.data_ptr(), ws_bytes,
           B, C, HW, int(groups), 1 if relu else 0)
     return dx, dgamma, dbeta
 
@@ -1587,18 +1609,22 @@ def add_cast(a, b):
     """(a f32 + b 16-bit) rounded once to b's dtype; same shapes, numel % 4 == 0."""
     if a.shape != b.shape:
         raise RuntimeError("add_cast: shapes differ")
+    _on_device("add_cast", "a b", a, b)
     out = torch.empty_like(b)
-    _call("hipie_add_cast", _chk(a, "a", torch.float32), _chk(b, "b"), out.data_ptr(), a.numel(), _DT[b.dtype])
+    _call("hipie_add_cast", _layout("add_cast", "a", a, torch.float32).data_ptr(), _layout("add_cast", "b", b).data_ptr(), out.data_ptr(), a.numel(),
+          _DT[b.dtype])
     return out
 
 
 @_timed("add_cast")
 def add_to_hl8(a, b_hl8):
     """HL8 of (a + b): a (..., C) fp32, b_hl8 (..., 2C) fp16 HL8 of the same rows -> (..., 2C) HL8, one pass (hipie_add_cast, HL8 form)."""
-    if b_hl8.dtype != torch.float16 or b_hl8.numel() != 2 * a.numel() or a.shape[-1] % 8 or not a.is_cuda:
+    if b_hl8.dtype != torch.float16 or b_hl8.numel() != 2 * a.numel() or a.shape[-1] % 8:
         raise RuntimeError("add_to_hl8: a (.., C) fp32 and b (.., 2C) HL8 device tensors, C %% 8 == 0")
+    _on_device("add_to_hl8", "a b_hl8", a, b_hl8)
     out = torch.empty_like(b_hl8)
-    _call("hipie_add_cast", _chk(a, "a", torch.float32), _chk(b_hl8, "b"), out.data_ptr(), a.numel(), HL8)
+    _call("hipie_add_cast", _layout("add_to_hl8", "a", a, torch.float32).data_ptr(), _layout("add_to_hl8", "b_hl8", b_hl8).data_ptr(), out.data_ptr(),
+          a.numel(), HL8)
     return out
 
 
@@ -1609,10 +1635,12 @@ def batched_nms(boxes, scores, classes, iou_threshold, coordinate_trick=None):
     B, Q = scores.shape
     if coordinate_trick is None:
         coordinate_trick = Q * 4 <= 4000                  # torchvision/ops/boxes.py batched_nms switch
+    _on_device("batched_nms", "boxes scores classes", boxes, scores, classes)
     order = scores.sort(dim=1, descending=True, stable=True)[1].to(torch.int32)
     keep = torch.empty(B, Q, dtype=torch.int32, device=boxes.device)
     count = torch.empty(B, dtype=torch.int32, device=boxes.device)
-    _call("hipie_batched_nms", _chk(boxes, "boxes", torch.float32), _chk(classes, "classes", torch.int64), order.data_ptr(),
+    _call("hipie_batched_nms", _layout("batched_nms", "boxes", boxes, torch.float32).data_ptr(),
+          _layout("batched_nms", "classes", classes, torch.int64).data_ptr(), order.data_ptr(),
           keep.data_ptr(), count.data_ptr(), B, Q, float(iou_threshold), int(coordinate_trick))
     return keep, count
 
@@ -1623,8 +1651,10 @@ def mask_finalize(masks, qidx, up, crop_hw, out_hw, threshold):
     bilinear x`up` -> sigmoid > threshold -> crop -> nearest resize to out_hw."""
     Q, hm, wm = masks.shape
     n = Q if qidx is None else int(qidx.shape[0])
+    _on_device("mask_finalize", "masks qidx", masks, qidx)
     out = torch.empty(n, out_hw[0], out_hw[1], dtype=torch.uint8, device=masks.device)
-    _call("hipie_mask_finalize", _chk(masks, "masks"), _DT[masks.dtype], None if qidx is None else _chk(qidx, "qidx", torch.int32),
+    _call("hipie_mask_finalize", _layout("mask_finalize", "masks", masks).data_ptr(), _DT[masks.dtype],
+          None if qidx is None else _layout("mask_finalize", "qidx", qidx, torch.int32).data_ptr(),
           n, hm, wm, int(up), int(crop_hw[0]), int(crop_hw[1]), int(out_hw[0]), int(out_hw[1]), float(threshold), out.data_ptr())
     return out
 
@@ -1646,6 +1676,7 @@ def sem_pan(masks_lo, cls_all, pscore, up, crop_hw, out_hw, precision=0):
     N, C = cls_all.shape
     _, hm, wm = masks_lo.shape
     dev = masks_lo.device
+    _on_device("sem_pan", "masks_lo cls_all pscore", masks_lo, cls_all, pscore)
     npad = (N + 15) // 16 * 16
     ps = torch.full((npad,), -1.0, dtype=torch.float32, device=dev)
     ps[:N] = pscore
@@ -1654,7 +1685,7 @@ def sem_pan(masks_lo, cls_all, pscore, up, crop_hw, out_hw, precision=0):
     pan_idx = torch.empty(oh, ow, dtype=torch.int32, device=dev)
     pan_own = torch.empty(oh, ow, dtype=torch.uint8, device=dev)
     area = torch.zeros(npad, dtype=torch.int32, device=dev)
-    masks_ptr = _chk(masks_lo, "masks", torch.float32)
+    masks_ptr = _layout("sem_pan", "masks_lo", masks_lo, torch.float32).data_ptr()
     spare = None
     for c0 in range(0, C, SEM_PAN_CLASSES):
         cn = min(SEM_PAN_CLASSES, C - c0)
@@ -1669,7 +1700,7 @@ def sem_pan(masks_lo, cls_all, pscore, up, crop_hw, out_hw, precision=0):
             if spare is None:
                 spare = (torch.empty_like(pan_idx), torch.empty_like(pan_own), torch.zeros_like(area))
             outs = spare
-        _call("hipie_sem_pan", masks_ptr, hi.data_ptr(), None if lo is None else lo.data_ptr(),
+        _call("hipie_sem_pan", masks_ptr, hi.data_ptr(), _ptr(lo),
               ps.data_ptr(), sem[c0:c0 + cn].data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(),
               N, npad, cn, hm, wm, int(up), int(crop_hw[0]), int(crop_hw[1]), oh, ow, int(precision))
     return sem, pan_idx, pan_own.bool(), area[:N]
@@ -1678,10 +1709,8 @@ def sem_pan(masks_lo, cls_all, pscore, up, crop_hw, out_hw, precision=0):
 _DIM_T = {}
 
 
-@_timed("sine_embed")
-def sine_embed(ref, num_pos_feats=128, temperature=10000, out_dtype=torch.float32):
-    """get_sine_pos_embed(ref, exchange_xy=True): ref (..., 2|4) f32 (last-dim stride 1) -> (..., ncoord * num_pos_feats)."""
-    import math
+def _sine_operands(ref, num_pos_feats, temperature):
+    """(ref as fp32 rows, their stride, the cached frequency table) of the two sine-embedding ops"""
     nc = ref.shape[-1]
     ref = ref.float()
     rs = nc
@@ -1695,10 +1724,18 @@ def sine_embed(ref, num_pos_feats=128, temperature=10000, out_dtype=torch.float3
         d = torch.arange(num_pos_feats, dtype=torch.float32, device=ref.device)
         dim_t = (temperature ** (2 * torch.div(d, 2, rounding_mode="floor") / num_pos_feats)).contiguous()
         _DIM_T[key] = dim_t
+    return ref, rs, dim_t
+
+
+@_timed("sine_embed")
+def sine_embed(ref, num_pos_feats=128, temperature=10000, out_dtype=torch.float32):
+    """get_sine_pos_embed(ref, exchange_xy=True): ref (..., 2|4) f32 (last-dim stride 1) -> (..., ncoord * num_pos_feats)."""
+    import math
+    nc = ref.shape[-1]
+    _on_device("sine_embed", "ref", ref)
+    ref, rs, dim_t = _sine_operands(ref, num_pos_feats, temperature)
     n = ref.numel() // nc
     out = torch.empty(ref.shape[:-1] + (nc * num_pos_feats,), dtype=out_dtype, device=ref.device)
-    if not ref.is_cuda:
-        raise RuntimeError("Not implemented on the CPU (ref must be a CUDA/HIP tensor)")
     _call("hipie_sine_embed", ref.data_ptr(), dim_t.data_ptr(), out.data_ptr(), n, nc, num_pos_feats, rs, 2 * math.pi, _DT[out_dtype])
     return out
 
@@ -1720,18 +1757,8 @@ def ref_point_mlp(ref, head, num_pos_feats=128, temperature=10000):
     """query_pos = head(get_sine_pos_embed(ref)) in one launch: ref (B, Q, 4) f32 (row-strided view allowed), head = the
     2-layer ref_point_head (512 -> 256 -> 256) -> (B, Q, 256) in the head's weight dtype."""
     import math
-    ref = ref.float()
-    rs = 4
-    if ref.dim() == 3 and ref.stride(-1) == 1 and ref.stride(0) == ref.shape[1] * ref.stride(1) and ref.stride(1) >= 4:
-        rs = ref.stride(1)
-    elif not ref.is_contiguous():
-        ref = ref.contiguous()
-    key = (num_pos_feats, temperature, str(ref.device))
-    dim_t = _DIM_T.get(key)
-    if dim_t is None:
-        d = torch.arange(num_pos_feats, dtype=torch.float32, device=ref.device)
-        dim_t = (temperature ** (2 * torch.div(d, 2, rounding_mode="floor") / num_pos_feats)).contiguous()
-        _DIM_T[key] = dim_t
+    _on_device("ref_point_mlp", "ref weight", ref, head.layers[0].weight)
+    ref, rs, dim_t = _sine_operands(ref, num_pos_feats, temperature)
     (w1t, b1), (w2t, b2) = _transposed(list(head.layers))
     dt = w1t.dtype
     n = ref.numel() // 4
@@ -1751,10 +1778,11 @@ def box_head_ok(x, mlp):
 @_timed("box_head")
 def box_head(x, ref, mlp, eps=1e-5):
     """sigmoid(mlp(x) + inverse_sigmoid(ref)) in one launch: x (..., 256) f32, ref (..., 4) f32, mlp = MLP(256, 256, 4, 3) f32."""
-    x, ref = x.contiguous(), ref.float().contiguous()
+    _on_device("box_head", "x ref weight", x, ref, mlp.layers[0].weight)
+    x, ref = _layout("box_head", "x", x, torch.float32, density=_ANY).contiguous(), ref.float().contiguous()
     (w1t, b1), (w2t, b2), (w3t, b3) = _transposed(list(mlp.layers))
     out = torch.empty_like(ref)
-    _call("hipie_box_head", _chk(x, "x", torch.float32), _chk(ref, "ref", torch.float32), w1t.data_ptr(), b1.data_ptr(), w2t.data_ptr(),
+    _call("hipie_box_head", x.data_ptr(), ref.data_ptr(), w1t.data_ptr(), b1.data_ptr(), w2t.data_ptr(),
           b2.data_ptr(), w3t.data_ptr(), b3.data_ptr(), out.data_ptr(), ref.numel() // 4, float(eps))
     return out
 
@@ -1762,15 +1790,17 @@ def box_head(x, ref, mlp, eps=1e-5):
 @_timed("box_refine")
 def box_refine(delta, ref, eps=1e-5):
     """sigmoid(delta + inverse_sigmoid(ref)): delta (..., 4) f32|f16|bf16, ref (..., 4) f32 -> (..., 4) f32."""
+    _on_device("box_refine", "delta ref", delta, ref)
     delta, ref = delta.contiguous(), ref.float().contiguous()
     out = torch.empty_like(ref)
-    _call("hipie_box_refine", _chk(delta, "delta"), _chk(ref, "ref", torch.float32), out.data_ptr(), ref.numel(), float(eps), _DT[delta.dtype])
+    _call("hipie_box_refine", delta.data_ptr(), ref.data_ptr(), out.data_ptr(), ref.numel(), float(eps), _DT[delta.dtype])
     return out
 
 
 def selftest(which, a, b=None):
+    _on_device("selftest", "a b", a, b)
     out = torch.empty(32 * 32 if which == 0 else 256, dtype=torch.float32, device=a.device)
-    _call("hipie_selftest", which, a.data_ptr(), None if b is None else b.data_ptr(), out.data_ptr())
+    _call("hipie_selftest", which, a.data_ptr(), _ptr(b), out.data_ptr())
     return out
 
 
@@ -1798,12 +1828,11 @@ def hl8_unpack(x):
 def to_hl8(x, scale=1.0):
     """(rows..., K) fp32 | fp16 device tensor (last dim contiguous, uniform row stride) -> (rows..., 2K) fp16 HL8 (hipie_to_hl8)."""
     K = x.shape[-1]
+    _on_device("to_hl8", "x", x)
     x2 = x.reshape(-1, K)
     if x2.stride(-1) != 1:
         x2 = x2.contiguous()
     out = torch.empty(*x.shape[:-1], 2 * K, dtype=torch.float16, device=x.device)
-    if not x.is_cuda:
-        raise RuntimeError("Not implemented on the CPU (to_hl8)")
     _call("hipie_to_hl8", x2.data_ptr(), x2.stride(0), out.data_ptr(), 2 * K, x2.shape[0], K, _DT[x.dtype], float(scale))
     return out
 
@@ -1812,8 +1841,8 @@ def to_hl8(x, scale=1.0):
 def to_hl8_t(x, pad_to=32, scale=1.0):
     """(M, C) fp32 device tensor (last dim contiguous, any row stride) -> (C, 2 Mp) fp16 HL8 of x^T, Mp = M rounded up to `pad_to`, the padding
     columns zero (hipie_to_hl8_t): a split operand whose K runs over the rows of x."""
-    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_cuda:
-        raise RuntimeError("to_hl8_t: a 2-D fp32 device tensor")
+    _layout("to_hl8_t", "x", x, torch.float32, ndim=2, density=_ANY)
+    _on_device("to_hl8_t", "x", x)
     if x.stride(1) != 1:
         x = x.contiguous()
     M, C = x.shape
@@ -1829,17 +1858,17 @@ def f16_pair(x, cols=None, scale=None):
     fp16 range saturate (hl_split).  One pass on the device (hipie_to_f16_pair)."""
     C = x.shape[-1]
     Cp = C if cols is None else max(cols, C)
-    if x.is_cuda and x.dtype == torch.float32 and Cp % 8 == 0:
-        x2 = x.reshape(-1, C)
-        if x2.stride(1) != 1 or (x2.shape[0] > 1 and x2.stride(0) < C):
-            x2 = x2.contiguous()
-        hi = torch.empty(*x.shape[:-1], Cp, dtype=torch.float16, device=x.device)
-        lo = torch.empty_like(hi)
-        sc = 0 if scale is None else scale.float().reshape(1).data_ptr()
-        _call("hipie_to_f16_pair", x2.data_ptr(), x2.stride(0) if x2.shape[0] > 1 else C, hi.data_ptr(), lo.data_ptr(), x2.shape[0], C, Cp, sc)
-        return hi, lo
-    raise RuntimeError("f16_pair: an fp32 device tensor and a column count that is a multiple of 8 (got %s %s on %s, %d columns)"
-                       % (x.dtype, tuple(x.shape), x.device, Cp))
+    if x.dtype != torch.float32 or Cp % 8:
+        raise RuntimeError("f16_pair: an fp32 device tensor and a column count that is a multiple of 8 (got %s %s on %s, %d columns)"
+                           % (x.dtype, tuple(x.shape), x.device, Cp))
+    _on_device("f16_pair", "x scale", x, scale)
+    x2 = x.reshape(-1, C)
+    if x2.stride(1) != 1 or (x2.shape[0] > 1 and x2.stride(0) < C):
+        x2 = x2.contiguous()
+    hi, lo = _f16_planes(x.shape[:-1] + (Cp,), x.device)
+    sc = 0 if scale is None else scale.float().reshape(1).data_ptr()
+    _call("hipie_to_f16_pair", x2.data_ptr(), x2.stride(0) if x2.shape[0] > 1 else C, hi.data_ptr(), lo.data_ptr(), x2.shape[0], C, Cp, sc)
+    return hi, lo
 
 
 # the two instances of the fused training attention (csrc/attn_train_tile.h): (entry-point stem, operand columns, rule on N, its wording)
@@ -1847,14 +1876,16 @@ _ATTN_TRAIN = ("attn_train", 224, lambda N: N >= 128 and N % 128 == 0, "N % 128 
 _ATTN_TRAIN_WIN = ("attn_train_win", 128, lambda N: 1 <= N <= 256, "1 <= N <= 256")
 
 
-def _attn_train_operands(who, inst, pairs, widths):
-    """the checks both directions share: every plane a contiguous fp16 device tensor, lo planes shaped like their hi planes, q' / k'
-    (BH, N, cols) with N as the instance takes it, the remaining pairs (BH, N, widths[i]) -> (the planes in entry order, BH, N)"""
+def _attn_train_operands(who, inst, names, pairs, widths):
+    """the checks both directions share: every plane (`names`: the pairs', whose planes are NAME_hi / NAME_lo) a contiguous fp16 device
+    tensor, lo planes shaped like their hi planes, q' / k' (BH, N, cols) with N as the instance takes it, the remaining pairs
+    (BH, N, widths[i]) -> (the planes in entry order, BH, N)"""
     _, cols, n_ok, rule = inst
     planes = [t for pair in pairs for t in pair]
-    for t in planes:
-        if not t.is_cuda or t.dtype != torch.float16 or not t.is_contiguous():
-            raise RuntimeError("%s: contiguous fp16 device planes" % who)
+    plane_names = [n + half for n in names.split() for half in ("_hi", "_lo")]
+    _on_device(who, " ".join(plane_names), *planes)
+    for n, t in zip(plane_names, planes):
+        _layout(who, n, t, torch.float16)
     qh, kh = pairs[0][0], pairs[1][0]
     if qh.dim() != 3 or qh.shape[-1] != cols or kh.shape != qh.shape or not n_ok(qh.shape[1]) or qh.shape[0] < 1 \
             or any(lo.shape != hi.shape for hi, lo in pairs) \
@@ -1866,7 +1897,7 @@ def _attn_train_operands(who, inst, pairs, widths):
 
 def _attn_train_forward(inst, q_pair, k_pair, v_pair):
     who = inst[0] + "_forward"
-    planes, BH, N = _attn_train_operands(who, inst, (q_pair, k_pair, v_pair), (80,))
+    planes, BH, N = _attn_train_operands(who, inst, "q k v", (q_pair, k_pair, v_pair), (80,))
     out = torch.empty(BH, N, 80, dtype=torch.float32, device=planes[0].device)
     lse = torch.empty(BH, N, dtype=torch.float32, device=planes[0].device)
     _call("hipie_" + who, *[t.data_ptr() for t in planes], out.data_ptr(), lse.data_ptr(), BH, N)
@@ -1875,9 +1906,10 @@ def _attn_train_forward(inst, q_pair, k_pair, v_pair):
 
 def _attn_train_backward(inst, q_pair, k_pair, v96_pair, do96_pair, lse, delta):
     who = inst[0] + "_backward"
-    planes, BH, N = _attn_train_operands(who, inst, (q_pair, k_pair, v96_pair, do96_pair), (96, 96))
-    if tuple(lse.shape) != (BH, N) or tuple(delta.shape) != (BH, N) or not lse.is_cuda or not delta.is_cuda:
+    planes, BH, N = _attn_train_operands(who, inst, "q k v96 do96", (q_pair, k_pair, v96_pair, do96_pair), (96, 96))
+    if tuple(lse.shape) != (BH, N) or tuple(delta.shape) != (BH, N):
         raise RuntimeError("%s: lse / delta (BH, N) on the device" % who)
+    _on_device(who, "lse delta", lse, delta)
     lse, delta = lse.float().contiguous(), delta.float().contiguous()
     dq = torch.empty(BH, N, inst[1], dtype=torch.float32, device=planes[0].device)
     dk = torch.empty(BH, N, 80, dtype=torch.float32, device=planes[0].device)
@@ -1917,27 +1949,6 @@ def attn_train_win_backward(q_pair, k_pair, v96_pair, do96_pair, lse, delta):
 ATTN_PACK_HD = 80
 
 
-def _attn_pack_dev(who, tensors, dtype=torch.float32):
-    for name, t in tensors:
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise RuntimeError("Not implemented on the CPU (%s: %s must be a CUDA/HIP tensor)" % (who, name))
-        if t.dtype != dtype:
-            raise RuntimeError("%s: %s must be %s, got %s" % (who, name, dtype, t.dtype))
-
-
-def _attn_pack_dense(who, name, t, shape):
-    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-        raise RuntimeError("%s: %s must be a contiguous %s tensor, got %s" % (who, name, tuple(shape), tuple(t.shape)))
-    return t.data_ptr()
-
-
-def _attn_pack_pair(who, name, pair, shape):
-    _attn_pack_dev(who, ((name + " hi", pair[0]), (name + " lo", pair[1])), torch.float16)
-    return [_attn_pack_dense(who, name, t, shape) for t in pair]
-
-
 def attn_pack_rows(N, padded):
     """rows per (image, head) item in the planes: N, or N rounded up to 128 (the padded form of functions.fused_attention)"""
     return -(-N // 128) * 128 if padded else N
@@ -1949,16 +1960,15 @@ def attn_pack_kv(qkv, heads, H, W, cols, padded=False):
     the k' pair (B' heads, Np, cols): [k | onehot(n // W) | onehot(n % W) | 0..], the v pair (B' heads, Np, 80)); cols 224 | 128;
     padded: Np = N rounded up to 128, the padding rows zero but for k' column 80 + H + W = -30000 (else Np = N)"""
     who = "attn_pack_kv"
-    _attn_pack_dev(who, (("qkv", qkv),))
+    _on_device(who, "qkv", qkv)
     N = H * W
     if qkv.dim() != 3 or qkv.shape[1] != N or qkv.shape[2] != 3 * heads * ATTN_PACK_HD:
         raise RuntimeError("%s: qkv (B', %d, %d), got %s" % (who, N, 3 * heads * ATTN_PACK_HD, tuple(qkv.shape)))
     B = qkv.shape[0]
-    _attn_pack_dense(who, "qkv", qkv, qkv.shape)
+    _layout(who, "qkv", qkv, torch.float32)
     Np, dev = attn_pack_rows(N, padded), qkv.device
     rq = torch.empty(B * heads, N, ATTN_PACK_HD, dtype=torch.float32, device=dev)
-    k = (torch.empty(B * heads, Np, cols, dtype=torch.float16, device=dev), torch.empty(B * heads, Np, cols, dtype=torch.float16, device=dev))
-    v = (torch.empty(B * heads, Np, ATTN_PACK_HD, dtype=torch.float16, device=dev), torch.empty(B * heads, Np, ATTN_PACK_HD, dtype=torch.float16, device=dev))
+    k, v = _f16_planes((B * heads, Np, cols), dev), _f16_planes((B * heads, Np, ATTN_PACK_HD), dev)
     _call("hipie_attn_pack_kv", qkv.data_ptr(), rq.data_ptr(), k[0].data_ptr(), k[1].data_ptr(), v[0].data_ptr(), v[1].data_ptr(), B, heads,
           H, W, Np, cols)
     return rq, k, v
@@ -1979,15 +1989,18 @@ def attn_pack_q(rq, rel_h, rel_w, heads, H, W, cols, padded=False):
     (BH, N, K)): the element strides go to the kernel, nothing is copied -> the q' pair (BH, Np, cols): [rq * 80^-0.5 | rel_h | rel_w | 0..],
     in the padded form column 80 + H + W = 1 on the real rows and the padding rows zero"""
     who = "attn_pack_q"
-    _attn_pack_dev(who, (("rq", rq), ("rel_h", rel_h), ("rel_w", rel_w)))
+    _on_device(who, "rq rel_h rel_w", rq, rel_h, rel_w)
     N = H * W
     BH = rq.shape[0]
-    _attn_pack_dense(who, "rq", rq, (BH, N, ATTN_PACK_HD))
+    _layout(who, "rq", rq, torch.float32, (BH, N, ATTN_PACK_HD))
+    if rel_h.dtype is not torch.float32 or rel_w.dtype is not torch.float32:          # any strides: only the dtype is refused
+        _layout(who, "rel_h", rel_h, torch.float32, None, None, _ANY)
+        _layout(who, "rel_w", rel_w, torch.float32, None, None, _ANY)
     if BH % heads:
         raise RuntimeError("%s: %d items are no multiple of %d heads" % (who, BH, heads))
     sh, sw = _attn_pack_strides(who, "rel_h", rel_h, (BH, H, W, H)), _attn_pack_strides(who, "rel_w", rel_w, (BH, H, W, W))
     Np = attn_pack_rows(N, padded)
-    q = (torch.empty(BH, Np, cols, dtype=torch.float16, device=rq.device), torch.empty(BH, Np, cols, dtype=torch.float16, device=rq.device))
+    q = _f16_planes((BH, Np, cols), rq.device)
     _call("hipie_attn_pack_q", rq.data_ptr(), rel_h.data_ptr(), *sh, rel_w.data_ptr(), *sw, q[0].data_ptr(), q[1].data_ptr(), BH // heads, heads,
           H, W, Np, cols, ATTN_PACK_HD ** -0.5)
     return q
@@ -1997,8 +2010,8 @@ def attn_pack_q(rq, rel_h, rel_w, heads, H, W, cols, padded=False):
 def attn_grad_amax(go):
     """hipie_attn_grad_amax: max |go| of a dense fp32 device tensor (a multiple of 4 elements) as a one-element device tensor -- the bits of
     go.abs().amax(), no host wait"""
-    _attn_pack_dev("attn_grad_amax", (("go", go),))
-    _attn_pack_dense("attn_grad_amax", "go", go, go.shape)
+    _on_device("attn_grad_amax", "go", go)
+    _layout("attn_grad_amax", "go", go, torch.float32)
     amax = torch.empty(1, dtype=torch.float32, device=go.device)
     _call("hipie_attn_grad_amax", go.data_ptr(), go.numel(), amax.data_ptr())
     return amax
@@ -2010,22 +2023,23 @@ def attn_pack_grad(go, out, v_pair, scale, heads, H, W):
     scale a one-element device tensor -> (the dO pair (BH, Np, 96) of scale * go, the v pair (BH, Np, 96), delta (BH, Np) fp32 =
     scale * sum_c go * out); rows >= N zero"""
     who = "attn_pack_grad"
-    _attn_pack_dev(who, (("go", go), ("out", out), ("scale", scale)))
+    _on_device(who, "go out scale v_hi v_lo", go, out, scale, v_pair[0], v_pair[1])
     N = H * W
     if go.dim() != 3 or go.shape[1] != N or go.shape[2] != heads * ATTN_PACK_HD:
         raise RuntimeError("%s: go (B', %d, %d), got %s" % (who, N, heads * ATTN_PACK_HD, tuple(go.shape)))
     B = go.shape[0]
     BH, Np = B * heads, out.shape[1] if out.dim() == 3 else -1
-    _attn_pack_dense(who, "go", go, go.shape)
-    _attn_pack_dense(who, "out", out, (BH, Np, ATTN_PACK_HD))
-    vp = _attn_pack_pair(who, "v", v_pair, (BH, Np, ATTN_PACK_HD))
+    _layout(who, "go", go, torch.float32)
+    _layout(who, "out", out, torch.float32, (BH, Np, ATTN_PACK_HD))
+    _layout(who, "v_hi", v_pair[0], torch.float16, (BH, Np, ATTN_PACK_HD))
+    _layout(who, "v_lo", v_pair[1], torch.float16, (BH, Np, ATTN_PACK_HD))
+    _layout(who, "scale", scale, torch.float32, density=_ANY)
     if scale.numel() != 1:
         raise RuntimeError("%s: scale must have one element" % who)
     dev = go.device
-    do = (torch.empty(BH, Np, 96, dtype=torch.float16, device=dev), torch.empty(BH, Np, 96, dtype=torch.float16, device=dev))
-    v96 = (torch.empty(BH, Np, 96, dtype=torch.float16, device=dev), torch.empty(BH, Np, 96, dtype=torch.float16, device=dev))
+    do, v96 = _f16_planes((BH, Np, 96), dev), _f16_planes((BH, Np, 96), dev)
     delta = torch.empty(BH, Np, dtype=torch.float32, device=dev)
-    _call("hipie_attn_pack_grad", go.data_ptr(), out.data_ptr(), vp[0], vp[1], scale.data_ptr(), do[0].data_ptr(), do[1].data_ptr(),
+    _call("hipie_attn_pack_grad", go.data_ptr(), out.data_ptr(), v_pair[0].data_ptr(), v_pair[1].data_ptr(), scale.data_ptr(), do[0].data_ptr(), do[1].data_ptr(),
           v96[0].data_ptr(), v96[1].data_ptr(), delta.data_ptr(), B, heads, H, W, Np)
     return do, v96, delta
 
@@ -2036,28 +2050,27 @@ def attn_unpack_grad(dq, dk, dv, dq_h, dq_w, inv, heads, H, W):
     terms of dq as (BH, H, W, 80) fp32 views with ANY strides that are multiples of 4 in front of the 80 contiguous columns; inv a one-element
     device tensor -> dqkv (B', H W, 3 heads 80) fp32: q = (dq'[..., :80] * 80^-0.5 + dq_h + dq_w) * inv, k = dk * inv, v = dv * inv"""
     who = "attn_unpack_grad"
-    _attn_pack_dev(who, (("dq", dq), ("dk", dk), ("dv", dv), ("dq_h", dq_h), ("dq_w", dq_w), ("inv", inv)))
+    _on_device(who, "dq dk dv dq_h dq_w inv", dq, dk, dv, dq_h, dq_w, inv)
     N = H * W
     if dq.dim() != 3 or dq.shape[0] % heads:
         raise RuntimeError("%s: dq' (BH, Np, cols), got %s" % (who, tuple(dq.shape)))
     BH, Np, cols = dq.shape
-    _attn_pack_dense(who, "dq", dq, dq.shape)
-    _attn_pack_dense(who, "dk", dk, (BH, Np, ATTN_PACK_HD))
-    _attn_pack_dense(who, "dv", dv, (BH, Np, ATTN_PACK_HD))
+    _layout(who, "dq", dq, torch.float32)
+    _layout(who, "dk", dk, torch.float32, (BH, Np, ATTN_PACK_HD))
+    _layout(who, "dv", dv, torch.float32, (BH, Np, ATTN_PACK_HD))
     strides = []
     for name, t in (("dq_h", dq_h), ("dq_w", dq_w)):
         if t is None:
             strides.append((0, 0, 0))
             continue
-        if tuple(t.shape) != (BH, H, W, ATTN_PACK_HD) or t.stride(3) != 1:
-            raise RuntimeError("%s: %s must be (%d, %d, %d, 80) with contiguous columns, got %s" % (who, name, BH, H, W, tuple(t.shape)))
+        _layout(who, name, t, torch.float32, (BH, H, W, ATTN_PACK_HD), density=_ROWS)
         strides.append(tuple(t.stride()[:3]))
+    _layout(who, "inv", inv, torch.float32, density=_ANY)
     if inv.numel() != 1:
         raise RuntimeError("%s: inv must have one element" % who)
     dqkv = torch.empty(BH // heads, N, 3 * heads * ATTN_PACK_HD, dtype=torch.float32, device=dq.device)
-    _call("hipie_attn_unpack_grad", dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), dq_h.data_ptr(), *strides[0],
-          None if dq_w is None else dq_w.data_ptr(), *strides[1], inv.data_ptr(), dqkv.data_ptr(), BH // heads, heads,
-          H, W, Np, cols, ATTN_PACK_HD ** -0.5)
+    _call("hipie_attn_unpack_grad", dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), dq_h.data_ptr(), *strides[0], _ptr(dq_w), *strides[1],
+          inv.data_ptr(), dqkv.data_ptr(), BH // heads, heads, H, W, Np, cols, ATTN_PACK_HD ** -0.5)
     return dqkv
 
 
@@ -2065,10 +2078,14 @@ def attn_unpack_grad(dq, dk, dv, dq_h, dq_w, inv, heads, H, W):
 def fill_rows(dst, rows, src_row):
     """dst[rows[i]] = src_row for every i (hipie_fill_rows): dst (R, W) contiguous device tensor, rows int32 (n,), src_row (W,) of dst's
     dtype; row bytes a multiple of 16.  In place; returns dst."""
-    if dst.dim() != 2 or not dst.is_cuda or src_row.dtype != dst.dtype or src_row.numel() != dst.shape[1]:
+    if dst.dim() != 2 or src_row.dtype != dst.dtype or src_row.numel() != dst.shape[1]:
         raise RuntimeError("fill_rows: dst (R, W) on the device, src_row (W,) of the same dtype")
-    _call("hipie_fill_rows", _chk(dst, "dst"), dst.stride(0) * dst.element_size(), _chk(rows, "rows", torch.int32), rows.numel(),
-          _chk(src_row, "src_row"), dst.shape[1] * dst.element_size())
+    _on_device("fill_rows", "dst rows src_row", dst, rows, src_row)
+    _layout("fill_rows", "dst", dst)
+    _layout("fill_rows", "rows", rows, torch.int32)
+    _layout("fill_rows", "src_row", src_row)
+    _call("hipie_fill_rows", dst.data_ptr(), dst.stride(0) * dst.element_size(), rows.data_ptr(), rows.numel(), src_row.data_ptr(),
+          dst.shape[1] * dst.element_size())
     return dst
 
 
@@ -2097,7 +2114,8 @@ def gemm(a, w, bias=None, resid=None, out_fmt=F32, act=ACT_NONE, alpha=1.0, osca
     (16-byte aligned): the kernel splits them after the LDS read -- no hipie_to_hl8 launch.  a may be a row-strided 2-d view.  bias (N) f32,
     resid (..., N) f32.  out_fmt F32 | F16 | HL8 -> (..., N) f32 / f16 or (..., 2N) fp16 HL8."""
     a_f32 = a.dtype == torch.float32 and bool(split)
-    if (a.dtype != torch.float16 and not a_f32) or w.dtype != torch.float16 or not a.is_cuda:
+    _on_device("gemm", "a w bias resid out out_row a_row alpha_dev", a, w, bias, resid, out, out_row, a_row, None if alpha_dev is _NO_ALPHA_DEV else alpha_dev)
+    if (a.dtype != torch.float16 and not a_f32) or w.dtype != torch.float16:
         raise RuntimeError("gemm: operands must be fp16 (plain or HL8) device tensors (a may be fp32 against HL8 weights)")
     if split is None:
         raise RuntimeError("gemm: say split=True (HL8 operands) or split=False (plain fp16)")
@@ -2131,53 +2149,32 @@ def gemm(a, w, bias=None, resid=None, out_fmt=F32, act=ACT_NONE, alpha=1.0, osca
             out = torch.empty(*lead, N, dtype=torch.float16, device=a.device)
         else:
             out = torch.empty(*lead, 2 * N, dtype=torch.float16, device=a.device)
-    o2 = out.reshape(-1, out.shape[-1])
-    r2 = None
-    if resid is not None:
-        r2 = resid.reshape(-1, N)
-        if r2.dtype != torch.float32 or r2.stride(-1) != 1:
-            raise RuntimeError("gemm: resid must be fp32 with contiguous rows")
-    if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous()):
-        raise RuntimeError("gemm: bias must be contiguous fp32")
+    o2 = out if out.dim() == 2 else out.reshape(-1, out.shape[-1])
+    r2 = _layout("gemm", "resid", None if resid is None else resid.reshape(-1, N), torch.float32, None, None, _ROWS)
+    _layout("gemm", "bias", bias, torch.float32)
+    _layout("gemm", "w", w)
+    # one list for the three entries: the gather form adds the row map before w and has its own operand code (args[13]); scaled: alpha_dev
+    args = [a2.data_ptr(), a2.stride(0), w.data_ptr(), w.shape[1], _ptr(bias), _ptr(r2), 0 if r2 is None else r2.stride(0), o2.data_ptr(),
+            o2.stride(0), _ptr(out_row), M, N, Kw, F32 if a_f32 else (HL8 if split else F16), int(out_fmt), int(act), float(alpha), float(oscale)]
     if a_row is not None:
-        _call("hipie_gemm_gather", a2.data_ptr(), a2.stride(0), a2.shape[0], a_row.data_ptr(), _chk(w, "w"), w.shape[1],
-              None if bias is None else bias.data_ptr(), None if r2 is None else r2.data_ptr(), 0 if r2 is None else r2.stride(0),
-              o2.data_ptr(), o2.stride(0), None if out_row is None else out_row.data_ptr(), M, N, Kw,
-              F32 if a_f32 else HL8, int(out_fmt), int(act), float(alpha), float(oscale))
-        return out
-    if alpha_dev is not _NO_ALPHA_DEV:       # gemm_scaled: the same call plus the device factor of alpha (None: NULL, hipie_gemm's bits)
-        _call("hipie_gemm_scaled", a2.data_ptr(), a2.stride(0), _chk(w, "w"), w.shape[1], None if bias is None else bias.data_ptr(),
-              None if r2 is None else r2.data_ptr(), 0 if r2 is None else r2.stride(0), o2.data_ptr(), o2.stride(0),
-              None if out_row is None else out_row.data_ptr(), M, N, Kw, F32 if a_f32 else (HL8 if split else F16), int(out_fmt), int(act),
-              float(alpha), float(oscale), None if alpha_dev is None else alpha_dev.data_ptr())
-        return out
-    _call("hipie_gemm", a2.data_ptr(), a2.stride(0), _chk(w, "w"), w.shape[1], None if bias is None else bias.data_ptr(),
-          None if r2 is None else r2.data_ptr(), 0 if r2 is None else r2.stride(0), o2.data_ptr(), o2.stride(0),
-          None if out_row is None else out_row.data_ptr(), M, N, Kw, F32 if a_f32 else (HL8 if split else F16), int(out_fmt), int(act),
-          float(alpha), float(oscale))
+        _call("hipie_gemm_gather", *args[:2], a2.shape[0], a_row.data_ptr(), *args[2:13], F32 if a_f32 else HL8, *args[14:])
+    elif alpha_dev is not _NO_ALPHA_DEV:
+        _call("hipie_gemm_scaled", *args, _ptr(alpha_dev))
+    else:
+        _call("hipie_gemm", *args)
     return out
-
-
-def _alpha_dev(who, alpha_dev):
-    """a one-element fp32 device tensor (a view into a scale block), or None"""
-    if alpha_dev is None:
-        return None
-    if not alpha_dev.is_cuda:
-        raise RuntimeError("Not implemented on the CPU (%s: alpha_dev must be a CUDA/HIP tensor)" % who)
-    if alpha_dev.dtype != torch.float32 or alpha_dev.numel() != 1:
-        raise RuntimeError("%s: alpha_dev must be one torch.float32 element, got %s %s" % (who, alpha_dev.dtype, tuple(alpha_dev.shape)))
-    return alpha_dev
 
 
 def gemm_scaled(a, w, alpha_dev, **kw):
     """gemm (hipie_gemm_scaled) whose alpha is multiplied by the DEVICE scalar alpha_dev (one fp32 element, e.g. grad_scale(dy)[1:]) in the
     kernel that writes the product: no host wait, no extra pass.  alpha_dev None: the NULL pointer, i.e. gemm's dispatch and bits.  The
     a_row (gather) form has no scaled entry."""
-    if not a.is_cuda:
-        raise RuntimeError("Not implemented on the CPU (gemm_scaled: a must be a CUDA/HIP tensor)")
+    _on_device("gemm_scaled", "a alpha_dev", a, alpha_dev)
     if kw.get("a_row") is not None:
         raise RuntimeError("gemm_scaled: the gather form (a_row) has no scaled entry")
-    return gemm(a, w, alpha_dev=_alpha_dev("gemm_scaled", alpha_dev), **kw)
+    if alpha_dev is not None and (alpha_dev.dtype != torch.float32 or alpha_dev.numel() != 1):          # a view into a scale block
+        raise RuntimeError("gemm_scaled: alpha_dev must be one torch.float32 element, got %s %s" % (alpha_dev.dtype, tuple(alpha_dev.shape)))
+    return gemm(a, w, alpha_dev=alpha_dev, **kw)
 
 
 @_timed(lambda qkv, tab_h, tab_w, grid_hw, heads: "vit_attn_global" if grid_hw[0] * grid_hw[1] > 256 else "vit_attn_window")
@@ -2185,13 +2182,32 @@ def vit_attn_split(qkv, tab_h, tab_w, grid_hw, heads):
     """hipie_vit_attn_split: qkv (B, gh*gw, 2 * 3*heads*hd) fp16 HL8 rows (q pre-scaled by scale*log2 e), tab_h (2*gh-1, 2*hd),
     tab_w (2*gw-1, 2*hd) HL8 (tables / scale) -> (B, N, 2 * heads*hd) HL8."""
     gh, gw = grid_hw
-    B, N, C6 = qkv.shape
-    hd = C6 // (6 * heads)
-    if qkv.dtype != torch.float16 or tab_h.dtype != torch.float16 or tab_w.dtype != torch.float16:
+    if qkv.dtype != torch.float16:
         raise RuntimeError("vit_attn_split: HL8 (fp16) operands expected")
+    B, N, hd = _vit_operands("vit_attn_split", qkv, tab_h, tab_w, torch.float16, heads, 6)
     out = torch.empty(B, N, 2 * heads * hd, dtype=torch.float16, device=qkv.device)
-    _call("hipie_vit_attn_split", _chk(qkv, "qkv"), _chk(tab_h, "tab_h"), _chk(tab_w, "tab_w"), out.data_ptr(), B, gh, gw, heads, hd)
+    _call("hipie_vit_attn_split", qkv.data_ptr(), tab_h.data_ptr(), tab_w.data_ptr(), out.data_ptr(), B, gh, gw, heads, hd)
     return out
+
+
+def _split_k_parts(who, a_hl8, w_hl8, nk):
+    """the front both split-k products share: what hipie_gemm_batched needs of the operands, then its ONE launch over the nk chunks of
+    the contraction -> the partial products (nk, M, N) fp32"""
+    _on_device(who, "a_hl8 w_hl8", a_hl8, w_hl8)
+    _layout(who, "a_hl8", a_hl8, torch.float16, ndim=2, align16=True)
+    _layout(who, "w_hl8", w_hl8, torch.float16, ndim=2, align16=True)
+    M, K2 = a_hl8.shape
+    N = w_hl8.shape[0]
+    K = K2 // 2
+    if w_hl8.shape[1] != K2 or nk < 1 or nk > 64 or K % (32 * nk):
+        raise RuntimeError("%s: HL8 operands (M, 2K) / (N, 2K), K a multiple of 32 * nk, nk <= 64" % who)
+    if N % 8:
+        raise RuntimeError("%s: N must be a multiple of 8" % who)
+    Kc = K // nk
+    part = torch.empty(nk, M, N, dtype=torch.float32, device=a_hl8.device)
+    _call("hipie_gemm_batched", a_hl8.data_ptr(), K2, 0, 2 * Kc, w_hl8.data_ptr(), K2, 0, 2 * Kc, part.data_ptr(), N, 0, M * N, 1, nk, M, N, Kc,
+          F32, 1.0)
+    return part
 
 
 @_timed("gemm_split_k")
@@ -2199,58 +2215,35 @@ def gemm_split_k(a_hl8, w_hl8, nk):
     """a . w^T for HL8 operands a (M, 2K), w (N, 2K) with the contraction cut into nk chunks (K / nk a multiple of 32): one problem per
     chunk in ONE hipie_gemm_batched launch, partial products summed -> (M, N) fp32.  For products whose M x N is a few tiles and whose K is
     long (the weight gradients of the training step)."""
-    M, K2 = a_hl8.shape
-    N = w_hl8.shape[0]
-    K = K2 // 2
-    if w_hl8.shape[1] != K2 or K % (32 * nk) or a_hl8.dtype != torch.float16 or w_hl8.dtype != torch.float16 or not a_hl8.is_cuda:
-        raise RuntimeError("gemm_split_k: HL8 device operands (M, 2K) / (N, 2K), K a multiple of 32 * nk")
-    if N % 8:
-        raise RuntimeError("gemm_split_k: N must be a multiple of 8")
-    Kc = K // nk
-    part = torch.empty(nk, M, N, dtype=torch.float32, device=a_hl8.device)
-    _call("hipie_gemm_batched", a_hl8.data_ptr(), K2, 0, 2 * Kc, w_hl8.data_ptr(), K2, 0, 2 * Kc, part.data_ptr(), N, 0, M * N, 1, nk, M, N, Kc,
-          F32, 1.0)
-    return part.sum(0)
+    return _split_k_parts("gemm_split_k", a_hl8, w_hl8, nk).sum(0)
 
 
 @_timed("gemm_split_k")
 def gemm_split_k_scaled(a_hl8, w_hl8, nk, alpha_dev):
     """gemm_split_k whose partial products are added in chunk order and multiplied by the device scalar alpha_dev (None: 1) in ONE pass
     (hipie_splitk_finish) instead of part.sum(0): the weight gradient of the scaled-gradient nodes.  M * N a multiple of 4."""
-    if not a_hl8.is_cuda or not w_hl8.is_cuda:
-        raise RuntimeError("Not implemented on the CPU (gemm_split_k_scaled: operands must be CUDA/HIP tensors)")
-    alpha_dev = _alpha_dev("gemm_split_k_scaled", alpha_dev)
-    if a_hl8.dim() != 2 or w_hl8.dim() != 2 or a_hl8.dtype != torch.float16 or w_hl8.dtype != torch.float16:
-        raise RuntimeError("gemm_split_k_scaled: HL8 (fp16) operands (M, 2K) / (N, 2K)")
-    M, K2 = a_hl8.shape
-    N = w_hl8.shape[0]
-    K = K2 // 2
-    if w_hl8.shape[1] != K2 or nk < 1 or nk > 64 or K % (32 * nk) or not a_hl8.is_contiguous() or not w_hl8.is_contiguous():
-        raise RuntimeError("gemm_split_k_scaled: contiguous operands (M, 2K) / (N, 2K), K a multiple of 32 * nk, nk <= 64")
-    if N % 8 or a_hl8.data_ptr() % 16 or w_hl8.data_ptr() % 16:
-        raise RuntimeError("gemm_split_k_scaled: N must be a multiple of 8, the operands 16-byte aligned")
-    Kc = K // nk
-    part = torch.empty(nk, M, N, dtype=torch.float32, device=a_hl8.device)
-    out = torch.empty(M, N, dtype=torch.float32, device=a_hl8.device)
-    _call("hipie_gemm_batched", a_hl8.data_ptr(), K2, 0, 2 * Kc, w_hl8.data_ptr(), K2, 0, 2 * Kc, part.data_ptr(), N, 0, M * N, 1, nk, M, N, Kc,
-          F32, 1.0)
-    _call("hipie_splitk_finish", part.data_ptr(), nk, M * N, None if alpha_dev is None else alpha_dev.data_ptr(), out.data_ptr())
+    who = "gemm_split_k_scaled"
+    _on_device(who, "alpha_dev", alpha_dev)          # a_hl8 and w_hl8: _split_k_parts
+    if alpha_dev is not None and (alpha_dev.dtype != torch.float32 or alpha_dev.numel() != 1):          # a view into a scale block
+        raise RuntimeError("%s: alpha_dev must be one torch.float32 element, got %s %s" % (who, alpha_dev.dtype, tuple(alpha_dev.shape)))
+    part = _split_k_parts(who, a_hl8, w_hl8, nk)
+    out = torch.empty(part.shape[1], part.shape[2], dtype=torch.float32, device=a_hl8.device)
+    _call("hipie_splitk_finish", part.data_ptr(), part.shape[0], out.numel(), _ptr(alpha_dev), out.data_ptr())
     return out
 
 
 def _grad_rows(who, dy):
-    """dy as the kernels of csrc/grad_pack.hip take it: 2-D fp32 on the device, contiguous rows, row stride a multiple of 4, 16-byte aligned"""
-    if not dy.is_cuda:
-        raise RuntimeError("Not implemented on the CPU (%s: dy must be a CUDA/HIP tensor)" % who)
-    if dy.dtype != torch.float32:
-        raise RuntimeError("%s: dy must be torch.float32, got %s" % (who, dy.dtype))
+    """the row stride of dy as the kernels of csrc/grad_pack.hip take it: 2-D fp32 on the device, contiguous rows that do not overlap, row
+    stride a multiple of 4, 16-byte aligned"""
+    _on_device(who, "dy", dy)
     if dy.dim() != 2 or dy.shape[0] == 0 or dy.shape[1] == 0:
         raise RuntimeError("%s: dy must be a non-empty 2-D tensor, got %s" % (who, tuple(dy.shape)))
-    if dy.stride(1) != 1 or (dy.shape[0] > 1 and (dy.stride(0) < dy.shape[1] or dy.stride(0) % 4)):
-        raise RuntimeError("%s: dy rows must be contiguous with a row stride that is a multiple of 4, got strides %s" % (who, tuple(dy.stride())))
-    if dy.data_ptr() % 16:
-        raise RuntimeError("%s: dy must be 16-byte aligned" % who)
-    return dy.stride(0) if dy.shape[0] > 1 else dy.shape[1]
+    rows, n = dy.shape
+    ld = dy.stride(0) if rows > 1 else n
+    if dy.dtype is not torch.float32 or dy.stride(1) != 1 or (rows > 1 and (ld % 4 or ld < n)) or dy.data_ptr() % 16:
+        _layout(who, "dy", dy, torch.float32, None, None, _ROWS, 4, True)          # the vocabulary's message; what it lets pass overlaps
+        raise RuntimeError("%s: dy rows overlap, got strides %s" % (who, tuple(dy.stride())))
+    return ld
 
 
 @_timed("grad_scale")
@@ -2272,8 +2265,7 @@ def grad_pack(dy, scale, want_rows=True, want_t=True, want_bias=False, rows_p=No
      db = dy.sum(0) of the UNSCALED values, (N,) fp32, summed in a fixed order | None).  N % 8 == 0; rows_p (default: rows rounded up to 32)
     a multiple of 32.  Everything is refused before a launch."""
     ldx = _grad_rows("grad_pack", dy)
-    if not scale.is_cuda:
-        raise RuntimeError("Not implemented on the CPU (grad_pack: scale must be a CUDA/HIP tensor)")
+    _on_device("grad_pack", "scale", scale)
     if scale.dtype != torch.float32 or scale.numel() != 2 or not scale.is_contiguous():
         raise RuntimeError("grad_pack: scale must be the contiguous {s, 1 / s} block of grad_scale (2 x torch.float32)")
     rows, N = dy.shape
@@ -2287,10 +2279,8 @@ def grad_pack(dy, scale, want_rows=True, want_t=True, want_bias=False, rows_p=No
     db = ws = None
     if want_bias:
         db = torch.empty(N, dtype=torch.float32, device=dy.device)
-        ws = torch.empty(_size("hipie_grad_pack_ws_bytes", rows_p, N), dtype=torch.uint8, device=dy.device)
-    _call("hipie_grad_pack", dy.data_ptr(), ldx, scale.data_ptr(), None if out_r is None else out_r.data_ptr(), 2 * N,
-          None if out_t is None else out_t.data_ptr(), 2 * rows_p, None if db is None else db.data_ptr(), None if ws is None else ws.data_ptr(),
-          rows, N, rows_p)
+        ws = _workspace(None, _size("hipie_grad_pack_ws_bytes", rows_p, N), dy.device, "grad_pack")
+    _call("hipie_grad_pack", dy.data_ptr(), ldx, scale.data_ptr(), _ptr(out_r), 2 * N, _ptr(out_t), 2 * rows_p, _ptr(db), _ptr(ws), rows, N, rows_p)
     return out_r, out_t, db
 
 
@@ -2301,8 +2291,9 @@ def matmul_nt_batched(a, w, alpha=1.0):
     per-image products of the heads (class logits = queries . token embeddings^T, VL_Align: deformable_detr.py:55-73)."""
     B, M, K = a.shape
     N = w.shape[1]
-    if w.shape[0] != B or w.shape[2] != K or K % 32 or not a.is_cuda:
+    if w.shape[0] != B or w.shape[2] != K or K % 32:
         raise RuntimeError("matmul_nt_batched: a (B, M, K), w (B, N, K) device tensors with K %% 32 == 0, got %s / %s" % (tuple(a.shape), tuple(w.shape)))
+    _on_device("matmul_nt_batched", "a w", a, w)
     Np = (N + 7) // 8 * 8
     if Np != N:
         wp = torch.zeros(B, Np, K, dtype=torch.float32, device=w.device)
@@ -2367,6 +2358,7 @@ def conv3x3_split(x, conv, act=ACT_NONE):
     x (B, C, H, W) in any memory format -> (B, N, H, W) fp32 in channels-last memory.  The input is copied once onto a zero-padded pixel grid
     (with guard rows), the kernel computes on that grid and the interior is cropped."""
     B, C, H, W = x.shape
+    _on_device("conv3x3_split", "x weight bias", x, conv.weight, conv.bias)
     N = conv.out_channels
     Hp, Wp = H + 2, W + 2
     guard = Wp + 1
@@ -2384,7 +2376,7 @@ def conv3x3_split(x, conv, act=ACT_NONE):
                            lambda: conv.weight.permute(0, 2, 3, 1).reshape(N, 9 * C), (lambda: conv.bias) if conv.bias is not None else None)
     out = torch.empty(rows, N, dtype=torch.float32, device=x.device)
     xin = buf[guard:]
-    _call("hipie_conv3x3_split", xin.data_ptr(), C, w.data_ptr(), None if b is None else b.data_ptr(), out.data_ptr(), N, rows, Wp, C, N,
+    _call("hipie_conv3x3_split", xin.data_ptr(), C, w.data_ptr(), _ptr(b), out.data_ptr(), N, rows, Wp, C, N,
           F32, F32, int(act))
     return out.view(B, Hp, Wp, N)[:, 1:-1, 1:-1].permute(0, 3, 1, 2).contiguous(memory_format=torch.channels_last)
 
@@ -2420,9 +2412,12 @@ def conv3x3_grid(buf, w_hl8, bias, B, H, W, relu=False):
     C, N = buf.shape[1], w_hl8.shape[0]
     if buf.shape[0] != rows + 2 * guard or w_hl8.shape[1] != 18 * C or w_hl8.dtype != torch.float16 or buf.dtype != torch.float32:
         raise RuntimeError("conv3x3_grid: a staged grid %s against an HL8 weight %s" % (tuple(buf.shape), tuple(w_hl8.shape)))
+    _on_device("conv3x3_grid", "buf w_hl8 bias", buf, w_hl8, bias)
+    _layout("conv3x3_grid", "buf", buf)
+    _layout("conv3x3_grid", "w_hl8", w_hl8)
+    _layout("conv3x3_grid", "bias", bias, torch.float32)
     out = torch.empty(rows, N, dtype=torch.float32, device=buf.device)
-    _call("hipie_conv3x3_split", _chk(buf, "grid") + 4 * guard * C, C, _chk(w_hl8, "w"), None if bias is None else _chk(bias, "bias", torch.float32),
-          out.data_ptr(), N, rows, Wp, C, N, F32, F32, ACT_RELU if relu else ACT_NONE)
+    _call("hipie_conv3x3_split", buf.data_ptr() + 4 * guard * C, C, w_hl8.data_ptr(), _ptr(bias), out.data_ptr(), N, rows, Wp, C, N, F32, F32, ACT_RELU if relu else ACT_NONE)
     return out
 
 
@@ -2437,13 +2432,17 @@ def conv3x3_wgrad(xbuf, dybuf, y_rows, B, H, W, want_bias=True):
     C, N = xbuf.shape[1], dybuf.shape[1]
     if xbuf.shape[0] != rows + 2 * guard or dybuf.shape[0] != rows + 2 * guard or (y_rows is not None and tuple(y_rows.shape) != (rows, N)):
         raise RuntimeError("conv3x3_wgrad: grids %s / %s for %d rows" % (tuple(xbuf.shape), tuple(dybuf.shape), rows))
+    who = "conv3x3_wgrad"
+    _on_device(who, "xbuf dybuf y_rows", xbuf, dybuf, y_rows)
+    _layout(who, "xbuf", xbuf, torch.float32)
+    _layout(who, "dybuf", dybuf, torch.float32)
+    _layout(who, "y_rows", y_rows, torch.float32)
     dw = torch.empty(N, 9, C, dtype=torch.float32, device=xbuf.device)
     db = torch.empty(N, dtype=torch.float32, device=xbuf.device) if want_bias else None
     ws_bytes = -(-rows // CONV_WGRAD_CHUNK) * (9 * C * N + N) * 4
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=xbuf.device)
-    _call("hipie_conv3x3_wgrad", _chk(xbuf, "x grid", torch.float32) + 4 * guard * C, C, _chk(dybuf, "dy grid", torch.float32) + 4 * guard * N, N,
-          None if y_rows is None else _chk(y_rows, "y", torch.float32), rows, Wp, C, N, dw.data_ptr(), None if db is None else db.data_ptr(),
-          ws.data_ptr(), ws_bytes)
+    ws = _workspace(None, ws_bytes, xbuf.device, who)
+    _call("hipie_conv3x3_wgrad", xbuf.data_ptr() + 4 * guard * C, C, dybuf.data_ptr() + 4 * guard * N, N, _ptr(y_rows), rows, Wp, C, N,
+          dw.data_ptr(), _ptr(db), ws.data_ptr(), ws_bytes)
     return dw, db
 
 
@@ -2461,6 +2460,7 @@ def ffn_fused(x_hl8, lin1, lin2):
     """linear2(relu(linear1(x))) in ONE launch at the split policy's accuracy (hipie_ffn_fused): x (..., 2*256) HL8 -> (..., 256) fp32.
     The hidden activations stay in registers; W2's columns are permuted once per parameter version into the order the MFMA C layout
     hands them over (rows 0-3, 8-11, 4-7, 12-15 of every 16)."""
+    _on_device("ffn_fused", "x_hl8 weight1 weight2", x_hl8, lin1.weight, lin2.weight)
     w1, b1, _ = split_weight(lin1, "w", [lin1.weight, lin1.bias], lambda: lin1.weight, lambda: lin1.bias)
     F_ = lin2.weight.shape[1]
     perm = _FFN_PERM.get(F_)
@@ -2514,8 +2514,9 @@ def split_linear(x, owner, key, weight, bias=None, act=ACT_NONE, out_fmt=F32, re
 def to_f8x(x_hl8):
     """HL8 rows (rows, 2K) fp16 on the device -> (q (rows, 2K) uint8: per 32-element block [q8(hi) | q8(lo)] e4m3, scale (rows, K/32, 2) uint8
     E8M0 [hi, lo]) with the quantiser hipie_gemm_f8x applies to its activations (hipie_to_f8x)."""
-    if x_hl8.dtype != torch.float16 or not x_hl8.is_cuda or x_hl8.shape[-1] % 64:
+    if x_hl8.dtype != torch.float16 or x_hl8.shape[-1] % 64:
         raise RuntimeError("to_f8x: HL8 rows (fp16, 2K columns with K a multiple of 32) on the device")
+    _on_device("to_f8x", "x_hl8", x_hl8)
     x2 = x_hl8.reshape(-1, x_hl8.shape[-1])
     if x2.stride(-1) != 1:
         x2 = x2.contiguous()
@@ -2543,8 +2544,9 @@ def f8x_weight(owner, key, params, weight_fn, bias_fn=None):
 def gemm_f8x(a, w8, wsc, bias=None, resid=None, out_fmt=F32, act=ACT_NONE, alpha=1.0, oscale=1.0, out=None, out_row=None, out_rows=None):
     """ops.gemm's split form with the cross terms on block-scaled e4m3 (hipie_gemm_f8x): a (..., 2K) HL8 rows against the f8x weight
     (w8 (N, 4K) uint8, wsc (N, K/32, 2) uint8, from f8x_weight or fp8x.pack_weight); epilogue, output formats and row maps as ops.gemm."""
-    if a.dtype != torch.float16 or w8.dtype != torch.uint8 or wsc.dtype != torch.uint8 or not a.is_cuda:
+    if a.dtype != torch.float16 or w8.dtype != torch.uint8 or wsc.dtype != torch.uint8:
         raise RuntimeError("gemm_f8x: a HL8 (fp16) rows, w8 / wsc uint8, on the device")
+    _on_device("gemm_f8x", "a w8 wsc bias resid out out_row", a, w8, wsc, bias, resid, out, out_row)
     N, K = w8.shape[0], w8.shape[1] // 4
     a2 = a if a.dim() == 2 else a.reshape(-1, a.shape[-1])
     if a2.stride(-1) != 1 or a2.shape[-1] != 2 * K or not w8.is_contiguous() or tuple(wsc.shape) != (N, K // 32, 2) or not wsc.is_contiguous():
@@ -2560,16 +2562,10 @@ def gemm_f8x(a, w8, wsc, bias=None, resid=None, out_fmt=F32, act=ACT_NONE, alpha
         dt, width = {F32: (torch.float32, N), F16: (torch.float16, N), HL8: (torch.float16, 2 * N)}[out_fmt]
         out = torch.empty(*lead, width, dtype=dt, device=a.device)
     o2 = out.reshape(-1, out.shape[-1])
-    r2 = None
-    if resid is not None:
-        r2 = resid.reshape(-1, N)
-        if r2.dtype != torch.float32 or r2.stride(-1) != 1:
-            raise RuntimeError("gemm_f8x: resid must be fp32 with contiguous rows")
-    if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous()):
-        raise RuntimeError("gemm_f8x: bias must be contiguous fp32")
-    _call("hipie_gemm_f8x", a2.data_ptr(), a2.stride(0), _chk(w8, "w8"), 2 * K, _chk(wsc, "wsc"), None if bias is None else bias.data_ptr(),
-          None if r2 is None else r2.data_ptr(), 0 if r2 is None else r2.stride(0), o2.data_ptr(), o2.stride(0),
-          None if out_row is None else out_row.data_ptr(), M, N, K, HL8, int(out_fmt), int(act), float(alpha), float(oscale))
+    r2 = None if resid is None else _layout("gemm_f8x", "resid", resid.reshape(-1, N), torch.float32, density=_ROWS)
+    _layout("gemm_f8x", "bias", bias, torch.float32)
+    _call("hipie_gemm_f8x", a2.data_ptr(), a2.stride(0), w8.data_ptr(), 2 * K, wsc.data_ptr(), _ptr(bias),
+          _ptr(r2), 0 if r2 is None else r2.stride(0), o2.data_ptr(), o2.stride(0), _ptr(out_row), M, N, K, HL8, int(out_fmt), int(act), float(alpha), float(oscale))
     return out
 
 
@@ -2591,6 +2587,8 @@ def split_linear_ln_ok(x, weight, norm_weight):
 def split_linear_ln(x, owner, key, weight, bias, resid, norm_weight, norm_bias, eps, x_hl8=False, want_hl8=True):
     """LayerNorm(resid + F.linear(x, weight, bias)) over 256 features as ONE launch (hipie_gemm_ln): returns (n fp32, n as HL8 or None).
     x (..., K) fp32 rows or HL8 (x_hl8); resid (..., 256) fp32; the HL8 copy of `weight` is cached on `owner` under `key` (split_weight)."""
+    who = "split_linear_ln"
+    _on_device(who, "x weight bias resid norm_weight norm_bias", x, weight, bias, resid, norm_weight, norm_bias)
     w, b, N = split_weight(owner, key, [weight] + ([bias] if bias is not None else []), lambda: weight, (lambda: bias) if bias is not None else None)
     if N != 256 or w.shape[0] != 256:
         raise RuntimeError("split_linear_ln: 256 output features expected")
@@ -2603,13 +2601,14 @@ def split_linear_ln(x, owner, key, weight, bias, resid, norm_weight, norm_bias, 
         raise RuntimeError("split_linear_ln: operand rows %s against weight %s" % (tuple(x.shape), tuple(weight.shape)))
     r2 = resid.reshape(-1, 256)
     M = a2.shape[0]
-    if r2.dtype != torch.float32 or r2.stride(-1) != 1 or r2.shape[0] != M or not r2.is_cuda:
-        raise RuntimeError("split_linear_ln: resid must be (rows, 256) fp32 on the device")
+    _layout(who, "resid", r2, torch.float32, (M, 256), density=_ROWS)
+    _layout(who, "norm_weight", norm_weight, torch.float32)
+    _layout(who, "norm_bias", norm_bias, torch.float32)
+    _layout(who, "w", w)          # the cached HL8 copy of weight (on weight's device)
     out = torch.empty(*resid.shape[:-1], 256, dtype=torch.float32, device=x.device)
     o16 = torch.empty(*resid.shape[:-1], 512, dtype=torch.float16, device=x.device) if want_hl8 else None
-    _call("hipie_gemm_ln", a2.data_ptr(), a2.stride(0), _chk(w, "w"), w.shape[1], None if b is None else b.data_ptr(), r2.data_ptr(), r2.stride(0),
-          _chk(norm_weight, "norm_weight", torch.float32), _chk(norm_bias, "norm_bias", torch.float32), float(eps),
-          out.data_ptr(), 256, None if o16 is None else o16.data_ptr(), 512, M, K, F32 if a_f32 else HL8, 1.0)
+    _call("hipie_gemm_ln", a2.data_ptr(), a2.stride(0), w.data_ptr(), w.shape[1], _ptr(b), r2.data_ptr(), r2.stride(0),
+          norm_weight.data_ptr(), norm_bias.data_ptr(), float(eps), out.data_ptr(), 256, _ptr(o16), 512, M, K, F32 if a_f32 else HL8, 1.0)
     return out, o16
 
 
@@ -2654,12 +2653,12 @@ def convt2x2_split(rows, owner, key, weight, bias, B, H, W):
 def topk(x, k, want_values=False):
     """row-wise top-k of a (rows, n) fp32 device tensor (row stride may exceed n), k <= 1024 -> indices (rows, k) int64 in descending value
     order (ties: ascending index) [, values].  hipie_topk: one launch, hipGraph-replay safe (torch.topk on this stack is neither)."""
-    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_cuda or x.stride(1) != 1:
-        raise RuntimeError("topk: (rows, n) fp32 device tensor with contiguous rows expected")
+    _layout("topk", "x", x, torch.float32, ndim=2, density=_ROWS)
+    _on_device("topk", "x", x)
     rows, n = x.shape
     idx = torch.empty(rows, k, dtype=torch.int64, device=x.device)
     val = torch.empty(rows, k, dtype=torch.float32, device=x.device) if want_values else None
-    _call("hipie_topk", x.data_ptr(), x.stride(0), rows, n, int(k), idx.data_ptr(), None if val is None else val.data_ptr())
+    _call("hipie_topk", x.data_ptr(), x.stride(0), rows, n, int(k), idx.data_ptr(), _ptr(val))
     return (idx, val) if want_values else idx
 
 
