@@ -209,6 +209,29 @@ extern "C" int hipie_gemm_batched(const void* A, int64_t lda, int64_t a_outer, i
   return (N % 320 == 0) ? launch_gemm<320, true>(p, st, batches) : launch_gemm<256, true>(p, st, batches);
 }
 
+// the batched launch of the PLAIN fp16 instances hipie_gemm runs for HIPIE_F16 operands (one product, 64-element k tiles), fp32 output, with
+// the device factor of hipie_gemm_scaled: the chunks of a split-K weight gradient of the half-precision training linears.  No new kernel
+// instance: gemm_kernel<320 | 256, false> reads the batch offsets and alpha_dev as every instance does.
+extern "C" int hipie_gemm_batched_f16(const void* A, int64_t lda, int64_t a_outer, int64_t a_inner, const void* W, int64_t ldw, int64_t w_outer,
+                                      int64_t w_inner, void* out, int64_t ldo, int64_t o_outer, int64_t o_inner, int n_outer, int n_inner, int M,
+                                      int N, int K, float alpha, const float* alpha_dev, void* stream) {
+  HIPIE_REQUIRE(A && W && out, "gemm_batched_f16: null pointer");
+  HIPIE_REQUIRE(M > 0 && N > 0 && K > 0 && N % 8 == 0 && K % 64 == 0, "gemm_batched_f16: M=%d N=%d K=%d (N %% 8, K %% 64)", M, N, K);
+  HIPIE_TRY(gm_check_batch_shape("gemm_batched_f16", n_outer, n_inner));
+  HIPIE_TRY(gm_check_operands("gemm_batched_f16", lda, ldw, K, 320));
+  HIPIE_TRY(gm_check_out("gemm_batched_f16", ldo, HIPIE_F32, N));
+  HIPIE_TRY(gm_check_batch_offsets("gemm_batched_f16", a_outer, a_inner, w_outer, w_inner, o_outer, o_inner));
+  HIPIE_TRY(gm_check_aligned("gemm_batched_f16", {A, W, out}));
+  HIPIE_REQUIRE(((uintptr_t)alpha_dev % 4) == 0, "gemm_batched_f16: alpha_dev must be 4-byte aligned");
+  GemmParams p;
+  gm_set_operands(p, A, lda, W, ldw, M, N, K, 64);
+  gm_set_batch(p, n_inner, a_outer, a_inner, w_outer, w_inner, o_outer, o_inner, 4);
+  p.out = (char*)out; p.ldo = ldo; p.out_fmt = HIPIE_F32; p.alpha = alpha; p.alpha_dev = alpha_dev;
+  hipStream_t st = (hipStream_t)stream;
+  const int batches = n_outer * n_inner;
+  return (N % 320 == 0) ? launch_gemm<320, false>(p, st, batches) : launch_gemm<256, false>(p, st, batches);
+}
+
 extern "C" int hipie_gemm_batched_resid(const void* A, int64_t lda, int64_t a_outer, int64_t a_inner, const void* W, int64_t ldw, int64_t w_outer,
                                         int64_t w_inner, const float* bias, const float* resid, int64_t ldr, int64_t r_outer, int64_t r_inner,
                                         float* out, int64_t ldo, int64_t o_outer, int64_t o_inner, int n_outer, int n_inner, int M, int N, int K,

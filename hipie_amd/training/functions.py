@@ -118,12 +118,13 @@ def _weight_grad(g2, x2):
     return ops.gemm_split_k(gt, xt, nk)
 
 
-def _weight_grad_chunks(M, N, K):
-    """the chunks _weight_grad cuts the M rows into: doubled while the N x K tiles leave CUs idle and the 32-row groups divide evenly"""
-    Mp = -(-M // 32) * 32
+def _weight_grad_chunks(M, N, K, group=32):
+    """the chunks _weight_grad cuts the M rows into: doubled while the N x K tiles leave CUs idle and the 32-row groups divide evenly
+    (group: the rows of one k tile -- 32 for the split operands, 64 for plain fp16)"""
+    Mp = -(-M // group) * group
     tiles = -(-N // 256) * -(-K // 256)
     nk = 1
-    while nk < 16 and tiles * nk < 256 and (Mp // 32) % (2 * nk) == 0:
+    while nk < 16 and tiles * nk < 256 and (Mp // group) % (2 * nk) == 0:
         nk *= 2
     return nk
 
@@ -377,6 +378,148 @@ def split_mlp_scaled(x, w1, b1, w2, b2, act):
         return ScaledMlpFunction.apply(x, w1, b1, w2, b2, act)
     f = {ops.ACT_GELU: torch.nn.functional.gelu, ops.ACT_RELU: torch.nn.functional.relu}[act]
     return split_linear_scaled(f(split_linear_scaled(x, w1, b1, w1, "w")), w2, b2, w2, "w")
+
+
+# ---- the same two nodes in HALF precision (csrc/half_pack.hip, ops_half.py; the opt-in policy net.half_policy): ONE fp16 MFMA product per
+# GEMM instead of three, fp32 master weights, fp32 accumulation and output.  A precision policy, not a bit-compatible group: 2^-11 per
+# operand.  Contract: x16 = fp16(x), W16 = fp16(W), round to nearest even, saturated at +-65504, no scale;
+# y = x16 . W16^T + b;  {s, 1/s} = grad_scale(dy), g16 = fp16(s dy);  dx = (1/s) g16 . W16;  dW = (1/s) g16^T . x16^T over the token rows
+# padded to 64, in the chunks of _weight_grad_chunks(group=64), added in chunk order;  db = the column sums of the unscaled dy.  All scale
+# factors are powers of two, every sum has a fixed order: the results for 2^e dy are 2^e times the results for dy, bit for bit.
+HALF_NODE_CALLS = collections.Counter()          # forward calls of the two nodes by name (tests: the node ran, not the fall-through)
+
+
+def _half_weight_grad(gt, x16, inv):
+    """dW = (1/s) g16^T . x16^T: gt = (s dy)^T as fp16 (N, Mp) from ops_half.half_pack, x16 the saved fp16 rows (M, K) -- transposed here in
+    one pass --, inv the device scalar 1 / s"""
+    from ..ops_half import gemm_split_k_half, half_pack
+    xt = half_pack(x16, None, want_rows=False, want_t=True)[1]
+    return gemm_split_k_half(gt, xt, _weight_grad_chunks(x16.shape[0], gt.shape[0], x16.shape[1], 64), inv)
+
+
+class HalfLinearFunction(torch.autograd.Function):
+    """F.linear(x, weight, bias) with forward AND backward on single fp16 operands (hipie_gemm with HIPIE_F16):
+        x16 = half_pack(x)              y  = x16 . W16^T + b                               W16 / W16^T cached on `owner` (ops_half.half_weight)
+        {s, 1/s} = grad_scale(dy)       (s dy) rows, (s dy)^T, db = half_pack(dy)          one pass over dy; a frozen input skips its form
+        dx = (1/s) (s dy) . W16         dW = (1/s) (s dy)^T . x16^T                        the factor is applied where the product is stored
+    Saved: x16 (fp16 rows, half the bytes of x) and the weight."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, owner, key):
+        from ..ops_half import half_pack, half_weight
+        HALF_NODE_CALLS["linear"] += 1
+        w16 = half_weight(owner, key, [weight], lambda: weight)
+        x16 = half_pack(_grad_rows(x, x.shape[-1]), None, want_rows=True, want_t=False)[0]
+        ctx.save_for_backward(x16 if ctx.needs_input_grad[1] else None, weight)
+        ctx.owner, ctx.key, ctx.lead, ctx.has_bias = owner, key, x.shape[:-1], bias is not None
+        y = ops.gemm(x16, w16, None if bias is None else bias.detach().float().contiguous(), split=False, out_fmt=ops.F32, tag="train_fwd")
+        return y.view(*x.shape[:-1], weight.shape[0])
+
+    @staticmethod
+    def backward(ctx, gy):
+        from ..ops_half import half_pack, half_weight
+        x16, weight = ctx.saved_tensors
+        N, K = weight.shape
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_b = ctx.has_bias and ctx.needs_input_grad[2]
+        gx = gw = gb = None
+        if not (need_x or need_w or need_b):
+            return None, None, None, None, None
+        g2 = _grad_rows(gy, N)
+        scale = ops.grad_scale(g2)
+        ga, gt, gb = half_pack(g2, scale, want_rows=need_x, want_t=need_w, want_bias=need_b)
+        inv = scale[1:]
+        if need_x:
+            wt16 = half_weight(ctx.owner, ctx.key + ".T", [weight], lambda: weight.t())
+            gx = ops.gemm_scaled(ga, wt16, inv, split=False, out_fmt=ops.F32, tag="train_dx").view(*ctx.lead, K)
+        if need_w:
+            gw = _half_weight_grad(gt, x16, inv)
+        return gx, gw, gb, None, None
+
+
+class HalfMlpFunction(torch.autograd.Function):
+    """linear -> activation -> linear as ONE node in half precision (MlpFunction's graph):
+        x16 = half_pack(x)      u = x16 . W1_16^T + b1 (fp32)      a16 = act_half(u)      y = a16 . W2_16^T + b2
+    Saved: x16, u (fp32: act_backward needs it) and the two weights.  dy and du each get a scale of their own:
+        {sy, 1/sy} = grad_scale(dy)     (sy dy) rows, (sy dy)^T, db2 = half_pack(dy)
+        da = (1/sy) (sy dy) . W2_16     du, a, db1 = act_backward(u, da)     dW2 = (1/sy) (sy dy)^T . fp16(a)^T   (a: recomputed, fp32, dies here)
+        {su, 1/su} = grad_scale(du)     (su du) rows, (su du)^T = half_pack(du)
+        dW1 = (1/su) (su du)^T . x16^T  dx = (1/su) (su du) . W1_16"""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, act):
+        from ..ops_half import act_half, half_pack, half_weight
+        HALF_NODE_CALLS["mlp"] += 1
+        w1_16 = half_weight(w1, "w", [w1], lambda: w1)
+        w2_16 = half_weight(w2, "w", [w2], lambda: w2)
+        x16 = half_pack(_grad_rows(x, x.shape[-1]), None, want_rows=True, want_t=False)[0]
+        u = ops.gemm(x16, w1_16, None if b1 is None else b1.detach().float().contiguous(), split=False, out_fmt=ops.F32, tag="train_fwd")
+        y = ops.gemm(act_half(u, act), w2_16, None if b2 is None else b2.detach().float().contiguous(), split=False, out_fmt=ops.F32, tag="train_fwd")
+        ctx.save_for_backward(x16 if ctx.needs_input_grad[1] else None, u, w1, w2)
+        ctx.act, ctx.lead, ctx.has_b1, ctx.has_b2 = int(act), x.shape[:-1], b1 is not None, b2 is not None
+        return y.view(*x.shape[:-1], w2.shape[0])
+
+    @staticmethod
+    def backward(ctx, gy):
+        from ..ops_half import act_half, gemm_split_k_half, half_pack, half_weight
+        x16, u, w1, w2 = ctx.saved_tensors
+        need_x, need_w1, need_b1, need_w2, need_b2 = ctx.needs_input_grad[:5]
+        need_b1, need_b2 = need_b1 and ctx.has_b1, need_b2 and ctx.has_b2
+        gx = gw1 = gb1 = gw2 = gb2 = du = at = None
+        if not (need_x or need_w1 or need_b1 or need_w2 or need_b2):
+            return None, None, None, None, None, None
+        need_da = need_x or need_w1 or need_b1
+        g2 = _grad_rows(gy, w2.shape[0])
+        sy = ops.grad_scale(g2)
+        ga, gt, gb2 = half_pack(g2, sy, want_rows=need_da, want_t=need_w2, want_bias=need_b2)
+        del g2
+        if need_da:
+            w2t16 = half_weight(w2, "w.T", [w2], lambda: w2.t())
+            da = ops.gemm_scaled(ga, w2t16, sy[1:], split=False, out_fmt=ops.F32, tag="train_dx")
+            ga = None
+            du, a, gb1 = ops.act_backward(u, da, ctx.act, want_a=need_w2, want_bias_grad=need_b1, out=da)
+            del da
+            if need_w2:
+                at = half_pack(a, None, want_rows=False, want_t=True)[1]
+            del a
+        elif need_w2:
+            at = half_pack(act_half(u, ctx.act), None, want_rows=False, want_t=True)[1]
+        if need_w2:
+            gw2 = gemm_split_k_half(gt, at, _weight_grad_chunks(u.shape[0], gt.shape[0], at.shape[0], 64), sy[1:])
+        at = gt = None
+        if need_x or need_w1:
+            su = ops.grad_scale(du)
+            ua, ut, _ = half_pack(du, su, want_rows=need_x, want_t=need_w1)
+            del du
+            if need_w1:
+                gw1 = _half_weight_grad(ut, x16, su[1:])
+            if need_x:
+                w1t16 = half_weight(w1, "w.T", [w1], lambda: w1.t())
+                gx = ops.gemm_scaled(ua, w1t16, su[1:], split=False, out_fmt=ops.F32, tag="train_dx").view(*ctx.lead, w1.shape[1])
+        return gx, gw1, gb1, gw2, gb2, None
+
+
+def half_linear_ok(x, weight, rows):
+    """the linears the half nodes take: fp32 device tensors, at least 256 rows, K % 64 == 0 (the contraction of y and the output rows of
+    dW) and N % 64 == 0 (the contraction of dx): the F16 k tile is 64 elements"""
+    K, N = weight.shape[1], weight.shape[0]
+    return bool(x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and K % 64 == 0 and N % 64 == 0 and rows >= 256)
+
+
+def half_linear(x, weight, bias, owner, key):
+    """F.linear in half precision with a backward (HalfLinearFunction); a shape outside half_linear_ok runs the split node (split_linear)"""
+    if half_linear_ok(x, weight, x.numel() // weight.shape[1] if weight.shape[1] else 0):
+        return HalfLinearFunction.apply(x, weight, bias, owner, key)
+    return split_linear(x, weight, bias, owner, key)
+
+
+def half_mlp(x, w1, b1, w2, b2, act):
+    """linear(act(linear(x, w1, b1)), w2, b2) as one node in half precision (HalfMlpFunction) when BOTH linears are ones half_linear takes;
+    any other shape runs the split node (split_mlp)"""
+    rows = x.numel() // w1.shape[1] if w1.shape[1] else 0
+    if half_linear_ok(x, w1, rows) and half_linear_ok(x, w2, rows) and act in (ops.ACT_GELU, ops.ACT_RELU):
+        return HalfMlpFunction.apply(x, w1, b1, w2, b2, act)
+    return split_mlp(x, w1, b1, w2, b2, act)
 
 
 def _attention_forward(ctx, qa, ka, v, cols, forward_op):

@@ -399,6 +399,46 @@ class HipBackendScaledGrads(HipBackend):
                                 {"gelu": ops.ACT_GELU, "relu": ops.ACT_RELU}[act])
 
 
+class HipBackendHalfLinears(HipBackend):
+    """HipBackend + the linears that carry the step's flops -- the ViT qkv / proj / fc1 / fc2 and the encoder FFNs -- in HALF precision: ONE
+    fp16 MFMA product per GEMM instead of the three of the split GEMM, fp32 master weights, fp32 accumulation and output, the output
+    gradient scaled by a power of two chosen on the device (functions.HalfLinearFunction / HalfMlpFunction, csrc/half_pack.hip).
+    A PRECISION POLICY, not a bit-compatible group: results differ from HipBackend's at the 2^-11 level of an fp16 operand, so it is NOT a
+    member of GROUPS / EXTRA_GROUPS / LATER_GROUPS (whose every name is held to the fp32-class bounds of the golden step) and net.backend
+    never returns it; half_policy(backend_class) composes it in front of a backend class.  NEW ops, so no op is defined twice: _blin asks
+    linear_half first, _bmlp asks mlp_half first when the backend also has `mlp` (without it: the three nodes over _blin).  Linears outside
+    functions.half_linear_ok run the split node."""
+
+    @staticmethod
+    def linear_half(x, sd, p):
+        """HipBackend.linear on single fp16 operands (functions.half_linear)"""
+        from .functions import half_linear
+        w = sd[p + "weight"]
+        return half_linear(x, w, sd.get(p + "bias"), w, "w")
+
+    @staticmethod
+    def mlp_half(x, sd, p_fc1, p_fc2, act):
+        """HipBackendMlp.mlp on single fp16 operands (functions.half_mlp)"""
+        from .. import ops
+        from .functions import half_mlp
+        return half_mlp(x, sd[p_fc1 + "weight"], sd.get(p_fc1 + "bias"), sd[p_fc2 + "weight"], sd.get(p_fc2 + "bias"),
+                        {"gelu": ops.ACT_GELU, "relu": ops.ACT_RELU}[act])
+
+
+_HALF_POLICY = {}
+
+
+def half_policy(backend_class):
+    """backend_class (HipBackend, or any class net.backend returns) with the half-precision linears composed in front of it: one class per
+    backend class, built once.  Opt-in; TrainStep's default stays HipBackend."""
+    if issubclass(backend_class, HipBackendHalfLinears):
+        return backend_class
+    if backend_class not in _HALF_POLICY:
+        _HALF_POLICY[backend_class] = type("Half" + backend_class.__name__, (HipBackendHalfLinears, backend_class),
+                                           {"__doc__": "the half-precision linears in front of " + backend_class.__name__})
+    return _HALF_POLICY[backend_class]
+
+
 # the opt-in kernel groups by name; a composed class lists its bases in this order
 GROUPS = {"norms": HipBackendNorms, "mlp": HipBackendMlp, "windows": HipBackendWindows, "packed_attention": HipBackendPackedAttention,
           "packed_windows": HipBackendPackedWindows, "deformable": HipBackendDeformable, "losses": HipBackendLosses, "criteria": HipBackendCriteria,
@@ -549,17 +589,17 @@ def get_rel_pos(q_size, k_size, rel_pos):
 
 def _blin(x, sd, p, be):
     """a linear that carries flops: the backend's split-GEMM form when it has one (HipBackend.linear; HipBackendScaledGrads.linear_scaled
-    in front of it), else F.linear"""
-    f = getattr(be, "linear_scaled", None) or getattr(be, "linear", None)
+    in front of it, HipBackendHalfLinears.linear_half in front of both), else F.linear"""
+    f = getattr(be, "linear_half", None) or getattr(be, "linear_scaled", None) or getattr(be, "linear", None)
     return f(x, sd, p) if f is not None else lin(x, sd, p)
 
 
 def _bmlp(x, sd, p_fc1, p_fc2, act, be):
     """linear -> activation -> linear: the backend's one-node form when it has one (HipBackendMlp.mlp; with it, HipBackendScaledGrads.mlp_scaled
-    in front of it), else the three nodes"""
+    in front of it, HipBackendHalfLinears.mlp_half in front of both), else the three nodes"""
     f = getattr(be, "mlp", None)
     if f is not None:
-        f = getattr(be, "mlp_scaled", None) or f
+        f = getattr(be, "mlp_half", None) or getattr(be, "mlp_scaled", None) or f
         return f(x, sd, p_fc1, p_fc2, act)
     return _blin((F.gelu if act == "gelu" else F.relu)(_blin(x, sd, p_fc1, be)), sd, p_fc2, be)
 

@@ -1021,6 +1021,48 @@ int hipie_grad_pack(const void* dy, int64_t ldx, const void* scale, void* out_ro
 int hipie_splitk_finish(const void* part, int nk, int64_t n, const float* alpha_dev, void* out, void* stream);
 
 /*
+ * Half-precision operands of the training linears (csrc/half_pack.hip; the opt-in precision policy net.half_policy): ONE fp16 MFMA product
+ * per GEMM instead of the three of the split GEMM, fp32 master weights, fp32 accumulation and output.  Arithmetic contract of a linear
+ * y = x . W^T + b:  x16 = fp16(x), W16 = fp16(W), round to nearest even, values beyond +-65504 saturate (as the split's hi does), no scale on
+ * activations or weights;  y = x16 . W16^T + b (hipie_gemm, HIPIE_F16);  {s, 1 / s} = hipie_grad_scale(dy), g16 = fp16(s dy);
+ * dx = (1 / s) g16 . W16 (hipie_gemm_scaled, HIPIE_F16);  dW = (1 / s) g16^T . x16^T over the token rows padded to 64, in chunks
+ * (hipie_gemm_batched_f16) added in chunk order (hipie_splitk_finish);  db = column sums of the unscaled dy.  All scale factors are exact
+ * powers of two and every sum has a fixed order: the results for 2^e dy are 2^e times the results for dy, bit for bit.  Relative accuracy
+ * 2^-11 per operand, NOT the fp32 class of the split GEMM.
+ *
+ * hipie_half_pack:  ONE pass over x (rows, N), x_fmt HIPIE_F32 | HIPIE_F16 rows with row stride ldx (elements; 16-byte pieces), N a multiple
+ *   of 8.  scale: the device block of hipie_grad_scale (s = scale[0]) or NULL: s = 1.  Writes, each unless NULL,
+ *   out_rows (rows, N) fp16 of s x, row stride ldo;
+ *   out_t    (N, rows_p) fp16 of (s x)^T, row stride ldt, columns rows <= m < rows_p zero, rows_p a multiple of 64 (the F16 k tile);
+ *   dbias    (N) f32 = sum over the rows of the UNSCALED x: per-tile column sums in ws (hipie_half_pack_ws_bytes(rows_p, N) bytes), added in
+ *            tile order, the order of hipie_grad_pack.  dbias and ws come together.
+ *   All three NULL: nothing is launched.  Refused (HIPIE_EINVAL, nothing launched): N % 8, rows_p % 64 or < rows, strides below the row
+ *   length or off 16-byte pieces, x / out_rows / out_t off a 16-byte boundary.
+ *   Replaces: the readers of dy in torch.nn.functional.linear's backward under autocast -- the fp16 cast of dy, its transposed copy and
+ *   dy.sum(0) -- and the casts of x and of the recomputed activation (hipie/backbone/vit.py:67-83, 193-197;
+ *   models/deformable_detr/deformable_transformer_dino.py:384-394).
+ * hipie_act_half:  a16 (rows, N) fp16 = fp16(act(u)), u (rows, N) f32 dense rows, N a multiple of 8, act 1 = GELU | 2 = ReLU: the value
+ *   hipie_act_forward writes, rounded once -- the fp16 operand of the second linear without an fp32 activation in HBM.
+ *   Replaces: nn.GELU() / ReLU followed by the autocast cast in front of fc2 / linear2 (hipie/backbone/vit.py:193-197,
+ *   models/deformable_detr/deformable_transformer_dino.py:384-394).
+ */
+int64_t hipie_half_pack_ws_bytes(int64_t rows_p, int N);
+int hipie_half_pack(const void* x, int64_t ldx, int x_fmt, const void* scale, void* out_rows, int64_t ldo, void* out_t, int64_t ldt, void* dbias,
+                    void* ws, int64_t rows, int N, int64_t rows_p, void* stream);
+int hipie_act_half(const void* u, void* a16, int64_t rows, int N, int act, void* stream);
+
+/*
+ * hipie_gemm_batched for PLAIN fp16 operands (HIPIE_F16 rows of K elements, K a multiple of 64: one product per k tile), fp32 output, with
+ * the device factor of hipie_gemm_scaled (alpha_dev, NULL: 1): the batched launch of the tile instances hipie_gemm runs for HIPIE_F16, so a
+ * problem of the batch has the bits of the hipie_gemm call on its operands.  Offsets in elements as hipie_gemm_batched (A / W: fp16, out: fp32).
+ * Replaces: the per-chunk launches and the `* inv` pass of the split-K weight gradient dW = dy^T . x of torch.nn.functional.linear's
+ * backward in half precision (hipie/backbone/vit.py:67-83 and every other big Linear of the step).
+ */
+int hipie_gemm_batched_f16(const void* A, int64_t lda, int64_t a_outer, int64_t a_inner, const void* W, int64_t ldw, int64_t w_outer,
+                           int64_t w_inner, void* out, int64_t ldo, int64_t o_outer, int64_t o_inner, int n_outer, int n_inner, int M, int N,
+                           int K, float alpha, const float* alpha_dev, void* stream);
+
+/*
  * hipie_gemm on n_outer x n_inner independent problems in ONE launch (split-fp16 HL8 operands only, no bias / residual / activation):
  * problem (o, i) reads A + o * a_outer + i * a_inner (fp16 elements), W + o * w_outer + i * w_inner, writes out + o * o_outer +
  * i * o_inner (elements of out_fmt: fp32, or fp16 units for HL8).  Used for the image -> text direction of the vision-language fusion

@@ -5,10 +5,13 @@ GPU (configs/training/vit_huge_32g.yaml:1 -- 32 GPUs x 2), the 80-class caption,
     python tools/bench_train_step.py [batch] [steps] [--hand-norms] [--fused-mlp] [--fused-windows] [--packed-attention] [--packed-windows] [--fused-msda]
                                                             [--fused-losses] [--fused-criteria] [--fused-matching] [--fused-hungarian] [--fused-assign] [--fused-pair-losses]
                                                             [--fused-group-norms] [--fused-query-attention] [--fused-fusion-attention] [--fused-convs] [--scaled-grads]
+                                                            [--half-linears]
 Each flag names one opt-in kernel group of hipie_amd/training/net.py (FLAGS, EXTRA_FLAGS and LATER_FLAGS below; the classes' docstrings say what each puts on which kernels);
 the step runs on net.backend(*groups), no flag: net.HipBackend.  Any set of flags composes.  A flag whose group another flag's group builds on
 adds nothing: --packed-windows includes --packed-attention and --fused-windows, and each of --fused-losses < --fused-criteria < --fused-matching <
 --fused-hungarian < --fused-assign < --fused-pair-losses includes the ones before it.
+--half-linears is not a group but a PRECISION POLICY: the backend the other flags name with net.half_policy in front of it (the big linears on
+single fp16 operands; results differ at the 2^-11 level).
 env: LIB_LINEAR=1 (library fp32 linears), PHASES=1 (synchronised forward phases), TORCH_PROF=1 (top kernels), COUNTS=1 (device launches and host
 waits of one step), HOSTPROF=1 (cProfile of a forward)"""
 import os
@@ -67,10 +70,15 @@ def backend_names(argv):
     return [flags[a] for a in argv if a in flags], [a for a in argv if a not in flags]
 
 
+HALF_FLAG = "--half-linears"          # net.half_policy in front of the backend the group flags name
+
+
 def main():
     from hipie_amd.training import net
-    names, argv = backend_names(sys.argv[1:])
+    names, argv = backend_names([a for a in sys.argv[1:] if a != HALF_FLAG])
     be = net.backend(*names)
+    if HALF_FLAG in sys.argv[1:]:
+        be = net.half_policy(be)
     if os.environ.get("LIB_LINEAR") == "1":                  # A/B: the big linears on the library instead of the split GEMM Function
 
         class LibBackend(be):

@@ -36,7 +36,60 @@ def worst(lane_map, swz, lo):
     return out
 
 
+# ---- the transposing read of the pack kernels (csrc/gemm.hip to_hl8_t_kernel, csrc/grad_pack.hip, csrc/half_pack.hip): a lane reads the 8
+# rows of row group g at column c of a 128-row x 64-column fp32 tile, one ds_read_b32 per row: banks (dword address) mod 32, conflicts
+# among the lanes of a 32-lane half.  The staging stores of half_pack are ds_write_b128: groups of 8 contiguous lanes, banks mod 32.
+def padded_at(r, c):              # to_hl8_t_kernel / grad_pack_kernel: tile[128][65]
+    return r * 65 + c
+
+
+def padded_lanes(lane, it):       # unit u = tid + 256 it: g = u % 16, c = u / 16 (wave 0)
+    return lane % 16, lane // 16 + 16 * it
+
+
+def rotated_at(r, c):             # hp_at of half_pack.hip: the columns of a group of 8 rows rotated by 4 per group
+    return r * 64 + ((c + 4 * ((r >> 3) & 7)) & 63)
+
+
+def rotated_lanes(lane, it):      # half_pack_kernel (wave 0): 8 row groups x 4 columns per 32-lane half
+    return (lane & 7) + 8 * (lane >> 5), 4 * (4 * it) + ((lane >> 3) & 3)
+
+
+def worst_transposed_read(at, lanes):
+    worst_of = 1
+    for it in range(4):
+        for e in range(8):
+            for half in (range(0, 32), range(32, 64)):
+                banks = {}
+                for lane in half:
+                    g, c = lanes(lane, it)
+                    banks.setdefault(at(8 * g + e, c) % 32, set()).add(at(8 * g + e, c))
+                worst_of = max(worst_of, max(len(v) for v in banks.values()))
+    return worst_of
+
+
+def worst_staging_store(swap):
+    """ds_write_b128 of half_pack's staging: lane k writes the two 16-byte halves of (row k >> 3, column group k & 7); swap: the half
+    (g >> 2) first.  Returns the worst number of different addresses on one bank within a group of 8 contiguous lanes."""
+    worst_of = 1
+    for first in (0, 1):
+        for base in range(0, 64, 8):
+            banks = {}
+            for lane in range(base, base + 8):
+                i, g = lane >> 3, lane & 7
+                sw = (g >> 2) & 1 if swap else 0
+                a = rotated_at(i, 8 * g + 4 * (sw if first == 0 else 1 - sw))
+                for d in range(4):
+                    banks.setdefault((a + d) % 32, set()).add(a + d)
+            worst_of = max(worst_of, max(len(v) for v in banks.values()))
+    return worst_of
+
+
 if __name__ == "__main__":
+    print("transposing ds_read_b32: tile[128][65] (to_hl8_t, grad_pack) %d-way, rotated tile (half_pack) %d-way"
+          % (worst_transposed_read(padded_at, padded_lanes), worst_transposed_read(rotated_at, rotated_lanes)))
+    print("half_pack staging ds_write_b128: halves in order %d-way, half (g >> 2) first %d-way" % (worst_staging_store(False), worst_staging_store(True)))
+    assert worst_transposed_read(rotated_at, rotated_lanes) == 1 and worst_staging_store(True) == 1
     for mname, m in (("32x32x16 lane map", map32), ("16x16x32 lane map", map16)):
         for sname, s in (("(r >> 1) & 7", swz32), ("gm_swz16", swz16)):
             print("%s on %-13s lo=0 %s  lo=1 %s" % (mname, sname, worst(m, s, 0), worst(m, s, 1)))
