@@ -873,6 +873,160 @@ def conv3x3_train(x, weight, bias=None, relu=False, stride=1, padding=1, dilatio
     return Conv3x3Function.apply(x, weight, bias, relu)
 
 
+def _patch_source(t):
+    """a map the pack reads in place: fp32, the unit stride that of W or of C, no dimension expanded (a broadcast gradient has stride 0), on
+    a 16-byte boundary (ops.grad_scale reads it too); anything else is copied to NCHW once"""
+    from ..ops_patch import _map_strides
+    t = t.float()
+    sb, sc, sh, sw = _map_strides(t)
+    if (sw != 1 and sc != 1) or min(sc, sh, sw) < 1 or sb < max(t.shape[1] * sc if sw == 1 else 0, t.shape[2] * sh) or t.data_ptr() % 16:
+        t = t.contiguous()
+        t = t.clone() if t.data_ptr() % 16 else t
+    return t
+
+
+def _patch_operands(t, k, scale=None, want_f32=False, want_rows=False, want_t=False, want_sum=False):
+    """(fp32 rows, HL8 rows, HL8 transpose, channel sums) of the map t in ONE pass: a channels-last k == 1 map IS its rows (a view), and the
+    existing row entries take it -- ops.grad_pack for a gradient, ops.to_hl8_t for an activation; every other map goes through
+    ops_patch.patch_pack"""
+    from .. import ops_patch
+    rows = ops_patch.patch_rows_view(t, k)
+    if rows is None:
+        return ops_patch.patch_pack(t, k, scale, want_f32=want_f32, want_rows=want_rows, want_t=want_t, want_sum=want_sum)
+    if scale is not None:
+        return (rows if want_f32 else None,) + tuple(ops.grad_pack(rows, scale, want_rows=want_rows, want_t=want_t, want_bias=want_sum))
+    if want_rows or want_sum:          # no caller: an unscaled map is an activation, wanted as fp32 rows or as the transposed operand
+        raise RuntimeError("_patch_operands: an unscaled rows view gives fp32 rows and the transposed operand only")
+    return rows if want_f32 else None, None, ops.to_hl8_t(rows, 32) if want_t else None, None
+
+
+def _amax_rows(t):
+    """a 2-D view of the map _patch_source returned for ops.grad_scale: the maximum does not depend on the layout"""
+    from .. import ops_patch
+    if t.is_contiguous():
+        return t.view(-1, t.shape[1] if t.shape[1] % 4 == 0 else 4)
+    rows = ops_patch.patch_rows_view(t, 1)
+    return rows if rows is not None else _amax_rows(t.contiguous())
+
+
+def _scaled_product_t(at, bt, rows, inv):
+    """inv * at . bt^T for two TRANSPOSED HL8 operands (Na, 2 Mp), (Nb, 2 Mp) whose contraction runs over the `rows` patch rows: the chunks
+    and the fixed-order sum of _scaled_weight_grad"""
+    nk = _weight_grad_chunks(rows, at.shape[0], bt.shape[0])
+    if nk == 1:
+        return ops.gemm_scaled(at, bt, inv, split=True, out_fmt=ops.F32, tag="train_dw")
+    return ops.gemm_split_k_scaled(at, bt, nk, inv)
+
+
+class PatchConvFunction(torch.autograd.Function):
+    """A convolution whose kernel equals its stride (k x k / stride k / padding 0: the 1 x 1 projections, the 16 x 16 patch embedding), or a
+    transposed 2 x 2 / stride 2 one, as ONE node of the graph: a linear over patch rows plus a layout change that is done once, by the
+    producer of the GEMM operands (ops_patch.patch_pack, csrc/patch_pack.hip; a channels-last k == 1 map is its own rows and costs no pass).
+    Patch row m = (b, h, w), column n = c k^2 + i k + j, W2 the 2-D view of the weight in that column order:
+      convolution   W2 = weight.reshape(Cout, Cin k k)      y rows = X . W2^T + b                  ops.gemm on split operands
+      transposed    W2 = weight.view(Cin, 4 Cout)           the k = 2 patch rows of y = X . W2 + b   the four row-mapped tap linears of
+                                                            ops.convt2x2_split: no shuffle pass
+    Both return a channels-last VIEW of the rows they wrote ((B, Cout, H/k, W/k) / (B, Cout, 2 H, 2 W)), as Conv3x3Function does.
+    Backward, always device-scaled ({s, 1/s} = ops.grad_scale(dy); G = the patch rows of s dy, k = 1 / k = 2 for the transposed form):
+      ONE pass over dy: G as HL8 rows if dx is needed, G^T if dW is needed, db = the channel sums of the unscaled dy if db is needed
+      convolution   dx rows = (1/s) G . W2          dW2 = (1/s) G^T . X         (Cout, Cin k k)
+      transposed    dx rows = (1/s) G . W2^T        dW2 = (1/s) X^T . G         (Cin, 4 Cout): one GEMM each, not four
+    dx is returned as a channels-last view; dW in the weight's own shape, contiguous.  Saved: x and weight only -- X^T is produced in the
+    backward by a pass over the saved x, no gathered copy is kept.  The weight products are cut into chunks over the rows and added in
+    chunk order (_scaled_weight_grad's form).  needs_input_grad is honoured: a frozen input, weight or bias skips its operand form and its
+    GEMM.  A trainable input with k > 1 has no scatter kernel: patch_conv_train declines it (the patch embedding's input is the image)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, k, transposed):
+        B, C, H, W = x.shape
+        xs = _patch_source(x)
+        rows = _patch_operands(xs, k, want_f32=True)[0]
+        if transposed:
+            Cout = weight.shape[1]
+            y = ops.convt2x2_split(rows, weight, "patch_t", weight, None if bias is None else bias.detach(), B, H, W)
+        else:
+            Cout = weight.shape[0]
+            w_hl8, _, _ = ops.split_weight(weight, "patch", [weight], lambda: weight.reshape(Cout, C * k * k))
+            y = ops.gemm(rows, w_hl8, None if bias is None else bias.detach().contiguous(), split=True, out_fmt=ops.F32, tag="train_fwd")
+            y = y.view(B, H // k, W // k, Cout)
+        ctx.save_for_backward(x, weight)
+        ctx.k, ctx.transposed, ctx.has_bias = int(k), bool(transposed), bias is not None
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        if not (need_x or need_w or need_b):
+            return None, None, None, None, None
+        B, C, H, W = x.shape
+        k, tr = ctx.k, ctx.transposed
+        M = B * (H // k) * (W // k)
+        g = _patch_source(dy)
+        scale = ops.grad_scale(_amax_rows(g))
+        inv = scale[1:]
+        _, ga, gt, gb = _patch_operands(g, 2 if tr else 1, scale, want_rows=need_x, want_t=need_w, want_sum=need_b)
+        dx = dw = None
+        if need_x:
+            if tr:                 # (N = Cin, K = 4 Cout): the weight's own view
+                w2, _, _ = ops.split_weight(weight, "patch_t.dx", [weight], lambda: weight.reshape(C, -1))
+            else:                  # k == 1: (N = Cin, K = Cout)
+                w2, _, _ = ops.split_weight(weight, "patch.T", [weight], lambda: weight.reshape(weight.shape[0], C).t().contiguous())
+            dx = ops.gemm_scaled(ga, w2, inv, split=True, out_fmt=ops.F32, tag="train_dx").view(B, H, W, C).permute(0, 3, 1, 2)
+        if need_w:
+            xt = _patch_operands(_patch_source(x), k, want_t=True)[2]
+            dw = (_scaled_product_t(xt, gt, M, inv) if tr else _scaled_product_t(gt, xt, M, inv)).view(weight.shape)
+        return dx, dw, gb, None, None
+
+
+def patch_conv_train_ok(x, weight, bias=None, stride=1, padding=0, dilation=1, groups=1, output_padding=0, transposed=False):
+    """the limits of the training projection node: fp32 device tensors; groups 1, dilation 1, padding 0, no output padding, a square kernel
+    equal to the stride (k = 2 for the transposed form) that divides H and W; both the contraction width and the output width of every
+    GEMM the node launches multiples of 32 -- Cin k^2 % 32 == 0 and Cout % 32 == 0 for a convolution, Cin % 32 == 0 and Cout % 8 == 0 (the
+    input gradient contracts over 4 Cout) for the transposed form -- which also makes every operand row a whole number of 16-byte pieces;
+    fewer than 2^31 patch rows.  No lower limit on the row count: the GEMM entries take one row."""
+    def one(v):
+        return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+    if x.dim() != 4 or weight.dim() != 4 or min(x.shape) < 1:
+        return False
+    k = weight.shape[2]
+    if weight.shape[3] != k or one(stride) != (k, k) or one(padding) != (0, 0) or one(dilation) != (1, 1) or groups != 1:
+        return False
+    if one(output_padding) != (0, 0) or (not transposed and (x.shape[2] % k or x.shape[3] % k)):
+        return False
+    if transposed:
+        Cin, Cout = weight.shape[0], weight.shape[1]
+        if k != 2 or Cin % 32 or Cout % 8:
+            return False
+    else:
+        Cout, Cin = weight.shape[0], weight.shape[1]
+        if (Cin * k * k) % 32 or Cout % 32:
+            return False
+    if Cin != x.shape[1] or x.shape[0] * x.shape[2] * x.shape[3] >= 1 << 31 or (bias is not None and tuple(bias.shape) != (Cout,)):
+        return False
+    if x.dtype != torch.float32 or weight.dtype != torch.float32 or (bias is not None and bias.dtype != torch.float32):
+        return False
+    return x.is_cuda and weight.is_cuda and (bias is None or bias.is_cuda)
+
+
+def patch_conv_train(x, weight, bias=None, stride=1, padding=0, dilation=1, groups=1):
+    """conv2d with kernel == stride as one node (PatchConvFunction), or None outside patch_conv_train_ok's limits and for a TRAINABLE input
+    with k > 1 (no scatter kernel): the caller's F.conv2d runs"""
+    if not patch_conv_train_ok(x, weight, bias, stride, padding, dilation, groups):
+        return None
+    if weight.shape[2] > 1 and x.requires_grad and torch.is_grad_enabled():
+        return None
+    return PatchConvFunction.apply(x, weight, bias, weight.shape[2], False)
+
+
+def patch_convt_train(x, weight, bias=None, stride=2, padding=0, output_padding=0, groups=1, dilation=1):
+    """conv_transpose2d 2 x 2 / stride 2 as one node (PatchConvFunction), or None outside patch_conv_train_ok's limits: the caller's
+    F.conv_transpose2d runs"""
+    if not patch_conv_train_ok(x, weight, bias, stride, padding, dilation, groups, output_padding, transposed=True):
+        return None
+    return PatchConvFunction.apply(x, weight, bias, 1, True)
+
+
 def _rows_ok(t):
     """rows the query-attention kernels read in place: contiguous columns, strides multiples of 4 elements, a 16-byte boundary"""
     return t.stride(2) == 1 and t.stride(0) % 4 == 0 and t.stride(1) % 4 == 0 and t.data_ptr() % 16 == 0

@@ -3,7 +3,7 @@ state_dict layout as the reference, hipie_amd/hipie_img.py), written for autogra
 kernels have no backward.  What is hand-written HIP here is what has a backward kernel: multi-scale deformable attention
 (hipie_msda_forward / hipie_msda_backward), the mask contraction and the CondInst dynamic mask head (training/functions.py); the dense
 linears, LayerNorm / GroupNorm, the softmax attentions and the convolutions run on the library kernels PyTorch-ROCm dispatches to, with
-torch.autograd providing their backward (the dense 3 x 3 convolutions have a node of their own in the opt-in group "convs").  More of the step runs on hand-written kernels opt-in, one HipBackend* class per kernel group:
+torch.autograd providing their backward (the dense 3 x 3 convolutions have a node of their own in the opt-in group "convs", the 1 x 1 and transposed ones in "projections").  More of the step runs on hand-written kernels opt-in, one HipBackend* class per kernel group:
 GROUPS, EXTRA_GROUPS and LATER_GROUPS below name them, backend(*names) composes any of them into the class TrainStep takes.
 
 Functional style over a dict ``sd`` of LIVE parameters (model.named_parameters() + buffers, reference key names), so gradients land in the
@@ -363,6 +363,37 @@ class HipBackendConvs(HipBackend):
         return conv3x3_train(x, weight, bias, relu)
 
 
+class HipBackendProjections(HipBackend):
+    """HipBackend + the convolutions whose kernel equals their stride, and the two transposed ones, as ONE autograd node each
+    (functions.PatchConvFunction): the simple feature pyramid's fpn1.0 and the pixel decoder's mask_features.0 (ConvTranspose2d 2 x 2 /
+    stride 2), the 1 x 1 input_proj.0-2 of both heads, adapter_1 and mask_features.3.  Each is a linear over patch rows on the split GEMM
+    -- forward, device-scaled input gradient and split-K weight gradient are the entries the linears use -- plus a layout change done once
+    by the operand producer hipie_patch_pack (csrc/patch_pack.hip); a channels-last map is its own rows.  Outputs and input gradients
+    are channels-last views.  NEW ops, so no op is defined by two groups.  The group runs on SPLIT operands under half_policy too: the
+    policy composes the half-precision linears in front of a backend and does not touch these ops.
+    Opt-in: TrainStep's default stays HipBackend.  NOT routed: the 16 x 16 patch embedding.  The node takes it (k = 16, input frozen;
+    tests/test_gpu_patch_conv.py, tools/bench_patch_conv.py), but with it in the group the golden step's sampling-offsets gradients are
+    5.5e-3 of their largest entry off the fixture, in every composition measured, where the step checker allows 5e-3: a 1e-7 change at
+    the root of the ViT moves a sampling point of the pixel decoder's first encoder layer across a pixel boundary, where that gradient is
+    discontinuous (docs/measurements.md).  vit_backbone keeps F.conv2d for it.  Not here either: the stride-2 3 x 3 input_proj.3 (two
+    sites of 512 rows x K = 11520), dy scaling of the 3 x 3 node, a scatter for a trainable input with k > 1 (declined), 16-bit
+    operands, making the group the default."""
+
+    @staticmethod
+    def conv_patch(x, weight, bias, stride):
+        """conv2d(x, weight, bias, stride=stride) for a k x k kernel with stride k and no padding -> (B, Cout, H/k, W/k), a channels-last
+        view, or None outside the limits (the caller's F.conv2d then runs; functions.patch_conv_train_ok names the limits)"""
+        from .functions import patch_conv_train
+        return patch_conv_train(x, weight, bias, stride)
+
+    @staticmethod
+    def convt2x2(x, weight, bias):
+        """conv_transpose2d(x, weight, bias, stride=2) for a 2 x 2 kernel -> (B, Cout, 2 H, 2 W), a channels-last view, or None outside the
+        limits (the caller's F.conv_transpose2d then runs)"""
+        from .functions import patch_convt_train
+        return patch_convt_train(x, weight, bias)
+
+
 class HipBackendScaledGrads(HipBackend):
     """HipBackend + SCALED gradient operands in the backward of the split linears -- the ViT qkv / proj / fc1 / fc2 and the encoder FFNs: every
     output gradient that enters a split GEMM is first multiplied by a power of two chosen on the device from its largest magnitude, in the
@@ -448,7 +479,7 @@ EXTRA_GROUPS = {"group_norms": HipBackendGroupNorms}
 # the table every later group joins, at its end: a composed class lists these after the GROUPS and EXTRA_GROUPS classes.
 # It GROWS: a test may assert that a name is in it and where it stands relative to another name, never the table's full contents.
 LATER_GROUPS = {"query_attention": HipBackendQueryAttention, "fusion_attention": HipBackendFusionAttention, "convs": HipBackendConvs,
-                "scaled_grads": HipBackendScaledGrads}
+                "scaled_grads": HipBackendScaledGrads, "projections": HipBackendProjections}
 # Among the bases of a composed class the two attention groups keep the END, in this order (tests/test_fusion_attention_cpu.py pins
 # HipBackendFusionAttention as the last base of the every-group class); a group that joins LATER_GROUPS behind them is listed in front of
 # them.  The groups are unrelated by inheritance and share no op, so the order of the bases changes nothing a step computes.
@@ -495,15 +526,35 @@ def mlp(x, sd, p, n):
 
 
 def conv(x, sd, p, stride=1, padding=0, be=None, relu=False):
-    """conv2d (+ ReLU); a backend with a `conv3x3` op is asked first for the 3 x 3 / stride 1 / padding 1 sites (None: outside its limits)"""
+    """conv2d (+ ReLU); a backend with a `conv3x3` op is asked first for the 3 x 3 / stride 1 / padding 1 sites, one with a `conv_patch` op
+    for the sites without padding whose kernel equals the stride (None: outside its limits)"""
     w, b = sd[p + "weight"], sd.get(p + "bias")
     op = getattr(be, "conv3x3", None) if (stride, padding) == (1, 1) else None
     y = op(x, w, b, relu) if op is not None else None
+    if y is None and padding == 0 and tuple(w.shape[2:]) == (stride, stride):
+        y = conv_patch(x, w, b, stride, be)
+        if relu:
+            y = F.relu(y)
+        return y
     if y is None:
         y = F.conv2d(x, w, b, stride=stride, padding=padding)
         if relu:
             y = F.relu(y)
     return y
+
+
+def conv_patch(x, weight, bias, stride, be=None):
+    """conv2d whose kernel equals its stride, no padding; a backend with a `conv_patch` op is asked first (None: outside its limits)"""
+    op = getattr(be, "conv_patch", None)
+    y = op(x, weight, bias, stride) if op is not None else None
+    return F.conv2d(x, weight, bias, stride=stride) if y is None else y
+
+
+def convt2x2(x, weight, bias, be=None):
+    """conv_transpose2d 2 x 2 / stride 2; a backend with a `convt2x2` op is asked first (None: outside its limits)"""
+    op = getattr(be, "convt2x2", None)
+    y = op(x, weight, bias) if op is not None else None
+    return F.conv_transpose2d(x, weight, bias, stride=2) if y is None else y
 
 
 def gn(x, sd, p, groups=32, be=None, relu=False):
@@ -665,6 +716,8 @@ def vit_attention(x, sd, p, heads, be=None):
 
 def vit_backbone(x, sd, p, cfg, be=None):
     """ViT.forward (vit.py:357-374) + the simple feature pyramid of D2ViT (fpn1 = ConvTranspose, identity, max pool)"""
+    # the patch embedding stays on the library: functions.PatchConvFunction takes it (k = 16, frozen input), but its fp32-class difference at
+    # the root of the ViT moves the sampling-offsets gradients of the golden step past the checker's bound (HipBackendProjections)
     x = F.conv2d(x, sd[p + "patch_embed.proj.weight"], sd[p + "patch_embed.proj.bias"], stride=cfg["vit_patch"]).permute(0, 2, 3, 1)
     x = x + get_abs_pos(sd[p + "pos_embed"], (x.shape[1], x.shape[2]))
     aln = getattr(be, "add_layer_norm", None)       # HipBackendNorms: every residual add is paired with the LayerNorm that follows it
@@ -692,7 +745,7 @@ def vit_backbone(x, sd, p, cfg, be=None):
             if i == cfg["vit_depth"] - 1:         # no norm follows the last block: a plain add
                 x = x + pending
     xp = x.permute(0, 3, 1, 2)
-    return {"res3": F.conv_transpose2d(xp, sd[p + "fpn1.0.weight"], sd[p + "fpn1.0.bias"], stride=2), "res4": xp, "res5": F.max_pool2d(xp, 2, 2)}
+    return {"res3": convt2x2(xp, sd[p + "fpn1.0.weight"], sd[p + "fpn1.0.bias"], be), "res4": xp, "res5": F.max_pool2d(xp, 2, 2)}
 
 
 # ------------------------------------------------------------------------------------------------ masks, positions
@@ -937,7 +990,7 @@ def maskdino_pixel_decoder(feats, sd, p, cfg, be):
     """MaskDINOEncoder.forward_features (maskdino/pixel_decoder/maskdino_encoder.py:368-434), low2high, masks None"""
     f3, f4, f5 = feats["res3"], feats["res4"], feats["res5"]
     extra = gn(conv(f5, sd, p + "input_proj.3.0.", stride=2, padding=1), sd, p + "input_proj.3.1.", be=be)
-    srcs = [gn(conv(f, sd, "%sinput_proj.%d.0." % (p, i)), sd, "%sinput_proj.%d.1." % (p, i), be=be) for i, f in enumerate((f3, f4, f5))] + [extra]
+    srcs = [gn(conv(f, sd, "%sinput_proj.%d.0." % (p, i), be=be), sd, "%sinput_proj.%d.1." % (p, i), be=be) for i, f in enumerate((f3, f4, f5))] + [extra]
     B, dev = f3.shape[0], f3.device
     zero = [torch.zeros(B, s.shape[2], s.shape[3], dtype=torch.bool, device=dev) for s in srcs]
     poses = [pos_sine(z, 128, offset=0.0) for z in zero]
@@ -953,11 +1006,11 @@ def maskdino_pixel_decoder(feats, sd, p, cfg, be):
     for (H, W) in shapes:
         outs.append(src[:, st:st + H * W].transpose(1, 2).reshape(B, -1, H, W))
         st += H * W
-    cur = gn(F.conv2d(f3, sd[p + "adapter_1.weight"]), sd, p + "adapter_1.norm.", be=be)
+    cur = gn(conv_patch(f3, sd[p + "adapter_1.weight"], None, 1, be), sd, p + "adapter_1.norm.", be=be)
     y = cur + F.interpolate(outs[0], size=cur.shape[-2:], mode="bilinear", align_corners=False)
     y = gn(conv(y, sd, p + "layer_1.", padding=1, be=be), sd, p + "layer_1.norm.", be=be, relu=True)       # the ReLU stays with GroupNorm
-    mf = gn(F.conv_transpose2d(y, sd[p + "mask_features.0.weight"], sd[p + "mask_features.0.bias"], stride=2), sd, p + "mask_features.1.", be=be, relu=True)
-    return conv(mf, sd, p + "mask_features.3."), outs
+    mf = gn(convt2x2(y, sd[p + "mask_features.0.weight"], sd[p + "mask_features.0.bias"], be), sd, p + "mask_features.1.", be=be, relu=True)
+    return conv(mf, sd, p + "mask_features.3.", be=be), outs
 
 
 def maskdino_decoder(ms_feats, mask_features, sd, p, cfg, be, dn=None, topk_override=None):
@@ -1032,7 +1085,7 @@ def backbone_and_projections(x, pad, sd, cfg, be=None):
     names = ["res3", "res4", "res5"]
     fmasks = [down_mask(pad, feats[n].shape[-2:]) for n in names]
     poses = [pos_sine(m, cfg["hidden_dim"] // 2) for m in fmasks]
-    srcs = [gn(conv(feats[n], sd, "%sinput_proj.%d.0." % (p, i)), sd, "%sinput_proj.%d.1." % (p, i), be=be) for i, n in enumerate(names)]
+    srcs = [gn(conv(feats[n], sd, "%sinput_proj.%d.0." % (p, i), be=be), sd, "%sinput_proj.%d.1." % (p, i), be=be) for i, n in enumerate(names)]
     s4 = gn(conv(feats["res5"], sd, p + "input_proj.3.0.", stride=2, padding=1), sd, p + "input_proj.3.1.", be=be)
     m4 = down_mask(fmasks[0], s4.shape[-2:])
     return feats, srcs + [s4], fmasks + [m4], poses + [pos_sine(m4, cfg["hidden_dim"] // 2)]

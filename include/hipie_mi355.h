@@ -1052,6 +1052,35 @@ int hipie_half_pack(const void* x, int64_t ldx, int x_fmt, const void* scale, vo
 int hipie_act_half(const void* u, void* a16, int64_t rows, int N, int act, void* stream);
 
 /*
+ * The map-to-rows pack of the training projections (csrc/patch_pack.hip; the opt-in backend group "projections"): a convolution whose
+ * kernel equals its stride, and a transposed one, are linears over patch rows plus a layout change; this entry does the layout change
+ * once, as the producer of the split GEMM's operands.
+ *
+ * hipie_patch_pack:  ONE pass over the fp32 map x of logical shape (B, C, H, W) with the element strides (sb, sc, sh, sw) -- NCHW-dense and
+ *   channels-last maps are read in place -- and the patch size k (any k <= 64 that divides H and W).  Patch row m = (b H/k + h) W/k + w,
+ *   column n = c k^2 + i k + j holds x[b, c, h k + i, w k + j]: M = B (H/k) (W/k) rows of N = C k^2 columns, the column order of
+ *   weight.reshape(Cout, Cin k k) of a convolution and of weight.view(Cin, Cout k k) of a transposed one.  scale: the device block of
+ *   hipie_grad_scale (s = scale[0]) or NULL: s = 1.  Writes, each unless NULL,
+ *   out_f32  (M, N) f32 rows, row stride ldf: the A operand of the forward GEMM of a map that is not channels-last;
+ *   out_rows (M, 2 N) HL8 of s x, row stride ldo: the bits of hipie_to_hl8 of the gathered rows with scale = s;
+ *   out_t    (N, 2 rows_p) HL8 of (s x)^T, row stride ldt, columns M <= m < rows_p zero (rows_p a multiple of 32): the bits of hipie_to_hl8_t;
+ *   dsum     (C) f32 = per-CHANNEL sums of the UNSCALED values over all pixels: per-tile column sums in ws
+ *            (hipie_patch_pack_ws_bytes(rows_p, N) bytes; ws_bytes = what the caller has), added in tile order and, per channel, in column
+ *            order: no floating-point atomic, the same bits on every call.  dsum and ws come together.
+ *   All outputs NULL: nothing is launched (HIPIE_OK).  Refused (HIPIE_EINVAL with a hipie_last_error() text, nothing launched): a NULL x,
+ *   N % 8, k not dividing H or W, rows_p % 32 or rows_p < M, a map whose unit stride is neither that of W nor that of C, output pointers or
+ *   strides off 16 bytes (or below the row length), dsum without ws or ws without dsum, a workspace that is too small.
+ *   Replaces: the .permute / .contiguous copies around F.conv2d / F.conv_transpose2d whose kernel equals its stride, the transposed copies
+ *   and the channel sums of the backward of torch's conv2d and conv_transpose2d at those sites -- PatchEmbed.proj and the simple feature
+ *   pyramid's ConvTranspose2d (backbone/vit.py:357-374), the 1 x 1 input_proj of both heads (models/ddetrs_dn.py:271-320,
+ *   maskdino/pixel_decoder/maskdino_encoder.py:368-434), adapter_1 and mask_features of the pixel decoder (ibid.).
+ */
+int64_t hipie_patch_pack_ws_bytes(int64_t rows_p, int N);
+int hipie_patch_pack(const void* x, int B, int C, int H, int W, int64_t sb, int64_t sc, int64_t sh, int64_t sw, int k, const void* scale,
+                     void* out_f32, int64_t ldf, void* out_rows, int64_t ldo, void* out_t, int64_t ldt, int64_t rows_p, void* dsum, void* ws,
+                     int64_t ws_bytes, void* stream);
+
+/*
  * hipie_gemm_batched for PLAIN fp16 operands (HIPIE_F16 rows of K elements, K a multiple of 64: one product per k tile), fp32 output, with
  * the device factor of hipie_gemm_scaled (alpha_dev, NULL: 1): the batched launch of the tile instances hipie_gemm runs for HIPIE_F16, so a
  * problem of the batch has the bits of the hipie_gemm call on its operands.  Offsets in elements as hipie_gemm_batched (A / W: fp16, out: fp32).

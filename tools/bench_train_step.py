@@ -4,7 +4,7 @@ GPU (configs/training/vit_huge_32g.yaml:1 -- 32 GPUs x 2), the 80-class caption,
 12544 mask points, random-init weights.  Prints ms for the forward (loss dictionary), the backward, and the peak memory.
     python tools/bench_train_step.py [batch] [steps] [--hand-norms] [--fused-mlp] [--fused-windows] [--packed-attention] [--packed-windows] [--fused-msda]
                                                             [--fused-losses] [--fused-criteria] [--fused-matching] [--fused-hungarian] [--fused-assign] [--fused-pair-losses]
-                                                            [--fused-group-norms] [--fused-query-attention] [--fused-fusion-attention] [--fused-convs] [--scaled-grads]
+                                                            [--fused-group-norms] [--fused-query-attention] [--fused-fusion-attention] [--fused-convs] [--scaled-grads] [--fused-projections]
                                                             [--half-linears]
 Each flag names one opt-in kernel group of hipie_amd/training/net.py (FLAGS, EXTRA_FLAGS and LATER_FLAGS below; the classes' docstrings say what each puts on which kernels);
 the step runs on net.backend(*groups), no flag: net.HipBackend.  Any set of flags composes.  A flag whose group another flag's group builds on
@@ -61,7 +61,7 @@ EXTRA_FLAGS = {"--fused-group-norms": "group_norms"}
 
 # flag -> group of net.LATER_GROUPS: the table later flags join (tests assert membership in it, not its full contents)
 LATER_FLAGS = {"--fused-query-attention": "query_attention", "--fused-fusion-attention": "fusion_attention", "--fused-convs": "convs",
-               "--scaled-grads": "scaled_grads"}
+               "--scaled-grads": "scaled_grads", "--fused-projections": "projections"}
 
 
 def backend_names(argv):

@@ -85,7 +85,54 @@ def worst_staging_store(swap):
     return worst_of
 
 
+# ---- csrc/patch_pack.hip on the same rotated tile.  PIXELS staging: a lane holds the 8 rows of row group g at column c (the lanes of
+# half_pack's transposing read) and writes them with 8 ds_write_b32: banks mod 32 per 32-lane half.  Row read of PIXELS / GATHER: lane u
+# reads the two 16-byte halves of (row u >> 3, column group u & 7) with ds_read_b128, the half ((row >> 1) & 1) first: 64 banks, the four
+# lane groups of GROUPS.  GATHER staging: one ds_write_b32 per element in the order the map is walked (k = 2).
+def worst_pixels_store():
+    return worst_transposed_read(rotated_at, rotated_lanes)          # the same addresses, written instead of read
+
+
+def worst_row_read(swap):
+    worst_of = 1
+    for it in range(4):
+        for first in (0, 1):
+            for grp in GROUPS:
+                slots = {}
+                for lane in grp:
+                    u = lane + 256 * it
+                    i, q = u >> 3, u & 7
+                    sw = (i >> 1) & 1 if swap else 0
+                    a = rotated_at(i, 8 * q + 4 * (sw if first == 0 else 1 - sw))
+                    slots.setdefault((a // 4) % 16, set()).add(a)
+                worst_of = max(worst_of, max(len(v) for v in slots.values()))
+    return worst_of
+
+
+def worst_gather_store(order, k):
+    worst_of = 1
+    k2 = k * k
+    for base in range(0, 128 * 64, 32):
+        banks = {}
+        for u in range(base, base + 32):
+            if order == 1:
+                t = u // k
+                r, c = t & 127, (t >> 7) * k + u % k
+            else:
+                ch = 64 // k2
+                t = u // ch
+                r, c = u >> 6, (u % ch) * k2 + t % k2
+            a = rotated_at(r, c)
+            banks.setdefault(a % 32, set()).add(a)
+        worst_of = max(worst_of, max(len(v) for v in banks.values()))
+    return worst_of
+
+
 if __name__ == "__main__":
+    print("patch_pack: PIXELS staging ds_write_b32 %d-way; row ds_read_b128 halves in order %d-way, half ((row >> 1) & 1) first %d-way; "
+          "GATHER staging ds_write_b32, k = 2: NCHW order %d-way, channels-last order %d-way"
+          % (worst_pixels_store(), worst_row_read(False), worst_row_read(True), worst_gather_store(1, 2), worst_gather_store(2, 2)))
+    assert worst_pixels_store() == 1 and worst_row_read(True) == 1
     print("transposing ds_read_b32: tile[128][65] (to_hl8_t, grad_pack) %d-way, rotated tile (half_pack) %d-way"
           % (worst_transposed_read(padded_at, padded_lanes), worst_transposed_read(rotated_at, rotated_lanes)))
     print("half_pack staging ds_write_b128: halves in order %d-way, half (g >> 2) first %d-way" % (worst_staging_store(False), worst_staging_store(True)))
