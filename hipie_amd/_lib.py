@@ -101,4 +101,4 @@ def load():
 def check(rc, what):
     if rc != 0:
         msg = load().hipie_last_error()
-        raise RuntimeError("%s failed (rc=%d): %s" % (what, rc, msg.decode() if msg else ""))
+        raise HipieLibraryError("%s failed (rc=%d): %s" % (what, rc, msg.decode() if msg else ""))
