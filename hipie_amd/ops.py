@@ -2165,6 +2165,12 @@ def gemm(a, w, bias=None, resid=None, out_fmt=F32, act=ACT_NONE, alpha=1.0, osca
     return out
 
 
+def _one_f32(who, alpha_dev):
+    """the device scalar of the scaled products: one fp32 element (a view into a scale block of grad_scale), or None"""
+    if alpha_dev is not None and (alpha_dev.dtype != torch.float32 or alpha_dev.numel() != 1):
+        raise RuntimeError("%s: alpha_dev must be one torch.float32 element, got %s %s" % (who, alpha_dev.dtype, tuple(alpha_dev.shape)))
+
+
 def gemm_scaled(a, w, alpha_dev, **kw):
     """gemm (hipie_gemm_scaled) whose alpha is multiplied by the DEVICE scalar alpha_dev (one fp32 element, e.g. grad_scale(dy)[1:]) in the
     kernel that writes the product: no host wait, no extra pass.  alpha_dev None: the NULL pointer, i.e. gemm's dispatch and bits.  The
@@ -2172,8 +2178,7 @@ def gemm_scaled(a, w, alpha_dev, **kw):
     _on_device("gemm_scaled", "a alpha_dev", a, alpha_dev)
     if kw.get("a_row") is not None:
         raise RuntimeError("gemm_scaled: the gather form (a_row) has no scaled entry")
-    if alpha_dev is not None and (alpha_dev.dtype != torch.float32 or alpha_dev.numel() != 1):          # a view into a scale block
-        raise RuntimeError("gemm_scaled: alpha_dev must be one torch.float32 element, got %s %s" % (alpha_dev.dtype, tuple(alpha_dev.shape)))
+    _one_f32("gemm_scaled", alpha_dev)
     return gemm(a, w, alpha_dev=alpha_dev, **kw)
 
 
@@ -2224,8 +2229,7 @@ def gemm_split_k_scaled(a_hl8, w_hl8, nk, alpha_dev):
     (hipie_splitk_finish) instead of part.sum(0): the weight gradient of the scaled-gradient nodes.  M * N a multiple of 4."""
     who = "gemm_split_k_scaled"
     _on_device(who, "alpha_dev", alpha_dev)          # a_hl8 and w_hl8: _split_k_parts
-    if alpha_dev is not None and (alpha_dev.dtype != torch.float32 or alpha_dev.numel() != 1):          # a view into a scale block
-        raise RuntimeError("%s: alpha_dev must be one torch.float32 element, got %s %s" % (who, alpha_dev.dtype, tuple(alpha_dev.shape)))
+    _one_f32(who, alpha_dev)
     part = _split_k_parts(who, a_hl8, w_hl8, nk)
     out = torch.empty(part.shape[1], part.shape[2], dtype=torch.float32, device=a_hl8.device)
     _call("hipie_splitk_finish", part.data_ptr(), part.shape[0], out.numel(), _ptr(alpha_dev), out.data_ptr())

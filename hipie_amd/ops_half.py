@@ -61,8 +61,7 @@ def gemm_split_k_half(a16, w16, nk, alpha_dev=None, want_parts=False):
     want_parts: the (nk, M, N) partial products instead (each has the bits of ops.gemm(..., split=False) on its slices)."""
     who = "gemm_split_k_half"
     _on_device(who, "a16 w16 alpha_dev", a16, w16, alpha_dev)
-    if alpha_dev is not None and (alpha_dev.dtype != torch.float32 or alpha_dev.numel() != 1):          # a view into a scale block
-        raise RuntimeError("%s: alpha_dev must be one torch.float32 element, got %s %s" % (who, alpha_dev.dtype, tuple(alpha_dev.shape)))
+    ops._one_f32(who, alpha_dev)
     _layout(who, "a16", a16, torch.float16, ndim=2, align16=True)
     _layout(who, "w16", w16, torch.float16, ndim=2, align16=True)
     M, K = a16.shape

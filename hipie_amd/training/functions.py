@@ -5,7 +5,7 @@ import collections
 import numpy as np
 import torch
 
-from .. import ops
+from .. import ops, ops_half
 
 
 class MaskEinsumFunction(torch.autograd.Function):
@@ -106,20 +106,13 @@ def deform_sample(value, shapes, ref, offsets, logits):
     return DeformSampleFunction.apply(value, ss, ls, ref, offsets, logits)
 
 
-def _weight_grad(g2, x2):
-    """dW = dy^T . x  (N x K, the contraction over the M token rows) on the split GEMM.  N x K is 25-100 tiles of 256 x 256 for the ViT-H
-    linears -- a fraction of the 256 CUs -- so the M rows are cut into nk chunks, one problem each in ONE hipie_gemm_batched launch, and
-    the partial products are summed (the 64 x 128-tile kernel the single problem fell to ran at 160 TFLOP/s: 0.51 ms per linear)."""
-    M, N = g2.shape
-    nk = _weight_grad_chunks(M, N, x2.shape[1])
-    gt, xt = ops.to_hl8_t(g2, 32), ops.to_hl8_t(x2, 32)                                           # (N | K, 2 Mp) fp16 pairs, one pass each
-    if nk == 1:
-        return ops.gemm(gt, xt, None, split=True, out_fmt=ops.F32, tag="train_dw")
-    return ops.gemm_split_k(gt, xt, nk)
-
-
+# ---- the training linears: TWO graphs, y = x . W^T + b and linear -> act -> linear, each written once (_linear_forward / _linear_backward,
+# _mlp_forward / _mlp_backward) over THREE operand policies, SPLIT, SCALED and HALF.  A policy answers only what differs between the formats:
+# which shapes it takes, how an operand is made (of x, of a weight, of the activation, of an output gradient) and which GEMM entry
+# consumes it.  The graph -- which gradient is needed when, what is recomputed, what is freed where -- is not the policy's business, and
+# the bodies do not ask which policy they run.  The six node classes below hand a policy to a body; they are the public names.
 def _weight_grad_chunks(M, N, K, group=32):
-    """the chunks _weight_grad cuts the M rows into: doubled while the N x K tiles leave CUs idle and the 32-row groups divide evenly
+    """the chunks a weight gradient cuts the M rows into: doubled while the N x K tiles leave CUs idle and the 32-row groups divide evenly
     (group: the rows of one k tile -- 32 for the split operands, 64 for plain fp16)"""
     Mp = -(-M // group) * group
     tiles = -(-N // 256) * -(-K // 256)
@@ -129,128 +122,6 @@ def _weight_grad_chunks(M, N, K, group=32):
     return nk
 
 
-class SplitLinearFunction(torch.autograd.Function):
-    """F.linear(x, weight, bias) with forward AND backward on hipie_gemm's split-fp16 operands (three MFMA products, fp32 accumulation:
-    fp32-class results at ~2.7x the rate of the fp32 matrix pipe): the linears of the training step that carry its flops (ViT qkv / proj /
-    fc1 / fc2, the encoder FFNs).
-        y  = x . W^T + b            hipie_gemm(A = x fp32 rows, W as HL8)
-        dx = dy . W                 hipie_gemm(A = dy fp32 rows, W^T as HL8)
-        dW = dy^T . x               split operands dy^T and x^T, the contraction over the M rows (padded to 32) cut into chunks that run as
-                                    one hipie_gemm_batched launch (_weight_grad)
-        db = sum_m dy
-    The two transposed operands cost one pass each; the HL8 copies of W and W^T are cached on `owner` (ops.split_weight; the training net
-    passes the weight tensor itself, so they die with it)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, owner, key):
-        w_hl8, _, _ = ops.split_weight(owner, key, [weight], lambda: weight)
-        x2 = x.reshape(-1, x.shape[-1]).contiguous()
-        ctx.save_for_backward(x2, weight)
-        ctx.owner, ctx.key, ctx.lead, ctx.has_bias = owner, key, x.shape[:-1], bias is not None
-        y = ops.gemm(x2, w_hl8, None if bias is None else bias.detach().float().contiguous(), split=True, out_fmt=ops.F32, tag="train_fwd")
-        return y.view(*x.shape[:-1], weight.shape[0])
-
-    @staticmethod
-    def backward(ctx, gy):
-        x2, weight = ctx.saved_tensors
-        N, K = weight.shape
-        g2 = gy.reshape(-1, N).float()
-        if g2.stride(-1) != 1:
-            g2 = g2.contiguous()
-        M = g2.shape[0]
-        gx = gw = gb = None
-        if ctx.needs_input_grad[0]:
-            wt_hl8, _, _ = ops.split_weight(ctx.owner, ctx.key + ".T", [weight], lambda: weight.t().contiguous())
-            gx = ops.gemm(g2, wt_hl8, None, split=True, out_fmt=ops.F32, tag="train_dx").view(*ctx.lead, K)
-        if ctx.needs_input_grad[1]:
-            gw = _weight_grad(g2, x2)
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            gb = g2.sum(0)
-        return gx, gw, gb, None, None
-
-
-def split_linear(x, weight, bias, owner, key):
-    """F.linear on the split GEMM with a backward (SplitLinearFunction); shapes it does not cover fall through to the library"""
-    K, N = weight.shape[1], weight.shape[0]
-    if x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and K % 32 == 0 and N % 32 == 0 and x.numel() // K >= 256:
-        return SplitLinearFunction.apply(x, weight, bias, owner, key)
-    return torch.nn.functional.linear(x, weight, bias)
-
-
-class MlpFunction(torch.autograd.Function):
-    """linear -> activation -> linear as ONE node of the graph: timm's Mlp of a ViT block (fc1 -> GELU -> fc2, backbone/vit.py:193-197) and the
-    FFN of an encoder layer (linear1 -> ReLU -> linear2, deformable_transformer_dino.py:384-394).
-        u = x . W1^T + b1     a = act(u)     y = a . W2^T + b2          the split GEMM of SplitLinearFunction, ops.act_forward between
-    Saved: x, u and the two weights.  a is NOT saved -- it is a pointwise function of u, and the backward's one pass over u and da
-    (ops.act_backward) writes it again, with the forward's bits, next to du = da * act'(u) (in place in da) and db1 = sum_m du:
-        da = dy . W2                    dW2 = dy^T . a      db2 = sum_m dy      (a dies here)
-        du, a, db1 = act_backward       dW1 = du^T . x      dx  = du . W1
-    act = ops.ACT_GELU | ops.ACT_RELU.  The HL8 copies of the weights are the ones SplitLinearFunction caches (on the weight, key "w")."""
-
-    @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, act):
-        w1_hl8, _, _ = ops.split_weight(w1, "w", [w1], lambda: w1)
-        w2_hl8, _, _ = ops.split_weight(w2, "w", [w2], lambda: w2)
-        x2 = x.reshape(-1, x.shape[-1]).contiguous()
-        u = ops.gemm(x2, w1_hl8, None if b1 is None else b1.detach().float().contiguous(), split=True, out_fmt=ops.F32, tag="train_fwd")
-        y = ops.gemm(ops.act_forward(u, act), w2_hl8, None if b2 is None else b2.detach().float().contiguous(), split=True, out_fmt=ops.F32,
-                     tag="train_fwd")
-        ctx.save_for_backward(x2, u, w1, w2)
-        ctx.act, ctx.lead, ctx.has_b1, ctx.has_b2 = int(act), x.shape[:-1], b1 is not None, b2 is not None
-        return y.view(*x.shape[:-1], w2.shape[0])
-
-    @staticmethod
-    def backward(ctx, gy):
-        x2, u, w1, w2 = ctx.saved_tensors
-        need_x, need_w1, need_b1, need_w2, need_b2 = ctx.needs_input_grad[:5]
-        need_b1, need_b2 = need_b1 and ctx.has_b1, need_b2 and ctx.has_b2
-        g2 = gy.reshape(-1, w2.shape[0]).float()
-        if g2.stride(-1) != 1:
-            g2 = g2.contiguous()
-        gx = gw1 = gb1 = gw2 = gb2 = du = a = None
-        if need_x or need_w1 or need_b1:
-            w2t_hl8, _, _ = ops.split_weight(w2, "w.T", [w2], lambda: w2.t().contiguous())
-            da = ops.gemm(g2, w2t_hl8, None, split=True, out_fmt=ops.F32, tag="train_dx")
-            du, a, gb1 = ops.act_backward(u, da, ctx.act, want_a=need_w2, want_bias_grad=need_b1, out=da)
-            del da
-        elif need_w2:
-            a = ops.act_forward(u, ctx.act)
-        if need_w2:
-            gw2 = _weight_grad(g2, a)
-        a = None
-        if need_b2:
-            gb2 = g2.sum(0)
-        if need_w1:
-            gw1 = _weight_grad(du, x2)
-        if need_x:
-            w1t_hl8, _, _ = ops.split_weight(w1, "w.T", [w1], lambda: w1.t().contiguous())
-            gx = ops.gemm(du, w1t_hl8, None, split=True, out_fmt=ops.F32, tag="train_dx").view(*ctx.lead, w1.shape[1])
-        return gx, gw1, gb1, gw2, gb2, None
-
-
-def _split_linear_ok(x, weight, rows):
-    """split_linear's own conditions"""
-    K, N = weight.shape[1], weight.shape[0]
-    return x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and K % 32 == 0 and N % 32 == 0 and rows >= 256
-
-
-def split_mlp(x, w1, b1, w2, b2, act):
-    """linear(act(linear(x, w1, b1)), w2, b2) as one node (MlpFunction) when BOTH linears are ones split_linear takes; any other shape runs
-    the three-node composition (split_linear -> library activation -> split_linear), so nothing is refused"""
-    rows = x.numel() // w1.shape[1] if w1.shape[1] else 0
-    if _split_linear_ok(x, w1, rows) and _split_linear_ok(x, w2, rows) and act in (ops.ACT_GELU, ops.ACT_RELU):
-        return MlpFunction.apply(x, w1, b1, w2, b2, act)
-    f = {ops.ACT_GELU: torch.nn.functional.gelu, ops.ACT_RELU: torch.nn.functional.relu}[act]
-    return split_linear(f(split_linear(x, w1, b1, w1, "w")), w2, b2, w2, "w")
-
-
-# ---- the same two nodes with SCALED gradient operands (csrc/grad_pack.hip; the opt-in group "scaled_grads" of training/net.py).
-# The split hi = fp16(dy), lo = fp16(dy - hi) is 2^-22 accurate only while dy is a normal fp16 number: a gradient of 1e-6 per element
-# reaches the products above with ~1.6 % error, one of 1e-9 as zero, one above 65504 saturated.  Here every output gradient that enters a
-# split GEMM is first multiplied by a power of two chosen on the device from its largest magnitude (ops.grad_scale: amax lands in
-# [2^14, 2^15)), in the ONE pass that also writes both of its operand forms and the bias gradient (ops.grad_pack: three readers of dy
-# become one), and the products are multiplied back by the kernel that writes them (ops.gemm_scaled, ops.gemm_split_k_scaled).  All
-# factors are exact powers of two and every sum has a fixed order: the results for 2^e dy are 2^e times the results for dy, bit for bit.
 def _grad_rows(gy, N):
     """the output gradient as the (M, N) fp32 rows ops.grad_scale / ops.grad_pack take: a view where the strides and the alignment allow"""
     g2 = gy.reshape(-1, N).float()
@@ -259,14 +130,243 @@ def _grad_rows(gy, N):
     return g2.clone() if g2.data_ptr() % 16 else g2
 
 
-def _scaled_weight_grad(gt, x2, inv):
-    """_weight_grad for a gradient that arrives PACKED: gt = (s dy)^T as HL8 (N, 2 Mp) from ops.grad_pack, inv = the device scalar 1 / s.
-    The same chunks; the partial products are added in chunk order and multiplied by inv in one pass (or, one chunk, in the GEMM's store)."""
-    nk = _weight_grad_chunks(x2.shape[0], gt.shape[0], x2.shape[1])
-    xt = ops.to_hl8_t(x2, 32)
+def _scaled_operands(pack, gy, N, need_rows, need_t, need_b):
+    """an output gradient for the policies that scale it: {s, 1/s} = grad_scale(dy), then ONE pass of `pack` (ops.grad_pack |
+    ops_half.half_pack) over dy -> ((s dy) rows, (s dy)^T, the column sums of the unscaled dy, the device scalar 1/s); a form that is not
+    needed is not written"""
+    g2 = _grad_rows(gy, N)
+    scale = ops.grad_scale(g2)
+    ga, gt, gb = pack(g2, scale, want_rows=need_rows, want_t=need_t, want_bias=need_b)
+    return ga, gt, gb, scale[1:]
+
+
+def _product_t(at, bt, rows, inv):
+    """inv * at . bt^T for two TRANSPOSED HL8 operands (Na, 2 Mp), (Nb, 2 Mp) whose contraction runs over `rows` rows: cut into the chunks of
+    _weight_grad_chunks, one problem each in ONE hipie_gemm_batched launch, the partial products added in chunk order and multiplied by the
+    device scalar inv in one pass (or, one chunk, in the GEMM's store).  The weight gradient of every scaled split node."""
+    nk = _weight_grad_chunks(rows, at.shape[0], bt.shape[0])
     if nk == 1:
-        return ops.gemm_scaled(gt, xt, inv, split=True, out_fmt=ops.F32, tag="train_dw")
-    return ops.gemm_split_k_scaled(gt, xt, nk, inv)
+        return ops.gemm_scaled(at, bt, inv, split=True, out_fmt=ops.F32, tag="train_dw")
+    return ops.gemm_split_k_scaled(at, bt, nk, inv)
+
+
+def _split_linear_ok(x, weight, rows):
+    """the linears the split nodes take"""
+    K, N = weight.shape[1], weight.shape[0]
+    return x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and K % 32 == 0 and N % 32 == 0 and rows >= 256
+
+
+def half_linear_ok(x, weight, rows):
+    """the linears the half nodes take: fp32 device tensors, at least 256 rows, K % 64 == 0 (the contraction of y and the output rows of
+    dW) and N % 64 == 0 (the contraction of dx): the F16 k tile is 64 elements"""
+    K, N = weight.shape[1], weight.shape[0]
+    return bool(x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and K % 64 == 0 and N % 64 == 0 and rows >= 256)
+
+
+class _SplitOperands:
+    """SPLIT: split-fp16 (HL8) weights against fp32 rows, three MFMA products per GEMM; the output gradient enters as it arrives.
+    dW = dy^T . x (N x K, the contraction over the M token rows): N x K is 25-100 tiles of 256 x 256 for the ViT-H linears -- a fraction of
+    the 256 CUs -- so the M rows (padded to 32) are cut into chunks, one problem each in ONE hipie_gemm_batched launch, and the partial
+    products are summed (the 64 x 128-tile kernel the single problem fell to ran at 160 TFLOP/s: 0.51 ms per linear)."""
+    split = True                                  # the operand code of the forward products
+    ok = staticmethod(_split_linear_ok)
+
+    def rows(self, x, keep):
+        """(the forward operand of x, what is saved of it): the fp32 rows, always saved"""
+        x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        return x2, x2
+
+    def weight(self, owner, key, w, transposed=False):
+        """the HL8 copy of W, or of W^T under key + ".T", cached on `owner` (ops.split_weight; the training net passes the weight tensor
+        itself, so the copies die with it)"""
+        if transposed:
+            return ops.split_weight(owner, key + ".T", [w], lambda: w.t().contiguous())[0]
+        return ops.split_weight(owner, key, [w], lambda: w)[0]
+
+    def act(self, u, act):
+        return ops.act_forward(u, act)
+
+    def grads(self, gy, N, need_rows, need_t, need_b):
+        """(dy fp32 rows, the same rows for dw, db = sum_m dy, no scale).  dy^T is NOT made here: dw transposes the rows itself, next to
+        the product that reads them, as the node always did (made here, its 126 MB at qkv would wait through the dx product)"""
+        g2 = gy.reshape(-1, N).float()
+        if g2.stride(-1) != 1:
+            g2 = g2.contiguous()
+        return g2, g2, g2.sum(0) if need_b else None, None
+
+    def dx(self, ga, wt, inv):
+        return ops.gemm(ga, wt, None, split=True, out_fmt=ops.F32, tag="train_dx")
+
+    def transposed(self, x):
+        """the operand dw takes of the rows (M, K) a weight gradient contracts with: x^T as HL8 (K, 2 Mp), one pass"""
+        return ops.to_hl8_t(x, 32)
+
+    def dw(self, g2, xt, rows, inv):
+        gt = ops.to_hl8_t(g2, 32)                                                             # (N, 2 Mp) fp16 pairs, one pass
+        nk = _weight_grad_chunks(rows, gt.shape[0], xt.shape[0])
+        if nk == 1:
+            return ops.gemm(gt, xt, None, split=True, out_fmt=ops.F32, tag="train_dw")
+        return ops.gemm_split_k(gt, xt, nk)
+
+
+# SCALED gradient operands (csrc/grad_pack.hip; the opt-in group "scaled_grads" of training/net.py).  The split hi = fp16(dy),
+# lo = fp16(dy - hi) is 2^-22 accurate only while dy is a normal fp16 number: a gradient of 1e-6 per element reaches the products above with
+# ~1.6 % error, one of 1e-9 as zero, one above 65504 saturated.  Here every output gradient that enters a split GEMM is first multiplied by
+# a power of two chosen on the device from its largest magnitude (ops.grad_scale: amax lands in [2^14, 2^15)), in the ONE pass that also
+# writes both of its operand forms and the bias gradient (ops.grad_pack: three readers of dy become one), and the products are multiplied
+# back by the kernel that writes them (ops.gemm_scaled, ops.gemm_split_k_scaled).  All factors are exact powers of two and every sum has a
+# fixed order: the results for 2^e dy are 2^e times the results for dy, bit for bit.
+class _ScaledOperands(_SplitOperands):
+    """SCALED: SPLIT's forward; the output gradient arrives PACKED -- (s dy) rows and (s dy)^T as HL8, 1/s applied where a product is stored"""
+
+    def grads(self, gy, N, need_rows, need_t, need_b):
+        return _scaled_operands(ops.grad_pack, gy, N, need_rows, need_t, need_b)
+
+    def dx(self, ga, wt, inv):
+        return ops.gemm_scaled(ga, wt, inv, split=True, out_fmt=ops.F32, tag="train_dx")
+
+    dw = staticmethod(_product_t)
+
+
+# HALF precision (csrc/half_pack.hip, ops_half.py; the opt-in policy net.half_policy): ONE fp16 MFMA product per GEMM instead of three, fp32
+# master weights, fp32 accumulation and output.  A precision policy, not a bit-compatible group: 2^-11 per operand.  Contract (DESIGN.md
+# section 9): x16 = fp16(x), W16 = fp16(W), round to nearest even, saturated at +-65504, no scale;  y = x16 . W16^T + b;
+# {s, 1/s} = grad_scale(dy), g16 = fp16(s dy);  dx = (1/s) g16 . W16;  dW = (1/s) g16^T . x16^T over the token rows padded to 64, in the
+# chunks of _weight_grad_chunks(group=64), added in chunk order;  db = the column sums of the unscaled dy.  All scale factors are powers of
+# two, every sum has a fixed order: the results for 2^e dy are 2^e times the results for dy, bit for bit.
+class _HalfOperands:
+    """HALF: single fp16 operands everywhere, the output gradient scaled as SCALED's is"""
+    split = False
+    ok = staticmethod(half_linear_ok)
+
+    def rows(self, x, keep):
+        """x16 = half_pack(x): fp16 rows, half the bytes of x; saved only when the weight needs a gradient (nothing else reads them)"""
+        x16 = ops_half.half_pack(_grad_rows(x, x.shape[-1]), None, want_rows=True, want_t=False)[0]
+        return x16, x16 if keep else None
+
+    def weight(self, owner, key, w, transposed=False):
+        """W16, or W16^T under key + ".T", cached on `owner` (ops_half.half_weight)"""
+        if transposed:
+            return ops_half.half_weight(owner, key + ".T", [w], lambda: w.t())
+        return ops_half.half_weight(owner, key, [w], lambda: w)
+
+    def act(self, u, act):
+        return ops_half.act_half(u, act)
+
+    def grads(self, gy, N, need_rows, need_t, need_b):
+        return _scaled_operands(ops_half.half_pack, gy, N, need_rows, need_t, need_b)
+
+    def dx(self, ga, wt, inv):
+        return ops.gemm_scaled(ga, wt, inv, split=False, out_fmt=ops.F32, tag="train_dx")
+
+    def transposed(self, x):
+        """x16^T (K, Mp) of the rows (M, K), fp16 (the saved x16) or fp32 (the recomputed activation), in one pass"""
+        return ops_half.half_pack(x, None, want_rows=False, want_t=True)[1]
+
+    def dw(self, gt, xt, rows, inv):
+        """dW = (1/s) g16^T . x16^T: gt = (s dy)^T as fp16 (N, Mp), inv the device scalar 1 / s; one chunk is the product itself"""
+        return ops_half.gemm_split_k_half(gt, xt, _weight_grad_chunks(rows, gt.shape[0], xt.shape[0], 64), inv)
+
+
+SPLIT, SCALED, HALF = _SplitOperands(), _ScaledOperands(), _HalfOperands()
+
+
+def _forward_product(policy, a, w, bias):
+    return ops.gemm(a, w, None if bias is None else bias.detach().float().contiguous(), split=policy.split, out_fmt=ops.F32, tag="train_fwd")
+
+
+def _linear_forward(policy, ctx, x, weight, bias, owner, key):
+    """y = x . W^T + b"""
+    w_op = policy.weight(owner, key, weight)
+    x_op, x_saved = policy.rows(x, ctx.needs_input_grad[1])
+    ctx.save_for_backward(x_saved, weight)
+    ctx.owner, ctx.key, ctx.lead, ctx.has_bias = owner, key, x.shape[:-1], bias is not None
+    return _forward_product(policy, x_op, w_op, bias).view(*x.shape[:-1], weight.shape[0])
+
+
+def _linear_backward(policy, ctx, gy):
+    """dx = dy . W      dW = dy^T . x      db = sum_m dy;  a frozen input skips its operand form and its product"""
+    x_saved, weight = ctx.saved_tensors
+    N, K = weight.shape
+    need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    need_b = ctx.has_bias and ctx.needs_input_grad[2]
+    gx = gw = None
+    if not (need_x or need_w or need_b):
+        return None, None, None, None, None
+    ga, gt, gb, inv = policy.grads(gy, N, need_x, need_w, need_b)
+    if need_x:
+        gx = policy.dx(ga, policy.weight(ctx.owner, ctx.key, weight, transposed=True), inv).view(*ctx.lead, K)
+    if need_w:
+        gw = policy.dw(gt, policy.transposed(x_saved), x_saved.shape[0], inv)
+    return gx, gw, gb, None, None
+
+
+def _mlp_forward(policy, ctx, x, w1, b1, w2, b2, act):
+    """u = x . W1^T + b1     a = act(u)     y = a . W2^T + b2.  Saved: x's operand, u (fp32) and the two weights.  a is NOT saved -- it is a
+    pointwise function of u, and the backward's one pass over u and da writes it again, with the forward's bits."""
+    w1_op, w2_op = policy.weight(w1, "w", w1), policy.weight(w2, "w", w2)
+    x_op, x_saved = policy.rows(x, ctx.needs_input_grad[1])
+    u = _forward_product(policy, x_op, w1_op, b1)
+    y = _forward_product(policy, policy.act(u, act), w2_op, b2)
+    ctx.save_for_backward(x_saved, u, w1, w2)
+    ctx.act, ctx.lead, ctx.has_b1, ctx.has_b2 = int(act), x.shape[:-1], b1 is not None, b2 is not None
+    return y.view(*x.shape[:-1], w2.shape[0])
+
+
+def _mlp_backward(policy, ctx, gy):
+    """da = dy . W2                    dW2 = dy^T . a      db2 = sum_m dy      (a dies here)
+    du, a, db1 = act_backward       dW1 = du^T . x      dx  = du . W1
+    ops.act_backward writes du = da * act'(u) in place in da, a with the forward's bits only when W2 needs it, and db1 = sum_m du.  dy and
+    du each get operands (and, where the policy scales, a scale) of their own; du is unscaled -- it is a product, so a power of two in da
+    passes through it exactly.  With x, W1 and b1 frozen there is no da: a is recomputed alone."""
+    x_saved, u, w1, w2 = ctx.saved_tensors
+    need_x, need_w1, need_b1, need_w2, need_b2 = ctx.needs_input_grad[:5]
+    need_b1, need_b2 = need_b1 and ctx.has_b1, need_b2 and ctx.has_b2
+    gx = gw1 = gb1 = gw2 = du = a = at = None
+    if not (need_x or need_w1 or need_b1 or need_w2 or need_b2):
+        return None, None, None, None, None, None
+    need_da = need_x or need_w1 or need_b1
+    ga, gt, gb2, inv = policy.grads(gy, w2.shape[0], need_da, need_w2, need_b2)
+    if need_da:
+        da = policy.dx(ga, policy.weight(w2, "w", w2, transposed=True), inv)
+        ga = None
+        du, a, gb1 = ops.act_backward(u, da, ctx.act, want_a=need_w2, want_bias_grad=need_b1, out=da)
+        del da
+    elif need_w2:
+        a = policy.act(u, ctx.act)
+    if need_w2:
+        at = policy.transposed(a)
+        a = None                                  # the product below runs without the fp32 activation in memory
+        gw2 = policy.dw(gt, at, u.shape[0], inv)
+    a = at = gt = None
+    if need_x or need_w1:
+        ua, ut, _, inv = policy.grads(du, w1.shape[0], need_x, need_w1, False)
+        del du
+        if need_w1:
+            gw1 = policy.dw(ut, policy.transposed(x_saved), u.shape[0], inv)
+        if need_x:
+            gx = policy.dx(ua, policy.weight(w1, "w", w1, transposed=True), inv).view(*ctx.lead, w1.shape[1])
+    return gx, gw1, gb1, gw2, gb2, None
+
+
+class SplitLinearFunction(torch.autograd.Function):
+    """F.linear(x, weight, bias) with forward AND backward on hipie_gemm's split-fp16 operands (three MFMA products, fp32 accumulation:
+    fp32-class results at ~2.7x the rate of the fp32 matrix pipe): the linears of the training step that carry its flops (ViT qkv / proj /
+    fc1 / fc2, the encoder FFNs).
+        y  = x . W^T + b            hipie_gemm(A = x fp32 rows, W as HL8)
+        dx = dy . W                 hipie_gemm(A = dy fp32 rows, W^T as HL8)
+        dW = dy^T . x               split operands dy^T and x^T, the contraction over the M rows (padded to 32) cut into chunks that run as
+                                    one hipie_gemm_batched launch (SPLIT.dw)
+        db = sum_m dy
+    The two transposed operands cost one pass each; the HL8 copies of W and W^T are cached on `owner`."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, owner, key):
+        return _linear_forward(SPLIT, ctx, x, weight, bias, owner, key)
+
+    @staticmethod
+    def backward(ctx, gy):
+        return _linear_backward(SPLIT, ctx, gy)
 
 
 class ScaledSplitLinearFunction(SplitLinearFunction):
@@ -276,23 +376,132 @@ class ScaledSplitLinearFunction(SplitLinearFunction):
 
     @staticmethod
     def backward(ctx, gy):
-        x2, weight = ctx.saved_tensors
-        N, K = weight.shape
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        need_b = ctx.has_bias and ctx.needs_input_grad[2]
-        gx = gw = gb = None
-        if not (need_x or need_w or need_b):
-            return None, None, None, None, None
-        g2 = _grad_rows(gy, N)
-        scale = ops.grad_scale(g2)
-        ga, gt, gb = ops.grad_pack(g2, scale, want_rows=need_x, want_t=need_w, want_bias=need_b)
-        inv = scale[1:]
-        if need_x:
-            wt_hl8, _, _ = ops.split_weight(ctx.owner, ctx.key + ".T", [weight], lambda: weight.t().contiguous())
-            gx = ops.gemm_scaled(ga, wt_hl8, inv, split=True, out_fmt=ops.F32, tag="train_dx").view(*ctx.lead, K)
-        if need_w:
-            gw = _scaled_weight_grad(gt, x2, inv)
-        return gx, gw, gb, None, None
+        return _linear_backward(SCALED, ctx, gy)
+
+
+HALF_NODE_CALLS = collections.Counter()          # forward calls of the two half nodes by name (tests: the node ran, not the fall-through)
+
+
+class HalfLinearFunction(torch.autograd.Function):
+    """F.linear(x, weight, bias) with forward AND backward on single fp16 operands (hipie_gemm with HIPIE_F16):
+        x16 = half_pack(x)              y  = x16 . W16^T + b                               W16 / W16^T cached on `owner` (ops_half.half_weight)
+        {s, 1/s} = grad_scale(dy)       (s dy) rows, (s dy)^T, db = half_pack(dy)          one pass over dy; a frozen input skips its form
+        dx = (1/s) (s dy) . W16         dW = (1/s) (s dy)^T . x16^T                        the factor is applied where the product is stored
+    Saved: x16 (fp16 rows, half the bytes of x) and the weight."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, owner, key):
+        HALF_NODE_CALLS["linear"] += 1
+        return _linear_forward(HALF, ctx, x, weight, bias, owner, key)
+
+    @staticmethod
+    def backward(ctx, gy):
+        return _linear_backward(HALF, ctx, gy)
+
+
+class MlpFunction(torch.autograd.Function):
+    """linear -> activation -> linear as ONE node of the graph: timm's Mlp of a ViT block (fc1 -> GELU -> fc2, backbone/vit.py:193-197) and the
+    FFN of an encoder layer (linear1 -> ReLU -> linear2, deformable_transformer_dino.py:384-394): _mlp_forward / _mlp_backward on the split
+    GEMM of SplitLinearFunction, ops.act_forward between.  act = ops.ACT_GELU | ops.ACT_RELU.  The HL8 copies of the weights are the ones
+    SplitLinearFunction caches (on the weight, key "w")."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, act):
+        return _mlp_forward(SPLIT, ctx, x, w1, b1, w2, b2, act)
+
+    @staticmethod
+    def backward(ctx, gy):
+        return _mlp_backward(SPLIT, ctx, gy)
+
+
+class ScaledMlpFunction(MlpFunction):
+    """MlpFunction (its forward, unchanged) with a backward on scaled operands; dy and du each get a scale of their own:
+        {sy, 1/sy} = grad_scale(dy)     (sy dy) rows, (sy dy)^T, db2 = grad_pack(dy)
+        da = (1/sy) (sy dy) . W2        dW2 = (1/sy) (sy dy)^T . a
+        du, a, db1 = act_backward       (unscaled)
+        {su, 1/su} = grad_scale(du)     (su du) rows, (su du)^T = grad_pack(du)
+        dW1 = (1/su) (su du)^T . x      dx = (1/su) (su du) . W1"""
+
+    @staticmethod
+    def backward(ctx, gy):
+        return _mlp_backward(SCALED, ctx, gy)
+
+
+class HalfMlpFunction(torch.autograd.Function):
+    """linear -> activation -> linear as ONE node in half precision (MlpFunction's graph):
+        x16 = half_pack(x)      u = x16 . W1_16^T + b1 (fp32)      a16 = act_half(u)      y = a16 . W2_16^T + b2
+    Saved: x16, u (fp32: act_backward needs it) and the two weights.  dy and du each get a scale of their own:
+        {sy, 1/sy} = grad_scale(dy)     (sy dy) rows, (sy dy)^T, db2 = half_pack(dy)
+        da = (1/sy) (sy dy) . W2_16     du, a, db1 = act_backward(u, da)     dW2 = (1/sy) (sy dy)^T . fp16(a)^T   (a: recomputed, fp32, dies here)
+        {su, 1/su} = grad_scale(du)     (su du) rows, (su du)^T = half_pack(du)
+        dW1 = (1/su) (su du)^T . x16^T  dx = (1/su) (su du) . W1_16"""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, act):
+        HALF_NODE_CALLS["mlp"] += 1
+        return _mlp_forward(HALF, ctx, x, w1, b1, w2, b2, act)
+
+    @staticmethod
+    def backward(ctx, gy):
+        return _mlp_backward(HALF, ctx, gy)
+
+
+def _library_linear(x, weight, bias, owner, key):
+    return torch.nn.functional.linear(x, weight, bias)
+
+
+def _linear_or(policy, node, otherwise, x, weight, bias, owner, key):
+    """the front door of a linear node: the node where the policy takes the shape, `otherwise` where it does not"""
+    if policy.ok(x, weight, x.numel() // weight.shape[1] if weight.shape[1] else 0):
+        return node.apply(x, weight, bias, owner, key)
+    return otherwise(x, weight, bias, owner, key)
+
+
+def _mlp_or(policy, node, otherwise, x, w1, b1, w2, b2, act):
+    """the front door of an MLP node: the node when the policy takes BOTH linears, `otherwise` for any other shape, so nothing is refused"""
+    rows = x.numel() // w1.shape[1] if w1.shape[1] else 0
+    if policy.ok(x, w1, rows) and policy.ok(x, w2, rows) and act in (ops.ACT_GELU, ops.ACT_RELU):
+        return node.apply(x, w1, b1, w2, b2, act)
+    return otherwise(x, w1, b1, w2, b2, act)
+
+
+def _three_nodes(linear, x, w1, b1, w2, b2, act):
+    """the composition an MLP node replaces: linear -> library activation -> linear"""
+    f = {ops.ACT_GELU: torch.nn.functional.gelu, ops.ACT_RELU: torch.nn.functional.relu}[act]
+    return linear(f(linear(x, w1, b1, w1, "w")), w2, b2, w2, "w")
+
+
+def split_linear(x, weight, bias, owner, key):
+    """F.linear on the split GEMM with a backward (SplitLinearFunction); shapes it does not cover fall through to the library"""
+    return _linear_or(SPLIT, SplitLinearFunction, _library_linear, x, weight, bias, owner, key)
+
+
+def split_linear_scaled(x, weight, bias, owner, key):
+    """split_linear with the scaled-gradient backward (ScaledSplitLinearFunction); the same shapes, the same fall-through to the library"""
+    return _linear_or(SCALED, ScaledSplitLinearFunction, _library_linear, x, weight, bias, owner, key)
+
+
+def half_linear(x, weight, bias, owner, key):
+    """F.linear in half precision with a backward (HalfLinearFunction); a shape outside half_linear_ok runs the split node (split_linear)"""
+    return _linear_or(HALF, HalfLinearFunction, split_linear, x, weight, bias, owner, key)
+
+
+def split_mlp(x, w1, b1, w2, b2, act):
+    """linear(act(linear(x, w1, b1)), w2, b2) as one node (MlpFunction) when BOTH linears are ones split_linear takes; any other shape runs
+    the three-node composition (split_linear -> library activation -> split_linear)"""
+    return _mlp_or(SPLIT, MlpFunction, lambda *a: _three_nodes(split_linear, *a), x, w1, b1, w2, b2, act)
+
+
+def split_mlp_scaled(x, w1, b1, w2, b2, act):
+    """split_mlp with the scaled-gradient backward (ScaledMlpFunction) under the same conditions; any other shape runs the three-node
+    composition over split_linear_scaled"""
+    return _mlp_or(SCALED, ScaledMlpFunction, lambda *a: _three_nodes(split_linear_scaled, *a), x, w1, b1, w2, b2, act)
+
+
+def half_mlp(x, w1, b1, w2, b2, act):
+    """linear(act(linear(x, w1, b1)), w2, b2) as one node in half precision (HalfMlpFunction) when BOTH linears are ones half_linear takes;
+    any other shape runs the split node (split_mlp)"""
+    return _mlp_or(HALF, HalfMlpFunction, split_mlp, x, w1, b1, w2, b2, act)
 
 
 class ScaledMaskEinsumFunction(MaskEinsumFunction):
@@ -317,209 +526,6 @@ class ScaledMaskEinsumFunction(MaskEinsumFunction):
 
 def mask_einsum_scaled(mask_embed, mask_features, row_bias=None):
     return ScaledMaskEinsumFunction.apply(mask_embed, mask_features, row_bias)
-
-
-def split_linear_scaled(x, weight, bias, owner, key):
-    """split_linear with the scaled-gradient backward (ScaledSplitLinearFunction); the same shapes, the same fall-through to the library"""
-    if _split_linear_ok(x, weight, x.numel() // weight.shape[1] if weight.shape[1] else 0):
-        return ScaledSplitLinearFunction.apply(x, weight, bias, owner, key)
-    return torch.nn.functional.linear(x, weight, bias)
-
-
-class ScaledMlpFunction(MlpFunction):
-    """MlpFunction (its forward, unchanged) with a backward on scaled operands; dy and du each get a scale of their own:
-        {sy, 1/sy} = grad_scale(dy)     (sy dy) rows, (sy dy)^T, db2 = grad_pack(dy)
-        da = (1/sy) (sy dy) . W2        dW2 = (1/sy) (sy dy)^T . a
-        du, a, db1 = act_backward       (unscaled: du = da * act'(u) is a product, so a power of two in da passes through it exactly)
-        {su, 1/su} = grad_scale(du)     (su du) rows, (su du)^T = grad_pack(du)
-        dW1 = (1/su) (su du)^T . x      dx = (1/su) (su du) . W1"""
-
-    @staticmethod
-    def backward(ctx, gy):
-        x2, u, w1, w2 = ctx.saved_tensors
-        need_x, need_w1, need_b1, need_w2, need_b2 = ctx.needs_input_grad[:5]
-        need_b1, need_b2 = need_b1 and ctx.has_b1, need_b2 and ctx.has_b2
-        gx = gw1 = gb1 = gw2 = gb2 = du = a = None
-        if not (need_x or need_w1 or need_b1 or need_w2 or need_b2):
-            return None, None, None, None, None, None
-        need_da = need_x or need_w1 or need_b1
-        g2 = _grad_rows(gy, w2.shape[0])
-        sy = ops.grad_scale(g2)
-        ga, gt, gb2 = ops.grad_pack(g2, sy, want_rows=need_da, want_t=need_w2, want_bias=need_b2)
-        del g2
-        if need_da:
-            w2t_hl8, _, _ = ops.split_weight(w2, "w.T", [w2], lambda: w2.t().contiguous())
-            da = ops.gemm_scaled(ga, w2t_hl8, sy[1:], split=True, out_fmt=ops.F32, tag="train_dx")
-            ga = None
-            du, a, gb1 = ops.act_backward(u, da, ctx.act, want_a=need_w2, want_bias_grad=need_b1, out=da)
-            del da
-        elif need_w2:
-            a = ops.act_forward(u, ctx.act)
-        if need_w2:
-            gw2 = _scaled_weight_grad(gt, a, sy[1:])
-        a = gt = None
-        if need_x or need_w1:
-            su = ops.grad_scale(du)
-            ua, ut, _ = ops.grad_pack(du, su, want_rows=need_x, want_t=need_w1)
-            del du
-            if need_w1:
-                gw1 = _scaled_weight_grad(ut, x2, su[1:])
-            if need_x:
-                w1t_hl8, _, _ = ops.split_weight(w1, "w.T", [w1], lambda: w1.t().contiguous())
-                gx = ops.gemm_scaled(ua, w1t_hl8, su[1:], split=True, out_fmt=ops.F32, tag="train_dx").view(*ctx.lead, w1.shape[1])
-        return gx, gw1, gb1, gw2, gb2, None
-
-
-def split_mlp_scaled(x, w1, b1, w2, b2, act):
-    """split_mlp with the scaled-gradient backward (ScaledMlpFunction) under the same conditions; any other shape runs the three-node
-    composition over split_linear_scaled, so nothing is refused"""
-    rows = x.numel() // w1.shape[1] if w1.shape[1] else 0
-    if _split_linear_ok(x, w1, rows) and _split_linear_ok(x, w2, rows) and act in (ops.ACT_GELU, ops.ACT_RELU):
-        return ScaledMlpFunction.apply(x, w1, b1, w2, b2, act)
-    f = {ops.ACT_GELU: torch.nn.functional.gelu, ops.ACT_RELU: torch.nn.functional.relu}[act]
-    return split_linear_scaled(f(split_linear_scaled(x, w1, b1, w1, "w")), w2, b2, w2, "w")
-
-
-# ---- the same two nodes in HALF precision (csrc/half_pack.hip, ops_half.py; the opt-in policy net.half_policy): ONE fp16 MFMA product per
-# GEMM instead of three, fp32 master weights, fp32 accumulation and output.  A precision policy, not a bit-compatible group: 2^-11 per
-# operand.  Contract (DESIGN.md section 9): x16 = fp16(x), W16 = fp16(W), round to nearest even, saturated at +-65504, no scale;
-# y = x16 . W16^T + b;  {s, 1/s} = grad_scale(dy), g16 = fp16(s dy);  dx = (1/s) g16 . W16;  dW = (1/s) g16^T . x16^T over the token rows
-# padded to 64, in the chunks of _weight_grad_chunks(group=64), added in chunk order;  db = the column sums of the unscaled dy.  All scale
-# factors are powers of two, every sum has a fixed order: the results for 2^e dy are 2^e times the results for dy, bit for bit.
-HALF_NODE_CALLS = collections.Counter()          # forward calls of the two nodes by name (tests: the node ran, not the fall-through)
-
-
-def _half_weight_grad(gt, x16, inv):
-    """dW = (1/s) g16^T . x16^T: gt = (s dy)^T as fp16 (N, Mp) from ops_half.half_pack, x16 the saved fp16 rows (M, K) -- transposed here in
-    one pass --, inv the device scalar 1 / s"""
-    from ..ops_half import gemm_split_k_half, half_pack
-    xt = half_pack(x16, None, want_rows=False, want_t=True)[1]
-    return gemm_split_k_half(gt, xt, _weight_grad_chunks(x16.shape[0], gt.shape[0], x16.shape[1], 64), inv)
-
-
-class HalfLinearFunction(torch.autograd.Function):
-    """F.linear(x, weight, bias) with forward AND backward on single fp16 operands (hipie_gemm with HIPIE_F16):
-        x16 = half_pack(x)              y  = x16 . W16^T + b                               W16 / W16^T cached on `owner` (ops_half.half_weight)
-        {s, 1/s} = grad_scale(dy)       (s dy) rows, (s dy)^T, db = half_pack(dy)          one pass over dy; a frozen input skips its form
-        dx = (1/s) (s dy) . W16         dW = (1/s) (s dy)^T . x16^T                        the factor is applied where the product is stored
-    Saved: x16 (fp16 rows, half the bytes of x) and the weight."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, owner, key):
-        from ..ops_half import half_pack, half_weight
-        HALF_NODE_CALLS["linear"] += 1
-        w16 = half_weight(owner, key, [weight], lambda: weight)
-        x16 = half_pack(_grad_rows(x, x.shape[-1]), None, want_rows=True, want_t=False)[0]
-        ctx.save_for_backward(x16 if ctx.needs_input_grad[1] else None, weight)
-        ctx.owner, ctx.key, ctx.lead, ctx.has_bias = owner, key, x.shape[:-1], bias is not None
-        y = ops.gemm(x16, w16, None if bias is None else bias.detach().float().contiguous(), split=False, out_fmt=ops.F32, tag="train_fwd")
-        return y.view(*x.shape[:-1], weight.shape[0])
-
-    @staticmethod
-    def backward(ctx, gy):
-        from ..ops_half import half_pack, half_weight
-        x16, weight = ctx.saved_tensors
-        N, K = weight.shape
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        need_b = ctx.has_bias and ctx.needs_input_grad[2]
-        gx = gw = gb = None
-        if not (need_x or need_w or need_b):
-            return None, None, None, None, None
-        g2 = _grad_rows(gy, N)
-        scale = ops.grad_scale(g2)
-        ga, gt, gb = half_pack(g2, scale, want_rows=need_x, want_t=need_w, want_bias=need_b)
-        inv = scale[1:]
-        if need_x:
-            wt16 = half_weight(ctx.owner, ctx.key + ".T", [weight], lambda: weight.t())
-            gx = ops.gemm_scaled(ga, wt16, inv, split=False, out_fmt=ops.F32, tag="train_dx").view(*ctx.lead, K)
-        if need_w:
-            gw = _half_weight_grad(gt, x16, inv)
-        return gx, gw, gb, None, None
-
-
-class HalfMlpFunction(torch.autograd.Function):
-    """linear -> activation -> linear as ONE node in half precision (MlpFunction's graph):
-        x16 = half_pack(x)      u = x16 . W1_16^T + b1 (fp32)      a16 = act_half(u)      y = a16 . W2_16^T + b2
-    Saved: x16, u (fp32: act_backward needs it) and the two weights.  dy and du each get a scale of their own:
-        {sy, 1/sy} = grad_scale(dy)     (sy dy) rows, (sy dy)^T, db2 = half_pack(dy)
-        da = (1/sy) (sy dy) . W2_16     du, a, db1 = act_backward(u, da)     dW2 = (1/sy) (sy dy)^T . fp16(a)^T   (a: recomputed, fp32, dies here)
-        {su, 1/su} = grad_scale(du)     (su du) rows, (su du)^T = half_pack(du)
-        dW1 = (1/su) (su du)^T . x16^T  dx = (1/su) (su du) . W1_16"""
-
-    @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, act):
-        from ..ops_half import act_half, half_pack, half_weight
-        HALF_NODE_CALLS["mlp"] += 1
-        w1_16 = half_weight(w1, "w", [w1], lambda: w1)
-        w2_16 = half_weight(w2, "w", [w2], lambda: w2)
-        x16 = half_pack(_grad_rows(x, x.shape[-1]), None, want_rows=True, want_t=False)[0]
-        u = ops.gemm(x16, w1_16, None if b1 is None else b1.detach().float().contiguous(), split=False, out_fmt=ops.F32, tag="train_fwd")
-        y = ops.gemm(act_half(u, act), w2_16, None if b2 is None else b2.detach().float().contiguous(), split=False, out_fmt=ops.F32, tag="train_fwd")
-        ctx.save_for_backward(x16 if ctx.needs_input_grad[1] else None, u, w1, w2)
-        ctx.act, ctx.lead, ctx.has_b1, ctx.has_b2 = int(act), x.shape[:-1], b1 is not None, b2 is not None
-        return y.view(*x.shape[:-1], w2.shape[0])
-
-    @staticmethod
-    def backward(ctx, gy):
-        from ..ops_half import act_half, gemm_split_k_half, half_pack, half_weight
-        x16, u, w1, w2 = ctx.saved_tensors
-        need_x, need_w1, need_b1, need_w2, need_b2 = ctx.needs_input_grad[:5]
-        need_b1, need_b2 = need_b1 and ctx.has_b1, need_b2 and ctx.has_b2
-        gx = gw1 = gb1 = gw2 = gb2 = du = at = None
-        if not (need_x or need_w1 or need_b1 or need_w2 or need_b2):
-            return None, None, None, None, None, None
-        need_da = need_x or need_w1 or need_b1
-        g2 = _grad_rows(gy, w2.shape[0])
-        sy = ops.grad_scale(g2)
-        ga, gt, gb2 = half_pack(g2, sy, want_rows=need_da, want_t=need_w2, want_bias=need_b2)
-        del g2
-        if need_da:
-            w2t16 = half_weight(w2, "w.T", [w2], lambda: w2.t())
-            da = ops.gemm_scaled(ga, w2t16, sy[1:], split=False, out_fmt=ops.F32, tag="train_dx")
-            ga = None
-            du, a, gb1 = ops.act_backward(u, da, ctx.act, want_a=need_w2, want_bias_grad=need_b1, out=da)
-            del da
-            if need_w2:
-                at = half_pack(a, None, want_rows=False, want_t=True)[1]
-            del a
-        elif need_w2:
-            at = half_pack(act_half(u, ctx.act), None, want_rows=False, want_t=True)[1]
-        if need_w2:
-            gw2 = gemm_split_k_half(gt, at, _weight_grad_chunks(u.shape[0], gt.shape[0], at.shape[0], 64), sy[1:])
-        at = gt = None
-        if need_x or need_w1:
-            su = ops.grad_scale(du)
-            ua, ut, _ = half_pack(du, su, want_rows=need_x, want_t=need_w1)
-            del du
-            if need_w1:
-                gw1 = _half_weight_grad(ut, x16, su[1:])
-            if need_x:
-                w1t16 = half_weight(w1, "w.T", [w1], lambda: w1.t())
-                gx = ops.gemm_scaled(ua, w1t16, su[1:], split=False, out_fmt=ops.F32, tag="train_dx").view(*ctx.lead, w1.shape[1])
-        return gx, gw1, gb1, gw2, gb2, None
-
-
-def half_linear_ok(x, weight, rows):
-    """the linears the half nodes take: fp32 device tensors, at least 256 rows, K % 64 == 0 (the contraction of y and the output rows of
-    dW) and N % 64 == 0 (the contraction of dx): the F16 k tile is 64 elements"""
-    K, N = weight.shape[1], weight.shape[0]
-    return bool(x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and K % 64 == 0 and N % 64 == 0 and rows >= 256)
-
-
-def half_linear(x, weight, bias, owner, key):
-    """F.linear in half precision with a backward (HalfLinearFunction); a shape outside half_linear_ok runs the split node (split_linear)"""
-    if half_linear_ok(x, weight, x.numel() // weight.shape[1] if weight.shape[1] else 0):
-        return HalfLinearFunction.apply(x, weight, bias, owner, key)
-    return split_linear(x, weight, bias, owner, key)
-
-
-def half_mlp(x, w1, b1, w2, b2, act):
-    """linear(act(linear(x, w1, b1)), w2, b2) as one node in half precision (HalfMlpFunction) when BOTH linears are ones half_linear takes;
-    any other shape runs the split node (split_mlp)"""
-    rows = x.numel() // w1.shape[1] if w1.shape[1] else 0
-    if half_linear_ok(x, w1, rows) and half_linear_ok(x, w2, rows) and act in (ops.ACT_GELU, ops.ACT_RELU):
-        return HalfMlpFunction.apply(x, w1, b1, w2, b2, act)
-    return split_mlp(x, w1, b1, w2, b2, act)
 
 
 def _attention_forward(ctx, qa, ka, v, cols, forward_op):
@@ -909,15 +915,6 @@ def _amax_rows(t):
     return rows if rows is not None else _amax_rows(t.contiguous())
 
 
-def _scaled_product_t(at, bt, rows, inv):
-    """inv * at . bt^T for two TRANSPOSED HL8 operands (Na, 2 Mp), (Nb, 2 Mp) whose contraction runs over the `rows` patch rows: the chunks
-    and the fixed-order sum of _scaled_weight_grad"""
-    nk = _weight_grad_chunks(rows, at.shape[0], bt.shape[0])
-    if nk == 1:
-        return ops.gemm_scaled(at, bt, inv, split=True, out_fmt=ops.F32, tag="train_dw")
-    return ops.gemm_split_k_scaled(at, bt, nk, inv)
-
-
 class PatchConvFunction(torch.autograd.Function):
     """A convolution whose kernel equals its stride (k x k / stride k / padding 0: the 1 x 1 projections, the 16 x 16 patch embedding), or a
     transposed 2 x 2 / stride 2 one, as ONE node of the graph: a linear over patch rows plus a layout change that is done once, by the
@@ -933,7 +930,7 @@ class PatchConvFunction(torch.autograd.Function):
       transposed    dx rows = (1/s) G . W2^T        dW2 = (1/s) X^T . G         (Cin, 4 Cout): one GEMM each, not four
     dx is returned as a channels-last view; dW in the weight's own shape, contiguous.  Saved: x and weight only -- X^T is produced in the
     backward by a pass over the saved x, no gathered copy is kept.  The weight products are cut into chunks over the rows and added in
-    chunk order (_scaled_weight_grad's form).  needs_input_grad is honoured: a frozen input, weight or bias skips its operand form and its
+    chunk order (_product_t, the scaled linears' own).  needs_input_grad is honoured: a frozen input, weight or bias skips its operand form and its
     GEMM.  A trainable input with k > 1 has no scatter kernel: patch_conv_train declines it (the patch embedding's input is the image)."""
 
     @staticmethod
@@ -975,7 +972,7 @@ class PatchConvFunction(torch.autograd.Function):
             dx = ops.gemm_scaled(ga, w2, inv, split=True, out_fmt=ops.F32, tag="train_dx").view(B, H, W, C).permute(0, 3, 1, 2)
         if need_w:
             xt = _patch_operands(_patch_source(x), k, want_t=True)[2]
-            dw = (_scaled_product_t(xt, gt, M, inv) if tr else _scaled_product_t(gt, xt, M, inv)).view(weight.shape)
+            dw = (_product_t(xt, gt, M, inv) if tr else _product_t(gt, xt, M, inv)).view(weight.shape)
         return dx, dw, gb, None, None
 
 
