@@ -8,7 +8,17 @@
 // uses the arithmetic of hipie_vit_attn_split instead: q (pre-multiplied by scale * log2 e), k and v are split IN THE KERNEL into fp16 pairs
 // x = hi + lo (22 mantissa bits), every logit is the three-product sum  q_lo.k_hi + q_hi.k_lo + q_hi.k_hi  with fp32 accumulation, the
 // probabilities are an fp16 pair as well and  O += V_hi^T.(P_hi + P_lo) + V_lo^T.P_hi.  Same operands and output as hipie_attn_f32 (fp32
-// views with strides), same semantics (key mask, fully masked rows give zeros): tests hold it to the exact kernel at 2e-6.
+// views with strides), same semantics (key mask, fully masked rows give zeros).
+//
+// What is held (tests/test_gpu_small_attn.py, docs/measurements.md): against float64, per (batch, head, 32-query block), 1e-5 of the block's
+// largest |output| -- the bound of hipie_attn_f32 -- on every launch line; against hipie_attn_f32 on the same random operands 4.2e-6, twice
+// the distance of the two formats' CPU emulations.  "fp32-class" carries two conditions, both measured by emulating the format:
+//   * V: the lo halves of V are fp16, so they lose bits once |v| 2^-11 falls under 2^-14.  With v ~ N(0, 1) x 2^e the bound holds down to
+//     e = -8 (|v| of a few 1e-3); every halving below that doubles the error (1.7e-5 at 2^-10, 5e-4 at 2^-15).  hipie_attn_f32 has no such
+//     limit (asserted 2^-20 below it).
+//   * P: the lo half of P has an absolute floor of 2^-25 of the row's largest probability.  Where one key holds the mass with a small V and
+//     hundreds of keys hold 2^-12 .. 2^-24 of it each, the output is small and the tail's rounding is 8e-5 of it; measured against the
+//     largest |v| of the attended keys of the head it is 4.6e-7 (the `sink` input of the tests).
 //
 // Structure: swapped products as in vit_attn_split.hip -- S^T = K.Q^T (keys are the 32 MFMA rows, a lane owns one query), online softmax
 // per lane over its 16 rows + one cross-half exchange, O^T = V^T.P^T with P used in place as the B operand and V^T fetched by

@@ -443,15 +443,19 @@ def bi_i2t_folded(v_hl8, M, cb, vl, text_mask, heads, wo, bo, resid=None, clamp=
     return out
 
 
-def _small_attn_args(who, q, k, v, mask):
-    """(B, Nq, H, hd, Nk) of the small fp32 attentions: q, k, v fp32 device (B, N, H, hd) views with hd contiguous and heads hd apart"""
+def _small_attn_args(who, q, k, v, mask, rows=False):
+    """(B, Nq, H, hd, Nk) of the small fp32 attentions: q (B, Nq, H, hd), k and v (B, Nk, H, hd) fp32 device views with hd contiguous and
+    heads hd apart; mask (B, Nk), with rows (B, Nq, Nk), of any type that converts to uint8.  The kernels index k, v and the mask by q's
+    B, H, hd and k's Nk, so operands that disagree about them are refused here"""
     _on_device(who, "q k v mask", q, k, v, mask)
-    B, Nq, H, hd = q.shape
+    B, Nq, H, hd = _layout(who, "q", q, ndim=4, density=_ANY).shape
+    Nk = _layout(who, "k", k, ndim=4, density=_ANY).shape[1]
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        _layout(who, n, t, torch.float32, density=_ROWS)
+        _layout(who, n, t, torch.float32, (B, Nq if t is q else Nk, H, hd), density=_ROWS)
         if H > 1 and t.stride(2) != hd:
             raise RuntimeError("%s: %s must be fp32 (B, N, H, hd) with hd contiguous and heads hd apart" % (who, n))
-    return B, Nq, H, hd, k.shape[1]
+    _layout(who, "query_mask" if rows else "key_mask", mask, shape=(B, Nq, Nk) if rows else (B, Nk), density=_ANY)
+    return B, Nq, H, hd, Nk
 
 
 def _small_attn(fn_name, q, k, v, scale, key_mask):
@@ -467,17 +471,17 @@ def _small_attn(fn_name, q, k, v, scale, key_mask):
 @_timed("attn_f32")
 def attn_f32(q, k, v, scale, key_mask=None):
     """hipie_attn_f32: exact fp32 softmax attention.  q (B,Nq,H,hd), k, v (B,Nk,H,hd) fp32 views with hd contiguous and heads hd apart
-    (column blocks of one projection output are fine); hd 32 | 64; key_mask (B,Nk) bool / uint8 -> (B, Nq, H*hd) fp32."""
+    (column blocks of one projection output are fine); hd 32 | 64; key_mask (B,Nk) bool / uint8, non-zero = attend -> (B, Nq, H*hd) fp32.
+    A batch item with no attended key gives zeros."""
     return _small_attn("hipie_attn_f32", q, k, v, scale, key_mask)
 
 
 @_timed("attn_rows")
 def attn_f32_rows(q, k, v, scale, query_mask, split=False):
-    """hipie_attn_f32_rows (exact fp32 FMA) / hipie_attn_split_rows (split=True: matrix pipe, fp32-class): attention with a mask per query row --
-    query_mask (B, Nq, Nk) bool / uint8, True = may attend"""
-    B, Nq, H, hd, Nk = _small_attn_args("attn_f32_rows", q, k, v, query_mask)
-    if tuple(query_mask.shape) != (B, Nq, Nk):
-        raise RuntimeError("attn_f32_rows: query_mask (B, Nq, Nk), got %s" % (tuple(query_mask.shape),))
+    """hipie_attn_f32_rows (exact fp32 FMA) / hipie_attn_split_rows (split=True: matrix pipe, fp32-class under the conditions of attn_split):
+    attention with a mask per query row -- query_mask (B, Nq, Nk) bool / uint8, non-zero = may attend; a row that may attend no key gives
+    zeros (masked_fill(-inf).softmax gives NaN there)"""
+    B, Nq, H, hd, Nk = _small_attn_args("attn_f32_rows", q, k, v, query_mask, rows=True)
     qm = query_mask.to(torch.uint8).contiguous()
     out = torch.empty(B, Nq, H * hd, dtype=torch.float32, device=q.device)
     _call("hipie_attn_split_rows" if split else "hipie_attn_f32_rows", q.data_ptr(), k.data_ptr(), v.data_ptr(), qm.data_ptr(), out.data_ptr(),
@@ -488,7 +492,12 @@ def attn_f32_rows(q, k, v, scale, query_mask, split=False):
 @_timed("attn_split")
 def attn_split(q, k, v, scale, key_mask=None):
     """hipie_attn_split: the same attention on the matrix pipe at fp32-class accuracy (operands split into fp16 pairs in the kernel, three
-    products per logit, probabilities as an fp16 pair): what the split policy runs for BERT and the decoders' query self-attention."""
+    products per logit, probabilities as an fp16 pair): what the split policy runs for BERT and the decoders' query self-attention.
+    fp32-class = attn_f32's bound, 1e-5 of the largest |output| of a (batch, head, 32-query block), under two conditions of the format
+    (csrc/attn_split.hip, tests/test_gpu_small_attn.py): |v| of a few 1e-3 or more (v ~ N(0, 1) x 2^-8 is the last scale that holds; the
+    lo halves of V are fp16 and go subnormal below it), and no row whose mass sits on one key of small V over a long tail of 2^-12 .. 2^-24
+    (the lo half of P has a floor of 2^-25 of the row's largest probability: the error there was measured at 5e-7 of the largest attended |v|,
+    8e-5 of the small output).  attn_f32 has neither limit."""
     return _small_attn("hipie_attn_split", q, k, v, scale, key_mask)
 
 

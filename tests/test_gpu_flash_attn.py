@@ -29,8 +29,9 @@ generic / forced split count paths sit behind HIPIE_FA_WAVES, HIPIE_FA_DEFER, HI
 compiles out without -DHIPIE_STUDY_KNOBS.
 
 Files.  This file covers flash_attn.hip and bi_xattn.hip only; vit_attn.hip (vit_attn_rel) and vit_attn_split.hip have their own file
-of this kind, tests/test_gpu_vit_attn.py.  Not covered by a conformance file of this kind yet: attn_f32.hip, attn_split.hip and the
-training kernels (attn_train*.hip); their tests are the older ones in tests/test_gpu_kernels.py, which stay as they are.
+of this kind, tests/test_gpu_vit_attn.py, and so have attn_f32.hip and attn_split.hip, tests/test_gpu_small_attn.py.  Not covered by a
+conformance file of this kind yet: the training kernels (attn_train*.hip); their tests are the older ones in tests/test_gpu_kernels.py,
+which stay as they are.
 
 References, both in float64 on the values the kernel reads (16-bit operands are rounded first, then upcast).  `ref_attn` is the formula of
 the header of flash_attn.hip in torch:  s[i,j] = clamp(scale q_i.k_j, +-clamp) + bias_h[j // kw, i] + bias_w[i, j % kw], masked keys

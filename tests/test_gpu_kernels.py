@@ -4,9 +4,9 @@ against the reference-generated golden fixtures.  Tolerances are written next to
   16-bit MFMA kernels: vs the oracle fed the SAME 16-bit-rounded inputs 1e-3 (fp16) / 8e-3 (bf16) -- the residual is the
   rounding of P and of the output to 16 bit; vs the fp32 golden 2e-3 (fp16) / 2e-2 (bf16).
 Per-branch float64 conformance files exist for csrc/msda.hip (tests/test_gpu_msda_forward.py) and for the 16-bit flash attention family,
-csrc/flash_attn.hip and csrc/bi_xattn.hip (tests/test_gpu_flash_attn.py: ops.flash_attn, vit_attn, vit_attn_fused, bi_xattn).  The other
-attention files -- attn_f32.hip, attn_split.hip, vit_attn.hip (vit_attn_rel), vit_attn_split.hip and the training kernels -- have no such
-file yet; the attention tests below are all they have."""
+csrc/flash_attn.hip and csrc/bi_xattn.hip (tests/test_gpu_flash_attn.py: ops.flash_attn, vit_attn, vit_attn_fused, bi_xattn), for
+vit_attn.hip (vit_attn_rel) and vit_attn_split.hip (tests/test_gpu_vit_attn.py) and for attn_f32.hip and attn_split.hip
+(tests/test_gpu_small_attn.py).  The training attention kernels have no such file yet; the attention tests below are all they have."""
 import pytest
 import torch
 
@@ -1484,6 +1484,8 @@ def test_flash_attn_reads_keys_from_hl8_hi_halves(Nk, L):
 
 
 # --------------------------------------------------------------------------- exact fp32 small attention
+# (workload-like shapes, one whole-tensor metric; the launch lines, tile edges, masked prefixes and the online-softmax rescale of these two
+# kernels are walked per 32-query block against float64 in tests/test_gpu_small_attn.py)
 @pytest.mark.gpu
 @pytest.mark.parametrize("B,Nq,Nk,H,hd,masked", [(2, 194, 194, 12, 64, True), (3, 910, 910, 8, 32, False), (2, 300, 300, 8, 32, False),
                                                  (1, 5, 37, 2, 64, True), (2, 512, 512, 12, 64, True)])

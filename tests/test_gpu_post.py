@@ -357,6 +357,8 @@ def test_post_maskclip_mixed_sizes_match_single_image_runs():
         assert rel_err(got.pred_boxes.tensor[:n].cpu(), alone.pred_boxes.tensor[:n].cpu()) < 1e-5
 
 
+# (key 0 is always visible here; masked leading key tiles, fully masked rows among live ones and the tile edges of the two _rows entries are
+# in tests/test_gpu_small_attn.py)
 @pytest.mark.gpu
 @pytest.mark.parametrize("B,H,Nq,Nk,hd", [(2, 16, 150, 577, 64), (1, 3, 5, 33, 32), (3, 2, 130, 64, 64)])
 def test_attn_f32_rows_mask_per_query_row(B, H, Nq, Nk, hd):
